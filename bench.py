@@ -33,7 +33,20 @@ collective in the data path; the (s, pi, z) examples are all-gathered once after
 (blackbird_amd/dist.py; the epoch-end exchange of SURVEY.md 8e).  Under torch.distributed.run the ranks are what the
 launcher made them; `python bench.py --gpus N` without a launcher starts that same command itself.
 
-usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c5|dc]
+A plain run does only what the headline needs: set-up, prefill, settle, warm-up, the K timed steps, the outputs if
+--dump-outputs is given, and the JSON line.  --full adds the legs beside it, each a run of its own after the timed region:
+`cpu_baseline` / `gpu_over_cpu` (the oracle on the host's cores) and, for c2 on one GPU, `api_games_per_sec` / `api`
+(--no-cpu-baseline and --no-api drop them again).
+
+--dump-outputs DIR: after the timed region (untimed), the same engine -- kernel, weights, noise, simulations per move --
+plays one fresh batch of `slots` games (game ids 0 .. slots - 1) from the initial position to the end, and their example
+records are written: one DIR/record_<field>.npy per record field, plus DIR/game_index.npy, game_winner.npy and
+game_records.npy per game (float32; ids float64).  A game's records depend only on its id, the weights and the seed, never
+on how the visits were scheduled, so the dump is the same from run to run.  The games of the timed window itself cannot
+be dumped that way: which of them finish inside it, and how many of their moves fell into the prefill's low simulation
+count, do depend on the schedule.
+
+usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c5|dc] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -229,6 +242,51 @@ def api_games_per_sec(n_games=8192, sims=800):
         os.chdir(cwd)
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this much in all
+
+
+def dump_games(eng, path, n, cap_steps, suffix="", budget=DUMP_BYTES):
+    """--dump-outputs, untimed after the timed region: the engine plays a fresh batch of games 0 .. n - 1 to the end (at
+    most `cap_steps` steps), then their records are written (dump_outputs)."""
+    eng.selfplay_begin(n, 1.0)
+    steps = 0
+    while not eng.selfplay_done()[0]:
+        if steps >= cap_steps or eng.counters()["overflow"]:
+            raise RuntimeError("--dump-outputs: %d games unfinished after %d steps (overflow %d)"
+                               % (n, steps, eng.counters()["overflow"]))
+        eng.selfplay_step(8)
+        steps += 8
+    hdr = eng.selfplay_headers(0, n)
+    ids = np.arange(n)
+    rec, offs, win = eng.fetch_games(ids, int(hdr[:, 0].sum()))
+    assert hdr[:, 3].all() and len(offs) == n + 1 and offs[-1] == len(rec) == int(hdr[:, 0].sum())
+    return dump_outputs(path, ids, rec, offs, win, suffix, budget)
+
+
+def dump_outputs(path, game_index, rec, offs, win, suffix="", budget=DUMP_BYTES):
+    """The records of the listed games (`offs` delimits each game's records in `rec`), one float32 array per record field
+    (game ids float64: exact for 32-bit ids), plus each game's index, winner and record count.  Games stay in ascending
+    index order; when the arrays would exceed `budget`, a fixed-seed sample of the games is kept (still in index order)."""
+    os.makedirs(path, exist_ok=True)
+    n = len(game_index)
+    counts = np.diff(offs[:n + 1]).astype(np.int64)
+    rec_bytes = sum((8 if f == "game_id" else 4) * int(np.prod(rec.dtype[f].shape, dtype=np.int64)) for f in rec.dtype.names)
+    room = budget - 16 * 128    # (.npy headers)
+    keep = np.arange(n)
+    if int(counts.sum()) * rec_bytes + n * 24 > room:
+        order = np.random.default_rng(0).permutation(n)
+        used = np.cumsum(counts[order] * rec_bytes + 24)
+        keep = np.sort(order[:int(np.searchsorted(used, room, side="right"))])
+    rows = np.concatenate([np.arange(offs[g], offs[g + 1]) for g in keep]) if len(keep) else np.zeros(0, np.int64)
+    sel = rec[rows]
+    for f in rec.dtype.names:
+        np.save(os.path.join(path, f"record_{f}{suffix}.npy"), sel[f].astype(np.float64 if f == "game_id" else np.float32))
+    np.save(os.path.join(path, f"game_index{suffix}.npy"), np.asarray(game_index)[keep].astype(np.float64))
+    np.save(os.path.join(path, f"game_winner{suffix}.npy"), np.asarray(win)[keep].astype(np.float32))
+    np.save(os.path.join(path, f"game_records{suffix}.npy"), counts[keep].astype(np.float32))
+    return len(keep), n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -239,8 +297,12 @@ def main():
     ap.add_argument("--prefill", type=int, default=None, help="untimed de-synchronisation plies at few sims/move")
     ap.add_argument("--settle", type=int, default=None, help="untimed full-strength steps after the prefill (default: max_plies + 2 for c2)")
     ap.add_argument("--launches", type=int, default=3, help="launches the K timed steps are split into (>= 3 by default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-api", action="store_true", help="skip the GenerateTrainingSamples end-to-end leg (c2, one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the CPU baseline and (c2, one GPU) the GenerateTrainingSamples leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-api", action="store_true", help="with --full: skip the GenerateTrainingSamples end-to-end leg (c2, one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the games that finished in the timed region as DIR/*.npy (at most 64 MB)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2",
                     help="c2 = BASELINE configs[1] (default, the headline); c5 = configs[4]'s 20x256 network on one GPU "
                          "(use --steps 1 --warmup 0 --prefill 1); dc = configs[3] DragonChess 1024 games x 400 sims")
@@ -252,6 +314,8 @@ def main():
     sims = w["sims"] if args.sims is None else args.sims
     prefill = w["prefill"][0] if args.prefill is None else args.prefill
     settle = w["settle"] if args.settle is None else args.settle
+    if K < 1:
+        ap.error("--steps must be at least 1")
     w["sims"] = sims
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -372,6 +436,10 @@ def main():
     else:
         allgather_s = None
         n_examples_all = None
+    if args.dump_outputs:
+        # (module docstring) several ranks: every rank writes its own games, `_rank<r>` files sharing the budget
+        dump_games(eng, args.dump_outputs, slots, cap_steps=2 * w["max_plies"] + 64,
+                   suffix=f"_rank{rank}" if world > 1 else "", budget=DUMP_BYTES // world)
 
     rc = 0
     if rank == 0:
@@ -475,13 +543,13 @@ def main():
             out["value"] = None
             out["error"] = "overflow counter is %d (summed over ranks): result invalid" % overflow_any
             rc = 1
-        elif world == 1 and not args.no_cpu_baseline:
+        elif world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, w, flat, mean_len)
             gps = games_rate if not dc else (out["games_per_sec_full_strength"] or out["games_per_sec_steady"])
             out["gpu_over_cpu"] = gps / out["cpu_baseline"]["value"] if (gps and out["cpu_baseline"]["value"]) else None
     eng.close()
     if rank == 0:
-        if rc == 0 and world == 1 and args.workload == "c2" and not args.no_api:
+        if rc == 0 and world == 1 and args.workload == "c2" and args.full and not args.no_api:
             api = api_games_per_sec(sims=sims)   # (the engine above is closed: the drop-in model creates its own)
             out["api_games_per_sec"] = api["value"]
             out["api"] = api
