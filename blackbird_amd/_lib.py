@@ -53,7 +53,8 @@ class Config(C.Structure):
 
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("sims", "sum_depth", "nodes", "terminal_leaves", "games_finished",
-                                           "plies", "overflow", "examples", "evals")]
+                                           "plies", "overflow", "examples", "evals",
+                                           "eval_cache_hits", "eval_cache_probes")]
 
 
 class BlackbirdHipError(RuntimeError):

@@ -217,6 +217,7 @@ struct bb_engine {
         int launch_steps = 64, queue_limit_s = 30, queue_netw = 0, queue_waves = 12;
         bool level_budget_set = false;
     } tune;
+    size_t eval_cache_bytes = 0; // evaluation cache of the persistent kernel (dev.eval_cache), zeroed with every weight load
     bool mega = false; // persistent per-CU self-play kernel with an LDS work queue (mega2.hip.h)
     bool async_selfplay = false; // dense games, DynamicMCTS, deterministic evaluators: k_tree_async rounds
     bool dc_fused = false;       // DragonChess, DynamicMCTS, 16-filter network: one wave keeps its game for a whole launch (mega_dc.hip.h)
@@ -329,6 +330,19 @@ static void make_views(bb_engine *e) {
 }
 
 // ---- pool sizing ------------------------------------------------------------------------------------------------
+// log2 of the entries of the evaluation cache (net.hip.h EvalCache: 64 bytes each) an engine of this configuration owns, 0 = none.
+// Only the persistent self-play kernel of Connect4 probes it.  BB_EVAL_CACHE=0 turns it off, BB_EVAL_CACHE_LOG2 sizes it
+// (default 26: 4 GiB) -- tuning knobs, read from the environment at bb_create / bb_fit_slots.
+static int eval_cache_log2_of(const bb_config *cfg) {
+    if (cfg->game != BB_GAME_CONNECT4 || cfg->mcts_kind != BB_MCTS_DYNAMIC || cfg->evaluator != BB_EVAL_NET ||
+        cfg->launch != BB_LAUNCH_AUTO)
+        return 0;
+    const char *on = getenv("BB_EVAL_CACHE"), *lg = getenv("BB_EVAL_CACHE_LOG2");
+    if (on && atoi(on) == 0) return 0;
+    const int k = lg ? atoi(lg) : 26;
+    return k < 10 ? 10 : k > 32 ? 32 : k;
+}
+
 static long node_capacity_of(const bb_config *cfg) {
     long cap = cfg->node_capacity > 0 ? cfg->node_capacity : (long)cfg->sims_per_move * cfg->max_plies + 2;
     if (cfg->mcts_kind == BB_MCTS_FIXED && cfg->node_capacity <= 0) cap = cap * cfg->max_depth;
@@ -350,6 +364,7 @@ static void pool_bytes(const bb_config *cfg, size_t *per_slot, size_t *fixed) {
     const size_t ng = (size_t)(cfg->max_games > 0 ? cfg->max_games : cfg->n_slots);
     *per_slot = ps;
     *fixed = ng * ((size_t)(cfg->max_plies + 1) * (size_t)gi.example_bytes + 16) + (64u << 20); // + weights, scratch, runtime slack
+    if (const int k = eval_cache_log2_of(cfg)) *fixed += (size_t)64 << k;
 }
 
 static int check_config(const bb_config *cfg) {
@@ -456,6 +471,16 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
     if (int v = env_int("BB_TREE_GPW", 0); v >= 1 && v <= 64 / e->info.S) d.gpw = v;
     d.temp = 1.0;
     GAME_SWITCH(cfg->game, rc = engine_alloc<G>(e); break);
+    if (!rc && e->mega) {
+        if (const int k = eval_cache_log2_of(cfg)) {
+            uint8_t *tab = nullptr;
+            e->eval_cache_bytes = (size_t)64 << k;
+            rc = dalloc(e, tab, e->eval_cache_bytes); // (zeroed: empty)
+            d.eval_cache = tab;
+            d.eval_cache_log2 = k;
+        }
+    }
+    if (!rc) rc = dalloc(e, d.eval_cache_ctr, 2);
     if (rc) {
         bb_destroy(e);
         return rc;
@@ -856,6 +881,8 @@ extern "C" int bb_load_weights(bb_engine *e, const bb_net_weights *w) {
         return fail(BB_ERR_ARG, "filters must be a multiple of 16 (MFMA tile), got %d", w->F);
     if (w->D <= 0 || w->D > 64 || w->R < 0) return fail(BB_ERR_ARG, "unsupported dense/blocks");
     HIPCHK(hipSetDevice(e->cfg.device));
+    // no evaluation outlives the weights (or the network form) it was made with
+    if (e->eval_cache_bytes) HIPCHK(hipMemsetAsync(e->dev.eval_cache, 0, e->eval_cache_bytes, e->stream));
     const int F = w->F, C = w->C, R = w->R, D = w->D, A = w->A;
     const int steps0 = (9 * C + 3) / 4;
     e->general_net = F != 16 || e->cfg.general_net != 0;
@@ -1559,6 +1586,10 @@ static int sum_counters(bb_engine *e, bb_counters *out) {
     out->plies = t[5];
     out->overflow = t[6];
     out->examples = t[7];
+    uint64_t ec[2];
+    HIPCHK(hipMemcpy(ec, e->dev.eval_cache_ctr, sizeof ec, hipMemcpyDeviceToHost));
+    out->eval_cache_hits = ec[0];
+    out->eval_cache_probes = ec[1];
     return BB_OK;
 }
 
@@ -1573,6 +1604,7 @@ extern "C" int bb_reset_counters(bb_engine *e) {
     HIPCHK(hipSetDevice(e->cfg.device));
     HIPCHK(hipMemsetAsync(e->dev.ctr, 0, (size_t)e->dev.n_slots * 64, e->stream));
     HIPCHK(hipMemsetAsync(e->dev.evals, 0, (size_t)e->dev.n_slots * 8, e->stream));
+    HIPCHK(hipMemsetAsync(e->dev.eval_cache_ctr, 0, 16, e->stream));
     return BB_OK;
 }
 

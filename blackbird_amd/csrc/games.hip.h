@@ -183,7 +183,32 @@ struct GridGame {
         out[1] = (int8_t)((s.p2 >> bit) & 1);
         out[2] = gs_player(s) == 1 ? 1 : -1;
     }
+
+    // Exact key of the network input of a position (the evaluation cache of the persistent kernel: net_x3.hip.h; the
+    // reference memoises the same evaluations with lru_cache, keyed by board and player).  Connect4 only (CACHE_KEY):
+    //     player 1's stones | one sentinel bit per column on its lowest empty cell (row H when full) | bit 63 = player 1 to move.
+    // The sentinels give the column heights, hence the occupied cells; player 1's stones among them are in the key and
+    // player 2's are the rest -- so the key determines encode_cell's three planes, and two different inputs never share
+    // a key.  Every column has a sentinel, so a key is never 0.  A board that is not one stack of stones per column (never
+    // reached in play; some parity fixtures probe them) has no such code and gets 0, which the cache never stores.
+    static constexpr bool CACHE_KEY = DROP;
+    BB_HD static uint64_t cache_key(const State &s) {
+        const uint64_t b1 = gs_cells(s.p1), b2 = gs_cells(s.p2), occ = b1 | b2, floor = (1ull << W) - 1;
+        const uint64_t above = (occ << STR) | floor; // cells on a stone or on the floor
+        if (!DROP || (b1 & b2) || (occ & ~board_mask()) || (occ & ~above)) return 0;
+        return b1 | (above & ~occ) | ((uint64_t)(gs_player(s) == 1) << 63);
+    }
 };
+
+// Bijective 64-bit mix (the murmur3 finaliser: xor-shifts and odd multipliers): spreads cache keys over the table's slots.
+BB_HD uint64_t bb_mix64(uint64_t z) {
+    z ^= z >> 33;
+    z *= 0xff51afd7ed558ccdull;
+    z ^= z >> 33;
+    z *= 0xc4ceb9fe1a85ec53ull;
+    z ^= z >> 33;
+    return z;
+}
 
 using Connect4 = GridGame<6, 7, 4, 8, 7, 8, 0>;
 using TicTacToe = GridGame<3, 3, 3, 4, 9, 16, 1>;
@@ -206,6 +231,7 @@ struct DragonChess {
     static constexpr int H = 8, W = 8, C = 17, A = 4032, S = 144, GID = 2;
     static constexpr int MAXPATH = 128;
     static constexpr bool CELL_BF16 = true;
+    static constexpr bool CACHE_KEY = false; // (no evaluation cache: GridGame::cache_key)
     using State = DCState;
 
     BB_HD static State initial() { // fen 'rnbqkbnr/pppppppp/8/8/8/8/3PPP2/4K3 w kq' (DragonChess.py:36-60)

@@ -650,6 +650,11 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
 #endif
     } else { // ---------------- network waves ----------------
         float *wl = lds + wave * WAVE_F;
+        // The evaluation cache (net.hip.h; off when dg.eval_cache is null): a hit costs the prior-noise tail instead of the tower.
+        // d.evals keeps counting tower runs -- the tree wave counted the leaf when it posted it, so a hit takes it back.
+        constexpr bool CACHE = X3 && G::CACHE_KEY && !TREE_HEADS;
+        const EvalCache ecache = {(u32x4 *)dg.eval_cache, dg.eval_cache_log2};
+        unsigned long long n_probes = 0, n_hits = 0;
 #ifdef BB_STAMPS
         long long t_work = 0, t_all0 = clock64(), n_evals = 0, t_qwait = 0;
 #endif
@@ -676,11 +681,20 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
                 if (l64 < G::A) d.eval_policy[(size_t)slot * S + l64] = bb_hash_policy(z, l64);
             }
 #else
-            if constexpr (X3)
-                net_body_x3<G, true, (BB_X3_LEAN != 0), false, TREE_HEADS>(ndl, x3l, 1, 0, &myslot[wave], (unsigned char *)wl, (const typename G::State *)d.leaf_state, nullptr,
+            if constexpr (X3) {
+                int probe = -1;
+                net_body_x3<G, true, (BB_X3_LEAN != 0), false, TREE_HEADS, CACHE>(ndl, x3l, 1, 0, &myslot[wave], (unsigned char *)wl, (const typename G::State *)d.leaf_state, nullptr,
                                      d.leaf_game_id, d.leaf_serial, noise_on, d.eval_value, nullptr, d.eval_policy, S, false, nullptr,
-                                     (noise_on && TREE_NOISE) ? s_noise + li * S : nullptr, TREE_HEADS ? s_pooled + li * 4 : nullptr);
-            else
+                                     (noise_on && TREE_NOISE) ? s_noise + li * S : nullptr, TREE_HEADS ? s_pooled + li * 4 : nullptr,
+                                     ecache, &probe);
+                if constexpr (CACHE) {
+                    n_probes += probe >= 0;
+                    if (probe > 0) {
+                        n_hits++;
+                        if (l64 == 0) d.evals[li] -= 1;
+                    }
+                }
+            } else
                 net_body<G, 1, BB_QUEUE_WMODE>(ndl, 1, 0, &myslot[wave], wl, (const typename G::State *)d.leaf_state, nullptr,
                                                d.leaf_game_id, d.leaf_serial, noise_on, d.eval_value, nullptr, d.eval_policy, S, false);
 #endif
@@ -719,6 +733,10 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
             atomicAdd(&d.stamps[10], (unsigned long long)t_qwait);
         }
 #endif
+        if (CACHE && l64 == 0 && n_probes && dg.eval_cache_ctr) {
+            atomicAdd(&dg.eval_cache_ctr[0], n_hits);
+            atomicAdd(&dg.eval_cache_ctr[1], n_probes);
+        }
     }
     __syncthreads();
 #ifdef BB_STAMPS_NET

@@ -203,13 +203,105 @@ __device__ __forceinline__ void wide_head_stats(WideHead &h, PK pdk, PK pdb, int
 // Every lane ends with the same bits; the tree does not depend on how positions are packed into waves.
 __device__ __forceinline__ float pooled_sum(float v) { return wave_sum_f32(v); }
 
+// ---- evaluation cache (persistent kernel, Connect4; the table is device memory of the engine: engine.hip) ------------------
+// Direct-mapped: 2^log2 entries of 64 bytes, the slot of a position is the top bits of bb_mix64(G::cache_key).  An entry is four
+// 16-byte chunks {u64 key, f32, f32} that hold [value, p0 .. p6], the network's value and its priors BEFORE the prior noise:
+// chunk c carries floats 2c and 2c + 1.  Every chunk is written and read as ONE 16-byte vector access of ONE lane, and counts
+// only if its own key matches -- an entry read while another position's is written over it is then a miss, never a mix.
+// That relies on aligned 16-byte accesses not tearing: observed on gfx950 (single-lane dwordx4 loads and stores), not
+// guaranteed by the architecture.  Evaluation is deterministic, so two writers of one key write the same bits, and chunks
+// of theirs may mix freely.  No fences: a store that another CU does not see yet (its L2 is another XCD's) only turns a hit
+// into a miss.  A zeroed table is empty (a key is never 0); the engine zeroes it whenever weights are loaded.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+struct EvalCache {
+    u32x4 *tab; // [2^log2][4] chunks; null: off
+    int log2;
+};
+__device__ __forceinline__ u32x4 *eval_cache_entry(const EvalCache &c, uint64_t key) {
+    return c.tab + 4 * (size_t)(bb_mix64(key) >> (64 - c.log2));
+}
+// lanes 0 .. 3 store chunk `lane` of the entry (value: wave-uniform; pr: action a's prior on lane a)
+template <int A>
+__device__ __forceinline__ void eval_cache_put(u32x4 *entry, uint64_t key, float value, float pr, int lane) {
+    static_assert(A == 7, "an entry holds the value and seven priors");
+    const int c = lane < 4 ? lane : 0;
+    const float lo = __shfl(pr, c > 0 ? 2 * c - 1 : 0, 64), hi = __shfl(pr, 2 * c, 64);
+    if (lane < 4)
+        *(__attribute__((address_space(1))) u32x4 *)(void *)(entry + lane) =
+            u32x4{(uint32_t)key, (uint32_t)(key >> 32), __float_as_uint(c == 0 ? value : lo), __float_as_uint(hi)};
+}
+// the probe: chunk `lane` of the entry on lanes 0 .. 3 (issued ahead; tested by eval_cache_hit)
+__device__ __forceinline__ u32x4 eval_cache_load(const u32x4 *entry, int lane) {
+    u32x4 z = {0u, 0u, 0u, 0u};
+    if (lane < 4) z = *(const __attribute__((address_space(1))) u32x4 *)(const void *)(entry + lane);
+    return z;
+}
+// wave-uniform: all four chunks carry `key`; then the value and this lane's prior (lanes >= A: 0, as head_one leaves them)
+template <int A>
+__device__ __forceinline__ bool eval_cache_hit(u32x4 ch, uint64_t key, int lane, float &value, float &pr) {
+    const bool ok = lane < 4 && ch[0] == (uint32_t)key && ch[1] == (uint32_t)(key >> 32);
+    if ((__ballot(ok) & 0xFull) != 0xFull) return false;
+    const float f0 = __uint_as_float(ch[2]), f1 = __uint_as_float(ch[3]);
+    value = lane_f32(f0, 0);
+    const int i = (lane < A ? lane : 0) + 1; // float i of the entry: chunk i / 2, half i % 2
+    const float lo = __shfl(f0, i >> 1, 64), hi = __shfl(f1, i >> 1, 64);
+    pr = lane < A ? ((i & 1) ? hi : lo) : 0.f;
+    return true;
+}
+
+// The end of a dense game's policy head, from the normalised priors on (action a on lane a; lanes >= A hold 0): the prior
+// noise mix and renormalisation, then the policy store.  head_one and a cache hit (net_x3.hip.h) both end here, so a hit
+// runs the same instructions on the same numbers as the evaluation it replaces.
+template <class G>
+__device__ __forceinline__ void dense_prior_tail(const NetDev &nd, float pr, int pos, bool live, const uint32_t *game_id,
+                                                 const int32_t *serial, int noise, float *policy_out, int pstride,
+                                                 const float *noise_ready, int lane) {
+    constexpr int A = G::A;
+    static_assert(2 * A <= 64, "the prior-noise draws use two lanes per action");
+    const bool act = lane < A;
+    constexpr bool ROW0 = A <= 16; // (every action on a lane of row 0)
+    if (noise) { // policy = (1-eps)*softmax + eps*Beta(alpha,1-alpha); policy /= sum(policy)   (NetworkFactory.py:176-182)
+        // two lanes per action: lane pair (2a, 2a+1) tries Philox pairs k and k+1 side by side
+        const float ia = nd.inv_alpha, ib = nd.inv_beta;
+        const int q = lane >> 1, sub = lane & 1;
+        const bool drawing = q < A && live;
+        const uint32_t gid = game_id ? game_id[live ? pos : 0] : (uint32_t)noise;
+        const uint32_t ser = serial ? (uint32_t)serial[live ? pos : 0] : (uint32_t)pos;
+        float r = ND_DBG(8) ? nd.alpha : -1.0f;
+        if (noise_ready) r = nd.alpha; // (the draws were made by the caller: persistent kernel, tree waves; see below)
+        for (uint32_t k = 0; k < 32 && __any(drawing && r < 0.0f); k += 2) {
+            float mine = (drawing && r < 0.0f) ? bb_beta_pair(nd.seed, gid, ser, (uint32_t)q, ia, ib, k + sub) : -1.0f;
+            float other = dpp_f32(mine, 0); // the pair's other lane (quad permute, no LDS round trip)
+            float first = sub ? other : mine, second = sub ? mine : other; // pair k before pair k+1
+            if (r < 0.0f) r = first >= 0.0f ? first : second;
+        }
+        r = r >= 0.0f ? r : nd.alpha;
+        float nz = __shfl(r, 2 * (act ? lane : 0), 64); // action a's draw sits on lane 2a
+        if (noise_ready) { // the same draws (bb_beta_noise: same trials in the same order), made by the tree wave that posted the leaf
+            // -- after it posted it (mega2.hip.h): wait for its flag in the spare slot of the game's noise row, take the draws,
+            // clear the flag for the game's next leaf.  (Bounded: a launch that is being aborted must still drain.)
+            float *nr = const_cast<float *>(noise_ready);
+            for (int spin = 0; spin < (1 << 16) && __hip_atomic_load(nr + G::S - 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0.f; spin++)
+                __builtin_amdgcn_s_sleep(1);
+            nz = act ? nr[lane] : 0.f;
+            wave_lds_handover();
+            if (lane == 0) __hip_atomic_store(nr + G::S - 1, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        pr = (1.0f - nd.eps) * pr + nd.eps * (act ? nz : 0.f);
+        const float t2 = ROW0 ? row0_sum_f32(pr) : wave_sum_f32(pr);
+        pr = pr * __builtin_amdgcn_rcpf(t2);
+    }
+    if (live && act && policy_out) policy_out[(size_t)pos * pstride + lane] = pr;
+}
+
 // One position's value / policy from its pooled activations (R, R0, R1 are wave-uniform); all 64 lanes take part.
-// `live` = the position exists (pos < n); outputs go to index `pos`.
+// `live` = the position exists (pos < n); outputs go to index `pos`.  cache_entry (dense games): the evaluation cache entry
+// that receives the value and the priors before the noise (key cache_key).
 template <class G>
 __device__ __forceinline__ void head_one(const NetDev &nd, float R, float R0, float R1, int pos, bool live,
                                          const uint32_t *game_id, const int32_t *serial, int noise, float *value_out,
                                          float *logits_out, float *policy_out, int pstride, WideHead *compact,
-                                         const float *noise_ready = nullptr) {
+                                         const float *noise_ready = nullptr, u32x4 *cache_entry = nullptr, uint64_t cache_key = 0) {
     constexpr int A = G::A, HW = G::H * G::W;
     int lane_ = threadIdx.x & 63;
     asm volatile("" : "+v"(lane_)); // (keeps the addresses below inside a persistent caller's loop: see net_body_x3)
@@ -300,39 +392,10 @@ __device__ __forceinline__ void head_one(const NetDev &nd, float R, float R0, fl
         float pr = act ? wide_expterm(l, m) : 0.f; // exp(l - m) on v_exp_f32, as the wide head does
         const float tot = ROW0 ? row0_sum_f32(pr) : wave_sum_f32(pr);
         pr = pr * __builtin_amdgcn_rcpf(tot); // (v_rcp_f32: one ulp; an IEEE division is twelve instructions on this tail, twice)
-        if (noise) { // policy = (1-eps)*softmax + eps*Beta(alpha,1-alpha); policy /= sum(policy)   (NetworkFactory.py:176-182)
-            // two lanes per action: lane pair (2a, 2a+1) tries Philox pairs k and k+1 side by side
-            const float ia = nd.inv_alpha, ib = nd.inv_beta;
-            const int q = lane >> 1, sub = lane & 1;
-            const bool drawing = q < A && live;
-            const uint32_t gid = game_id ? game_id[live ? pos : 0] : (uint32_t)noise;
-            const uint32_t ser = serial ? (uint32_t)serial[live ? pos : 0] : (uint32_t)pos;
-            float r = ND_DBG(8) ? nd.alpha : -1.0f;
-            if (noise_ready) r = nd.alpha; // (the draws were made by the caller: persistent kernel, tree waves; see below)
-            for (uint32_t k = 0; k < 32 && __any(drawing && r < 0.0f); k += 2) {
-                float mine = (drawing && r < 0.0f) ? bb_beta_pair(nd.seed, gid, ser, (uint32_t)q, ia, ib, k + sub) : -1.0f;
-                float other = dpp_f32(mine, 0); // the pair's other lane (quad permute, no LDS round trip)
-                float first = sub ? other : mine, second = sub ? mine : other; // pair k before pair k+1
-                if (r < 0.0f) r = first >= 0.0f ? first : second;
-            }
-            r = r >= 0.0f ? r : nd.alpha;
-            float nz = __shfl(r, 2 * (act ? lane : 0), 64); // action a's draw sits on lane 2a
-            if (noise_ready) { // the same draws (bb_beta_noise: same trials in the same order), made by the tree wave that posted the leaf
-                // -- after it posted it (mega2.hip.h): wait for its flag in the spare slot of the game's noise row, take the draws,
-                // clear the flag for the game's next leaf.  (Bounded: a launch that is being aborted must still drain.)
-                float *nr = const_cast<float *>(noise_ready);
-                for (int spin = 0; spin < (1 << 16) && __hip_atomic_load(nr + G::S - 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0.f; spin++)
-                    __builtin_amdgcn_s_sleep(1);
-                nz = act ? nr[lane] : 0.f;
-                wave_lds_handover();
-                if (lane == 0) __hip_atomic_store(nr + G::S - 1, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            pr = (1.0f - nd.eps) * pr + nd.eps * (act ? nz : 0.f);
-            const float t2 = ROW0 ? row0_sum_f32(pr) : wave_sum_f32(pr);
-            pr = pr * __builtin_amdgcn_rcpf(t2);
-        }
+        if constexpr (A == 7)
+            if (cache_entry) eval_cache_put<A>(cache_entry, cache_key, value, pr, lane); // (fire and forget)
         if (live && act && logits_out) logits_out[(size_t)pos * A + lane] = l;
-        if (live && act && policy_out) policy_out[(size_t)pos * pstride + lane] = pr;
+        dense_prior_tail<G>(nd, pr, pos, live, game_id, serial, noise, policy_out, pstride, noise_ready, lane);
     }
 }
 

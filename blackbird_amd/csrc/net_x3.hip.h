@@ -184,13 +184,17 @@ __device__ __forceinline__ bf16x8 x3_ldg(const unsigned char *p) {
 #define NSUB(i) do {} while (0)
 #endif
 #define X3_DBG(bit) ND_DBG(bit) // ablation switches of the diagnostic build (bb_timing_net; results are wrong when set)
-template <class G, bool WLDS, bool LEAN = false, bool PP = false, bool HEADS_OUT = false>
+// CACHE (persistent kernel, Connect4): the position's evaluation cache entry (net.hip.h) is requested before the prologue and
+// tested after it -- on a miss the probe's latency hides under the prologue.  A hit skips the tower and the heads and runs only
+// dense_prior_tail on the cached value / priors; a miss stores them in head_one.  *probe_out: -1 no probe (cache off, or a
+// board without a key), 0 miss, 1 hit.
+template <class G, bool WLDS, bool LEAN = false, bool PP = false, bool HEADS_OUT = false, bool CACHE = false>
 __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, int n, int pos0, const int *slot_list,
                                             unsigned char *wl, const typename G::State *states, const int8_t *planes,
                                             const uint32_t *game_id, const int32_t *serial, int noise, float *value_out,
                                             float *logits_out, float *policy_out, int pstride, bool zero_lds,
                                             WideHead *compact = nullptr, const float *noise_ready = nullptr,
-                                            float *pooled_out = nullptr) {
+                                            float *pooled_out = nullptr, EvalCache cache = {nullptr, 0}, int *probe_out = nullptr) {
     using XG = X3Geom<G>;
     constexpr int W = XG::W, CIN = XG::CIN, HW = XG::HW, NT = XG::NT, SB = XG::SLOT_B, RS = XG::RS;
     constexpr bool WIDE_IN = XG::WIDE_IN;
@@ -217,6 +221,18 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
     typename G::State my_state;
     if constexpr (PP) sst_in = as_lds(&states[OI(live ? pos0 : 0)]);
     else my_state = planes ? G::initial() : states[OI(live ? pos0 : 0)];
+    static_assert(!CACHE || (G::CACHE_KEY && !PP && !HEADS_OUT), "the evaluation cache: Connect4, value and priors formed here");
+    uint64_t ckey = 0;
+    u32x4 *centry = nullptr;
+    u32x4 cchunk = {0u, 0u, 0u, 0u};
+    if constexpr (CACHE) {
+        if (cache.tab && live && !planes) ckey = G::cache_key(my_state); // (wave-uniform)
+        if (ckey) {
+            centry = eval_cache_entry(cache, ckey);
+            cchunk = eval_cache_load(centry, lane);
+        }
+        if (probe_out) *probe_out = ckey ? 0 : -1;
+    }
     const unsigned char *w0p = x3.w0;
     bf16x8 w0a[WIDE_IN ? 27 : 3]; // wide input: [tap][plane], all requested now (L2), consumed tap by tap
     bf16x8 w0b;                   // narrow input: tap 8's three weight planes side by side in one K = 32 operand
@@ -308,6 +324,15 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         *(u32x2 *)(X + ((y + 1) * RS + (x + 1)) * SB) = u32x2{b[0] | (b[1] << 16), b[2] | (b[3] << 16)};
     }
     NSUB(7);
+    if constexpr (CACHE) {
+        float cv, cpr;
+        if (centry && eval_cache_hit<G::A>(cchunk, ckey, lane, cv, cpr)) { // the position was evaluated before: no tower, no heads
+            if (probe_out) *probe_out = 1;
+            if (lane == 0 && value_out) value_out[OI(pos0)] = cv;
+            dense_prior_tail<G>(nd, cpr, OI(pos0), true, game_id, serial, noise, policy_out, pstride, noise_ready, lane);
+            return;
+        }
+    }
     // ---- per-tile addressing (bytes; X3Geom: tile_slot, swz).  Offsets are biased by the window's top-left tap, so every
     // tap of a row slice is a non-negative immediate on one address register.
     // A tile's slots are the previous tile's + TS bytes (the swizzle repeats every 8 slots), so one address register per
@@ -775,8 +800,14 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
             pooled_out[2] = R1;
         }
     } else {
+    if constexpr (CACHE) { // a miss: its entry again from the board (nothing held in registers through the tower)
+        if (centry) {
+            ckey = G::cache_key(states[OI(pos0)]);
+            centry = eval_cache_entry(cache, ckey);
+        }
+    }
     head_one<G>(nd, R, R0, R1, live ? OI(pos0) : 0, live, game_id, serial, noise, value_out,
-                logits_out, policy_out, pstride, compact, noise_ready);
+                logits_out, policy_out, pstride, compact, noise_ready, centry, ckey);
     }
     NSTAMP(4);
 }

@@ -130,6 +130,10 @@ struct TreeDev {
     // visits (async_game calls) the running persistent launch may still hand out; its workgroups draw them in chunks
     int *visit_pool;
     float noise_alpha;
+    // evaluation cache of the persistent kernel (net.hip.h EvalCache; null: off) and its counters [hits, probes]
+    void *eval_cache;
+    int eval_cache_log2;
+    unsigned long long *eval_cache_ctr;
     unsigned long long *stamps; // diagnostic build only (BB_STAMPS): [apply, fence, select, levels, waves]
 };
 

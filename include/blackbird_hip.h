@@ -159,7 +159,9 @@ typedef struct {
     uint64_t plies;           /* moves played in self-play */
     uint64_t overflow;        /* simulations cut short by pool/path limits (must be 0) */
     uint64_t examples;        /* examples stored */
-    uint64_t evals;           /* leaves evaluated (< sims when known terminal values are reused) */
+    uint64_t evals;           /* network tower runs (< sims when known terminal values are reused; evaluation-cache hits not included) */
+    uint64_t eval_cache_hits;   /* evaluations served by the evaluation cache (persistent Connect4 self-play) */
+    uint64_t eval_cache_probes; /* evaluations that looked it up: hits + the tower runs among them */
 } bb_counters;
 
 /* bb_create fails with BB_ERR_CAPACITY (before allocating anything) when the pools of cfg->n_slots games -- sized for the
