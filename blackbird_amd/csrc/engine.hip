@@ -214,7 +214,7 @@ struct bb_engine {
     int vround[2] = {0, 0};
     // kernel-tuning knobs, read from the environment ONCE in bb_create (never on the step path); not part of the API
     struct {
-        int launch_steps = 64, queue_limit_s = 30, queue_netw = 0, queue_waves = 12;
+        int launch_steps = 64, queue_limit_s = 30;
         bool level_budget_set = false;
     } tune;
     size_t eval_cache_bytes = 0; // evaluation cache of the persistent kernel (dev.eval_cache), zeroed with every weight load
@@ -457,8 +457,6 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
     }
     e->tune.launch_steps = env_int("BB_LAUNCH_STEPS", 64);
     e->tune.queue_limit_s = env_int("BB_QUEUE_LIMIT_S", 30);
-    e->tune.queue_netw = env_int("BB_QUEUE_NETW", 0);
-    e->tune.queue_waves = env_int("BB_QUEUE_WAVES", 12);
     if (cfg->launch < 0 || cfg->launch > BB_LAUNCH_ROUNDS || cfg->net_form < 0 || cfg->net_form > BB_NET_FORM_SPLIT) {
         delete e;
         return fail(BB_ERR_ARG, "bad bb_config.launch / net_form");
@@ -1448,30 +1446,12 @@ static int selfplay_rounds_async(bb_engine *e, int rounds) {
             const int own = rounds - (rounds + 7) / 8;
             k_set_i32<<<1, 1, 0, e->stream>>>(d.visit_pool, d.n_slots * (rounds - own));
             const int lim = e->tune.queue_limit_s;
-            const int netw = e->tune.queue_netw ? e->tune.queue_netw : 8; // network waves of the 12 (tuning)
-            if (e->x3.w0) { // bf16-pipe network: 8 waves of 256 VGPRs -- Connect4 5 network + 3 tree waves, TicTacToe 4 + 4
-                if constexpr (G::S <= 8) {
-                    const int waves = e->tune.queue_waves;
-                    const int nw = e->tune.queue_netw ? netw : (waves == 12 ? 8 : 5);
-#define QX3(NW, WV) k_selfplay_queue<G, NW, true, WV><<<nb, WV * 64, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own)
-                    if (waves == 12) { // 8 network + 4 tree waves of 168 VGPRs (default); BB_QUEUE_WAVES=8: 5 + 3 (6 + 2) waves of 256
-                        if (nw == 6) QX3(6, 12);
-                        else if (nw == 7) QX3(7, 12);
-                        else if (nw == 9) QX3(9, 12);
-                        else if (nw == 10) QX3(10, 12);
-                        else QX3(8, 12);
-                    } else {
-                        if (nw == 4) QX3(4, 8);
-                        else if (nw == 6) QX3(6, 8);
-                        else QX3(5, 8);
-                    }
-#undef QX3
-                } else {
-                    k_selfplay_queue<G, 4, true, 8><<<nb, 512, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
-                }
-            } else if (netw == 7) k_selfplay_queue<G, 7><<<nb, 768, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
-            else if (netw == 6) k_selfplay_queue<G, 6><<<nb, 768, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
-            else k_selfplay_queue<G, 8><<<nb, 768, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
+            if (e->x3.w0) { // bf16-pipe network: Connect4 8 network + 4 tree waves (168 VGPRs), TicTacToe 4 + 4 waves
+                if constexpr (G::S <= 8) k_selfplay_queue<G, 8, true, 12><<<nb, 768, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
+                else k_selfplay_queue<G, 4, true, 8><<<nb, 512, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
+            } else { // float32-MFMA network: 8 network + 4 tree waves
+                k_selfplay_queue<G, 8><<<nb, 768, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
+            }
             HIPCHK(hipGetLastError());
             if (timed) {
                 HIPCHK(hipEventRecord(e->ev_pool[e->ev_used + 1], e->stream));

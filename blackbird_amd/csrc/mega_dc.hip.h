@@ -63,7 +63,7 @@ __device__ __forceinline__ void dc_fused_net_x3(const NetDev &nd_, const NetX3 &
     slot = as_lds(slot);
     nl = as_lds(nl);
     hl = as_lds(hl);
-    net_body_x3<DragonChess, false, false, true>(nd, x3, 1, 0, slot, (unsigned char *)nl, (const DCState *)d.leaf_state, nullptr, d.leaf_game_id,
+    net_body_x3<DragonChess, false, true>(nd, x3, 1, 0, slot, (unsigned char *)nl, (const DCState *)d.leaf_state, nullptr, d.leaf_game_id,
                                     d.leaf_serial, 0, nullptr, nullptr, nullptr, DragonChess::A, true, &hl->h);
     __threadfence_block();
 }

@@ -25,9 +25,6 @@
 #include "rng.hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#ifndef BB_FUSED_WMODE
-#define BB_FUSED_WMODE 1 // k_net_fused16: weights stream from L2 (net_body WMODE)
-#endif
 
 // Lanes of a wave hand data to each other through LDS (a layer's output pixels are the next layer's neighbours).  The
 // hardware runs a wave's LDS operations in order, but the COMPILER orders memory operations per lane: a store to
@@ -254,8 +251,7 @@ __device__ __forceinline__ bool eval_cache_hit(u32x4 ch, uint64_t key, int lane,
 // runs the same instructions on the same numbers as the evaluation it replaces.
 template <class G>
 __device__ __forceinline__ void dense_prior_tail(const NetDev &nd, float pr, int pos, bool live, const uint32_t *game_id,
-                                                 const int32_t *serial, int noise, float *policy_out, int pstride,
-                                                 const float *noise_ready, int lane) {
+                                                 const int32_t *serial, int noise, float *policy_out, int pstride, int lane) {
     constexpr int A = G::A;
     static_assert(2 * A <= 64, "the prior-noise draws use two lanes per action");
     const bool act = lane < A;
@@ -268,7 +264,6 @@ __device__ __forceinline__ void dense_prior_tail(const NetDev &nd, float pr, int
         const uint32_t gid = game_id ? game_id[live ? pos : 0] : (uint32_t)noise;
         const uint32_t ser = serial ? (uint32_t)serial[live ? pos : 0] : (uint32_t)pos;
         float r = ND_DBG(8) ? nd.alpha : -1.0f;
-        if (noise_ready) r = nd.alpha; // (the draws were made by the caller: persistent kernel, tree waves; see below)
         for (uint32_t k = 0; k < 32 && __any(drawing && r < 0.0f); k += 2) {
             float mine = (drawing && r < 0.0f) ? bb_beta_pair(nd.seed, gid, ser, (uint32_t)q, ia, ib, k + sub) : -1.0f;
             float other = dpp_f32(mine, 0); // the pair's other lane (quad permute, no LDS round trip)
@@ -276,17 +271,7 @@ __device__ __forceinline__ void dense_prior_tail(const NetDev &nd, float pr, int
             if (r < 0.0f) r = first >= 0.0f ? first : second;
         }
         r = r >= 0.0f ? r : nd.alpha;
-        float nz = __shfl(r, 2 * (act ? lane : 0), 64); // action a's draw sits on lane 2a
-        if (noise_ready) { // the same draws (bb_beta_noise: same trials in the same order), made by the tree wave that posted the leaf
-            // -- after it posted it (mega2.hip.h): wait for its flag in the spare slot of the game's noise row, take the draws,
-            // clear the flag for the game's next leaf.  (Bounded: a launch that is being aborted must still drain.)
-            float *nr = const_cast<float *>(noise_ready);
-            for (int spin = 0; spin < (1 << 16) && __hip_atomic_load(nr + G::S - 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0.f; spin++)
-                __builtin_amdgcn_s_sleep(1);
-            nz = act ? nr[lane] : 0.f;
-            wave_lds_handover();
-            if (lane == 0) __hip_atomic_store(nr + G::S - 1, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+        const float nz = __shfl(r, 2 * (act ? lane : 0), 64); // action a's draw sits on lane 2a
         pr = (1.0f - nd.eps) * pr + nd.eps * (act ? nz : 0.f);
         const float t2 = ROW0 ? row0_sum_f32(pr) : wave_sum_f32(pr);
         pr = pr * __builtin_amdgcn_rcpf(t2);
@@ -301,7 +286,7 @@ template <class G>
 __device__ __forceinline__ void head_one(const NetDev &nd, float R, float R0, float R1, int pos, bool live,
                                          const uint32_t *game_id, const int32_t *serial, int noise, float *value_out,
                                          float *logits_out, float *policy_out, int pstride, WideHead *compact,
-                                         const float *noise_ready = nullptr, u32x4 *cache_entry = nullptr, uint64_t cache_key = 0) {
+                                         u32x4 *cache_entry = nullptr, uint64_t cache_key = 0) {
     constexpr int A = G::A, HW = G::H * G::W;
     int lane_ = threadIdx.x & 63;
     asm volatile("" : "+v"(lane_)); // (keeps the addresses below inside a persistent caller's loop: see net_body_x3)
@@ -310,7 +295,6 @@ __device__ __forceinline__ void head_one(const NetDev &nd, float R, float R0, fl
     const int D = nd.D; // <= 64 (bb_load_weights)
     const float *d1k = hp + nd.off_d1k, *d1b = hp + nd.off_d1b, *d2k = hp + nd.off_d2k, *d2b = hp + nd.off_d2b;
     const float *pdk = hp + nd.off_pdk, *pdb = hp + nd.off_pdb;
-    auto lane_f = [](float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); };
     // value head: dense_1 on the pooled activation (unit d on lane d), ReLU, dense_2 = the products folded by the fixed pairwise
     // tree of pooled_sum (TensorFlow leaves the order of a matmul's sum open; the oracle restates this one), + bias, tanh.
     // (Until round 3 an fma chain in unit order: D dependent steps of two v_readlane each on the tail every game waits for.)
@@ -395,69 +379,8 @@ __device__ __forceinline__ void head_one(const NetDev &nd, float R, float R0, fl
         if constexpr (A == 7)
             if (cache_entry) eval_cache_put<A>(cache_entry, cache_key, value, pr, lane); // (fire and forget)
         if (live && act && logits_out) logits_out[(size_t)pos * A + lane] = l;
-        dense_prior_tail<G>(nd, pr, pos, live, game_id, serial, noise, policy_out, pstride, noise_ready, lane);
+        dense_prior_tail<G>(nd, pr, pos, live, game_id, serial, noise, policy_out, pstride, lane);
     }
-}
-
-// head_one's value / policy tails for a dense game, computed by the S lanes of a tree wave that own the game (persistent
-// kernel: the network wave stops at the pooled activations R, R0, R1 and the tree wave that picks the result up finishes it --
-// the network waves are the busy side).  Same operations in the same order as head_one, so the same bits: every lane forms
-// the value chain redundantly (no cross-lane traffic), action a sits on lane a of the game's lane group, the ordered softmax
-// sums gather their terms with ds_bpermute (`base` = first lane of the group).  `nz` = this lane's prior-noise draw (made
-// ahead by the same tree wave).  Returns the value; *prior_out = this lane's prior (lanes >= A: 0).
-template <class G>
-__device__ __forceinline__ float head_tree(const NetDev &nd, const float *hp, float R, float R0, float R1, int lane, int base, bool noise,
-                                           float nz, float *prior_out) {
-    constexpr int A = G::A, HW = G::H * G::W;
-    const int D = nd.D;
-    const float *d1k = hp + nd.off_d1k, *d1b = hp + nd.off_d1b, *d2k = hp + nd.off_d2k, *d2b = hp + nd.off_d2b;
-    const float *pdk = hp + nd.off_pdk, *pdb = hp + nd.off_pdb;
-    // (the orders of head_one: products / terms in slots 0 .. 63 of a vector -- the rest zero -- folded by strides 1, 2, ..., 32,
-    // i.e. the tree of wave_sum_f32; zeros add exactly, so only the occupied part of the tree is walked)
-    auto tree16 = [](float *t) __attribute__((always_inline)) { // 16 slots -> t[0]
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1)
-#pragma unroll
-            for (int i = 0; i < 16; i += 2 * o) t[i] = t[i] + t[i + o];
-        return t[0];
-    };
-    float e = 0.f;
-    { // (four units per round trip: the three parameter rows are 16-byte aligned in the packed head -- engine.hip `push`)
-        float blk[4] = {0.f, 0.f, 0.f, 0.f}; // sums of slots 0-15, 16-31, 32-47, 48-63
-        for (int b16 = 0; b16 < 4 && b16 * 16 < D; b16++) {
-            float t[16];
-#pragma unroll
-            for (int r = 0; r < 16; r++) t[r] = 0.f;
-            for (int dd = b16 * 16; dd < D && dd < b16 * 16 + 16; dd++) {
-                const float sdv = fmaxf(__builtin_fmaf(R, d1k[dd], (float)HW * d1b[dd]), 0.f);
-                t[dd & 15] = sdv * d2k[dd];
-            }
-            blk[b16] = tree16(t);
-        }
-        e = ((blk[0] + blk[1]) + (blk[2] + blk[3])) + d2b[0];
-    }
-    const float value = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(e * 2.88539008177792681472f) + 1.0f);
-    const bool act = lane < A;
-    const int la = act ? lane : 0;
-    const float l = act ? wide_logit<HW>(R0, R1, pdk[la], pdk[A + la], pdb[la]) : -INFINITY;
-    static_assert(A <= 16, "head_tree: the actions of a dense game fit one 16-slot block of the tree");
-    float m = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < A; a++) m = fmaxf(m, __shfl(l, base + a, 64));
-    float pr = act ? wide_expterm(l, m) : 0.f;
-    auto gsum = [&](float v) __attribute__((always_inline)) {
-        float t[16];
-#pragma unroll
-        for (int a = 0; a < 16; a++) t[a] = a < A ? __shfl(v, base + a, 64) : 0.f;
-        return tree16(t);
-    };
-    pr = pr * __builtin_amdgcn_rcpf(gsum(pr));
-    if (noise) {
-        pr = (1.0f - nd.eps) * pr + nd.eps * (act ? nz : 0.f);
-        pr = pr * __builtin_amdgcn_rcpf(gsum(pr));
-    }
-    *prior_out = act ? pr : 0.f;
-    return value;
 }
 
 // The same for PW positions whose per-pixel head activations sit in memory (LDS): rv[PW*HW], rp[PW*HW][2].
@@ -485,24 +408,15 @@ __device__ __forceinline__ void net_head_tail(const NetDev &nd, int n, int pos0,
 // engine slot slot_list[i] (inputs are read from, and outputs written to, that slot's mailbox).
 // WMODE: how the tower's operands reach the MFMAs (see conv_layer below): 0 plain, 1 weights from L2 with next-layer
 // prefetch, 2 weights in LDS with next-tap prefetch.
-// Team: the evaluation may be shared by PARTS waves working in the SAME LDS region (mega_dc.hip.h: two waves of a
-// DragonChess game on two SIMDs): every wave takes NT / PARTS of the 16-pixel tiles of each conv layer, part 0 alone does the
-// prologue (zero fill, input planes) and the heads, and `team.sync()` is called wherever one part's LDS writes are another
-// part's reads: after the prologue and after every conv layer.  The default team is the wave on its own.
-struct SoloTeam {
-    static constexpr int PARTS = 1, PART = 0;
-    __device__ __forceinline__ void sync() const {}
-};
-template <class G, int PW, int WMODE = 0, class Team = SoloTeam>
+template <class G, int PW, int WMODE = 0>
 __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, const int *slot_list, float *wlds,
                                          const typename G::State *states, const int8_t *planes,
                                          const uint32_t *game_id, const int32_t *serial, int noise, float *value_out,
                                          float *logits_out, float *policy_out, int pstride, bool zero_lds = true,
-                                         WideHead *compact = nullptr, Team team = Team()) {
+                                         WideHead *compact = nullptr) {
     using NG = NetGeom<G, PW>;
-    static_assert(NG::NT % Team::PARTS == 0, "whole tiles per team member");
-    constexpr int W = NG::W, CIN = NG::CIN, A = NG::A, HW = NG::HW, SLOTS = NG::SLOTS, CP = NG::CP,
-                  NT = NG::NT / Team::PARTS, T0 = Team::PART * NT, STEPS0 = NG::STEPS0, ACT = NG::ACT, PLANE = NG::PLANE;
+    constexpr int W = NG::W, CIN = NG::CIN, HW = NG::HW, SLOTS = NG::SLOTS, CP = NG::CP, NT = NG::NT,
+                  STEPS0 = NG::STEPS0, ACT = NG::ACT, PLANE = NG::PLANE;
     const int lane = threadIdx.x & 63;
     const int j = lane >> 4, nn = lane & 15;
     float *actA = wlds;
@@ -523,7 +437,7 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
     const f32x4 bias0 = *(const f32x4 *)(nd.epi + 4 * j), scale0 = *(const f32x4 *)(nd.epi + 16 + 4 * j),
                 shift0 = *(const f32x4 *)(nd.epi + 32 + 4 * j);
     // ---- zero this wave's LDS (halo pixels must read as 0 forever) --------------------------
-    if (zero_lds && Team::PART == 0) { // a persistent caller zeroes once: halos are never written, interiors are always rewritten
+    if (zero_lds) { // a persistent caller zeroes once: halos are never written, interiors are always rewritten
         f32x4 z = {0.f, 0.f, 0.f, 0.f};
         f32x4 *p = (f32x4 *)actA;
         for (int i = lane; i < NG::WAVE_FLOATS / 4; i += 64) p[i] = z;
@@ -531,10 +445,10 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
     // the PW boards go through LDS so that every lane can decode any cell of any position
     typename G::State *sst = (typename G::State *)(inp + PW * SLOTS * CP);
     wave_lds_handover(); // (the zero fill above and the data written below touch the same words from different lanes)
-    if (!planes && lane < PW && Team::PART == 0) sst[lane] = my_state;
+    if (!planes && lane < PW) sst[lane] = my_state;
     wave_lds_handover();
     // ---- input planes -> inp[pos][slot][CP] ---------------------------------------------------
-    for (int q = lane; Team::PART == 0 && q < PW * HW; q += 64) {
+    for (int q = lane; q < PW * HW; q += 64) {
         int pp = q / HW, cell = q % HW, y = cell / W, x = cell % W;
         int pos = pos0 + pp;
         if (pos >= n) continue;
@@ -571,7 +485,7 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
     int ioffb[NT];  // float offset of (pos, slot - TAP0) inside inp
 #pragma unroll
     for (int t = 0; t < NT; t++) {
-        int q = (T0 + t) * 16 + nn;
+        int q = t * 16 + nn;
         int qq = q < PW * HW ? q : PW * HW - 1;
         int pp = qq / HW, cell = qq % HW, y = cell / W, x = cell % W;
         int slot = (y + 1) * (W + 1) + (x + 1);
@@ -579,7 +493,6 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
         ioffb[t] = (pp * SLOTS + slot - TAP0) * CP;
     }
     wave_lds_handover(); // input planes (and the staged boards) written above are read by other lanes below
-    team.sync();
     NSTAMP(0);
     f32x4 acc[NT];
     // ---- first conv: K = 9*CIN in natural (tap, c) order, 4 k per MFMA ---------------------------
@@ -636,7 +549,6 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
         }
     }
     wave_lds_handover();
-    team.sync();
     NSTAMP(1);
     // ---- residual tower: 2R convs, K order (tap, r, j) with channel c = 4j + r ---------------------
     // One layer = 9 taps x 4 k-steps x NT tiles of MFMAs + the epilogue; written once (conv_layer) and instantiated for
@@ -779,13 +691,11 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
             *(f32x4 *)(out + aoffb[t] + CTR) = y;
         }
         wave_lds_handover(); // this layer's pixels are the next layer's (and the heads') operands, across lanes
-        team.sync();
     };
     for (int blk = 0; blk < R_eff; blk++) {
         conv_layer(2 * blk, actA, actB, std::false_type{});
         conv_layer(2 * blk + 1, actB, actA, std::true_type{});
     }
-    if constexpr (Team::PART != 0) return; // the heads are part 0's
     if (ND_DBG(1)) {
         if (value_out && lane == 0) value_out[OI(pos0)] = acc[0][0];
         return;
@@ -857,7 +767,7 @@ k_net_fused16(NetDev nd, int n, const typename G::State *states, const int8_t *p
     const int wave = threadIdx.x >> 6;
     const int pos0 = (blockIdx.x * 4 + wave) * PW;
     if (pos0 >= n) return; // whole wave idle (no block-level sync anywhere)
-    net_body<G, PW, BB_FUSED_WMODE>(nd, n, pos0, nullptr, lds + wave * NG::WAVE_FLOATS, states, planes, game_id, serial, noise, value_out,
+    net_body<G, PW, 1>(nd, n, pos0, nullptr, lds + wave * NG::WAVE_FLOATS, states, planes, game_id, serial, noise, value_out,
                           logits_out, policy_out, pstride);
 }
 

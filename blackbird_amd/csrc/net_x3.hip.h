@@ -39,7 +39,7 @@
 //   channels 8 (g & 1) .. +7 of the slice's tap g >> 1), then tap 8 -- K = 16 per plane pair -- as THREE K = 32 products by
 //   concatenating planes along K:  [w1|w1].[x1;x2] + [w2|w2].[x1;x2] + [w1|w3].[x3;x1]  (lane groups 0,1 hold the first
 //   plane of each pair, groups 2,3 the second): 27 MFMAs per tile and layer instead of 30 with zero-extended K = 16 operands.
-//   Products are accumulated in ONE order in every variant (default / LEAN / PP): per slice w3 x1, w2 x1, w1 x1, w2 x2, w1 x2,
+//   Products are accumulated in ONE order in both forms (single buffer / PP): per slice w3 x1, w2 x1, w1 x1, w2 x2, w1 x2,
 //   w1 x3, then the tap-8 products in the order above reversed -- so all launch structures give the same bits.
 //   Weights: pre-split and pre-swizzled on the host into the A-operand lane order (engine.hip: pack_x3); planes 1 and 2 may
 //   live in the caller's LDS, plane 3 always streams from L2 a layer ahead.
@@ -162,15 +162,10 @@ __device__ __forceinline__ void x3_split4(const f32x4 y, u32x2 &p1, u32x2 &p2, u
 }
 
 // WLDS: the packed weights (x3.w0 / x3.wt, nd.epi, nd.head) are in LDS (persistent kernel) -- else global (L2-resident).
-// LEAN: two network waves share each SIMD (12-wave persistent kernel, 168 VGPRs): the partner's MFMAs cover this wave's LDS
-// round trips, so operands are read tile by tile right where they are used instead of a phase ahead -- a third of the
-// operand registers.
 // PP (with !WLDS; the caller provides X3Geom::WAVE_BYTES_PP): two activation buffers.  A lone wave per SIMD cannot hide its
 // epilogue (float32 -> three planes, ~35 vector instructions and three writes per tile) behind its own MFMAs while it
 // rewrites the buffer it reads; with a second buffer the layer runs tile by tile and tile t - 1's epilogue issues while
 // tile t's 27 MFMAs execute (a bf16 MFMA leaves 8 of its 16 cycles to the wave's vector instructions).
-// HEADS_OUT (persistent kernel): the wave stops after the three pooled head activations (R, R0, R1) and hands them to the
-// caller's `pooled_out` -- the value / policy tails (head_one) then run on the tree wave that picks the result up.
 // 16 bytes of packed weights from device memory through the global address space.  In a kernel that reaches its weights
 // through a descriptor copied to LDS (mega_dc.hip.h) the pointers are generic, the loads flat: a flat load counts on lgkmcnt
 // too and may return out of order with LDS reads, so with one in flight every wait for an LDS operand becomes a wait for
@@ -188,13 +183,12 @@ __device__ __forceinline__ bf16x8 x3_ldg(const unsigned char *p) {
 // tested after it -- on a miss the probe's latency hides under the prologue.  A hit skips the tower and the heads and runs only
 // dense_prior_tail on the cached value / priors; a miss stores them in head_one.  *probe_out: -1 no probe (cache off, or a
 // board without a key), 0 miss, 1 hit.
-template <class G, bool WLDS, bool LEAN = false, bool PP = false, bool HEADS_OUT = false, bool CACHE = false>
+template <class G, bool WLDS, bool PP = false, bool CACHE = false>
 __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, int n, int pos0, const int *slot_list,
                                             unsigned char *wl, const typename G::State *states, const int8_t *planes,
                                             const uint32_t *game_id, const int32_t *serial, int noise, float *value_out,
                                             float *logits_out, float *policy_out, int pstride, bool zero_lds,
-                                            WideHead *compact = nullptr, const float *noise_ready = nullptr,
-                                            float *pooled_out = nullptr, EvalCache cache = {nullptr, 0}, int *probe_out = nullptr) {
+                                            WideHead *compact = nullptr, EvalCache cache = {nullptr, 0}, int *probe_out = nullptr) {
     using XG = X3Geom<G>;
     constexpr int W = XG::W, CIN = XG::CIN, HW = XG::HW, NT = XG::NT, SB = XG::SLOT_B, RS = XG::RS;
     constexpr bool WIDE_IN = XG::WIDE_IN;
@@ -221,7 +215,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
     typename G::State my_state;
     if constexpr (PP) sst_in = as_lds(&states[OI(live ? pos0 : 0)]);
     else my_state = planes ? G::initial() : states[OI(live ? pos0 : 0)];
-    static_assert(!CACHE || (G::CACHE_KEY && !PP && !HEADS_OUT), "the evaluation cache: Connect4, value and priors formed here");
+    static_assert(!CACHE || (G::CACHE_KEY && !PP), "the evaluation cache: Connect4, value and priors formed here");
     uint64_t ckey = 0;
     u32x4 *centry = nullptr;
     u32x4 cchunk = {0u, 0u, 0u, 0u};
@@ -329,7 +323,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         if (centry && eval_cache_hit<G::A>(cchunk, ckey, lane, cv, cpr)) { // the position was evaluated before: no tower, no heads
             if (probe_out) *probe_out = 1;
             if (lane == 0 && value_out) value_out[OI(pos0)] = cv;
-            dense_prior_tail<G>(nd, cpr, OI(pos0), true, game_id, serial, noise, policy_out, pstride, noise_ready, lane);
+            dense_prior_tail<G>(nd, cpr, OI(pos0), true, game_id, serial, noise, policy_out, pstride, lane);
             return;
         }
     }
@@ -451,40 +445,6 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         // slice's weights and its first plane arrive -- a third of the registers of a whole-slice double buffer (which
         // measured slower: spills).
         auto xoff = [&](int s, int t) __attribute__((always_inline)) { return s < 3 ? aA(t) + s * RS * SB : aB(t); };
-        if constexpr (LEAN) {
-            static_assert(!LEAN || WLDS, "the in-place schedule reads its weights from LDS");
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                const bf16x8 wa = *(const bf16x8 *)(wp + ((s * 2 + 0) * 64 + lane) * 16), wb = *(const bf16x8 *)(wp + ((s * 2 + 1) * 64 + lane) * 16);
-#pragma unroll
-                for (int t = 0; t < NT; t++) {
-                    const bf16x8 xa = *(const bf16x8 *)(X + xoff(s, t)), xb = *(const bf16x8 *)(X + xoff(s, t) + 32),
-                                 xc_ = *(const bf16x8 *)(X + xoff(s, t) + 64);
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3c[s], xa, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb, xa, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xa, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb, xb, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xc_, acc[t], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            const bf16x8 a1 = *(const bf16x8 *)(wp + 4 * 2 * 64 * 16 + w8lane), a2 = *(const bf16x8 *)(wp + 4 * 2 * 64 * 16 + 512 + w8lane);
-            const bf16x8 a3 = w3c[4];
-            bf16x8 y1[NT], y3[NT];
-#pragma unroll
-            for (int t = 0; t < NT; t++) {
-                y1[t] = *(const bf16x8 *)(X + aC1(t));
-                y3[t] = *(const bf16x8 *)(X + aC3(t));
-            }
-            if (l + 1 < L) request_layer(l + 1);
-#pragma unroll
-            for (int t = 0; t < NT; t++) {
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, y3[t], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, y1[t], acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, y1[t], acc[t], 0, 0, 0);
-            }
-        } else {
         bf16x8 wc[2], wn[2], x0[NT], x1[NT], x2[NT];
 #pragma unroll
         for (int q = 0; q < 2; q++) {
@@ -547,7 +507,6 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         for (int q = 1; q >= 0; q--)
 #pragma unroll
             for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wc[q], x1[t], acc[t], 0, 0, 0);
-        }
         // (the batch-norm constants are read here, not at the top of the layer: 8 registers less through the slices)
         const f32x4 scale = *(const f32x4 *)(ep + 16 + 4 * g), shift = *(const f32x4 *)(ep + 32 + 4 * g);
         wave_lds_handover(); // every lane's reads of X are done (their results feed the MFMAs above) before X is rewritten
@@ -793,13 +752,6 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         R1 = lane_f32(xs, 32);
     }
     NSTAMP(3);
-    if constexpr (HEADS_OUT) {
-        if (lane == 0) {
-            pooled_out[0] = R;
-            pooled_out[1] = R0;
-            pooled_out[2] = R1;
-        }
-    } else {
     if constexpr (CACHE) { // a miss: its entry again from the board (nothing held in registers through the tower)
         if (centry) {
             ckey = G::cache_key(states[OI(pos0)]);
@@ -807,8 +759,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         }
     }
     head_one<G>(nd, R, R0, R1, live ? OI(pos0) : 0, live, game_id, serial, noise, value_out,
-                logits_out, policy_out, pstride, compact, noise_ready, centry, ckey);
-    }
+                logits_out, policy_out, pstride, compact, centry, ckey);
     NSTAMP(4);
 }
 

@@ -19,17 +19,6 @@
 #include "games.hip.h"
 #include "rng.hip.h"
 
-// Measured on MI355X (4096 games, 800 sims): touching all 7 children's rows per level makes the
-// descent bandwidth-bound (46 MB/step) and is not faster than the plain dependent row load.
-#ifndef BB_PREFETCH_CHILDREN
-#ifndef BB_PREFETCH_BEST
-#define BB_PREFETCH_BEST 0
-#endif
-#define BB_PREFETCH_CHILDREN 0
-#endif
-#ifndef BB_MOVE_BODY_ATTR
-#define BB_MOVE_BODY_ATTR __forceinline__ // (an out-of-line callee takes TreeDev by reference: the struct then lives in scratch and every field use is a scratch load)
-#endif
 #define NODE_EXPANDED 1
 #define NODE_TERMINAL 2
 #define NODE_CACHED 4 // terminal node whose evaluator value is stored in pad0 (Model.SampleValue's lru_cache)
@@ -481,7 +470,6 @@ __device__ void phase_select(const TreeDev &d, int g, int lane) {
     typename G::State st;
     int flags = 0;
     bool have = false; // st/flags of `cur` already in registers (node created this simulation)
-    int pf0 = 0, pf1 = 0, spec = 0; // speculative touches of the children's rows (see below)
 #ifdef BB_STAMPS
     long long acc_load = 0, acc_iter = 0;
 #endif
@@ -501,7 +489,6 @@ __device__ void phase_select(const TreeDev &d, int g, int lane) {
         float Wi = rollout ? node->W[lane] : 0.f;
         double cPi = node->cP[lane];
         int ci = node->child[lane];
-        spec ^= pf0 ^ pf1; // previous level's touches are older than the loads above: no extra stall
         asm volatile("" ::"v"(flags_l), "v"(mask), "v"(sq), "v"(Ni), "v"(Qi), "v"(cPi), "v"(ci)); // keep them ahead of the branches
 #ifdef BB_STAMPS
         acc_load += clock64() - ts0;
@@ -524,15 +511,6 @@ __device__ void phase_select(const TreeDev &d, int g, int lane) {
             ci = CHILD_NONE;
         }
         if (mask == 0) break; // np.sum(LegalActions) == 0
-        // While the PUCT arithmetic runs, lane i pulls its own child's row towards this CU, so the
-        // next level's (dependent) row load hits cache instead of paying an HBM round trip.
-        pf0 = 0;
-        pf1 = 0;
-        if (BB_PREFETCH_CHILDREN && lane < A && ci >= 0 && !(ci & CHILD_TERM_BIT)) {
-            const int *pc = (const int *)(pool + ci);
-            pf0 = pc[0];
-            pf1 = pc[32];
-        }
         double u = puct_score(child_q(d, Qi, Wi, Ni), cPi, sq, Ni, lane < A && ((mask >> lane) & 1u));
         int child = ci;
         int a = grp_argmax<S>(u, lane, child);
@@ -559,8 +537,6 @@ __device__ void phase_select(const TreeDev &d, int g, int lane) {
         atomicAdd(&d.stamps[7], 1ull);
     }
 #endif
-    spec ^= pf0 ^ pf1;
-    if (spec == 0x5bd1e995 && depth == -7) d.ctr[(size_t)g * 8 + 6] += 1; // never true: keeps the touches alive
     if (lane == 0) {
         ((typename G::State *)d.leaf_state)[g] = st;
         d.leaf_game_id[g] = d.first_game_id + (uint32_t)d.game_lid[g];
@@ -905,10 +881,10 @@ __device__ __forceinline__ void write_example(const TreeDev &d, int lid, int ply
     ((uint32_t *)(p + sizeof(ExampleHdr) + sizeof(typename G::State)))[lane] = (uint32_t)Ni;
 }
 
-// apply the last pending leaf, then FindMove's tail + the body of GenerateTrainingSamples' while loop
 // FindMove's tail + the body of GenerateTrainingSamples' while loop for one slot (all lanes of the group call)
+// (inlined: an out-of-line callee takes TreeDev by reference, the struct then lives in scratch and every field use is a scratch load)
 template <class G>
-__device__ BB_MOVE_BODY_ATTR void selfplay_move_body(const TreeDev &d, int g, int lane) {
+__device__ __forceinline__ void selfplay_move_body(const TreeDev &d, int g, int lane) {
     using Node = DenseNode<G>;
     constexpr int S = G::S;
     int lid = d.game_lid[g];
@@ -1012,9 +988,6 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
     constexpr int S = G::S, A = G::A;
     if (d.game_lid[g] < 0) return false;
     Node *pool = (Node *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
-#ifdef BB_STAMPS_DEEP
-    long long sa0 = clock64(), s_apply = 0, s_level = 0, s_backup = 0, s_move = 0;
-#endif
 #ifdef BB_STAMPS_LIGHT
     int lt_in = (int)clock64(), lt_loop = 0, ln_levels = 0, lt_create = 0, lt_puct = 0;
 #endif
@@ -1024,28 +997,16 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
         if (lane == 0) d.sims_left[g] -= 1;
         __threadfence_block();
     }
-#ifdef BB_STAMPS_DEEP
-    s_apply = clock64() - sa0;
-#endif
     int budget = d.level_budget;
     uint32_t *path = d.path + (size_t)g * G::MAXPATH;
     int sims_done = 0, depth_sum = 0, term_hits = 0;
     bool posted = false;
-#ifdef BB_STAMPS_DEEP
-    long long st_load = 0, st_levels = 0, st_t0 = clock64();
-#endif
     for (;;) {
-#ifdef BB_STAMPS_DEEP
-        long long sm0 = clock64();
-#endif
         if (d.sims_left[g] <= 0) { // MCTS.FindMove's tail, GenerateTrainingSamples' loop body
             selfplay_move_body<G>(d, g, lane);
             __threadfence_block();
             if (d.game_lid[g] < 0) break;
         }
-#ifdef BB_STAMPS_DEEP
-        s_move += clock64() - sm0;
-#endif
         int cur = d.resume_cur[g], depth = 0;
         if (cur >= 0) depth = d.resume_depth[g];
         else cur = d.root[g];
@@ -1056,7 +1017,6 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
         // every exit of the loop below pays a three-instruction merge for each of them on every iteration
         enum { F_PARKED = 2, F_LEAF = 4, F_TERM = 8, F_EXPAND = 16, F_OVERFLOW = 32 };
         int fl = 0;
-        int pf_touch = 0; // speculative touch of the likeliest child's row (BB_PREFETCH_BEST)
 #ifdef BB_STAMPS_LIGHT
         int lt_e = (int)clock64();
 #endif
@@ -1065,15 +1025,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
             budget--;
 #ifdef BB_STAMPS_LIGHT
             ln_levels++;
-#ifndef BB_STAMPS_LIGHT2
             int lt_a = (int)clock64();
-#endif
-#endif
-#ifdef BB_STAMPS_DEEP
-            st_levels++;
-#ifdef BB_STAMPS_PERLEVEL
-            long long ts0 = clock64();
-#endif
 #endif
             Node *node = pool + cur;
             typename G::State st_l = node->st;
@@ -1091,11 +1043,8 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
                 Wi = node->W[lane];
                 all_l = node->all;
             }
-            asm volatile("" ::"v"(flags_l), "v"(mask), "v"(sq), "v"(Ni), "v"(Qi), "v"(cPi), "v"(ci), "v"(pf_touch)); // (the previous level's touch is older than these loads)
-#if defined(BB_STAMPS_DEEP) && defined(BB_STAMPS_PERLEVEL)
-            st_load += clock64() - ts0;
-#endif
-#if defined(BB_STAMPS_LIGHT) && !defined(BB_STAMPS_LIGHT2)
+            asm volatile("" ::"v"(flags_l), "v"(mask), "v"(sq), "v"(Ni), "v"(Qi), "v"(cPi), "v"(ci)); // one wait for the whole row
+#ifdef BB_STAMPS_LIGHT
             int lt_b = (int)clock64(); // the row has arrived (the asm above made the loads' results live)
             lt_create += lt_b - lt_a;
 #endif
@@ -1106,27 +1055,15 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
                 if (flags & NODE_TERMINAL) {
                     fl |= F_TERM;
                     if (flags & NODE_CACHED) { // value already known: finish this simulation here
-#ifdef BB_STAMPS_DEEP
-                        long long sb0 = clock64();
-#endif
                         float v01 = (float)cached;
-#ifdef BB_STAMPS_LIGHT2
-                        int lt_k = (int)clock64();
-#endif
                         __threadfence_block(); // path stores of this descent
                         if (REC) backup_path_rec<G>(d, g, lane, pool, depth, v01, gs_prev(st));
                         else backup_path<G>(d, g, lane, pool, depth, v01, gs_prev(st));
                         if (lane == 0) d.sims_left[g] -= 1;
                         __threadfence_block();
-#ifdef BB_STAMPS_LIGHT2
-                        lt_puct += (int)clock64() - lt_k;
-#endif
                         sims_done++;
                         depth_sum += depth;
                         term_hits++;
-#ifdef BB_STAMPS_DEEP
-                        s_backup += clock64() - sb0;
-#endif
                         fl &= ~F_LEAF; // nothing to post; start the next simulation
                     }
                 } else {
@@ -1138,22 +1075,10 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
             // only if it is not terminal, and a non-terminal board has an empty cell, so the case cannot arise; likewise a
             // path cannot outgrow MAXPATH = H*W + 2 edges, one move each.  Two loop exits less in the hottest loop.)
             static_assert(G::MAXPATH >= G::H * G::W + 2, "a descent places at most H*W stones");
-#if BB_PREFETCH_BEST
-            { // the most visited child is the likeliest next step: pull its row towards this CU while the PUCT arithmetic runs
-                int key = (ci >= 0 && lane < A) ? ((Ni << 4) | lane) : -1;
-                int best = key;
-                best = max(best, dpp_step_i<0>(best));
-                best = max(best, dpp_step_i<1>(best));
-                best = max(best, dpp_step_i<2>(best));
-                if (S == 16) best = max(best, dpp_step_i<3>(best));
-                int bchild = __shfl(ci, best & 15, S);
-                if (best >= 0) pf_touch = ((const int *)(pool + (bchild & ~CHILD_TERM_BIT)))[lane * 8];
-            }
-#endif
             // (float32 evaluators only reach this kernel: a child's WinRate is its float32 Q, child_q)
             int child = ci;
             int a = grp_argmax_puct<S>(Qi, cPi, sq, Ni, lane < A && ((mask >> lane) & 1u), child);
-#if defined(BB_STAMPS_LIGHT) && !defined(BB_STAMPS_LIGHT2)
+#ifdef BB_STAMPS_LIGHT
             asm volatile("" ::"v"(a), "v"(child));
             lt_puct += (int)clock64() - lt_b;
 #endif
@@ -1168,14 +1093,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
             if (child == CHILD_NONE) {
                 typename G::State st2;
                 bool terminal;
-#ifdef BB_STAMPS_LIGHT2
-                int lt_c = (int)clock64();
-#endif
                 child = create_child<G>(d, g, pool, node, st, a, lane, nn, st2, terminal, &flags);
-#ifdef BB_STAMPS_LIGHT2
-                asm volatile("" ::"v"(child));
-                lt_create += (int)clock64() - lt_c;
-#endif
                 if (child == CHILD_NONE) { fl |= F_OVERFLOW | F_LEAF; break; }
                 // the node just created is the leaf of this descent (never expanded, never cached): finish here instead of
                 // going round the loop once more to read back the row that was written a moment ago
@@ -1219,17 +1137,6 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
         posted = true;
         break;
     }
-#ifdef BB_STAMPS_DEEP
-    if (lane == 0 && d.stamps) {
-        atomicAdd(&d.stamps[6], (unsigned long long)st_load);
-        atomicAdd(&d.stamps[7], (unsigned long long)st_levels);
-        atomicAdd(&d.stamps[8], (unsigned long long)s_apply);
-        atomicAdd(&d.stamps[9], (unsigned long long)s_backup);
-        atomicAdd(&d.stamps[10], (unsigned long long)s_move);
-        atomicAdd(&d.stamps[11], (unsigned long long)(clock64() - st_t0));
-        atomicAdd(&d.stamps[12], 1ull);
-    }
-#endif
 #ifdef BB_STAMPS_LIGHT
     g_light_loop = lt_loop;
     g_light_load = lt_create;

@@ -193,7 +193,7 @@ int bb_timing_net(bb_engine *e, int iters, int noise, int ablate, double *ms_per
  * simulation), 1 asynchronous rounds, 3 persistent per-CU kernel with a work queue between its tree and network
  * waves (default for networks that fit LDS), 5 DragonChess with the 16-filter network: one wave keeps its game for a
  * whole launch -- tree step, network and move in the same wave.  (2 and 4 were launch structures that measured slower
- * and were retired: tools/experimental/.) */
+ * and were retired.) */
 int bb_selfplay_mode(bb_engine *e);
 /* Which arithmetic the loaded network's conv tower runs in (after bb_load_weights): 0 float32 MFMA, fused 16-filter
  * tower (bit-identical to the k-ordered fmaf chain); 1 float32 MFMA, one launch per conv layer (any multiple of 16
