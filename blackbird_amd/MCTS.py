@@ -5,12 +5,12 @@ bb_move_roots / bb_set_roots.  No search arithmetic happens on the host.
 
 Differences a user can observe (documented in DESIGN.md):
   * `Root` is a read-only view of the engine's node rows, not a linked Node graph: `Root.Children[i]` builds the child's view
-    on demand (bb_node_view; as deep as the caller walks) and `Parent` is only set on views reached that way;
+    on demand (bb_node_edges; as deep as the caller walks) and `Parent` is only set on views reached that way;
   * GetPriors/SampleValue are not per-call Python hooks: the evaluator is chosen per class
-    (base/Fixed: priors = ones + random rollouts, MCTS.py:346-383; Model: the network);
-  * DragonChess: ResetRoot re-primes the tree at the position the search started from (statistics are dropped) and Children
-    stay None -- the dense-action games keep the reference's behaviour (bb_reset_roots: the root goes back to its top-most
-    ancestor with every simulation's statistics, MCTS.py:214-225).
+    (base/Fixed: priors = ones + random rollouts, MCTS.py:346-383; Model: the network).
+Every game keeps the reference's ResetRoot (bb_reset_roots: the root goes back to its top-most ancestor with every simulation's
+statistics, MCTS.py:214-225), and DragonChess's compact child lists are spread over its 4032 actions, so its Root and Children
+have the reference's shapes.
 """
 from time import time
 
@@ -26,6 +26,20 @@ def _seed_from_numpy():
     np.random.choice consumes in the reference."""
     key = np.random.get_state()[1]
     return int(key[0]) ^ (int(key[1]) << 16) ^ int(np.random.get_state()[2])
+
+
+def _by_action(r, A):
+    """bb_node_edges' child list spread over the game's A actions: child / plays / value [A] (child -1 where no simulation has
+    reached the move) and the legal mask [A] of an expanded node."""
+    act = r['action']
+    on = act >= 0
+    a = act[on]
+    child = np.full(A, -1, dtype=np.int32)
+    plays = np.zeros(A, dtype=np.int32)
+    value = np.zeros(A, dtype=np.float32)
+    legal = np.zeros(A, dtype=np.float64)
+    child[a], plays[a], value[a], legal[a] = r['child'][on], r['plays'][on], r['value'][on], 1.0
+    return dict(child=child, plays=plays, value=value, legal=legal)
 
 
 class _Children(object):
@@ -85,15 +99,15 @@ class Node(object):
     @classmethod
     def _from_engine(cls, engine, state_cls, node, plays, value, slot=0):
         """The node at pool index `node` (-1: the root) of the engine's slot; Plays / Value are its parent's record of it."""
-        r = engine.node_view(slot, node)
-        A = engine.info.A
+        r = engine.node_edges(slot, node)
+        rows = _by_action(r, engine.info.A)
         state = state_cls._from_packed(r['state'])
         expanded = bool(r['flags'] & 1)
-        legal = np.array([(r['legal_mask'] >> a) & 1 for a in range(A)], dtype=np.float64) if expanded else state.LegalActions()
-        n = cls(state, legal, plays, value, r['plays'][:A] * legal, r['value'][:A] * legal, expanded)
+        legal = rows['legal'] if expanded else state.LegalActions()
+        n = cls(state, legal, plays, value, rows['plays'] * legal, rows['value'] * legal, expanded)
         n._engine, n._cls = engine, state_cls
         if expanded:
-            n.Children = _Children(n, r)
+            n.Children = _Children(n, rows)
         return n
 
     def WinRate(self):
@@ -123,10 +137,8 @@ class MCTS(object):
         self.Root = None
         self._engine = None
         self._root_state = None   # host mirror of the engine's root position
-        self._first_state = None
         self._root_sims = 0       # simulations run since the root was primed
         self._moves = 0
-        self._anc_depth = 0       # MoveRoot steps since the tree was primed
 
     # ---- engine plumbing ---------------------------------------------------------------------------
     def _max_depth(self):
@@ -142,8 +154,7 @@ class MCTS(object):
             plies = {_lib.GAME_CONNECT4: 43, _lib.GAME_TICTACTOE: 10}.get(state.GAME_ID, 64)
             cap = self._MAX_NODES if self.PlayLimit is None else min(self._MAX_NODES,
                                                                      int(self.PlayLimit) * plies * self._max_depth() + 64)
-            self._engine = self._make_engine(state.GAME_ID, 1, self.PlayLimit or 64, node_capacity=cap,
-                                             track_ancestors=state.GAME_ID != _lib.GAME_DRAGONCHESS)
+            self._engine = self._make_engine(state.GAME_ID, 1, self.PlayLimit or 64, node_capacity=cap, track_ancestors=True)
             self._after_engine_created(self._engine)
         return self._engine
 
@@ -174,8 +185,6 @@ class MCTS(object):
         if self._root_state is None:
             eng.set_roots(state._packed(), slots=[0], game_ids=[self._moves])
             self._root_state = state
-            self._first_state = state   # the top-most ancestor of whatever this tree grows into (ResetRoot)
-            self._anc_depth = 0
             self._root_sims = 0
         assert self._root_state == state, 'Primed for the correct input state.'
 
@@ -222,7 +231,6 @@ class MCTS(object):
                 self._engine.move_roots([int(a)])
                 self._root_state = child
                 self._moves += 1
-                self._anc_depth += 1
                 out = self._engine.sample_moves(0.0)
                 A = self._engine.info.A
                 self._root_sims = int(out['root_plays'][0])
@@ -230,14 +238,18 @@ class MCTS(object):
                 return
 
     def _root_view(self, state, legal, out, expanded):
-        """Root as a Node view from bb_sample_moves' outputs (+ lazy Children for the dense-action games)."""
+        """Root as a Node view from bb_sample_moves' outputs, spread over the game's actions (child_action: DragonChess lists
+        its legal moves compactly, a dense game puts action i at entry i), with lazy Children."""
         A = self._engine.info.A
         plays = int(out['root_plays'][0])
         value = np.float32(out['root_winrate'][0]) * np.float32(max(plays, 1))
-        root = Node(state, legal, plays, value, out['child_plays'][0, :A], out['child_value'][0, :A], expanded)
-        if expanded and self._engine.info.dense:
+        r = dict(action=out['child_action'][0], child=np.full(self._engine.info.S, -1, dtype=np.int32),
+                 plays=out['child_plays'][0], value=out['child_value'][0])
+        rows = _by_action(r, A)
+        root = Node(state, legal, plays, value, rows['plays'], rows['value'], expanded)
+        if expanded:
             root._engine, root._cls = self._engine, type(state)
-            root.Children = _Children(root, self._engine.node_view(0, -1))
+            root.Children = _Children(root, _by_action(self._engine.node_edges(0, -1), A))
         return root
 
     def ResetRoot(self):
@@ -246,15 +258,10 @@ class MCTS(object):
         current root, :252-258; the engine does the same for engines created with track_ancestors)."""
         if self._root_state is None or self.Root is None:
             return
-        if self._engine is None or not self._engine.info.dense:   # DragonChess: statistics are dropped (module docstring)
-            first = self._first_state
-            self.DropRoot()
-            self._first_state = first
-            return
         self._engine.reset_roots()
-        if self._anc_depth:
-            self._root_state = self._first_state
-            self._anc_depth = 0
+        # where the root is now, from the engine: a tree that restarted on its way (a move from an unexpanded root, a full
+        # node pool) keeps its root
+        self._root_state = type(self._root_state)._from_packed(self._engine.root_states())
         out = self._engine.sample_moves(0.0)
         self._root_sims = int(out['root_plays'][0])
         self.Root = self._root_view(self._root_state, self._root_state.LegalActions(), out, out['action'][0] != -3)

@@ -24,7 +24,7 @@ EXPORTS = (
     "bb_game_encode", "bb_game_initial", "bb_create", "bb_destroy", "bb_load_weights", "bb_get_counters",
     "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked",
     "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_step",
-    "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
+    "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
 )
 
 
@@ -112,6 +112,7 @@ def lib():
     L.bb_selfplay_headers.argtypes = [vp, ip, ip, vp]
     L.bb_reset_roots.argtypes = [vp]
     L.bb_node_view.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp]
+    L.bb_node_edges.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp, vp]
     L.bb_examples_fetch_games.argtypes = [vp, ip, vp, vp, ip, vp, vp]
     L.bb_examples_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp)]
     for name in EXPORTS:
@@ -453,6 +454,19 @@ class Engine:
         check(lib().bb_node_view(self.h, int(slot), int(node), ptr(child), ptr(plays), ptr(value), ptr(state), ptr(info)))
         return dict(child=child, plays=plays, value=value, state=state.view(STATE_DTYPE[self.game]), flags=int(info[0]),
                     legal_mask=int(np.uint32(info[1])), node=int(info[2]))
+
+    def node_edges(self, slot=0, node=-1):
+        """bb_node_edges: dict(action, child, plays, value [S] -- entry k is one child, action -1: none --, state (packed), flags,
+        n_children, node).  Every game: the dense ones put action i at entry i."""
+        S = self.info.S
+        action, child = np.zeros(S, np.int32), np.zeros(S, np.int32)
+        plays, value = np.zeros(S, np.int32), np.zeros(S, np.float32)
+        state = np.zeros((1, self.info.state_bytes), dtype=np.uint8)
+        info = np.zeros(3, np.int32)
+        check(lib().bb_node_edges(self.h, int(slot), int(node), ptr(action), ptr(child), ptr(plays), ptr(value), ptr(state),
+                                  ptr(info)))
+        return dict(action=action, child=child, plays=plays, value=value, state=state.view(STATE_DTYPE[self.game]),
+                    flags=int(info[0]), n_children=int(info[1]), node=int(info[2]))
 
     def root_states(self):
         buf = np.zeros((self.n_slots, self.info.state_bytes), dtype=np.uint8)

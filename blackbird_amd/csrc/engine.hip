@@ -264,7 +264,7 @@ static int engine_alloc(bb_engine *e) {
         dalloc(e, d.sims_left, n) || dalloc(e, d.pend_leaf, n) || dalloc(e, d.pend_expand, n) ||
         dalloc(e, d.path_len, n) || dalloc(e, d.game_lid, n) || dalloc(e, d.sim_serial, n) ||
         dalloc(e, d.root_W, n) || dalloc(e, d.root_pp, n) || dalloc(e, d.path, n * G::MAXPATH) ||
-        dalloc(e, d.anc, n * (size_t)(c.max_plies + 2)) || dalloc(e, d.anc_len, n) || dalloc(e, d.top_N, n) ||
+        dalloc(e, d.anc, n * (size_t)(c.max_plies + 2) * (DC ? 2 : 1)) || dalloc(e, d.anc_len, n) || dalloc(e, d.top_N, n) ||
         dalloc(e, d.path_N, n * G::MAXPATH) || dalloc(e, d.path_all, n * G::MAXPATH) || dalloc(e, d.path_W, n * G::MAXPATH) || dalloc(e, d.leaf_flags, n) ||
         dalloc(e, d.leaf_game_id, n) || dalloc(e, d.leaf_serial, n) || dalloc(e, d.eval_value, n) ||
         dalloc(e, d.eval_policy, n * PSTRIDE) || dalloc(e, d.ctr, n * 8) || dalloc(e, d.evals, n) || dalloc(e, d.out_action, n) ||
@@ -432,7 +432,7 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
     d.evaluator = cfg->evaluator;
     d.priors_ones = (cfg->mcts_kind == BB_MCTS_FIXED || cfg->evaluator == BB_EVAL_ROLLOUT) ? 1 : 0;
     d.salt_per_game = cfg->salt_per_game;
-    d.track_anc = (cfg->track_ancestors != 0 && cfg->game != BB_GAME_DRAGONCHESS) ? 1 : 0;
+    d.track_anc = cfg->track_ancestors != 0 ? 1 : 0;
     d.max_games = cfg->max_games > 0 ? cfg->max_games : cfg->n_slots;
     e->cfg.max_games = d.max_games;
     d.c_puct = cfg->c_puct;
@@ -1292,13 +1292,21 @@ extern "C" int bb_reset_roots(bb_engine *e) {
     HIPCHK(hipSetDevice(e->cfg.device));
     GAME_SWITCH(e->cfg.game, {
         if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
-            return fail(BB_ERR_ARG, "ancestors are kept for the dense-action games");
+            // a slot whose chain outgrew its max_plies + 2 entries cannot find its top-most ancestor (tree_dc.hip.h DC_ANC_BROKEN)
+            std::vector<int32_t> na((size_t)e->dev.n_slots);
+            HIPCHK(sync_all(e));
+            HIPCHK(hipMemcpy(na.data(), e->dev.anc_len, na.size() * 4, hipMemcpyDeviceToHost));
+            for (size_t g = 0; g < na.size(); g++)
+                if (na[g] < 0)
+                    return fail(BB_ERR_CAPACITY, "slot %zu moved its root more than max_plies + 2 times (max_plies %d) since the tree "
+                                                 "was primed: its ancestors were not all kept", g, e->cfg.max_plies);
+            k_dc_reset_roots<<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev);
         } else {
             k_reset_roots<G><<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev);
-            HIPCHK(hipGetLastError());
-            HIPCHK(sync_all(e));
-            return BB_OK;
         }
+        HIPCHK(hipGetLastError());
+        HIPCHK(sync_all(e));
+        return BB_OK;
     });
 }
 
@@ -1326,6 +1334,55 @@ extern "C" int bb_node_view(bb_engine *e, int slot, int node, int32_t *child_nod
             HIPCHK(hipMemcpy(info_out, di.p, 12, hipMemcpyDeviceToHost));
             return BB_OK;
         }
+    });
+}
+
+extern "C" int bb_node_edges(bb_engine *e, int slot, int node, int32_t *child_action_out, int32_t *child_node_out,
+                             int32_t *child_plays_out, float *child_value_out, void *state_out, int32_t *info_out) {
+    if (!e || slot < 0 || slot >= e->cfg.n_slots || !child_action_out || !child_node_out || !child_plays_out || !child_value_out ||
+        !state_out || !info_out)
+        return fail(BB_ERR_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(sync_all(e));
+    int32_t nn = 0;
+    HIPCHK(hipMemcpy(&nn, e->dev.n_nodes + slot, 4, hipMemcpyDeviceToHost));
+    if (node >= nn) return fail(BB_ERR_ARG, "node %d is not in slot %d's tree (%d nodes)", node, slot, nn);
+    GAME_SWITCH(e->cfg.game, {
+        constexpr int S = G::S;
+        DevBuf da, dc, dp, dv, ds, di;
+        if (da.alloc(S * 4) || dc.alloc(S * 4) || dp.alloc(S * 4) || dv.alloc(S * 4) || ds.alloc(sizeof(typename G::State)) || di.alloc(16))
+            return BB_ERR_HIP;
+        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
+            k_dc_node_edges<<<1, 64, 0, e->stream>>>(e->dev, e->edges, slot, node, (int32_t *)da.p, (int32_t *)dc.p, (int32_t *)dp.p,
+                                                     (float *)dv.p, (DCState *)ds.p, (int32_t *)di.p);
+        else
+            k_node_view<G><<<1, 64, 0, e->stream>>>(e->dev, slot, node, (int32_t *)dc.p, (int32_t *)dp.p, (float *)dv.p,
+                                                    (typename G::State *)ds.p, (int32_t *)di.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(sync_all(e));
+        HIPCHK(hipMemcpy(child_node_out, dc.p, S * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(child_plays_out, dp.p, S * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(child_value_out, dv.p, S * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(state_out, ds.p, sizeof(typename G::State), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(info_out, di.p, 12, hipMemcpyDeviceToHost));
+        if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
+            HIPCHK(hipMemcpy(child_action_out, da.p, S * 4, hipMemcpyDeviceToHost));
+        } else { // slot i is action i; the node view's info word 1 is the legal mask
+            const uint32_t legal = (uint32_t)info_out[1];
+            int cnt = 0;
+            for (int i = 0; i < S; i++) {
+                const bool on = i < G::A && ((legal >> i) & 1u);
+                child_action_out[i] = on ? i : -1;
+                if (!on) {
+                    child_node_out[i] = CHILD_NONE;
+                    child_plays_out[i] = 0;
+                    child_value_out[i] = 0.f;
+                }
+                cnt += on;
+            }
+            info_out[1] = cnt;
+        }
+        return BB_OK;
     });
 }
 
@@ -1385,6 +1442,8 @@ extern "C" int bb_set_rng_stream(bb_engine *e, uint64_t seed, uint32_t first_gam
 extern "C" int bb_selfplay_begin(bb_engine *e, int n_games, double temp) {
     if (!e) return fail(BB_ERR_ARG, "null engine");
     if (n_games <= 0) return fail(BB_ERR_ARG, "Use a positive integer for number of games."); // Blackbird.py:235-236
+    if (e->dev.track_anc && e->cfg.game == BB_GAME_DRAGONCHESS) // (its self-play kernels do not keep the chain)
+        return fail(BB_ERR_STATE, "DragonChess self-play does not keep ancestor chains: create the engine without track_ancestors");
     if (n_games > e->cfg.max_games)
         return fail(BB_ERR_CAPACITY, "n_games %d exceeds the engine's max_games %d", n_games, e->cfg.max_games);
     if (e->sims_now < 2 && temp != 0.0)

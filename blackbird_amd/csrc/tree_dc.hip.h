@@ -391,8 +391,20 @@ __device__ __forceinline__ T *dc_ctl(T *p) {
     if constexpr (SH) return as_lds(p);
     else return p;
 }
-template <bool SH = false>
+// The ancestor chain of a DragonChess slot (TreeDev::track_anc, tree.hip.h): d.anc[g] holds the node of every entry, top-most
+// first, and the second half of the same allocation (made twice as long for DragonChess engines) the edge taken from it as the
+// slot's edge index | player << 30 -- the encoding of DCEdges::path_edge.  It is not a field of DCEdges because the persistent
+// kernel copies that struct into its LDS (mega_dc.hip.h), and the chain has no business there.
+#define DC_ANC_BROKEN (-1) // anc_len of a slot whose chain outgrew max_plies + 2 entries: bb_reset_roots refuses it
+__device__ __forceinline__ uint32_t *dc_anc_edge(const TreeDev &d, int g) {
+    return d.anc + ((size_t)d.n_slots + (size_t)g) * (size_t)(d.max_plies + 2);
+}
+
+// ANC: also back up through the ancestor chain when the engine keeps one.  Only the launch-per-simulation kernels
+// (k_dc_tree_step / k_dc_tree_apply, which bb_run_sims drives) are built with it; self-play refuses track_ancestors engines.
+template <bool SH = false, bool ANC = false>
 __device__ void dc_phase_apply(const TreeDev &d, const DCEdges &E, int g, int lane, float *lds, const DCHeadLocal *hl = nullptr) {
+    static_assert(!(SH && ANC), "the ancestor chain is walked by the launch-per-simulation kernels only");
     // One wave per game and one wave per SIMD: this step is a chain of dependent HBM round trips (2-3 us each on
     // these sparsely touched pools), so every word that does not depend on another load is requested up front, and
     // the statistics the backup will update are fetched BEFORE the expansion, whose work then hides their latency.
@@ -489,6 +501,26 @@ __device__ void dc_phase_apply(const TreeDev &d, const DCEdges &E, int g, int la
         E.e[e].Q = __fdiv_rn(w, (float)n);
         nd->all = all;
         nd->sq = __dsqrt_rn(1.0 + (double)all);
+    }
+    if constexpr (ANC) {
+        if (d.track_anc) { // the reference's recursion does not stop at the current root: the edges above it (MCTS.py:252-258)
+            const int na = d.anc_len[g];
+            const uint32_t *an = d.anc + (size_t)g * (d.max_plies + 2), *ae = dc_anc_edge(d, g);
+            for (int k = lane; k < na; k += 64) { // (above the root: never one of the path's edges)
+                DCNode *nd = pool + an[k];
+                uint32_t ew = ae[k];
+                int pl = (int)(ew >> 30);
+                size_t e = (size_t)(g + d.pool_g0) * E.edge_cap + (ew & 0x3FFFFFFFu);
+                int n = E.e[e].N + 1, all = nd->all + 1;
+                float w = E.e[e].W + ((pl == prev) ? v01 : vflip);
+                E.e[e].N = n;
+                E.e[e].W = w;
+                E.e[e].Q = __fdiv_rn(w, (float)n);
+                nd->all = all;
+                nd->sq = __dsqrt_rn(1.0 + (double)all);
+            }
+            if (lane == 0) d.top_N[g] += 1;
+        }
     }
     if (lane == 0) {
         dc_ctl<SH>(d.root_N)[g] = root_n + 1;
@@ -799,7 +831,7 @@ __global__ void __launch_bounds__(256) k_dc_tree_step(TreeDev d, DCEdges E) {
     __threadfence_block();
     long long t0 = clock64();
 #endif
-    dc_phase_apply(d, E, g, lane, lds);
+    dc_phase_apply<false, true>(d, E, g, lane, lds);
 #ifdef BB_STAMPS
     long long t1 = clock64();
 #endif
@@ -820,7 +852,7 @@ __global__ void __launch_bounds__(256) k_dc_tree_apply(TreeDev d, DCEdges E) {
     __shared__ __attribute__((aligned(16))) float lds[4][DC_LDS_FLOATS];
     int g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (g >= d.n_slots) return;
-    dc_phase_apply(d, E, g, lane, lds[wv]);
+    dc_phase_apply<false, true>(d, E, g, lane, lds[wv]);
 }
 
 // ---- root statistics / move choice ------------------------------------------------------------------------
@@ -936,15 +968,31 @@ __device__ __forceinline__ void dc_reset_slot(const TreeDev &d, const DCEdges &E
     d.game_lid[g] = lid;
 }
 
-// _moveRoot by action id (all lanes call; lane 0 writes)
+// A tree restarted at a new root: the chain above it is gone (ANC: the engine may keep one)
+template <bool ANC>
+__device__ __forceinline__ void dc_anc_clear(const TreeDev &d, int g) {
+    if constexpr (ANC) {
+        if (d.track_anc) {
+            d.anc_len[g] = 0;
+            d.top_N[g] = 0;
+        }
+    }
+}
+
+// _moveRoot by action id (all lanes call; lane 0 writes).  ANC: push the edge taken onto the slot's ancestor chain when the
+// engine keeps one (bb_move_roots); the self-play kernels, persistent one included, are built without it.
+template <bool ANC = false>
 __device__ void dc_advance_root(const TreeDev &d, const DCEdges &E, int g, int lane, int action, DCState &new_st) {
     DCNode *pool = (DCNode *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
     DCNode *node = pool + d.root[g];
     DCState st = node->st;
-    if (!(node->flags & NODE_EXPANDED)) {
+    if (!(node->flags & NODE_EXPANDED)) { // `Root.Children is None` -> Root = None; re-prime with the new state
         new_st = st;
         DragonChess::apply(new_st, action);
-        if (lane == 0) dc_reset_slot(d, E, g, d.game_lid[g], new_st);
+        if (lane == 0) {
+            dc_reset_slot(d, E, g, d.game_lid[g], new_st);
+            dc_anc_clear<ANC>(d, g);
+        }
         return;
     }
     int n = node->n_edges;
@@ -969,6 +1017,7 @@ __device__ void dc_advance_root(const TreeDev &d, const DCEdges &E, int g, int l
             if (lane == 0) {
                 int lid = d.game_lid[g], ply = d.ply[g];
                 dc_reset_slot(d, E, g, lid, new_st);
+                dc_anc_clear<ANC>(d, g);
                 d.ply[g] = ply;
                 d.ctr[(size_t)g * 8 + 6] += 1;
             }
@@ -982,6 +1031,18 @@ __device__ void dc_advance_root(const TreeDev &d, const DCEdges &E, int g, int l
         new_st = pool[child & ~CHILD_TERM_BIT].st;
     }
     if (lane == 0) {
+        if constexpr (ANC) {
+            if (d.track_anc) { // a full chain is marked, never cut short: ResetRoot would land on the wrong node
+                const int na = d.anc_len[g], cap = d.max_plies + 2;
+                if (na >= 0 && na < cap) {
+                    d.anc[(size_t)g * cap + na] = (uint32_t)d.root[g];
+                    dc_anc_edge(d, g)[na] = (uint32_t)(node->edge_off + k) | ((uint32_t)st.player << 30);
+                    d.anc_len[g] = na + 1;
+                } else {
+                    d.anc_len[g] = DC_ANC_BROKEN;
+                }
+            }
+        }
         d.root[g] = child & ~CHILD_TERM_BIT;
         d.root_N[g] = cn;
         d.root_W[g] = cw;
@@ -995,7 +1056,7 @@ __global__ void __launch_bounds__(256) k_dc_move_roots(TreeDev d, DCEdges E, con
     int a = actions[g];
     if (a < 0 || a >= DragonChess::A || d.game_lid[g] < 0) return;
     DCState ns;
-    dc_advance_root(d, E, g, lane, a, ns);
+    dc_advance_root<true>(d, E, g, lane, a, ns);
     if (lane == 0) d.ply[g] += 1;
 }
 
@@ -1006,7 +1067,58 @@ __global__ void __launch_bounds__(256) k_dc_set_roots(TreeDev d, DCEdges E, int 
     int g = slots ? slots[i] : i;
     if (g < 0 || g >= d.n_slots) return;
     dc_reset_slot(d, E, g, game_ids ? (int)game_ids[i] : g, states[i]);
+    dc_anc_clear<true>(d, g);
     d.sims_left[g] = 0;
+}
+
+// MCTS.ResetRoot (MCTS.py:214-225): the root goes back to the node at the top of the chain; nothing is forgotten.  (A broken
+// chain, DC_ANC_BROKEN, is refused by the host before the launch.)
+__global__ void __launch_bounds__(256) k_dc_reset_roots(TreeDev d) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= d.n_slots || !d.track_anc || d.game_lid[g] < 0 || d.anc_len[g] <= 0) return;
+    d.root[g] = (int)d.anc[(size_t)g * (d.max_plies + 2)];
+    d.root_N[g] = d.top_N[g];
+    d.root_W[g] = 0.f;
+    d.root_pp[g] = 0;
+    d.anc_len[g] = 0;
+}
+
+// One node of a slot's tree for the host's Node view (MCTS.py:7-98): node < 0 = the root.  One wave; per edge k of the node's
+// run: the action id, the child's pool index (CHILD_NONE where no simulation has reached it), Plays, Value; unused entries up
+// to S: -1, CHILD_NONE, 0, 0.  info_out: flags, number of edges (0 unless expanded), the node's own index.
+__global__ void __launch_bounds__(64) k_dc_node_edges(TreeDev d, DCEdges E, int g, int node, int32_t *action_out, int32_t *child_out,
+                                                      int32_t *plays_out, float *value_out, DCState *state_out, int32_t *info_out) {
+    constexpr int S = DragonChess::S;
+    const int lane = threadIdx.x;
+    if (lane >= 64) return;
+    const DCNode *pool = (const DCNode *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
+    if (node < 0) node = d.root[g];
+    const DCNode *n = pool + node;
+    const int flags = n->flags, off = n->edge_off;
+    int ne = (flags & NODE_EXPANDED) ? n->n_edges : 0;
+    if (ne < 0 || ne > S || off < 0 || off > E.used[g] - ne) ne = 0; // (only a run inside the slot's used edges is read)
+    const size_t base = (size_t)(g + d.pool_g0) * E.edge_cap + (size_t)(ne > 0 ? off : 0);
+    for (int k = lane; k < S; k += 64) {
+        int32_t a = -1, c = CHILD_NONE, np = 0;
+        float w = 0.f;
+        if (k < ne) {
+            const DCEdge r = dc_edge_load(E.e + base + k);
+            a = r.act;
+            c = r.child;
+            np = r.N;
+            w = r.W;
+        }
+        action_out[k] = a;
+        child_out[k] = c;
+        plays_out[k] = np;
+        value_out[k] = w;
+    }
+    if (lane == 0) {
+        *state_out = n->st;
+        info_out[0] = flags;
+        info_out[1] = ne;
+        info_out[2] = node;
+    }
 }
 
 __global__ void __launch_bounds__(256) k_dc_get_roots(TreeDev d, DCState *out) {
