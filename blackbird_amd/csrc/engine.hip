@@ -217,7 +217,7 @@ struct bb_engine {
         int launch_steps = 64, queue_limit_s = 30;
         bool level_budget_set = false;
     } tune;
-    size_t eval_cache_bytes = 0; // evaluation cache of the persistent kernel (dev.eval_cache), zeroed with every weight load
+    size_t eval_cache_bytes = 0; // evaluation cache of the persistent self-play kernels (dev.eval_cache), zeroed with every weight load
     bool mega = false; // persistent per-CU self-play kernel with an LDS work queue (mega2.hip.h)
     bool async_selfplay = false; // dense games, DynamicMCTS, deterministic evaluators: k_tree_async rounds
     bool dc_fused = false;       // DragonChess, DynamicMCTS, 16-filter network: one wave keeps its game for a whole launch (mega_dc.hip.h)
@@ -330,16 +330,19 @@ static void make_views(bb_engine *e) {
 }
 
 // ---- pool sizing ------------------------------------------------------------------------------------------------
-// log2 of the entries of the evaluation cache (net.hip.h EvalCache: 64 bytes each) an engine of this configuration owns, 0 = none.
-// Only the persistent self-play kernel of Connect4 probes it.  BB_EVAL_CACHE=0 turns it off, BB_EVAL_CACHE_LOG2 sizes it
-// (default 26: 4 GiB) -- tuning knobs, read from the environment at bb_create / bb_fit_slots.
+// log2 of the entries of the evaluation cache (net.hip.h EvalCache) an engine of this configuration owns, 0 = none.
+// The persistent self-play kernel of Connect4 (mega2.hip.h, 64-byte entries; default 2^26: 4 GiB) and the one-wave-per-game
+// kernel of DragonChess (mega_dc.hip.h, 128-byte entries; default 2^24: 2 GiB, ~16 M positions against the ~0.4 M a ply of
+// 1024 games evaluates, next to pools of ~190 GB) probe it.  BB_EVAL_CACHE=0 turns it off, BB_EVAL_CACHE_LOG2 sizes it --
+// tuning knobs, read from the environment at bb_create / bb_fit_slots.
+static size_t eval_cache_entry_bytes(const bb_config *cfg) { return cfg->game == BB_GAME_DRAGONCHESS ? 128 : 64; }
 static int eval_cache_log2_of(const bb_config *cfg) {
-    if (cfg->game != BB_GAME_CONNECT4 || cfg->mcts_kind != BB_MCTS_DYNAMIC || cfg->evaluator != BB_EVAL_NET ||
-        cfg->launch != BB_LAUNCH_AUTO)
+    if ((cfg->game != BB_GAME_CONNECT4 && cfg->game != BB_GAME_DRAGONCHESS) || cfg->mcts_kind != BB_MCTS_DYNAMIC ||
+        cfg->evaluator != BB_EVAL_NET || cfg->launch != BB_LAUNCH_AUTO)
         return 0;
     const char *on = getenv("BB_EVAL_CACHE"), *lg = getenv("BB_EVAL_CACHE_LOG2");
     if (on && atoi(on) == 0) return 0;
-    const int k = lg ? atoi(lg) : 26;
+    const int k = lg ? atoi(lg) : cfg->game == BB_GAME_DRAGONCHESS ? 24 : 26;
     return k < 10 ? 10 : k > 32 ? 32 : k;
 }
 
@@ -364,7 +367,7 @@ static void pool_bytes(const bb_config *cfg, size_t *per_slot, size_t *fixed) {
     const size_t ng = (size_t)(cfg->max_games > 0 ? cfg->max_games : cfg->n_slots);
     *per_slot = ps;
     *fixed = ng * ((size_t)(cfg->max_plies + 1) * (size_t)gi.example_bytes + 16) + (64u << 20); // + weights, scratch, runtime slack
-    if (const int k = eval_cache_log2_of(cfg)) *fixed += (size_t)64 << k;
+    if (const int k = eval_cache_log2_of(cfg)) *fixed += eval_cache_entry_bytes(cfg) << k;
 }
 
 static int check_config(const bb_config *cfg) {
@@ -469,10 +472,10 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
     if (int v = env_int("BB_TREE_GPW", 0); v >= 1 && v <= 64 / e->info.S) d.gpw = v;
     d.temp = 1.0;
     GAME_SWITCH(cfg->game, rc = engine_alloc<G>(e); break);
-    if (!rc && e->mega) {
+    if (!rc && (e->mega || e->dc_fused)) {
         if (const int k = eval_cache_log2_of(cfg)) {
             uint8_t *tab = nullptr;
-            e->eval_cache_bytes = (size_t)64 << k;
+            e->eval_cache_bytes = eval_cache_entry_bytes(cfg) << k;
             rc = dalloc(e, tab, e->eval_cache_bytes); // (zeroed: empty)
             d.eval_cache = tab;
             d.eval_cache_log2 = k;

@@ -227,11 +227,26 @@ struct alignas(16) DCState {
 };
 static_assert(sizeof(DCState) == 80, "packed DragonChess state is 80 bytes");
 
+// The evaluation cache's key of a DragonChess position (DragonChess::cache_key: 261 bits of network input in five words)
+struct DCKey {
+    uint64_t w[5];
+    BB_HD bool none() const { return (w[0] | w[1] | w[2] | w[3] | w[4]) == 0; }
+    BB_HD bool operator==(const DCKey &o) const {
+        return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3] && w[4] == o.w[4];
+    }
+    // 64-bit digest: picks the table slot (top bits) and tags every chunk of the entry (net.hip.h)
+    BB_HD uint64_t tag() const {
+        uint64_t t = bb_mix64(w[0]);
+        for (int i = 1; i < 5; i++) t = bb_mix64(t ^ w[i]);
+        return t;
+    }
+};
+
 struct DragonChess {
     static constexpr int H = 8, W = 8, C = 17, A = 4032, S = 144, GID = 2;
     static constexpr int MAXPATH = 128;
     static constexpr bool CELL_BF16 = true;
-    static constexpr bool CACHE_KEY = false; // (no evaluation cache: GridGame::cache_key)
+    static constexpr bool CACHE_KEY = false; // (not GridGame's one-word key: DragonChess's is DCKey, cache_key below)
     using State = DCState;
 
     BB_HD static State initial() { // fen 'rnbqkbnr/pppppppp/8/8/8/8/3PPP2/4K3 w kq' (DragonChess.py:36-60)
@@ -493,5 +508,41 @@ struct DragonChess {
         out[7] = bf(s.castle[2]) | (bf(s.castle[3]) << 16);
         out[8] = (s.player == 1 && s.prev == 1) ? 0x3F80u : 0u;
         for (int j = 9; j < 16; j++) out[j] = 0u;
+    }
+
+    // Exact key of the network input of a position (the evaluation cache of the one-wave-per-game kernel: mega_dc.hip.h).
+    // encode_cell's 17 planes are a function of the 64 piece codes, the four castle flags and plane 16 (White's first move
+    // of two); nothing else of the state reaches the network, and its output (value for the side to move, WideHead) is
+    // not flipped before the tree takes it -- so the side to move beyond plane 16 does not belong in the key.
+    //     w[j], j < 4: bit j of (code + 6) of square i at bit i (0 .. 12 per square: 13 codes, 4 bit-planes)
+    //     w[4]: castle flags at bits 0 .. 3, plane 16 at bit 4, bit 5 = 1 (a key is never all-zero)
+    // Two different inputs never share a key.  A state with a code outside -6 .. 6 or a castle flag other than 0 / 1 (never
+    // reached in play) gets the all-zero key, which the cache never probes.
+    BB_HD static DCKey cache_key(const State &s) {
+        DCKey k = {{0, 0, 0, 0, 0}};
+        uint64_t bad = 0;
+        for (int i = 0; i < 64; i++) {
+            const int n = s.b[i] + 6;
+            bad |= (uint64_t)(n < 0 || n > 12);
+            for (int j = 0; j < 4; j++) k.w[j] |= (uint64_t)((n >> j) & 1) << i;
+        }
+        uint64_t f = 32;
+        for (int j = 0; j < 4; j++) {
+            bad |= (uint64_t)(s.castle[j] != 0 && s.castle[j] != 1);
+            f |= (uint64_t)(s.castle[j] & 1) << j;
+        }
+        k.w[4] = f | ((uint64_t)(s.player == 1 && s.prev == 1) << 4);
+        if (bad) k = DCKey{{0, 0, 0, 0, 0}};
+        return k;
+    }
+    // The same key with one square per lane (s: the wave's own copy; wave-uniform result, the four bit-planes are ballots).
+    __device__ __forceinline__ static DCKey cache_key_wave(const State &s, int lane) {
+        const int n = s.b[lane] + 6, c0 = s.castle[0], c1 = s.castle[1], c2 = s.castle[2], c3 = s.castle[3];
+        DCKey k;
+        for (int j = 0; j < 4; j++) k.w[j] = __ballot((n >> j) & 1);
+        const bool bad = __ballot(n < 0 || n > 12) != 0 || ((c0 | c1 | c2 | c3) & ~1) != 0;
+        k.w[4] = 32 | (uint64_t)(c0 | (c1 << 1) | (c2 << 2) | (c3 << 3)) | ((uint64_t)(s.player == 1 && s.prev == 1) << 4);
+        if (bad) k = DCKey{{0, 0, 0, 0, 0}};
+        return k;
     }
 };

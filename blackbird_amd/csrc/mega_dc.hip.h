@@ -28,20 +28,55 @@ __device__ __attribute__((noinline)) void dc_fused_tree(const TreeDev &d_, const
     dc_phase_select<true>(d, E, g, lane, tl);
     __threadfence_block();
 }
+// The evaluation cache (net.hip.h, DragonChess entries; off when d.eval_cache is null).  dc_fused_probe opens the network
+// phase with the leaf's key, formed from the wave's LDS copy of the leaf, and its probe; it returns -1 no probe (cache off,
+// or a state without a key), 0 miss, 1 hit.  A hit has put the cached evaluation in hl->h and skips the network; it takes
+// the leaf back from d.evals, which counts tower runs (the select phase counted the leaf when it posted it).  The probe
+// cannot start earlier: the tree phases are out-of-line functions, and a call returns only once its memory requests are
+// back.  Both network forms call it first thing (dc_fused_net, dc_fused_net_x3); net_body / net_body_x3 are unchanged.
+__device__ __forceinline__ int dc_fused_probe(const TreeDev &d, int g, DCHeadLocal *hl, int lane) {
+    const EvalCache c = {(u32x4 *)d.eval_cache, d.eval_cache_log2};
+    if (!c.tab) return -1;
+    const DCKey key = DragonChess::cache_key_wave(as_lds((const DCState *)d.leaf_state)[g], lane);
+    if (key.none()) return -1;
+    const uint64_t tag = key.tag();
+    WideHead h;
+    if (!dc_eval_cache_hit(dc_eval_cache_load(dc_eval_cache_entry(c, tag), lane), key, tag, lane, h)) return 0;
+    if (lane == 0) {
+        hl->h = h;
+        d.evals[g] -= 1;
+    }
+    __threadfence_block();
+    return 1;
+}
+// A miss: the entry of the evaluation just made, fire and forget (the key again from the leaf: nothing of the probe is
+// held in registers through the network).
+__device__ __forceinline__ void dc_fused_store(const TreeDev &d, int g, const DCHeadLocal *hl, int lane) {
+    const EvalCache c = {(u32x4 *)d.eval_cache, d.eval_cache_log2};
+    const DCKey key = DragonChess::cache_key_wave(as_lds((const DCState *)d.leaf_state)[g], lane);
+    const uint64_t tag = key.tag();
+    dc_eval_cache_put(dc_eval_cache_entry(c, tag), key, tag, hl->h, lane);
+}
+
 // The network for the wave's own leaf.  Nothing 4032-wide leaves the wave: the policy head is reduced to (R0, R1, max,
 // 1 / sum exp) in `hl` (net.hip.h: WideHead) and the expansion of the next tree phase computes the probabilities of its
 // legal moves from those and the head weights in LDS -- instead of a 16 KB policy row written to and gathered from
 // memory, and 189 L2 loads per lane for the head weights, per evaluation.  (The prior noise of a wide game is mixed in
 // at expansion, over the legal moves only: dc_expand.)
-__device__ __attribute__((noinline)) void dc_fused_net(const NetDev &nd_, const TreeDev &d_, const int *slot, float *nl, DCHeadLocal *hl) {
+__device__ __attribute__((noinline)) int dc_fused_net(const NetDev &nd_, const TreeDev &d_, const int *slot, float *nl, DCHeadLocal *hl) {
     const NetDev &nd = *as_lds(&nd_);
     const TreeDev &d = *as_lds(&d_);
     slot = as_lds(slot);
     nl = as_lds(nl);
     hl = as_lds(hl);
+    const int lane = threadIdx.x & 63, g = *slot;
+    const int probe = dc_fused_probe(d, g, hl, lane);
+    if (probe > 0) return probe;
     net_body<DragonChess, 1, 1>(nd, 1, 0, slot, nl, (const DCState *)d.leaf_state, nullptr, d.leaf_game_id, d.leaf_serial, 0,
                              nullptr, nullptr, nullptr, DragonChess::A, true, &hl->h);
+    if (probe == 0) dc_fused_store(d, g, hl, lane);
     __threadfence_block();
+    return probe;
 }
 // The evaluated leaf alone (what dc_fused_tree does first): the last thing a wave does when the launch's pool of
 // simulations is dry, so that nothing of the evaluation has to outlive the launch (its policy summary `hl` is in LDS).
@@ -55,17 +90,22 @@ __device__ __attribute__((noinline)) void dc_fused_apply(const TreeDev &d_, cons
 }
 // The same on the bf16 matrix pipe (net_x3.hip.h): every operand plane of the tower streams from L2 a layer ahead (this
 // kernel's LDS holds the four waves' scratch and the 4032-wide head).
-__device__ __forceinline__ void dc_fused_net_x3(const NetDev &nd_, const NetX3 &x3_, const TreeDev &d_, const int *slot, float *nl,
-                                                          DCHeadLocal *hl) {
+__device__ __forceinline__ int dc_fused_net_x3(const NetDev &nd_, const NetX3 &x3_, const TreeDev &d_, const int *slot, float *nl,
+                                                         DCHeadLocal *hl) {
     const NetDev &nd = *as_lds(&nd_);
     const NetX3 &x3 = *as_lds(&x3_);
     const TreeDev &d = *as_lds(&d_);
     slot = as_lds(slot);
     nl = as_lds(nl);
     hl = as_lds(hl);
+    const int lane = threadIdx.x & 63, g = *slot;
+    const int probe = dc_fused_probe(d, g, hl, lane);
+    if (probe > 0) return probe;
     net_body_x3<DragonChess, false, true>(nd, x3, 1, 0, slot, (unsigned char *)nl, (const DCState *)d.leaf_state, nullptr, d.leaf_game_id,
                                     d.leaf_serial, 0, nullptr, nullptr, nullptr, DragonChess::A, true, &hl->h);
+    if (probe == 0) dc_fused_store(d, g, hl, lane);
     __threadfence_block();
+    return probe;
 }
 __device__ __attribute__((noinline)) void dc_fused_move(const TreeDev &d_, const DCEdges &E_, int g, int lane, float *tl, const DCHeadLocal *hl) {
     const TreeDev &d = *as_lds(&d_);
@@ -191,6 +231,7 @@ __global__ void __launch_bounds__(256) k_dc_selfplay_fused(TreeDev d_arg, DCEdge
     // others, wherever its game is in its move (sims_left carries over), instead of the launch waiting for the game with the
     // slowest `plies` moves.
     int chunk = own_sims;
+    unsigned n_probes = 0, n_hits = 0; // evaluation cache, this wave's launch (one counter update per wave at the end)
     while (mine) {
         if (d.game_lid[g] < 0) break; // this slot has played its last game
         if (d.sims_left[g] <= 0) {    // MCTS.FindMove's tail and the self-play loop body (applies the last leaf first)
@@ -217,15 +258,20 @@ __global__ void __launch_bounds__(256) k_dc_selfplay_fused(TreeDev d_arg, DCEdge
 #ifdef BB_STAMPS
         long long c1 = clock64();
 #endif
-        if (d.pend_leaf[g] >= 0) { // (uniform) a leaf was posted: evaluate it right here
-            if (s_x3.w0) dc_fused_net_x3(nd, s_x3, d, &myslot[wv], nl, hl);
-            else dc_fused_net(nd, d, &myslot[wv], nl, hl);
+        if (d.pend_leaf[g] >= 0) { // (uniform) a leaf was posted: evaluate it right here, unless the evaluation cache has it
+            const int probe = s_x3.w0 ? dc_fused_net_x3(nd, s_x3, d, &myslot[wv], nl, hl) : dc_fused_net(nd, d, &myslot[wv], nl, hl);
+            n_probes += probe >= 0;
+            n_hits += probe > 0;
         }
 #ifdef BB_STAMPS
         DST(0, c1 - c0);          // tree phases (tools/dc_stamps.py)
         DST(2, clock64() - c1);   // network
         DST(4, 1);
 #endif
+    }
+    if (lane == 0 && n_probes && d.eval_cache_ctr) {
+        atomicAdd(&d.eval_cache_ctr[0], (unsigned long long)n_hits);
+        atomicAdd(&d.eval_cache_ctr[1], (unsigned long long)n_probes);
     }
 #ifdef BB_STAMPS
     if (mine && lane == 0 && d.stamps)

@@ -200,7 +200,7 @@ __device__ __forceinline__ void wide_head_stats(WideHead &h, PK pdk, PK pdb, int
 // Every lane ends with the same bits; the tree does not depend on how positions are packed into waves.
 __device__ __forceinline__ float pooled_sum(float v) { return wave_sum_f32(v); }
 
-// ---- evaluation cache (persistent kernel, Connect4; the table is device memory of the engine: engine.hip) ------------------
+// ---- evaluation cache (persistent kernels: Connect4 here, DragonChess below; the table is device memory of the engine: engine.hip) ----
 // Direct-mapped: 2^log2 entries of 64 bytes, the slot of a position is the top bits of bb_mix64(G::cache_key).  An entry is four
 // 16-byte chunks {u64 key, f32, f32} that hold [value, p0 .. p6], the network's value and its priors BEFORE the prior noise:
 // chunk c carries floats 2c and 2c + 1.  Every chunk is written and read as ONE 16-byte vector access of ONE lane, and counts
@@ -244,6 +244,50 @@ __device__ __forceinline__ bool eval_cache_hit(u32x4 ch, uint64_t key, int lane,
     const float lo = __shfl(f0, i >> 1, 64), hi = __shfl(f1, i >> 1, 64);
     pr = lane < A ? ((i & 1) ? hi : lo) : 0.f;
     return true;
+}
+
+// DragonChess entries (one-wave-per-game kernel, mega_dc.hip.h; the same rules as above).  A key is 261 bits (DCKey), so
+// it does not fit every chunk: an entry is 128 bytes, eight 16-byte chunks {u64 tag, u64 payload} with tag = DCKey::tag()
+// (whose top bits also pick the slot).  Payloads: chunks 0 .. 4 the key words w[0] .. w[4], chunk 5 (value, R0), chunk 6
+// (R1, m), chunk 7 (inv, 0) -- the network's WideHead, which is all an evaluation leaves (the prior noise is drawn at the
+// expansion, per node).  A probe hits when all eight chunks carry its tag and chunks 0 .. 4 its key: an empty (zeroed) entry
+// never does (a key's w[4] is never 0), nor does an entry of another position, whole or torn.  The one residual case: two
+// DIFFERENT positions with the same 64-bit tag (hence the same slot) written over each other while a probe of one reads
+// the slot, so that it sees its own key chunks beside the other's result chunks.  That takes a 2^-64 digest collision
+// between two positions evaluated at the same moment -- below any hardware error rate; it is accepted, not designed away.
+__device__ __forceinline__ u32x4 *dc_eval_cache_entry(const EvalCache &c, uint64_t tag) {
+    return c.tab + 8 * (size_t)(tag >> (64 - c.log2));
+}
+// the probe: chunk `lane` of the entry on lanes 0 .. 7
+__device__ __forceinline__ u32x4 dc_eval_cache_load(const u32x4 *entry, int lane) {
+    u32x4 z = {0u, 0u, 0u, 0u};
+    if (lane < 8) z = *(const __attribute__((address_space(1))) u32x4 *)(const void *)(entry + lane);
+    return z;
+}
+// (Keys and heads are passed by value: with reference parameters here the ROCm 7.2 compiler crashes in its optimiser.)
+__device__ __forceinline__ uint64_t dc_key_word(DCKey k, int lane) { // w[lane] (lanes 0 .. 4)
+    return lane == 0 ? k.w[0] : lane == 1 ? k.w[1] : lane == 2 ? k.w[2] : lane == 3 ? k.w[3] : k.w[4];
+}
+// wave-uniform: the entry holds `key`; then its WideHead
+__device__ __forceinline__ bool dc_eval_cache_hit(u32x4 ch, DCKey key, uint64_t tag, int lane, WideHead &h) {
+    const uint64_t pay = (uint64_t)ch[2] | ((uint64_t)ch[3] << 32);
+    const bool ok = lane < 8 && ch[0] == (uint32_t)tag && ch[1] == (uint32_t)(tag >> 32) && (lane >= 5 || pay == dc_key_word(key, lane));
+    if ((__ballot(ok) & 0xFFull) != 0xFFull) return false;
+    const float f0 = __uint_as_float(ch[2]), f1 = __uint_as_float(ch[3]);
+    h.value = lane_f32(f0, 5);
+    h.R0 = lane_f32(f1, 5);
+    h.R1 = lane_f32(f0, 6);
+    h.m = lane_f32(f1, 6);
+    h.inv = lane_f32(f0, 7);
+    return true;
+}
+// lanes 0 .. 7 store chunk `lane` of the entry (h: wave-uniform)
+__device__ __forceinline__ void dc_eval_cache_put(u32x4 *entry, DCKey key, uint64_t tag, WideHead h, int lane) {
+    const uint64_t kw = dc_key_word(key, lane);
+    const uint32_t lo = lane < 5 ? (uint32_t)kw : __float_as_uint(lane == 5 ? h.value : lane == 6 ? h.R1 : h.inv);
+    const uint32_t hi = lane < 5 ? (uint32_t)(kw >> 32) : lane == 5 ? __float_as_uint(h.R0) : lane == 6 ? __float_as_uint(h.m) : 0u;
+    if (lane < 8)
+        *(__attribute__((address_space(1))) u32x4 *)(void *)(entry + lane) = u32x4{(uint32_t)tag, (uint32_t)(tag >> 32), lo, hi};
 }
 
 // The end of a dense game's policy head, from the normalised priors on (action a on lane a; lanes >= A hold 0): the prior

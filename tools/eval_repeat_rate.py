@@ -1,13 +1,19 @@
-"""How many network evaluations of Connect4 self-play repeat a position evaluated before (CPU only, the oracle).
+"""How many network evaluations of self-play repeat a position evaluated before (CPU only, the oracle).
 
-Plays n full games at the bench's settings (weights seed 0, 800 simulations, prior noise alpha 0.2 / eps 0.3 per (game, node
-serial)) through the oracle's keyed evaluator callback and counts, among the FIRST evaluation of every node, those whose
-position (network input) was already evaluated: in the same game, and in the same game or any earlier one.  This is the
-hit rate an unbounded evaluation cache would reach with that many games sharing it (the persistent kernel's table is bounded
-and is shared by 4096 concurrent games).
+Plays n games at the bench's settings (random weights seed 0, prior noise alpha 0.2 / eps 0.3 per (game, node serial))
+through the oracle's keyed evaluator callback and counts, among the FIRST evaluation of every node, those whose position
+(network input) was already evaluated: in the same game, and in the same game or any earlier one.  This is the hit rate an
+unbounded evaluation cache would reach with that many games sharing it (the persistent kernels' tables are bounded and are
+shared by 4096 concurrent Connect4 games / 1024 DragonChess games).
 
-usage: python tools/eval_repeat_rate.py [games] [sims]
+  --game c4 (default): Connect4, R4/F16 on 3 planes, 800 simulations, full games.
+  --game dc: DragonChess (bench.py --workload dc), R4/F16 on 17 planes, 4032-wide policy, 400 simulations; the CPU oracle
+             plays ~30 plies a minute there, so --plies caps every game (default 40).  The noise is drawn for the legal
+             moves only (the priors are renormalised over them anyway; only their rounding differs from the oracle's own).
+
+usage: python tools/eval_repeat_rate.py [games] [sims] [--game c4|dc] [--plies N]
 """
+import argparse
 import ctypes as C
 import os
 import sys
@@ -20,54 +26,72 @@ from blackbird_amd import weights as W  # noqa: E402
 from oracle import orc  # noqa: E402
 
 ALPHA, EPS, SEED = 0.2, 0.3, 1234
+GAMES = {  # game, H, W, planes, actions, simulations, ply cap
+    "c4": (orc.C4, 6, 7, 3, 7, 800, 42),
+    "dc": (orc.DC, 8, 8, 17, 4032, 400, 40),
+}
 
 
 def main():
-    n_games = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-    sims = int(sys.argv[2]) if len(sys.argv) > 2 else 800
+    ap = argparse.ArgumentParser()
+    ap.add_argument("games", type=int, nargs="?", default=20)
+    ap.add_argument("sims", type=int, nargs="?", default=None)
+    ap.add_argument("--game", choices=sorted(GAMES), default="c4")
+    ap.add_argument("--plies", type=int, default=None, help="ply cap of every game")
+    args = ap.parse_args()
+    game, H, Wd, Cc, A, sims, plies = GAMES[args.game]
+    sims = args.sims or sims
+    plies = args.plies or plies
     orc.build()
     L = orc.lib()
     L.orc_beta_noise.restype = C.c_float
     L.orc_beta_noise.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float]
-    flat = W.flatten(W.init_weights(3, 16, 4, 16, 7, seed=0))
-    net = orc.NetWeights(6, 7, 3, 16, 4, 16, 7, flat)
+    flat = W.flatten(W.init_weights(Cc, 16, 4, 16, A, seed=0))
+    net = orc.NetWeights(H, Wd, Cc, 16, 4, 16, A, flat)
     seen_all, seen_game, first = set(), set(), set()
-    rows = []  # per game: first visits, repeats in the game, repeats in this or an earlier game
+    rows = []  # per game: first visits, repeats in the game, repeats in this or an earlier game, all evaluations, their repeats
 
     def evaluate(_ctx, stp, gid, serial, vp, pp):
-        planes = orc.encode(orc.C4, stp.contents)
+        planes = orc.encode(game, stp.contents)
         v, _l, p = orc.net_forward(net, planes)
         vp[0] = float(v[0])
         if pp:
-            q = [(1.0 - EPS) * float(p[0, a]) + EPS * L.orc_beta_noise(SEED, gid, serial, a, ALPHA) for a in range(7)]
-            t = sum(q)
-            for a in range(7):
-                pp[a] = q[a] / t
-        if (gid, serial) in first:
-            return
-        first.add((gid, serial))
+            acts = np.nonzero(orc.legal(game, stp.contents))[0] if game == orc.DC else range(A)
+            q = np.zeros(A, dtype=np.float64)
+            for a in acts:
+                q[a] = (1.0 - EPS) * float(p[0, a]) + EPS * L.orc_beta_noise(SEED, gid, serial, int(a), ALPHA)
+            q /= max(q.sum(), 1e-30)
+            for a in acts:
+                pp[a] = q[a]
         key = planes.tobytes()
         r = rows[-1]
-        r[0] += 1
-        r[1] += key in seen_game
-        r[2] += key in seen_all
+        r[3] += 1
+        r[4] += key in seen_all
+        if (gid, serial) not in first:
+            first.add((gid, serial))
+            r[0] += 1
+            r[1] += key in seen_game
+            r[2] += key in seen_all
         seen_game.add(key)
         seen_all.add(key)
 
-    cfg = orc.make_cfg(orc.C4, evaluator=orc.EVAL_CALLBACK_KEYED, seed=SEED, noise_on=True, alpha=ALPHA, eps=EPS,
+    cfg = orc.make_cfg(game, evaluator=orc.EVAL_CALLBACK_KEYED, seed=SEED, noise_on=True, alpha=ALPHA, eps=EPS,
                        cb2=orc.EVAL_CB2(evaluate))
     sims_total = 0
-    for g in range(n_games):
-        rows.append([0, 0, 0])
+    print("%s: %d simulations per move, games capped at %d plies" % (args.game, sims, plies), flush=True)
+    for g in range(args.games):
+        rows.append([0, 0, 0, 0, 0])
         seen_game.clear()
-        o = orc.selfplay_game(cfg, g, 1.0, sims, 42)
+        o = orc.selfplay_game(cfg, g, 1.0, sims, plies)
         sims_total += o["stats"].sims
-        n, same, shared = rows[-1]
-        print("game %3d: %5d first visits, repeats: same game %.3f, with the %d earlier games %.3f"
-              % (g, n, same / max(n, 1), g, shared / max(n, 1)), flush=True)
+        n, same, shared, _ne, _nr = rows[-1]
+        print("game %3d: %3d plies, %5d first visits, repeats: same game %.3f, with the %d earlier games %.3f"
+              % (g, o["n"] - 1, n, same / max(n, 1), g, shared / max(n, 1)), flush=True)
     a = np.array(rows, dtype=np.float64)
-    print("all %d games: first visits / simulations %.3f, repeats: same game %.3f, shared table %.3f"
-          % (n_games, a[:, 0].sum() / max(sims_total, 1), a[:, 1].sum() / a[:, 0].sum(), a[:, 2].sum() / a[:, 0].sum()))
+    print("all %d games: first visits / simulations %.3f, repeats: same game %.3f, shared table %.3f; "
+          "every evaluation (first visits or not): %d, repeats %.3f"
+          % (args.games, a[:, 0].sum() / max(sims_total, 1), a[:, 1].sum() / a[:, 0].sum(), a[:, 2].sum() / a[:, 0].sum(),
+             a[:, 3].sum(), a[:, 4].sum() / a[:, 3].sum()))
 
 
 if __name__ == "__main__":
