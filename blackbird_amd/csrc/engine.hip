@@ -8,6 +8,7 @@
 #include "net_x3.hip.h"
 #include "gnet.hip.h"
 #include "gnet_x3.hip.h"
+#include "eval_probe.hip.h"
 #include "tree.hip.h"
 #include "tree_dc.hip.h"
 #include "mega2.hip.h"
@@ -217,7 +218,16 @@ struct bb_engine {
         int launch_steps = 64, queue_limit_s = 30;
         bool level_budget_set = false;
     } tune;
-    size_t eval_cache_bytes = 0; // evaluation cache of the persistent self-play kernels (dev.eval_cache), zeroed with every weight load
+    size_t eval_cache_bytes = 0; // evaluation cache of self-play (dev.eval_cache: the persistent kernels and the asynchronous rounds), zeroed with every weight load
+    // asynchronous rounds with the cache: the posted leaves the probe kernel did not answer (eval_probe.hip.h), what the
+    // network launches of a round take.  Per view like post_count / post_slot: counters [4 v .. 4 v + 3], slots from slot_offset.
+    // They are probed for the launch-per-layer networks (general_net) only: for a 16-filter network that plays as rounds the
+    // probe launch costs more than the shorter k_net_x3 launch saves (75.8 against 60.5 ms per 800-visit step of 4096 games
+    // with 36 % hits) -- such an engine owns the table, because it cannot know its network at bb_create, and
+    // leaves it alone.
+    int *miss_count = nullptr; // [8]
+    int *miss_slot = nullptr;  // [n_slots]
+    int miss_next[2] = {0, 0}; // per view: the round whose counter the last probe launch cleared ahead (the rotation holds only across consecutive probed rounds)
     bool mega = false; // persistent per-CU self-play kernel with an LDS work queue (mega2.hip.h)
     bool async_selfplay = false; // dense games, DynamicMCTS, deterministic evaluators: k_tree_async rounds
     bool dc_fused = false;       // DragonChess, DynamicMCTS, 16-filter network: one wave keeps its game for a whole launch (mega_dc.hip.h)
@@ -331,14 +341,16 @@ static void make_views(bb_engine *e) {
 
 // ---- pool sizing ------------------------------------------------------------------------------------------------
 // log2 of the entries of the evaluation cache (net.hip.h EvalCache) an engine of this configuration owns, 0 = none.
-// The persistent self-play kernel of Connect4 (mega2.hip.h, 64-byte entries; default 2^26: 4 GiB) and the one-wave-per-game
-// kernel of DragonChess (mega_dc.hip.h, 128-byte entries; default 2^24: 2 GiB, ~16 M positions against the ~0.4 M a ply of
-// 1024 games evaluates, next to pools of ~190 GB) probe it.  BB_EVAL_CACHE=0 turns it off, BB_EVAL_CACHE_LOG2 sizes it --
-// tuning knobs, read from the environment at bb_create / bb_fit_slots.
+// Connect4 self-play (64-byte entries; default 2^26: 4 GiB) probes it in the persistent kernel (mega2.hip.h) and in the
+// asynchronous rounds that any other network or BB_LAUNCH_ROUNDS runs as (eval_probe.hip.h); DragonChess in its
+// one-wave-per-game kernel (mega_dc.hip.h, 128-byte entries; default 2^24: 2 GiB, ~16 M positions against the ~0.4 M a ply
+// of 1024 games evaluates, next to pools of ~190 GB).  The lock-step search does not.  BB_EVAL_CACHE=0 turns it off,
+// BB_EVAL_CACHE_LOG2 sizes it -- tuning knobs, read from the environment at bb_create / bb_fit_slots.
 static size_t eval_cache_entry_bytes(const bb_config *cfg) { return cfg->game == BB_GAME_DRAGONCHESS ? 128 : 64; }
 static int eval_cache_log2_of(const bb_config *cfg) {
+    const bool rounds_too = cfg->game == BB_GAME_CONNECT4; // (DragonChess has no round structure)
     if ((cfg->game != BB_GAME_CONNECT4 && cfg->game != BB_GAME_DRAGONCHESS) || cfg->mcts_kind != BB_MCTS_DYNAMIC ||
-        cfg->evaluator != BB_EVAL_NET || cfg->launch != BB_LAUNCH_AUTO)
+        cfg->evaluator != BB_EVAL_NET || !(cfg->launch == BB_LAUNCH_AUTO || (rounds_too && cfg->launch == BB_LAUNCH_ROUNDS)))
         return 0;
     const char *on = getenv("BB_EVAL_CACHE"), *lg = getenv("BB_EVAL_CACHE_LOG2");
     if (on && atoi(on) == 0) return 0;
@@ -472,7 +484,7 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
     if (int v = env_int("BB_TREE_GPW", 0); v >= 1 && v <= 64 / e->info.S) d.gpw = v;
     d.temp = 1.0;
     GAME_SWITCH(cfg->game, rc = engine_alloc<G>(e); break);
-    if (!rc && (e->mega || e->dc_fused)) {
+    if (!rc) { // (a configuration that owns a table plays through a structure that probes it: eval_cache_log2_of)
         if (const int k = eval_cache_log2_of(cfg)) {
             uint8_t *tab = nullptr;
             e->eval_cache_bytes = eval_cache_entry_bytes(cfg) << k;
@@ -482,6 +494,7 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
         }
     }
     if (!rc) rc = dalloc(e, d.eval_cache_ctr, 2);
+    if (!rc && d.eval_cache && e->async_selfplay) rc = dalloc(e, e->miss_count, 8) || dalloc(e, e->miss_slot, (size_t)cfg->n_slots);
     if (rc) {
         bb_destroy(e);
         return rc;
@@ -720,7 +733,9 @@ static int load_general_weights(bb_engine *e, const bb_net_weights *w) {
 template <class G>
 static int launch_gnet(bb_engine *e, int n_max, const int *n_ptr, const int *slot_list, const typename G::State *states,
                        const int8_t *planes, const uint32_t *game_id, const int32_t *serial, int noise, float *value,
-                       float *logits, float *policy, int pstride, hipStream_t st, int buf_offset = 0) {
+                       float *logits, float *policy, int pstride, hipStream_t st, int buf_offset = 0,
+                       EvalCache store = {nullptr, 0}) {
+    // store: the evaluation cache the heads fill (the batch is a round's miss list: eval_probe.hip.h)
     // buf_offset: first position of the activation buffers this call may use (the two slot-range views of pipelined
     // rounds run on two streams at once and must not share scratch)
     using GG = GNetGeom<G>;
@@ -785,7 +800,7 @@ static int launch_gnet(bb_engine *e, int n_max, const int *n_ptr, const int *slo
         k_gnet_conv<G, false><<<grid, 256, 0, st>>>(g, 1 + l, n_max, n_ptr, g.act[l & 1], g.act[(l & 1) ^ 1], l & 1, ppw);
     }
     k_gnet_heads<G><<<(n_max + 3) / 4, 256, 0, st>>>(g, e->net, n_max, n_ptr, slot_list, g.act[0], game_id, serial, noise, value,
-                                                     logits, policy, pstride);
+                                                     logits, policy, pstride, store, planes ? nullptr : states);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }
@@ -1014,7 +1029,7 @@ static int launch_net(bb_engine *e, int n, const typename G::State *states, cons
     {
         if (e->x3.w0) { // one position per wave on the bf16 pipe: the same arithmetic everywhere (bb_net_eval, search, self-play)
             k_net_x3<G><<<(n + 3) / 4, 256, 0, st>>>(e->net, e->x3, n, nullptr, nullptr, states, planes, game_id, serial, noise, value,
-                                                     logits, policy, pstride);
+                                                     logits, policy, pstride, EvalCache{nullptr, 0});
             HIPCHK(hipGetLastError());
             return BB_OK;
         }
@@ -1461,8 +1476,10 @@ extern "C" int bb_selfplay_begin(bb_engine *e, int n_games, double temp) {
     HIPCHK(hipMemsetAsync(e->dev.game_hdr, 0, (size_t)e->cfg.max_games * 16, e->stream));
     HIPCHK(hipMemsetAsync(e->dev.resume_cur, 0xFF, (size_t)e->dev.n_slots * 4, e->stream));
     HIPCHK(hipMemsetAsync(e->dev.post_count, 0, 8 * sizeof(int), e->stream));
+    if (e->miss_count) HIPCHK(hipMemsetAsync(e->miss_count, 0, 8 * sizeof(int), e->stream));
     HIPCHK(sync_all(e));
     e->vround[0] = e->vround[1] = 0;
+    e->miss_next[0] = e->miss_next[1] = 0;
     GAME_SWITCH(e->cfg.game, {
         if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
             k_dc_selfplay_begin<<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev, e->edges);
@@ -1537,20 +1554,39 @@ static int selfplay_rounds_async(bb_engine *e, int rounds) {
                     bool timed = v == 0 && e->time_every > 0 && (e->eval_launches++ % (uint64_t)e->time_every) == 0 &&
                                  e->ev_used + 2 <= e->ev_pool.size();
                     if (timed) HIPCHK(hipEventRecord(e->ev_pool[e->ev_used], st));
+                    // the round's batch: the posted leaves -- or, with the evaluation cache, those of them that the probe kernel
+                    // did not answer from the table (eval_probe.hip.h); the heads of these store their entries
+                    const int *n_ptr = d.post_count + (round & 3), *slot_list = d.post_slot;
+                    EvalCache store = {nullptr, 0};
+                    if constexpr (G::CACHE_KEY) {
+                        if (d.eval_cache && e->miss_count && e->general_net) {
+                            store = {(u32x4 *)d.eval_cache, d.eval_cache_log2};
+                            int *mc = e->miss_count + 4 * v, *ms = e->miss_slot + d.slot_offset;
+                            if (e->miss_next[v] != round) // (weights of the other kind were loaded in between: unprobed rounds)
+                                HIPCHK(hipMemsetAsync(mc, 0, 4 * sizeof(int), st));
+                            e->miss_next[v] = round + 1;
+                            k_eval_cache_probe<G><<<(d.n_slots + 3) / 4, 256, 0, st>>>(e->net, store, n_ptr, slot_list, mc, round, ms, ls,
+                                                                                       d.leaf_game_id, d.leaf_serial, e->cfg.noise_on,
+                                                                                       d.eval_value, d.eval_policy, G::S, d.evals,
+                                                                                       d.eval_cache_ctr);
+                            n_ptr = mc + (round & 3);
+                            slot_list = ms;
+                        }
+                    }
                     if (e->general_net) {
-                        int rc = launch_gnet<G>(e, d.n_slots, d.post_count + (round & 3), d.post_slot, ls, nullptr, d.leaf_game_id,
+                        int rc = launch_gnet<G>(e, d.n_slots, n_ptr, slot_list, ls, nullptr, d.leaf_game_id,
                                                 d.leaf_serial, e->cfg.noise_on, d.eval_value, nullptr, d.eval_policy, G::S, st,
-                                                d.slot_offset);
+                                                d.slot_offset, store);
                         if (rc) return rc;
                     } else if (e->x3.w0) {
                         if constexpr (G::C <= 4)
-                            k_net_x3<G><<<(d.n_slots + 3) / 4, 256, 0, st>>>(e->net, e->x3, 0, d.post_count + (round & 3), d.post_slot, ls,
+                            k_net_x3<G><<<(d.n_slots + 3) / 4, 256, 0, st>>>(e->net, e->x3, 0, n_ptr, slot_list, ls,
                                                                               nullptr, d.leaf_game_id, d.leaf_serial, e->cfg.noise_on,
-                                                                              d.eval_value, nullptr, d.eval_policy, G::S);
+                                                                              d.eval_value, nullptr, d.eval_policy, G::S, store);
                     } else
-                    k_net_compact<G, PWMAX><<<nb, 256, 0, st>>>(e->net, d.post_count + (round & 3), d.post_slot, ls,
+                    k_net_compact<G, PWMAX><<<nb, 256, 0, st>>>(e->net, n_ptr, slot_list, ls,
                                                                  d.leaf_game_id, d.leaf_serial, e->cfg.noise_on, d.eval_value,
-                                                                 d.eval_policy, G::S);
+                                                                 d.eval_policy, G::S, store);
                     HIPCHK(hipGetLastError());
                     if (timed) {
                         HIPCHK(hipEventRecord(e->ev_pool[e->ev_used + 1], st));

@@ -237,11 +237,12 @@ __global__ void __launch_bounds__(256) k_gnet_conv(GNetDev gd, int layer, int n_
 }
 
 // ---- heads: one wave per position ----------------------------------------------------------------------------------
+// store / states: the evaluation cache the heads fill for a round's miss list (net.hip.h eval_cache_store_entry; null table: off)
 template <class G>
 __global__ void __launch_bounds__(256) k_gnet_heads(GNetDev gd, NetDev nd, int n_max, const int *n_ptr, const int *slot_list,
                                                     const float *act, const uint32_t *game_id, const int32_t *serial,
                                                     int noise, float *value_out, float *logits_out, float *policy_out,
-                                                    int pstride) {
+                                                    int pstride, EvalCache store, const typename G::State *states) {
     using GG = GNetGeom<G>;
     constexpr int HW = GG::HW, W = GG::W, PLANE = GG::PLANE, A = G::A;
     __shared__ float scratch[4][3 * HW + 64 + 2 * (A <= 64 ? A : 0) + 8];
@@ -271,5 +272,6 @@ __global__ void __launch_bounds__(256) k_gnet_heads(GNetDev gd, NetDev nd, int n
         rp[2 * q + 1] = fmaxf(__builtin_fmaf(a1, p6[3], p6[5]), 0.f);
     }
     wave_lds_handover();
-    net_head_tail<G, 1>(nd, n, pos, slot_list, rv, rp, game_id, serial, noise, value_out, logits_out, policy_out, pstride);
+    net_head_tail<G, 1>(nd, n, pos, slot_list, rv, rp, game_id, serial, noise, value_out, logits_out, policy_out, pstride, nullptr, store,
+                        states);
 }

@@ -427,12 +427,28 @@ __device__ __forceinline__ void head_one(const NetDev &nd, float R, float R0, fl
     }
 }
 
+// The evaluation cache entry that head_one fills for the position in `states[pos]` (asynchronous rounds: the probe kernel,
+// eval_probe.hip.h, put it on the miss list; the key is formed again here, nothing is carried through the tower).
+// Null when the cache is off, for a game without a key and for a board without one.
+template <class G>
+__device__ __forceinline__ u32x4 *eval_cache_store_entry(const EvalCache &store, const typename G::State *states, int pos, bool live,
+                                                         uint64_t &key) {
+    key = 0;
+    if constexpr (G::CACHE_KEY) {
+        if (store.tab && states && live) key = G::cache_key(states[pos]);
+        if (key) return eval_cache_entry(store, key);
+    }
+    return nullptr;
+}
+
 // The same for PW positions whose per-pixel head activations sit in memory (LDS): rv[PW*HW], rp[PW*HW][2].
+// store / states: see eval_cache_store_entry.
 template <class G, int PW>
 __device__ __forceinline__ void net_head_tail(const NetDev &nd, int n, int pos0, const int *slot_list, const float *rv,
                                               const float *rp, const uint32_t *game_id, const int32_t *serial, int noise,
                                               float *value_out, float *logits_out, float *policy_out, int pstride,
-                                              WideHead *compact = nullptr) {
+                                              WideHead *compact = nullptr, EvalCache store = {nullptr, 0},
+                                              const typename G::State *states = nullptr) {
     constexpr int HW = G::H * G::W;
     static_assert(HW <= 64, "one lane per pixel of a position");
     const int lane = threadIdx.x & 63;
@@ -442,8 +458,10 @@ __device__ __forceinline__ void net_head_tail(const NetDev &nd, int n, int pos0,
         const int pos = live ? (slot_list ? slot_list[pos0 + pp] : pos0 + pp) : 0;
         const float x = lane < HW ? rv[pp * HW + lane] : 0.f;
         const float x0 = lane < HW ? rp[2 * (pp * HW + lane)] : 0.f, x1 = lane < HW ? rp[2 * (pp * HW + lane) + 1] : 0.f;
+        uint64_t ckey;
+        u32x4 *centry = eval_cache_store_entry<G>(store, states, pos, live, ckey);
         head_one<G>(nd, pooled_sum(x), pooled_sum(x0), pooled_sum(x1), pos, live, game_id, serial, noise, value_out, logits_out,
-                    policy_out, pstride, compact ? compact + pp : nullptr);
+                    policy_out, pstride, compact ? compact + pp : nullptr, centry, ckey);
     }
 }
 
@@ -451,13 +469,13 @@ __device__ __forceinline__ void net_head_tail(const NetDev &nd, int n, int pos0,
 // own LDS region `wlds` (NetGeom<G,PW>::WAVE_FLOATS floats).  slot_list != nullptr: batch entry i is
 // engine slot slot_list[i] (inputs are read from, and outputs written to, that slot's mailbox).
 // WMODE: how the tower's operands reach the MFMAs (see conv_layer below): 0 plain, 1 weights from L2 with next-layer
-// prefetch, 2 weights in LDS with next-tap prefetch.
+// prefetch, 2 weights in LDS with next-tap prefetch.  store: the evaluation cache the heads fill (eval_cache_store_entry).
 template <class G, int PW, int WMODE = 0>
 __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, const int *slot_list, float *wlds,
                                          const typename G::State *states, const int8_t *planes,
                                          const uint32_t *game_id, const int32_t *serial, int noise, float *value_out,
                                          float *logits_out, float *policy_out, int pstride, bool zero_lds = true,
-                                         WideHead *compact = nullptr) {
+                                         WideHead *compact = nullptr, EvalCache store = {nullptr, 0}) {
     using NG = NetGeom<G, PW>;
     constexpr int W = NG::W, CIN = NG::CIN, HW = NG::HW, SLOTS = NG::SLOTS, CP = NG::CP, NT = NG::NT,
                   STEPS0 = NG::STEPS0, ACT = NG::ACT, PLANE = NG::PLANE;
@@ -774,8 +792,11 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
         if (lane < HW) head_convs(lane, x, x0, x1);
         NSTAMP(3);
         const bool live = pos0 < n;
-        head_one<G>(nd, pooled_sum(x), pooled_sum(x0), pooled_sum(x1), live ? OI(pos0) : 0, live, game_id, serial, noise, value_out,
-                    logits_out, policy_out, pstride, compact);
+        const int opos = live ? OI(pos0) : 0;
+        uint64_t ckey;
+        u32x4 *centry = eval_cache_store_entry<G>(store, planes ? nullptr : states, opos, live, ckey);
+        head_one<G>(nd, pooled_sum(x), pooled_sum(x0), pooled_sum(x1), opos, live, game_id, serial, noise, value_out,
+                    logits_out, policy_out, pstride, compact, centry, ckey);
         NSTAMP(4);
     } else {
         float *rv = actB;               // [PW*HW] value-conv output
@@ -790,7 +811,7 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
         wave_lds_handover();
         NSTAMP(3);
         net_head_tail<G, PW>(nd, n, pos0, slot_list, rv, rp, game_id, serial, noise, value_out, logits_out, policy_out, pstride,
-                             compact);
+                             compact, store, planes ? nullptr : states);
         NSTAMP(4);
         if (!zero_lds) { // persistent caller: the head scratch overlaid actB's halo slots -- restore the zeros
             wave_lds_handover();
@@ -817,12 +838,13 @@ k_net_fused16(NetDev nd, int n, const typename G::State *states, const int8_t *p
 
 // Compacted batch: *n_ptr leaves were posted this round (slots listed in slot_list).  The grid is always
 // 256 workgroups x 4 waves; the leaves are dealt evenly, pw = ceil(n / 1024) per wave, so a round with
-// fewer fresh leaves runs fewer MFMA tiles per wave instead of leaving CUs idle.
+// fewer fresh leaves runs fewer MFMA tiles per wave instead of leaving CUs idle.  store: the evaluation cache whose probe
+// kernel made this list (eval_probe.hip.h); off when its table is null.
 template <class G, int PWMAX>
 __global__ void __launch_bounds__(256, 1)
 k_net_compact(NetDev nd, const int *n_ptr, const int *slot_list, const typename G::State *states,
               const uint32_t *game_id, const int32_t *serial, int noise, float *value_out, float *policy_out,
-              int pstride) {
+              int pstride, EvalCache store) {
     __shared__ __attribute__((aligned(16))) float lds[4 * NetGeom<G, PWMAX>::WAVE_FLOATS];
     const int n = *n_ptr;
     const int wave = threadIdx.x >> 6, gw = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
@@ -832,9 +854,9 @@ k_net_compact(NetDev nd, const int *n_ptr, const int *slot_list, const typename 
     if (pos0 >= n) return;
     float *wl = lds + wave * NetGeom<G, PWMAX>::WAVE_FLOATS;
     switch (pw) {
-    case 1: net_body<G, 1>(nd, n, pos0, slot_list, wl, states, nullptr, game_id, serial, noise, value_out, nullptr, policy_out, pstride); break;
-    case 2: net_body<G, 2>(nd, n, pos0, slot_list, wl, states, nullptr, game_id, serial, noise, value_out, nullptr, policy_out, pstride); break;
-    case 3: net_body<G, 3>(nd, n, pos0, slot_list, wl, states, nullptr, game_id, serial, noise, value_out, nullptr, policy_out, pstride); break;
-    default: net_body<G, PWMAX>(nd, n, pos0, slot_list, wl, states, nullptr, game_id, serial, noise, value_out, nullptr, policy_out, pstride); break;
+    case 1: net_body<G, 1>(nd, n, pos0, slot_list, wl, states, nullptr, game_id, serial, noise, value_out, nullptr, policy_out, pstride, true, nullptr, store); break;
+    case 2: net_body<G, 2>(nd, n, pos0, slot_list, wl, states, nullptr, game_id, serial, noise, value_out, nullptr, policy_out, pstride, true, nullptr, store); break;
+    case 3: net_body<G, 3>(nd, n, pos0, slot_list, wl, states, nullptr, game_id, serial, noise, value_out, nullptr, policy_out, pstride, true, nullptr, store); break;
+    default: net_body<G, PWMAX>(nd, n, pos0, slot_list, wl, states, nullptr, game_id, serial, noise, value_out, nullptr, policy_out, pstride, true, nullptr, store); break;
     }
 }

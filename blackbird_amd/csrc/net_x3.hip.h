@@ -183,6 +183,8 @@ __device__ __forceinline__ bf16x8 x3_ldg(const unsigned char *p) {
 // tested after it -- on a miss the probe's latency hides under the prologue.  A hit skips the tower and the heads and runs only
 // dense_prior_tail on the cached value / priors; a miss stores them in head_one.  *probe_out: -1 no probe (cache off, or a
 // board without a key), 0 miss, 1 hit.
+// Without CACHE a non-null `cache` is store-only (asynchronous rounds: the probe kernel of eval_probe.hip.h has looked the
+// position up already and put it on the miss list): head_one fills the entry, nothing is probed here.
 template <class G, bool WLDS, bool PP = false, bool CACHE = false>
 __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, int n, int pos0, const int *slot_list,
                                             unsigned char *wl, const typename G::State *states, const int8_t *planes,
@@ -757,6 +759,8 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
             ckey = G::cache_key(states[OI(pos0)]);
             centry = eval_cache_entry(cache, ckey);
         }
+    } else if constexpr (!PP) {
+        centry = eval_cache_store_entry<G>(cache, planes ? nullptr : states, live ? OI(pos0) : 0, live, ckey);
     }
     head_one<G>(nd, R, R0, R1, live ? OI(pos0) : 0, live, game_id, serial, noise, value_out,
                 logits_out, policy_out, pstride, compact, centry, ckey);
@@ -772,11 +776,11 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
 #undef aH3
 #undef iA
 // bb_net_eval / lock-step and asynchronous-round search: one position per wave, four waves per workgroup, the packed
-// weights streamed from L2
+// weights streamed from L2.  store: the evaluation cache the heads fill for a round's miss list (null table: off)
 template <class G>
 __global__ void __launch_bounds__(256) k_net_x3(NetDev nd, NetX3 x3, int n, const int *n_ptr, const int *slot_list, const typename G::State *states,
                                                 const int8_t *planes, const uint32_t *game_id, const int32_t *serial, int noise,
-                                                float *value_out, float *logits_out, float *policy_out, int pstride) {
+                                                float *value_out, float *logits_out, float *policy_out, int pstride, EvalCache store) {
     using XG = X3Geom<G>;
     __shared__ __attribute__((aligned(16))) unsigned char lds[4 * XG::WAVE_BYTES];
     const int wave = threadIdx.x >> 6;
@@ -784,5 +788,5 @@ __global__ void __launch_bounds__(256) k_net_x3(NetDev nd, NetX3 x3, int n, cons
     if (n_ptr) n = *n_ptr; // compacted batch of an asynchronous round: the leaves posted this round, slots in slot_list
     if (pos0 >= n) return;
     net_body_x3<G, false>(nd, x3, n, pos0, slot_list, lds + wave * XG::WAVE_BYTES, states, planes, game_id, serial, noise, value_out,
-                          logits_out, policy_out, pstride, true);
+                          logits_out, policy_out, pstride, true, nullptr, store);
 }

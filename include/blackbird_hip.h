@@ -161,7 +161,7 @@ typedef struct {
     uint64_t overflow;        /* simulations cut short by pool/path limits (must be 0) */
     uint64_t examples;        /* examples stored */
     uint64_t evals;           /* network tower runs (< sims when known terminal values are reused; evaluation-cache hits not included) */
-    uint64_t eval_cache_hits;   /* evaluations served by the evaluation cache (persistent Connect4 and one-wave-per-game DragonChess self-play) */
+    uint64_t eval_cache_hits;   /* evaluations served by the evaluation cache: Connect4 self-play in the persistent kernel and in asynchronous rounds (any network, BB_LAUNCH_ROUNDS), one-wave-per-game DragonChess self-play; the lock-step search (bb_run_sims) does not probe */
     uint64_t eval_cache_probes; /* evaluations that looked it up: hits + the tower runs among them */
 } bb_counters;
 
