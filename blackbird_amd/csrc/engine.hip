@@ -227,6 +227,7 @@ struct bb_engine {
     // leaves it alone.
     int *miss_count = nullptr; // [8]
     int *miss_slot = nullptr;  // [n_slots]
+    unsigned char *miss_way = nullptr; // [n_slots] the way of its bucket a missed slot's entry goes to
     int miss_next[2] = {0, 0}; // per view: the round whose counter the last probe launch cleared ahead (the rotation holds only across consecutive probed rounds)
     bool mega = false; // persistent per-CU self-play kernel with an LDS work queue (mega2.hip.h)
     bool async_selfplay = false; // dense games, DynamicMCTS, deterministic evaluators: k_tree_async rounds
@@ -341,7 +342,9 @@ static void make_views(bb_engine *e) {
 
 // ---- pool sizing ------------------------------------------------------------------------------------------------
 // log2 of the entries of the evaluation cache (net.hip.h EvalCache) an engine of this configuration owns, 0 = none.
-// Connect4 self-play (64-byte entries; default 2^26: 4 GiB) probes it in the persistent kernel (mega2.hip.h) and in the
+// Connect4 self-play (64-byte entries in two-way buckets; default 2^27: 8 GiB -- the smallest table whose games/s is within
+// the run-to-run spread of the best, and the largest that bb_create still allocates in milliseconds: DESIGN.md section 11)
+// probes it in the persistent kernel (mega2.hip.h) and in the
 // asynchronous rounds that any other network or BB_LAUNCH_ROUNDS runs as (eval_probe.hip.h); DragonChess in its
 // one-wave-per-game kernel (mega_dc.hip.h, 128-byte entries; default 2^24: 2 GiB, ~16 M positions against the ~0.4 M a ply
 // of 1024 games evaluates, next to pools of ~190 GB).  The lock-step search does not.  BB_EVAL_CACHE=0 turns it off,
@@ -354,7 +357,7 @@ static int eval_cache_log2_of(const bb_config *cfg) {
         return 0;
     const char *on = getenv("BB_EVAL_CACHE"), *lg = getenv("BB_EVAL_CACHE_LOG2");
     if (on && atoi(on) == 0) return 0;
-    const int k = lg ? atoi(lg) : cfg->game == BB_GAME_DRAGONCHESS ? 24 : 26;
+    const int k = lg ? atoi(lg) : cfg->game == BB_GAME_DRAGONCHESS ? 24 : 27;
     return k < 10 ? 10 : k > 32 ? 32 : k;
 }
 
@@ -494,7 +497,8 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
         }
     }
     if (!rc) rc = dalloc(e, d.eval_cache_ctr, 2);
-    if (!rc && d.eval_cache && e->async_selfplay) rc = dalloc(e, e->miss_count, 8) || dalloc(e, e->miss_slot, (size_t)cfg->n_slots);
+    if (!rc && d.eval_cache && e->async_selfplay)
+        rc = dalloc(e, e->miss_count, 8) || dalloc(e, e->miss_slot, (size_t)cfg->n_slots) || dalloc(e, e->miss_way, (size_t)cfg->n_slots);
     if (rc) {
         bb_destroy(e);
         return rc;
@@ -1560,12 +1564,13 @@ static int selfplay_rounds_async(bb_engine *e, int rounds) {
                     EvalCache store = {nullptr, 0};
                     if constexpr (G::CACHE_KEY) {
                         if (d.eval_cache && e->miss_count && e->general_net) {
-                            store = {(u32x4 *)d.eval_cache, d.eval_cache_log2};
+                            store = {(u32x4 *)d.eval_cache, d.eval_cache_log2, e->miss_way + d.slot_offset};
                             int *mc = e->miss_count + 4 * v, *ms = e->miss_slot + d.slot_offset;
                             if (e->miss_next[v] != round) // (weights of the other kind were loaded in between: unprobed rounds)
                                 HIPCHK(hipMemsetAsync(mc, 0, 4 * sizeof(int), st));
                             e->miss_next[v] = round + 1;
-                            k_eval_cache_probe<G><<<(d.n_slots + 3) / 4, 256, 0, st>>>(e->net, store, n_ptr, slot_list, mc, round, ms, ls,
+                            k_eval_cache_probe<G><<<(d.n_slots + 3) / 4, 256, 0, st>>>(e->net, store, n_ptr, slot_list, mc, round, ms,
+                                                                                       e->miss_way + d.slot_offset, ls,
                                                                                        d.leaf_game_id, d.leaf_serial, e->cfg.noise_on,
                                                                                        d.eval_value, d.eval_policy, G::S, d.evals,
                                                                                        d.eval_cache_ctr);

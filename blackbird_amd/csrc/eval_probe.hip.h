@@ -7,12 +7,13 @@
 //         (game id, serial), i.e. the node's prior noise drawn exactly as head_one draws it -- and taken back out of
 //         d.evals[slot], which keeps counting tower runs (mega2.hip.h does the same);
 //   miss: the slot goes on a second compacted list (miss_count / miss_slot), which is what the network launches take; their
-//         heads store the entry (head_one's cache_entry; the key is formed from the leaf state again there).
+//         heads store the entry (head_one's cache_entry; the key is formed from the leaf state again there) into the way of
+//         the bucket that the probe chose from the keys it read (miss_way[slot]: eval_cache_pick_way).
 // A board without a key (G::cache_key == 0) is a miss that is neither probed nor stored.  The table rules are those of
 // net.hip.h: 16-byte single-lane accesses, every chunk carries its own key, no fences, key 0 never probed or stored.
 // Nothing depends on two leaves of a round being different positions: two hits of a key read the same entry, two misses
-// both run the tower and store the same bits (duplicates inside a round are not merged), and a probe that reads an entry
-// while another view's head stores it sees either all four chunks of its key or a miss.
+// both run the tower and store the same bits into the same way (duplicates inside a round are not merged), and a probe that
+// reads an entry while another view's head stores it sees either all four chunks of its key or a miss.
 #pragma once
 #include "net.hip.h"
 
@@ -22,6 +23,7 @@
 template <class G>
 __global__ void __launch_bounds__(256)
 k_eval_cache_probe(NetDev nd, EvalCache cache, const int *n_ptr, const int *slot_list, int *miss_count, int round, int *miss_slot,
+                   unsigned char *miss_way,
                    const typename G::State *states, const uint32_t *game_id, const int32_t *serial, int noise, float *value_out,
                    float *policy_out, int pstride, uint64_t *evals, unsigned long long *ctr) {
     static_assert(G::CACHE_KEY, "a game whose positions have a one-word key (Connect4)");
@@ -30,15 +32,16 @@ k_eval_cache_probe(NetDev nd, EvalCache cache, const int *n_ptr, const int *slot
     const int n = *n_ptr, pos = blockIdx.x * 4 + wave;
     const bool live = pos < n;
     // clamped addresses, selected afterwards: no load sits in a divergent branch (entry 0 of a list that was zeroed at
-    // allocation is a slot number, key 0 maps to the table's entry 0); what depends on `live` alone is a uniform branch
+    // allocation is a slot number, key 0 maps to the table's bucket 0); what depends on `live` alone is a uniform branch
     const int slot = slot_list[live ? pos : 0];
     const typename G::State st = states[slot];
     const uint64_t key = live ? G::cache_key(st) : 0; // (wave-uniform)
-    u32x4 *const entry = eval_cache_entry(cache, key);
-    const u32x4 chunk = eval_cache_load(entry, lane); // issued before anything that does not depend on it
+    u32x4 *const bucket = eval_cache_bucket(cache, key);
+    const u32x4 chunk = eval_cache_load(bucket, lane); // issued before anything that does not depend on it
     if (blockIdx.x == 0 && threadIdx.x == 0) miss_count[(round + 2) & 3] = 0;
     float cv = 0.f, cpr = 0.f;
-    const bool hit = eval_cache_hit<G::A>(chunk, key, lane, cv, cpr) && key != 0; // (an empty entry carries key 0)
+    int way = 0;
+    const bool hit = eval_cache_hit<G>(chunk, key, lane, cv, cpr, way) && key != 0; // (an empty entry carries key 0)
     if (hit) {
         if (lane == 0) {
             value_out[slot] = cv;
@@ -48,6 +51,7 @@ k_eval_cache_probe(NetDev nd, EvalCache cache, const int *n_ptr, const int *slot
     }
     if (lane == 0) {
         s_slot[wave] = live && !hit ? slot : -1;
+        if (live && !hit) miss_way[slot] = (unsigned char)way;
         s_probe[wave] = key ? 1 + (int)hit : 0;
     }
     __syncthreads();

@@ -198,6 +198,16 @@ struct GridGame {
         if (!DROP || (b1 & b2) || (occ & ~board_mask()) || (occ & ~above)) return 0;
         return b1 | (above & ~occ) | ((uint64_t)(gs_player(s) == 1) << 63);
     }
+    // The stones on the board of a (non-zero) key: a column's sentinel is its highest bit, smeared down the column it covers
+    // height + 1 cells (the evaluation cache ranks the positions of a bucket by it: net.hip.h eval_cache_pick_way).
+    BB_HD static int key_stones(uint64_t key) {
+        static_assert(H + 1 <= 8 && (H + 1) * STR <= 63, "three doubling steps reach the floor; bit 63 is the player");
+        uint64_t f = key & ~(1ull << 63);
+        f |= f >> STR;
+        f |= f >> (2 * STR);
+        f |= f >> (4 * STR);
+        return bb_popc64(f) - W;
+    }
 };
 
 // Bijective 64-bit mix (the murmur3 finaliser: xor-shifts and odd multipliers): spreads cache keys over the table's slots.
@@ -212,6 +222,25 @@ BB_HD uint64_t bb_mix64(uint64_t z) {
 
 using Connect4 = GridGame<6, 7, 4, 8, 7, 8, 0>;
 using TicTacToe = GridGame<3, 3, 3, 4, 9, 16, 1>;
+
+// The way of its bucket (evaluation cache, net.hip.h: two entries per bucket) a missed position `key` is stored into.
+// whole0 / whole1: the way holds one position, i.e. its four chunks carry one non-zero key (else it is empty, or torn by a
+// store in flight: free either way); occ0: that key of way 0.  An empty or torn way is taken first.  Otherwise way 0 is the kept way -- replaced only by a position with no more stones than its occupant (a
+// shallow position is reachable by more games and by more later searches of one game: the two-tier transposition-table
+// rule) -- and way 1 is always replaced.
+template <class G>
+BB_HD int eval_cache_pick_way(uint64_t key, bool whole0, uint64_t occ0, bool whole1) {
+    if (!whole0) return 0;
+    if (!whole1) return 1;
+    return G::key_stones(key) <= G::key_stones(occ0) ? 0 : 1;
+}
+// the same from the eight chunk keys of a bucket as they sit in memory (the host-side statement of the rule: tests)
+template <class G>
+BB_HD int eval_cache_pick_way_of(uint64_t key, const uint64_t k[8]) {
+    const bool whole0 = k[0] != 0 && k[1] == k[0] && k[2] == k[0] && k[3] == k[0];
+    const bool whole1 = k[4] != 0 && k[5] == k[4] && k[6] == k[4] && k[7] == k[4];
+    return eval_cache_pick_way<G>(key, whole0, k[0], whole1);
+}
 
 // ------------------------------------------------------------------------------------------------
 // DragonChess (DragonChess.py:10-371): White = K + 3 pawns and moves twice per turn, Black = full army,

@@ -201,21 +201,28 @@ __device__ __forceinline__ void wide_head_stats(WideHead &h, PK pdk, PK pdb, int
 __device__ __forceinline__ float pooled_sum(float v) { return wave_sum_f32(v); }
 
 // ---- evaluation cache (persistent kernels: Connect4 here, DragonChess below; the table is device memory of the engine: engine.hip) ----
-// Direct-mapped: 2^log2 entries of 64 bytes, the slot of a position is the top bits of bb_mix64(G::cache_key).  An entry is four
-// 16-byte chunks {u64 key, f32, f32} that hold [value, p0 .. p6], the network's value and its priors BEFORE the prior noise:
-// chunk c carries floats 2c and 2c + 1.  Every chunk is written and read as ONE 16-byte vector access of ONE lane, and counts
-// only if its own key matches -- an entry read while another position's is written over it is then a miss, never a mix.
-// That relies on aligned 16-byte accesses not tearing: observed on gfx950 (single-lane dwordx4 loads and stores), not
-// guaranteed by the architecture.  Evaluation is deterministic, so two writers of one key write the same bits, and chunks
-// of theirs may mix freely.  No fences: a store that another CU does not see yet (its L2 is another XCD's) only turns a hit
-// into a miss.  A zeroed table is empty (a key is never 0); the engine zeroes it whenever weights are loaded.
+// Two-way set-associative: 2^log2 entries of 64 bytes in buckets of two, a bucket is ONE 128-byte line and is picked by the top
+// bits of bb_mix64(G::cache_key).  An entry (a "way") is four 16-byte chunks {u64 key, f32, f32} that hold [value, p0 .. p6], the
+// network's value and its priors BEFORE the prior noise: chunk c carries floats 2c and 2c + 1.  Every chunk is written and read
+// as ONE 16-byte vector access of ONE lane, and counts only if its own key matches -- an entry read while another position's
+// is written over it is then a miss, never a mix.  That relies on aligned 16-byte accesses not tearing: observed on gfx950
+// (single-lane dwordx4 loads and stores), not guaranteed by the architecture.  Evaluation is deterministic, so two writers of
+// one key write the same bits, and chunks of theirs may mix freely.  No fences: a store that another CU does not see yet (its
+// L2 is another XCD's) only turns a hit into a miss.  A zeroed table is empty (a key is never 0); the engine zeroes it
+// whenever weights are loaded.
+// A probe is one dwordx4 load on lanes 0 .. 7 (the whole bucket: one line, one round trip); a hit is "all four chunks of way 0
+// carry the key" or the same of way 1.  A miss stores into the way eval_cache_pick_way (games.hip.h) names, from the keys the probe has
+// read: way 0 keeps the shallower position, way 1 takes whatever comes.  A hit stores nothing, and whichever way an entry sits
+// in it holds the bits the tower produced: the replacement rule changes hit counts, never a result.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct EvalCache {
-    u32x4 *tab; // [2^log2][4] chunks; null: off
+    u32x4 *tab; // [2^(log2-1)][2][4] chunks; null: off
     int log2;
+    // store-only users (asynchronous rounds): the way the probe kernel chose for the position in slot s (eval_probe.hip.h)
+    const unsigned char *way = nullptr;
 };
-__device__ __forceinline__ u32x4 *eval_cache_entry(const EvalCache &c, uint64_t key) {
-    return c.tab + 4 * (size_t)(bb_mix64(key) >> (64 - c.log2));
+__device__ __forceinline__ u32x4 *eval_cache_bucket(const EvalCache &c, uint64_t key) {
+    return c.tab + 8 * (size_t)(bb_mix64(key) >> (65 - c.log2));
 }
 // lanes 0 .. 3 store chunk `lane` of the entry (value: wave-uniform; pr: action a's prior on lane a)
 template <int A>
@@ -227,21 +234,33 @@ __device__ __forceinline__ void eval_cache_put(u32x4 *entry, uint64_t key, float
         *(__attribute__((address_space(1))) u32x4 *)(void *)(entry + lane) =
             u32x4{(uint32_t)key, (uint32_t)(key >> 32), __float_as_uint(c == 0 ? value : lo), __float_as_uint(hi)};
 }
-// the probe: chunk `lane` of the entry on lanes 0 .. 3 (issued ahead; tested by eval_cache_hit)
-__device__ __forceinline__ u32x4 eval_cache_load(const u32x4 *entry, int lane) {
+// the probe: chunk `lane` of the bucket on lanes 0 .. 7 (issued ahead; tested by eval_cache_hit)
+__device__ __forceinline__ u32x4 eval_cache_load(const u32x4 *bucket, int lane) {
     u32x4 z = {0u, 0u, 0u, 0u};
-    if (lane < 4) z = *(const __attribute__((address_space(1))) u32x4 *)(const void *)(entry + lane);
+    if (lane < 8) z = *(const __attribute__((address_space(1))) u32x4 *)(const void *)(bucket + lane);
     return z;
 }
-// wave-uniform: all four chunks carry `key`; then the value and this lane's prior (lanes >= A: 0, as head_one leaves them)
-template <int A>
-__device__ __forceinline__ bool eval_cache_hit(u32x4 ch, uint64_t key, int lane, float &value, float &pr) {
-    const bool ok = lane < 4 && ch[0] == (uint32_t)key && ch[1] == (uint32_t)(key >> 32);
-    if ((__ballot(ok) & 0xFull) != 0xFull) return false;
+// wave-uniform: all four chunks of one way carry `key`; then the value and this lane's prior (lanes >= A: 0, as head_one
+// leaves them).  On a miss `way` is where the position is to be stored (eval_cache_pick_way on the keys just read).
+template <class G>
+__device__ __forceinline__ bool eval_cache_hit(u32x4 ch, uint64_t key, int lane, float &value, float &pr, int &way) {
+    constexpr int A = G::A;
+    const bool ok = lane < 8 && ch[0] == (uint32_t)key && ch[1] == (uint32_t)(key >> 32);
+    const unsigned m = (unsigned)__ballot(ok) & 0xFFu;
+    if ((m & 0x0Fu) != 0x0Fu && (m & 0xF0u) != 0xF0u) {
+        const uint64_t mine = (uint64_t)ch[0] | ((uint64_t)ch[1] << 32);
+        const uint64_t k0 = ((uint64_t)__builtin_amdgcn_readlane(ch[1], 0) << 32) | (uint32_t)__builtin_amdgcn_readlane(ch[0], 0);
+        const uint64_t k1 = ((uint64_t)__builtin_amdgcn_readlane(ch[1], 4) << 32) | (uint32_t)__builtin_amdgcn_readlane(ch[0], 4);
+        const unsigned w = (unsigned)__ballot(lane < 8 && mine != 0 && mine == (lane < 4 ? k0 : k1)) & 0xFFu;
+        way = eval_cache_pick_way<G>(key, (w & 0x0Fu) == 0x0Fu, k0, (w & 0xF0u) == 0xF0u);
+        return false;
+    }
+    const int o = (m & 0x0Fu) == 0x0Fu ? 0 : 4; // the matching way's first chunk
+    way = o >> 2;
     const float f0 = __uint_as_float(ch[2]), f1 = __uint_as_float(ch[3]);
-    value = lane_f32(f0, 0);
+    value = lane_f32(f0, o);
     const int i = (lane < A ? lane : 0) + 1; // float i of the entry: chunk i / 2, half i % 2
-    const float lo = __shfl(f0, i >> 1, 64), hi = __shfl(f1, i >> 1, 64);
+    const float lo = __shfl(f0, o + (i >> 1), 64), hi = __shfl(f1, o + (i >> 1), 64);
     pr = lane < A ? ((i & 1) ? hi : lo) : 0.f;
     return true;
 }
@@ -428,15 +447,15 @@ __device__ __forceinline__ void head_one(const NetDev &nd, float R, float R0, fl
 }
 
 // The evaluation cache entry that head_one fills for the position in `states[pos]` (asynchronous rounds: the probe kernel,
-// eval_probe.hip.h, put it on the miss list; the key is formed again here, nothing is carried through the tower).
-// Null when the cache is off, for a game without a key and for a board without one.
+// eval_probe.hip.h, put it on the miss list and left the way it chose in store.way[pos]; the key is formed again here,
+// nothing is carried through the tower).  Null when the cache is off, for a game without a key and for a board without one.
 template <class G>
 __device__ __forceinline__ u32x4 *eval_cache_store_entry(const EvalCache &store, const typename G::State *states, int pos, bool live,
                                                          uint64_t &key) {
     key = 0;
     if constexpr (G::CACHE_KEY) {
         if (store.tab && states && live) key = G::cache_key(states[pos]);
-        if (key) return eval_cache_entry(store, key);
+        if (key) return eval_cache_bucket(store, key) + 4 * (store.way ? store.way[pos] & 1 : 0);
     }
     return nullptr;
 }

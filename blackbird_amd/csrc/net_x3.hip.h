@@ -224,7 +224,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
     if constexpr (CACHE) {
         if (cache.tab && live && !planes) ckey = G::cache_key(my_state); // (wave-uniform)
         if (ckey) {
-            centry = eval_cache_entry(cache, ckey);
+            centry = eval_cache_bucket(cache, ckey);
             cchunk = eval_cache_load(centry, lane);
         }
         if (probe_out) *probe_out = ckey ? 0 : -1;
@@ -322,12 +322,17 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
     NSUB(7);
     if constexpr (CACHE) {
         float cv, cpr;
-        if (centry && eval_cache_hit<G::A>(cchunk, ckey, lane, cv, cpr)) { // the position was evaluated before: no tower, no heads
+        int cway = 0;
+        if (centry && eval_cache_hit<G>(cchunk, ckey, lane, cv, cpr, cway)) { // the position was evaluated before: no tower, no heads
             if (probe_out) *probe_out = 1;
             if (lane == 0 && value_out) value_out[OI(pos0)] = cv;
             dense_prior_tail<G>(nd, cpr, OI(pos0), true, game_id, serial, noise, policy_out, pstride, lane);
             return;
         }
+        // a miss: the way its store takes waits in the wave's LDS (the state area, unused by a board that is decoded from
+        // registers), not in a register through the tower
+        static_assert(!WIDE_IN && XG::STATE_B >= 4, "the state area is free");
+        if (lane == 0) *(int *)sst = cway;
     }
     // ---- per-tile addressing (bytes; X3Geom: tile_slot, swz).  Offsets are biased by the window's top-left tap, so every
     // tap of a row slice is a non-negative immediate on one address register.
@@ -757,7 +762,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
     if constexpr (CACHE) { // a miss: its entry again from the board (nothing held in registers through the tower)
         if (centry) {
             ckey = G::cache_key(states[OI(pos0)]);
-            centry = eval_cache_entry(cache, ckey);
+            centry = eval_cache_bucket(cache, ckey) + 4 * (*(const int *)sst & 1);
         }
     } else if constexpr (!PP) {
         centry = eval_cache_store_entry<G>(cache, planes ? nullptr : states, live ? OI(pos0) : 0, live, ckey);
