@@ -182,6 +182,19 @@ extern "C" int bb_game_initial(int game, void *state_out) {
 }
 
 // ---- engine ----------------------------------------------------------------------------------------
+// The launch structures of self-play (bb_selfplay_mode's values): lock-step launches per simulation (run_sims); dense games:
+// k_tree_async rounds + evaluator; persistent per-CU kernel with an LDS work queue (mega2.hip.h); DragonChess: mega_dc.hip.h
+enum { PLAY_LOCKSTEP = 0, PLAY_ROUNDS = 1, PLAY_QUEUE = 3, PLAY_DC_FUSED = 5 };
+// What a configuration asks for -- the ONE place that reads mcts_kind / evaluator / launch / game for this.  (Whether the
+// network fits a persistent kernel's LDS is known only at bb_load_weights: selfplay_structure.)
+static int selfplay_plan(const bb_config *cfg) {
+    const bool net_auto = cfg->evaluator == BB_EVAL_NET && cfg->launch == BB_LAUNCH_AUTO;
+    if (cfg->mcts_kind != BB_MCTS_DYNAMIC) return PLAY_LOCKSTEP;
+    if (cfg->game == BB_GAME_DRAGONCHESS) return net_auto ? PLAY_DC_FUSED : PLAY_LOCKSTEP;
+    if (net_auto) return PLAY_QUEUE; // (else rounds, for the deterministic evaluators)
+    return cfg->evaluator != BB_EVAL_ROLLOUT && (cfg->launch == BB_LAUNCH_AUTO || cfg->launch == BB_LAUNCH_ROUNDS) ? PLAY_ROUNDS : PLAY_LOCKSTEP;
+}
+
 struct bb_engine {
     bb_config cfg;
     bb_game_info info;
@@ -229,9 +242,7 @@ struct bb_engine {
     int *miss_slot = nullptr;  // [n_slots]
     unsigned char *miss_way = nullptr; // [n_slots] the way of its bucket a missed slot's entry goes to
     int miss_next[2] = {0, 0}; // per view: the round whose counter the last probe launch cleared ahead (the rotation holds only across consecutive probed rounds)
-    bool mega = false; // persistent per-CU self-play kernel with an LDS work queue (mega2.hip.h)
-    bool async_selfplay = false; // dense games, DynamicMCTS, deterministic evaluators: k_tree_async rounds
-    bool dc_fused = false;       // DragonChess, DynamicMCTS, 16-filter network: one wave keeps its game for a whole launch (mega_dc.hip.h)
+    int plan = PLAY_LOCKSTEP; // selfplay_plan(cfg); what it plays through once its network is known: selfplay_structure
     int round = 0;
     int time_every = 0;
     uint64_t eval_launches = 0;
@@ -262,6 +273,10 @@ static int dalloc(bb_engine *e, T *&p, size_t count, bool zero = true) {
     return 0;
 }
 
+#define SLOT_EXTENTS(G, max_plies) /* what the rows of BB_SLOT_ARRAYS (tree.hip.h) are written in */ \
+    constexpr size_t S = G::S, MP = G::MAXPATH, PS = G::GID == BB_GAME_DRAGONCHESS ? G::A : G::S; \
+    const size_t ANC = (size_t)((max_plies) + 2) * (G::GID == BB_GAME_DRAGONCHESS ? 2 : 1)
+
 template <class G>
 static int engine_alloc(bb_engine *e) {
     TreeDev &d = e->dev;
@@ -269,21 +284,14 @@ static int engine_alloc(bb_engine *e) {
     size_t n = (size_t)c.n_slots;
     constexpr bool DC = G::GID == BB_GAME_DRAGONCHESS;
     constexpr size_t NODE_BYTES = DC ? sizeof(DCNode) : sizeof(DenseNode<typename std::conditional<DC, Connect4, G>::type>);
-    constexpr size_t PSTRIDE = DC ? (size_t)G::A : (size_t)G::S;
     e->node_bytes = NODE_BYTES;
-    if (dalloc(e, d.root, n) || dalloc(e, d.root_N, n) || dalloc(e, d.n_nodes, n) || dalloc(e, d.ply, n) ||
-        dalloc(e, d.sims_left, n) || dalloc(e, d.pend_leaf, n) || dalloc(e, d.pend_expand, n) ||
-        dalloc(e, d.path_len, n) || dalloc(e, d.game_lid, n) || dalloc(e, d.sim_serial, n) ||
-        dalloc(e, d.root_W, n) || dalloc(e, d.root_pp, n) || dalloc(e, d.path, n * G::MAXPATH) ||
-        dalloc(e, d.anc, n * (size_t)(c.max_plies + 2) * (DC ? 2 : 1)) || dalloc(e, d.anc_len, n) || dalloc(e, d.top_N, n) ||
-        dalloc(e, d.path_N, n * G::MAXPATH) || dalloc(e, d.path_all, n * G::MAXPATH) || dalloc(e, d.path_W, n * G::MAXPATH) || dalloc(e, d.leaf_flags, n) ||
-        dalloc(e, d.leaf_game_id, n) || dalloc(e, d.leaf_serial, n) || dalloc(e, d.eval_value, n) ||
-        dalloc(e, d.eval_policy, n * PSTRIDE) || dalloc(e, d.ctr, n * 8) || dalloc(e, d.evals, n) || dalloc(e, d.out_action, n) ||
-        dalloc(e, d.out_root_plays, n) || dalloc(e, d.out_child_plays, n * G::S) ||
-        dalloc(e, d.out_root_winrate, n) || dalloc(e, d.out_child_value, n * G::S) || dalloc(e, e->d_u, n) ||
-        dalloc(e, e->d_actions, n) || dalloc(e, d.stamps, 16 * 64) || dalloc(e, d.visit_pool, 16) || dalloc(e, d.resume_cur, n) ||
-        dalloc(e, d.resume_depth, n) || dalloc(e, d.post_count, 8) || dalloc(e, d.post_slot, n) ||
-        false)
+    SLOT_EXTENTS(G, c.max_plies);
+    bool bad = false;
+#define X(T, f, per) bad = bad || dalloc(e, d.f, n * (per));
+    BB_SLOT_ARRAYS(X)
+#undef X
+    if (bad || dalloc(e, e->d_u, n) || dalloc(e, e->d_actions, n) || dalloc(e, e->d_child_action, n * S) ||
+        dalloc(e, d.stamps, 16 * 64) || dalloc(e, d.visit_pool, 16) || dalloc(e, d.post_count, 8))
         return BB_ERR_HIP;
     typename G::State *ls;
     if (dalloc(e, ls, n)) return BB_ERR_HIP;
@@ -291,13 +299,15 @@ static int engine_alloc(bb_engine *e) {
     uint8_t *nodes;
     if (dalloc(e, nodes, n * (size_t)d.node_cap * NODE_BYTES, false)) return BB_ERR_HIP;
     d.nodes = nodes;
-    if (dalloc(e, e->d_child_action, n * G::S)) return BB_ERR_HIP;
     if constexpr (DC) {
         DCEdges &E = e->edges;
         E.edge_cap = d.node_cap * 24; // ~15-25 legal moves per position; overflow is counted, never silent
         size_t ne = n * (size_t)E.edge_cap;
-        if (dalloc(e, E.e, ne, false) || dalloc(e, E.used, n) || dalloc(e, E.path_edge, n * G::MAXPATH))
-            return BB_ERR_HIP;
+        bad = dalloc(e, E.e, ne, false);
+#define X(T, f, per) bad = bad || dalloc(e, E.f, n * (per));
+        BB_DC_SLOT_ARRAYS(X)
+#undef X
+        if (bad) return BB_ERR_HIP;
         E.noise_on = c.noise_on;
         E.alpha = c.alpha;
         E.eps = c.epsilon;
@@ -319,23 +329,19 @@ template <class G>
 static void make_views(bb_engine *e) {
     const TreeDev &d = e->dev;
     int n = d.n_slots;
+    SLOT_EXTENTS(G, d.max_plies);
     for (int v = 0; v < e->n_views; v++) {
         TreeDev w = d;
         int off = v == 0 ? 0 : n / 2;
         int cnt = e->n_views == 1 ? n : (v == 0 ? n / 2 : n - n / 2);
         w.n_slots = cnt;
         w.slot_offset = off;
-        w.root += off; w.root_N += off; w.n_nodes += off; w.ply += off; w.sims_left += off; w.pend_leaf += off;
-        w.pend_expand += off; w.path_len += off; w.game_lid += off; w.sim_serial += off; w.root_W += off;
-        w.root_pp += off; w.path += (size_t)off * G::MAXPATH;
-        w.anc += (size_t)off * (d.max_plies + 2); w.anc_len += off; w.top_N += off;
-        w.path_N += (size_t)off * G::MAXPATH; w.path_all += (size_t)off * G::MAXPATH; w.path_W += (size_t)off * G::MAXPATH; w.leaf_flags += off;
+#define X(T, f, per) w.f += (size_t)off * (per);
+        BB_SLOT_ARRAYS(X) // (the dense games' anc by the stride it is allocated with; DragonChess, whose anc is two planes, gets one view)
+#undef X
         w.leaf_state = (char *)d.leaf_state + (size_t)off * sizeof(typename G::State);
-        w.leaf_game_id += off; w.leaf_serial += off; w.eval_value += off;
-        w.eval_policy += (size_t)off * (G::GID == BB_GAME_DRAGONCHESS ? G::A : G::S);
-        w.evals += off; w.ctr += (size_t)off * 8;
         w.nodes = (char *)d.nodes + (size_t)off * d.node_cap * e->node_bytes;
-        w.resume_cur += off; w.resume_depth += off; w.post_slot += off; w.post_count += 4 * v;
+        w.post_count += 4 * v; // per view, not per slot
         e->view[v] = w;
     }
 }
@@ -351,10 +357,14 @@ static void make_views(bb_engine *e) {
 // BB_EVAL_CACHE_LOG2 sizes it -- tuning knobs, read from the environment at bb_create / bb_fit_slots.
 static size_t eval_cache_entry_bytes(const bb_config *cfg) { return cfg->game == BB_GAME_DRAGONCHESS ? 128 : 64; }
 static int eval_cache_log2_of(const bb_config *cfg) {
-    const bool rounds_too = cfg->game == BB_GAME_CONNECT4; // (DragonChess has no round structure)
-    if ((cfg->game != BB_GAME_CONNECT4 && cfg->game != BB_GAME_DRAGONCHESS) || cfg->mcts_kind != BB_MCTS_DYNAMIC ||
-        cfg->evaluator != BB_EVAL_NET || !(cfg->launch == BB_LAUNCH_AUTO || (rounds_too && cfg->launch == BB_LAUNCH_ROUNDS)))
-        return 0;
+    // THE rule of who owns a table: a configuration whose structure probes one.  (TicTacToe has no key: games.hip.h CACHE_KEY.)
+    const bool c4 = cfg->game == BB_GAME_CONNECT4;
+    switch (selfplay_plan(cfg)) {
+    case PLAY_DC_FUSED: break;                                                // mega_dc.hip.h
+    case PLAY_QUEUE: if (!c4) return 0; break;                                // mega2.hip.h, and the rounds of a network that does not fit it
+    case PLAY_ROUNDS: if (!c4 || cfg->evaluator != BB_EVAL_NET) return 0; break; // eval_probe.hip.h (the hash evaluator's rounds probe nothing)
+    default: return 0;                                                        // the lock-step search does not
+    }
     const char *on = getenv("BB_EVAL_CACHE"), *lg = getenv("BB_EVAL_CACHE_LOG2");
     if (on && atoi(on) == 0) return 0;
     const int k = lg ? atoi(lg) : cfg->game == BB_GAME_DRAGONCHESS ? 24 : 27;
@@ -368,7 +378,9 @@ static long node_capacity_of(const bb_config *cfg) {
 }
 
 // device bytes engine_alloc<G> asks for: per slot (node pool, DragonChess edge pool, mailboxes, paths) and per engine
-// (example store of max_games games)
+// (example store of max_games games).  bb_fit_slots reports the per-slot figure, and it UNDER-COUNTS against the table
+// (tree.hip.h BB_SLOT_ARRAYS): of the MAXPATH-long rows it has `path` (and path_edge) but not path_N, path_all and path_W, and
+// it has no `anc` at all -- noise next to a node pool; a change of what bb_fit_slots returns should sum the rows instead.
 template <class G>
 static void pool_bytes(const bb_config *cfg, size_t *per_slot, size_t *fixed) {
     constexpr bool DC = G::GID == BB_GAME_DRAGONCHESS;
@@ -479,15 +491,12 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
         delete e;
         return fail(BB_ERR_ARG, "bad bb_config.launch / net_form");
     }
-    e->async_selfplay = cfg->game != BB_GAME_DRAGONCHESS && cfg->mcts_kind == BB_MCTS_DYNAMIC &&
-                        cfg->evaluator != BB_EVAL_ROLLOUT && cfg->launch != BB_LAUNCH_LOCKSTEP;
-    e->mega = e->async_selfplay && cfg->evaluator == BB_EVAL_NET && cfg->launch == BB_LAUNCH_AUTO;
-    e->dc_fused = cfg->game == BB_GAME_DRAGONCHESS && cfg->mcts_kind == BB_MCTS_DYNAMIC && cfg->evaluator == BB_EVAL_NET &&
-                  cfg->launch == BB_LAUNCH_AUTO;
+    e->plan = selfplay_plan(cfg);
+    const bool rounds_kernels = e->plan == PLAY_ROUNDS || e->plan == PLAY_QUEUE; // (a queue engine plays rounds when its network does not fit)
     if (int v = env_int("BB_TREE_GPW", 0); v >= 1 && v <= 64 / e->info.S) d.gpw = v;
     d.temp = 1.0;
     GAME_SWITCH(cfg->game, rc = engine_alloc<G>(e); break);
-    if (!rc) { // (a configuration that owns a table plays through a structure that probes it: eval_cache_log2_of)
+    if (!rc) { // (a configuration that owns a table plays through a structure that probes it: eval_cache_log2_of asks selfplay_plan)
         if (const int k = eval_cache_log2_of(cfg)) {
             uint8_t *tab = nullptr;
             e->eval_cache_bytes = eval_cache_entry_bytes(cfg) << k;
@@ -497,15 +506,15 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
         }
     }
     if (!rc) rc = dalloc(e, d.eval_cache_ctr, 2);
-    if (!rc && d.eval_cache && e->async_selfplay)
+    if (!rc && d.eval_cache && rounds_kernels)
         rc = dalloc(e, e->miss_count, 8) || dalloc(e, e->miss_slot, (size_t)cfg->n_slots) || dalloc(e, e->miss_way, (size_t)cfg->n_slots);
     if (rc) {
         bb_destroy(e);
         return rc;
     }
     e->n_views = 1;
-    if (e->async_selfplay && !e->mega && cfg->evaluator == BB_EVAL_NET && cfg->n_slots >= 512) e->n_views = 2;
-    if (const char *env = getenv("BB_GROUPS")) e->n_views = (atoi(env) == 2 && e->async_selfplay && cfg->n_slots >= 2) ? 2 : 1; // (tuning)
+    if (e->plan == PLAY_ROUNDS && cfg->evaluator == BB_EVAL_NET && cfg->n_slots >= 512) e->n_views = 2;
+    if (const char *env = getenv("BB_GROUPS")) e->n_views = (atoi(env) == 2 && rounds_kernels && cfg->n_slots >= 2) ? 2 : 1; // (tuning)
     e->vstream[0] = e->stream;
     if (e->n_views == 2) HIPCHK(hipStreamCreateWithFlags(&e->vstream[1], hipStreamNonBlocking));
     GAME_SWITCH(cfg->game, make_views<G>(e); break);
@@ -570,14 +579,17 @@ extern "C" int bb_net_form(bb_engine *e) {
     return e->x3.w0 ? 2 : 0;
 }
 
-extern "C" int bb_selfplay_mode(bb_engine *e) {
-    if (!e) return fail(BB_ERR_ARG, "null engine");
-    // the persistent kernels carry a 16-filter network of at most MEGA_RMAX blocks in LDS; anything else runs as rounds
-    const bool fits = !e->has_weights || (!e->general_net && e->net.R <= MEGA_RMAX && e->net.head_floats <= MEGA_HEAD_FLOATS);
-    if (e->mega && fits) return 3;
-    if (e->dc_fused && (!e->has_weights || (!e->general_net && e->net.head_floats <= DC_HEAD_FLOATS && e->net.R <= DC_RMAX))) return 5;
-    return e->async_selfplay ? 1 : 0;
+// The structure the engine plays through at this moment: its plan, unless that is a persistent kernel whose LDS the loaded network
+// does not fit (16 filters, at most rmax blocks and head_max packed head parameters).  Without weights the plan is the answer, which
+// only bb_selfplay_mode sees: a step needs bb_selfplay_begin, and that refuses a network evaluator without weights (check_eval).
+static int selfplay_structure(const bb_engine *e) {
+    auto fits = [&](int rmax, int head_max) { return !e->has_weights || (!e->general_net && e->net.R <= rmax && e->net.head_floats <= head_max); };
+    if (e->plan == PLAY_QUEUE && !fits(MEGA_RMAX, MEGA_HEAD_FLOATS)) return PLAY_ROUNDS;
+    if (e->plan == PLAY_DC_FUSED && !fits(DC_RMAX, DC_HEAD_FLOATS)) return PLAY_LOCKSTEP;
+    return e->plan;
 }
+
+extern "C" int bb_selfplay_mode(bb_engine *e) { return e ? selfplay_structure(e) : fail(BB_ERR_ARG, "null engine"); }
 
 extern "C" int bb_synchronize(bb_engine *e) {
     if (!e) return fail(BB_ERR_ARG, "null engine");
@@ -1127,19 +1139,24 @@ extern "C" int bb_hash_eval(bb_engine *e, int n, const void *states, float *valu
 template <class G>
 static int launch_eval_inner(bb_engine *e);
 
-template <class G>
-static int launch_eval(bb_engine *e) {
-    bool timed = e->time_every > 0 && (e->eval_launches++ % (uint64_t)e->time_every) == 0 &&
-                 e->ev_used + 2 <= e->ev_pool.size();
-    if (timed) HIPCHK(hipEventRecord(e->ev_pool[e->ev_used], e->stream));
-    int rc = launch_eval_inner<G>(e);
-    if (rc) return rc;
+// bb_timing_enable: `launch` between a pair of HIP events on `st` while the pool has one left: every time_every-th of the evaluator
+// launches (the rounds count their first view's only and never time the second's), each of the persistent launches.
+enum { TIME_NEVER, TIME_SAMPLED, TIME_EACH };
+template <class F>
+static int timed_launch(bb_engine *e, hipStream_t st, int which, F launch) {
+    const bool timed = which != TIME_NEVER && e->time_every > 0 &&
+                       (which == TIME_EACH || (e->eval_launches++ % (uint64_t)e->time_every) == 0) && e->ev_used + 2 <= e->ev_pool.size();
+    if (timed) HIPCHK(hipEventRecord(e->ev_pool[e->ev_used], st));
+    if (int rc = launch()) return rc;
     if (timed) {
-        HIPCHK(hipEventRecord(e->ev_pool[e->ev_used + 1], e->stream));
+        HIPCHK(hipEventRecord(e->ev_pool[e->ev_used + 1], st));
         e->ev_used += 2;
     }
     return BB_OK;
 }
+
+template <class G>
+static int launch_eval(bb_engine *e) { return timed_launch(e, e->stream, TIME_SAMPLED, [&] { return launch_eval_inner<G>(e); }); }
 
 template <class G>
 static int launch_eval_inner(bb_engine *e) {
@@ -1502,33 +1519,29 @@ extern "C" int bb_selfplay_begin(bb_engine *e, int n_games, double temp) {
 
 __global__ void k_set_i32(int *p, int v) { *p = v; }
 
+// A persistent launch's visits, per_slot each: 7/8 dealt to the slots (returned), the rest pooled (mega2.hip.h, mega_dc.hip.h)
+static int deal_visits(bb_engine *e, int per_slot) {
+    const int own = per_slot - (per_slot + 7) / 8;
+    k_set_i32<<<1, 1, 0, e->stream>>>(e->dev.visit_pool, e->dev.n_slots * (per_slot - own));
+    return own;
+}
+
+// PLAY_QUEUE: persistent launches of at most 64 steps' worth of visits (3 s at 4096 Connect4 games x 800 visits): every spin
+// loop inside is bounded by BB_QUEUE_LIMIT_S of wall clock (30 s), so a launch must stay far below it whatever the caller asks
+// for.  Not shorter either: a launch ends when its SLOWEST workgroup is done, ~35 ms after the fastest: 4 % of 16 steps.
 template <class G>
-static int selfplay_rounds_async(bb_engine *e, int rounds) {
-    if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
-        return fail(BB_ERR_ARG, "asynchronous self-play is for the dense-action games");
-    } else {
-        constexpr int PWMAX = NetPW<G>::v;
-        if (e->mega && !e->general_net && e->net.R <= MEGA_RMAX && e->net.head_floats <= MEGA_HEAD_FLOATS) {
-            // persistent launches of at most 64 steps' worth of visits each (3 s at 4096 Connect4 games x 800 visits): every
-            // spin loop inside is bounded by BB_QUEUE_LIMIT_S of wall clock (30 s), so one launch must stay far below it
-            // whatever the caller asks for.  Not shorter than necessary either: a launch ends when its SLOWEST workgroup has
-            // given each of its games the requested visits, ~35 ms after the fastest one -- 4 % of a 16-step launch.
-            TreeDev &d = e->dev;
-            int nb = (d.n_slots + 15) / 16;
-            int per_launch = e->tune.launch_steps * (e->sims_now > 0 ? e->sims_now : 1);
-            if (per_launch > (1 << 30) / d.n_slots) per_launch = (1 << 30) / d.n_slots; // the launch's visit pool is an int
-            const int all_rounds = rounds;
-          for (int done_rounds = 0; done_rounds < all_rounds; done_rounds += per_launch) {
-            rounds = all_rounds - done_rounds < per_launch ? all_rounds - done_rounds : per_launch;
-            bool timed = e->time_every > 0 && e->ev_used + 2 <= e->ev_pool.size();
-            if (timed) HIPCHK(hipEventRecord(e->ev_pool[e->ev_used], e->stream));
+static int selfplay_queue(bb_engine *e, int visits) {
+    const TreeDev &d = e->dev;
+    const int nb = (d.n_slots + 15) / 16;
+    int per_launch = e->tune.launch_steps * (e->sims_now > 0 ? e->sims_now : 1);
+    if (per_launch > (1 << 30) / d.n_slots) per_launch = (1 << 30) / d.n_slots; // the launch's visit pool is an int
+    for (int done = 0; done < visits; done += per_launch) {
+        const int now = visits - done < per_launch ? visits - done : per_launch;
+        if (int rc = timed_launch(e, e->stream, TIME_EACH, [&]() -> int {
             TreeDev dm = d;
             // tree levels per call: 10 / 12 / 16 / 20 / 24 -> 155.6 / 155.8 / 153.6 / 151.6 / 151.2 M sims/s (Connect4 @800, bf16-pipe network)
             if (!e->tune.level_budget_set) dm.level_budget = 12;
-            // the launch's visits: 7/8 dealt to the workgroups (per slot), the rest in the launch-wide pool (mega2.hip.h)
-            const int own = rounds - (rounds + 7) / 8;
-            k_set_i32<<<1, 1, 0, e->stream>>>(d.visit_pool, d.n_slots * (rounds - own));
-            const int lim = e->tune.queue_limit_s;
+            const int own = deal_visits(e, now), lim = e->tune.queue_limit_s;
             if (e->x3.w0) { // bf16-pipe network: Connect4 8 network + 4 tree waves (168 VGPRs), TicTacToe 4 + 4 waves
                 if constexpr (G::S <= 8) k_selfplay_queue<G, 8, true, 12><<<nb, 768, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
                 else k_selfplay_queue<G, 4, true, 8><<<nb, 512, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
@@ -1536,76 +1549,89 @@ static int selfplay_rounds_async(bb_engine *e, int rounds) {
                 k_selfplay_queue<G, 8><<<nb, 768, 0, e->stream>>>(dm, e->net, e->x3, e->cfg.noise_on, lim, own);
             }
             HIPCHK(hipGetLastError());
-            if (timed) {
-                HIPCHK(hipEventRecord(e->ev_pool[e->ev_used + 1], e->stream));
-                e->ev_used += 2;
-            }
-          }
             return BB_OK;
-        }
-        for (int r = 0; r < rounds; r++) {
-            for (int v = 0; v < e->n_views; v++) {
-                TreeDev &d = e->view[v];
-                hipStream_t st = e->vstream[v];
-                int tb = nblk((size_t)((d.n_slots + d.gpw - 1) / d.gpw) * 64);
-                int nb = (d.n_slots + 4 * PWMAX - 1) / (4 * PWMAX);
-                if (e->n_views == 2) nb = 256 > nb ? 256 : nb; // spread a half batch over every CU (pw <= 2)
-                int round = e->vround[v]++;
-                k_tree_async<G><<<tb, 256, 0, st>>>(d, round);
-                HIPCHK(hipGetLastError());
-                const typename G::State *ls = (const typename G::State *)d.leaf_state;
-                if (d.evaluator == BB_EVAL_NET) {
-                    bool timed = v == 0 && e->time_every > 0 && (e->eval_launches++ % (uint64_t)e->time_every) == 0 &&
-                                 e->ev_used + 2 <= e->ev_pool.size();
-                    if (timed) HIPCHK(hipEventRecord(e->ev_pool[e->ev_used], st));
-                    // the round's batch: the posted leaves -- or, with the evaluation cache, those of them that the probe kernel
-                    // did not answer from the table (eval_probe.hip.h); the heads of these store their entries
-                    const int *n_ptr = d.post_count + (round & 3), *slot_list = d.post_slot;
-                    EvalCache store = {nullptr, 0};
-                    if constexpr (G::CACHE_KEY) {
-                        if (d.eval_cache && e->miss_count && e->general_net) {
-                            store = {(u32x4 *)d.eval_cache, d.eval_cache_log2, e->miss_way + d.slot_offset};
-                            int *mc = e->miss_count + 4 * v, *ms = e->miss_slot + d.slot_offset;
-                            if (e->miss_next[v] != round) // (weights of the other kind were loaded in between: unprobed rounds)
-                                HIPCHK(hipMemsetAsync(mc, 0, 4 * sizeof(int), st));
-                            e->miss_next[v] = round + 1;
-                            k_eval_cache_probe<G><<<(d.n_slots + 3) / 4, 256, 0, st>>>(e->net, store, n_ptr, slot_list, mc, round, ms,
-                                                                                       e->miss_way + d.slot_offset, ls,
-                                                                                       d.leaf_game_id, d.leaf_serial, e->cfg.noise_on,
-                                                                                       d.eval_value, d.eval_policy, G::S, d.evals,
-                                                                                       d.eval_cache_ctr);
-                            n_ptr = mc + (round & 3);
-                            slot_list = ms;
-                        }
-                    }
-                    if (e->general_net) {
-                        int rc = launch_gnet<G>(e, d.n_slots, n_ptr, slot_list, ls, nullptr, d.leaf_game_id,
-                                                d.leaf_serial, e->cfg.noise_on, d.eval_value, nullptr, d.eval_policy, G::S, st,
-                                                d.slot_offset, store);
-                        if (rc) return rc;
-                    } else if (e->x3.w0) {
-                        if constexpr (G::C <= 4)
-                            k_net_x3<G><<<(d.n_slots + 3) / 4, 256, 0, st>>>(e->net, e->x3, 0, n_ptr, slot_list, ls,
-                                                                              nullptr, d.leaf_game_id, d.leaf_serial, e->cfg.noise_on,
-                                                                              d.eval_value, nullptr, d.eval_policy, G::S, store);
-                    } else
-                    k_net_compact<G, PWMAX><<<nb, 256, 0, st>>>(e->net, n_ptr, slot_list, ls,
-                                                                 d.leaf_game_id, d.leaf_serial, e->cfg.noise_on, d.eval_value,
-                                                                 d.eval_policy, G::S, store);
-                    HIPCHK(hipGetLastError());
-                    if (timed) {
-                        HIPCHK(hipEventRecord(e->ev_pool[e->ev_used + 1], st));
-                        e->ev_used += 2;
-                    }
-                } else { // validation evaluator over every slot's mailbox of the view
-                    k_hash_eval<G><<<nblk(d.n_slots), 256, 0, st>>>(d.n_slots, ls, d.leaf_game_id, d.salt, d.salt_per_game,
-                                                                    d.first_game_id, d.eval_value, d.eval_policy, G::S);
-                    HIPCHK(hipGetLastError());
-                }
-            }
-        }
-        return BB_OK;
+        })) return rc;
     }
+    return BB_OK;
+}
+
+// PLAY_DC_FUSED: at most 64 plies' worth of simulations per launch (a launch is plies x sims x ~45 us long; nothing inside can
+// spin); the waves draw them from one pool (mega_dc.hip.h)
+static int selfplay_dc_fused(bb_engine *e, int plies) {
+    int cap = 64;
+    if ((long)cap * e->sims_now * e->dev.n_slots > (1l << 30)) cap = (int)((1l << 30) / ((long)e->sims_now * e->dev.n_slots));
+    if (cap < 1) cap = 1;
+    for (int done = 0; done < plies; done += cap) {
+        const int now = plies - done < cap ? plies - done : cap;
+        if (int rc = timed_launch(e, e->stream, TIME_EACH, [&]() -> int {
+            const int own = deal_visits(e, now * e->sims_now);
+            k_dc_selfplay_fused<<<nblk((size_t)e->dev.n_slots * 64), 256, 0, e->stream>>>(e->dev, e->edges, e->net, e->x3, e->cfg.noise_on, own);
+            HIPCHK(hipGetLastError());
+            return BB_OK;
+        })) return rc;
+    }
+    return BB_OK;
+}
+
+// PLAY_ROUNDS: per view, k_tree_async and then the evaluator over the leaves it posted
+template <class G>
+static int selfplay_rounds_async(bb_engine *e, int rounds) {
+    constexpr int PWMAX = NetPW<G>::v;
+    for (int r = 0; r < rounds; r++) {
+        for (int v = 0; v < e->n_views; v++) {
+            TreeDev &d = e->view[v];
+            hipStream_t st = e->vstream[v];
+            int tb = nblk((size_t)((d.n_slots + d.gpw - 1) / d.gpw) * 64);
+            int nb = (d.n_slots + 4 * PWMAX - 1) / (4 * PWMAX);
+            if (e->n_views == 2) nb = 256 > nb ? 256 : nb; // spread a half batch over every CU (pw <= 2)
+            int round = e->vround[v]++;
+            k_tree_async<G><<<tb, 256, 0, st>>>(d, round);
+            HIPCHK(hipGetLastError());
+            const typename G::State *ls = (const typename G::State *)d.leaf_state;
+            if (d.evaluator != BB_EVAL_NET) { // validation evaluator over every slot's mailbox of the view
+                k_hash_eval<G><<<nblk(d.n_slots), 256, 0, st>>>(d.n_slots, ls, d.leaf_game_id, d.salt, d.salt_per_game,
+                                                                d.first_game_id, d.eval_value, d.eval_policy, G::S);
+                HIPCHK(hipGetLastError());
+                continue;
+            }
+            if (int rc = timed_launch(e, st, v == 0 ? TIME_SAMPLED : TIME_NEVER, [&]() -> int { // (the first view's launches only, as ever)
+                // the round's batch: the posted leaves -- or, with the evaluation cache, those of them that the probe kernel
+                // did not answer from the table (eval_probe.hip.h); the heads of these store their entries
+                const int *n_ptr = d.post_count + (round & 3), *slot_list = d.post_slot;
+                EvalCache store = {nullptr, 0};
+                if constexpr (G::CACHE_KEY) {
+                    if (d.eval_cache && e->miss_count && e->general_net) {
+                        store = {(u32x4 *)d.eval_cache, d.eval_cache_log2, e->miss_way + d.slot_offset};
+                        int *mc = e->miss_count + 4 * v, *ms = e->miss_slot + d.slot_offset;
+                        if (e->miss_next[v] != round) // (weights of the other kind were loaded in between: unprobed rounds)
+                            HIPCHK(hipMemsetAsync(mc, 0, 4 * sizeof(int), st));
+                        e->miss_next[v] = round + 1;
+                        k_eval_cache_probe<G><<<(d.n_slots + 3) / 4, 256, 0, st>>>(e->net, store, n_ptr, slot_list, mc, round, ms,
+                                                                                   e->miss_way + d.slot_offset, ls, d.leaf_game_id,
+                                                                                   d.leaf_serial, e->cfg.noise_on, d.eval_value,
+                                                                                   d.eval_policy, G::S, d.evals, d.eval_cache_ctr);
+                        n_ptr = mc + (round & 3);
+                        slot_list = ms;
+                    }
+                }
+                if (e->general_net) {
+                    if (int rc = launch_gnet<G>(e, d.n_slots, n_ptr, slot_list, ls, nullptr, d.leaf_game_id, d.leaf_serial, e->cfg.noise_on,
+                                                d.eval_value, nullptr, d.eval_policy, G::S, st, d.slot_offset, store)) return rc;
+                } else if (e->x3.w0) {
+                    if constexpr (G::C <= 4)
+                        k_net_x3<G><<<(d.n_slots + 3) / 4, 256, 0, st>>>(e->net, e->x3, 0, n_ptr, slot_list, ls, nullptr, d.leaf_game_id,
+                                                                          d.leaf_serial, e->cfg.noise_on, d.eval_value, nullptr,
+                                                                          d.eval_policy, G::S, store);
+                } else {
+                    k_net_compact<G, PWMAX><<<nb, 256, 0, st>>>(e->net, n_ptr, slot_list, ls, d.leaf_game_id, d.leaf_serial,
+                                                                 e->cfg.noise_on, d.eval_value, d.eval_policy, G::S, store);
+                }
+                HIPCHK(hipGetLastError());
+                return BB_OK;
+            })) return rc;
+        }
+    }
+    return BB_OK;
 }
 
 extern "C" int bb_selfplay_step(bb_engine *e, int plies) {
@@ -1613,34 +1639,17 @@ extern "C" int bb_selfplay_step(bb_engine *e, int plies) {
     if (e->n_games_target <= 0) return fail(BB_ERR_ARG, "bb_selfplay_begin has not been called");
     HIPCHK(hipSetDevice(e->cfg.device));
     GAME_SWITCH(e->cfg.game, {
-        if (e->async_selfplay) return selfplay_rounds_async<G>(e, plies * e->sims_now);
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
-            if (e->dc_fused && e->has_weights && !e->general_net && e->net.head_floats <= DC_HEAD_FLOATS && e->net.R <= DC_RMAX) {
-                // at most 64 plies' worth of simulations per launch (a launch is plies x sims x ~45 us long; nothing inside can
-                // spin); the waves draw them from one pool (mega_dc.hip.h)
-                int cap = 64;
-                if ((long)cap * e->sims_now * e->dev.n_slots > (1l << 30)) cap = (int)((1l << 30) / ((long)e->sims_now * e->dev.n_slots));
-                if (cap < 1) cap = 1;
-                for (int done = 0; done < plies; done += cap) {
-                    const int now = plies - done < cap ? plies - done : cap;
-                    bool timed = e->time_every > 0 && e->ev_used + 2 <= e->ev_pool.size();
-                    if (timed) HIPCHK(hipEventRecord(e->ev_pool[e->ev_used], e->stream));
-                    const int per_slot = now * e->sims_now, own = per_slot - (per_slot + 7) / 8; // 7/8 dealt to the games, the rest pooled
-                    k_set_i32<<<1, 1, 0, e->stream>>>(e->dev.visit_pool, e->dev.n_slots * (per_slot - own));
-                    k_dc_selfplay_fused<<<nblk((size_t)e->dev.n_slots * 64), 256, 0, e->stream>>>(e->dev, e->edges, e->net, e->x3, e->cfg.noise_on, own);
-                    HIPCHK(hipGetLastError());
-                    if (timed) {
-                        HIPCHK(hipEventRecord(e->ev_pool[e->ev_used + 1], e->stream));
-                        e->ev_used += 2;
-                    }
-                }
-                return BB_OK;
-            }
+        constexpr bool DC = G::GID == BB_GAME_DRAGONCHESS; // (selfplay_plan gives each game its own structures only)
+        const int mode = selfplay_structure(e);
+        if constexpr (DC) {
+            if (mode == PLAY_DC_FUSED) return selfplay_dc_fused(e, plies);
+        } else if (mode == PLAY_QUEUE || mode == PLAY_ROUNDS) {
+            return mode == PLAY_QUEUE ? selfplay_queue<G>(e, plies * e->sims_now) : selfplay_rounds_async<G>(e, plies * e->sims_now);
         }
-        for (int p = 0; p < plies; p++) {
+        for (int p = 0; p < plies; p++) { // PLAY_LOCKSTEP
             int rc = run_sims<G>(e, e->sims_now);
             if (rc) return rc;
-            if constexpr (G::GID == BB_GAME_DRAGONCHESS)
+            if constexpr (DC)
                 k_dc_selfplay_move<<<nblk((size_t)e->dev.n_slots * 64), 256, 0, e->stream>>>(e->dev, e->edges);
             else
                 k_selfplay_move<G><<<nblk((size_t)e->dev.n_slots * G::S), 256, 0, e->stream>>>(e->dev);

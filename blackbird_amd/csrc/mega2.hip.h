@@ -49,48 +49,45 @@ __device__ __forceinline__ void release_global_then_lds() {
 // workgroup's first slot for the node pools, which stay in HBM), so the pointers are the plain addresses of __shared__
 // arrays: the compiler sees the LDS address space and emits ds_read / ds_write with immediate offsets from one base
 // register, instead of flat_* instructions through twenty 64-bit generic addresses held in VGPR pairs.
+// The rows it keeps (B: always, R: in its REC form), and the order it copies them in, by name alone.  That is not the rows' order:
+// the register allocation of the whole kernel follows the order of the copy loops.  A name that is no member does not compile,
+// and the two lists' lengths are compared (which one name twice and another left out would still pass).
+#define BB_QUEUE_SHADOWED(B, R) BB_SLOTS_TREE(B, B, R) BB_SLOTS_MAILBOX(B, B) BB_SLOTS_RESUME(B)
+#define BB_QUEUE_COPY_ORDER(X)                                                                                           \
+    X(root) X(root_N) X(n_nodes) X(ply) X(sims_left) X(pend_leaf) X(pend_expand) X(path_len) X(game_lid) X(sim_serial)   \
+    X(leaf_serial) X(resume_cur) X(resume_depth) X(leaf_game_id) X(root_W) X(eval_value) X(eval_policy) X(evals) X(ctr)  \
+    X(path) X(root_pp) X(leaf_flags)
+#define BB_QUEUE_COPY_ORDER_REC(X) X(path_N) X(path_all) X(path_W)
+#define BB_COUNT(...) +1
+#define BB_SHADOW_PER(f) ((int)(sizeof(f) / sizeof(f[0])) / GW) // its row's `per`
 template <class G, int GW, bool REC>
 struct GameShadow {
-    static constexpr int S = G::S, MP = G::MAXPATH;
-    int32_t root[GW], root_N[GW], n_nodes[GW], ply[GW], sims_left[GW], pend_leaf[GW], pend_expand[GW], path_len[GW],
-        game_lid[GW], sim_serial[GW], leaf_serial[GW], resume_cur[GW], resume_depth[GW], leaf_flags[GW];
-    int32_t path_N[REC ? GW * MP : 1], path_all[REC ? GW * MP : 1]; // (REC: what the descent recorded of every edge)
-    float path_W[REC ? GW * MP : 1];
-    uint32_t leaf_game_id[GW];
-    float root_W[GW], eval_value[GW];
-    float eval_policy[GW * S];
-    uint64_t evals[GW];
-    uint64_t ctr[GW * 8];
+    static constexpr int S = G::S, MP = G::MAXPATH, PS = S;
+#define X(T, f, per) T f[REC ? GW * (per) : 1];
+    BB_QUEUE_SHADOWED(BB_SHADOW_MEMBER, X)
+#undef X
     typename G::State leaf_state[GW];
-    uint32_t path[GW * MP];
-    int8_t root_pp[GW];
-
-#define BB_SHADOW_ARRAYS(X)                                                                                           \
-    X(root, 1) X(root_N, 1) X(n_nodes, 1) X(ply, 1) X(sims_left, 1) X(pend_leaf, 1) X(pend_expand, 1) X(path_len, 1)  \
-    X(game_lid, 1) X(sim_serial, 1) X(leaf_serial, 1) X(resume_cur, 1) X(resume_depth, 1) X(leaf_game_id, 1)          \
-    X(root_W, 1) X(eval_value, 1) X(eval_policy, S) X(evals, 1) X(ctr, 8) X(path, MP) X(root_pp, 1) X(leaf_flags, 1)
-#define BB_SHADOW_REC_ARRAYS(X) X(path_N, MP) X(path_all, MP) X(path_W, MP)
-
+    static_assert(0 BB_QUEUE_COPY_ORDER(BB_COUNT) BB_QUEUE_COPY_ORDER_REC(BB_COUNT) == 0 BB_QUEUE_SHADOWED(BB_COUNT, BB_COUNT), "a row is not copied");
     // all threads of the workgroup; n = games of this workgroup that exist (g0 + i < n_slots)
     __device__ __forceinline__ void load(const TreeDev &d, int g0, int n, int nthreads) {
-#define X(f, per) for (int i = threadIdx.x; i < n * (per); i += nthreads) f[i] = d.f[(size_t)g0 * (per) + i];
-        BB_SHADOW_ARRAYS(X)
-        if constexpr (REC) { BB_SHADOW_REC_ARRAYS(X) }
+#define X(f) BB_SHADOW_LOAD(d, f, BB_SHADOW_PER(f))
+        BB_QUEUE_COPY_ORDER(X)
+        if constexpr (REC) { BB_QUEUE_COPY_ORDER_REC(X) }
 #undef X
         for (int i = threadIdx.x; i < n; i += nthreads) leaf_state[i] = ((const typename G::State *)d.leaf_state)[g0 + i];
     }
     __device__ __forceinline__ void store(const TreeDev &d, int g0, int n, int nthreads) {
-#define X(f, per) for (int i = threadIdx.x; i < n * (per); i += nthreads) d.f[(size_t)g0 * (per) + i] = f[i];
-        BB_SHADOW_ARRAYS(X)
-        if constexpr (REC) { BB_SHADOW_REC_ARRAYS(X) }
+#define X(f) BB_SHADOW_STORE(d, f, BB_SHADOW_PER(f))
+        BB_QUEUE_COPY_ORDER(X)
+        if constexpr (REC) { BB_QUEUE_COPY_ORDER_REC(X) }
 #undef X
         for (int i = threadIdx.x; i < n; i += nthreads) ((typename G::State *)d.leaf_state)[g0 + i] = leaf_state[i];
     }
     __device__ __forceinline__ TreeDev local(const TreeDev &d, int g0) {
         TreeDev r = d;
-#define X(f, per) r.f = f;
-        BB_SHADOW_ARRAYS(X)
-        if constexpr (REC) { BB_SHADOW_REC_ARRAYS(X) }
+#define X(f) r.f = f;
+        BB_QUEUE_COPY_ORDER(X)
+        if constexpr (REC) { BB_QUEUE_COPY_ORDER_REC(X) }
 #undef X
         r.leaf_state = leaf_state;
         r.pool_g0 = g0;

@@ -123,37 +123,32 @@ __device__ __attribute__((noinline)) void dc_fused_move(const TreeDev &d_, const
 // TreeDev::pool_g0 carries the workgroup's first slot for the node and edge pools, which stay in HBM.
 struct DCShadow {
     static constexpr int GW = 4, MP = DragonChess::MAXPATH;
-    int32_t root[GW], root_N[GW], n_nodes[GW], ply[GW], sims_left[GW], pend_leaf[GW], pend_expand[GW], path_len[GW],
-        game_lid[GW], sim_serial[GW], leaf_serial[GW], used[GW];
-    uint32_t leaf_game_id[GW];
-    float root_W[GW], eval_value[GW];
-    uint64_t evals[GW];
-    uint64_t ctr[GW * 8];
+    BB_SLOT_SHADOWED(BB_SHADOW_MEMBER)
+    BB_DC_SLOT_ARRAYS(BB_SHADOW_MEMBER)
     DCState leaf_state[GW];
-    uint32_t path[GW * MP], path_edge[GW * MP];
-    int8_t root_pp[GW];
-
-#define BB_DC_SHADOW_ARRAYS(X)                                                                                       \
-    X(d, root, 1) X(d, root_N, 1) X(d, n_nodes, 1) X(d, ply, 1) X(d, sims_left, 1) X(d, pend_leaf, 1) X(d, pend_expand, 1) \
-    X(d, path_len, 1) X(d, game_lid, 1) X(d, sim_serial, 1) X(d, leaf_serial, 1) X(d, leaf_game_id, 1) X(d, root_W, 1)   \
-    X(d, eval_value, 1) X(d, evals, 1) X(d, ctr, 8) X(d, path, MP) X(d, root_pp, 1) X(E, used, 1) X(E, path_edge, MP)
-
+#define BB_DC_SHADOW_EACH(XD, XE) BB_SLOT_SHADOWED(XD) BB_DC_SLOT_ARRAYS(XE) // XD: rows of TreeDev d, XE: rows of DCEdges E
     __device__ __forceinline__ void load(const TreeDev &d, const DCEdges &E, int g0, int n, int nthreads) {
-#define X(o, f, per) for (int i = threadIdx.x; i < n * (per); i += nthreads) f[i] = o.f[(size_t)g0 * (per) + i];
-        BB_DC_SHADOW_ARRAYS(X)
-#undef X
+#define XD(T, f, per) BB_SHADOW_LOAD(d, f, per)
+#define XE(T, f, per) BB_SHADOW_LOAD(E, f, per)
+        BB_DC_SHADOW_EACH(XD, XE)
+#undef XD
+#undef XE
         for (int i = threadIdx.x; i < n; i += nthreads) leaf_state[i] = ((const DCState *)d.leaf_state)[g0 + i];
     }
     __device__ __forceinline__ void store(const TreeDev &d, const DCEdges &E, int g0, int n, int nthreads) {
-#define X(o, f, per) for (int i = threadIdx.x; i < n * (per); i += nthreads) o.f[(size_t)g0 * (per) + i] = f[i];
-        BB_DC_SHADOW_ARRAYS(X)
-#undef X
+#define XD(T, f, per) BB_SHADOW_STORE(d, f, per)
+#define XE(T, f, per) BB_SHADOW_STORE(E, f, per)
+        BB_DC_SHADOW_EACH(XD, XE)
+#undef XD
+#undef XE
         for (int i = threadIdx.x; i < n; i += nthreads) ((DCState *)d.leaf_state)[g0 + i] = leaf_state[i];
     }
     __device__ __forceinline__ void point(TreeDev &d, DCEdges &E, int g0) { // d, E: copies of the kernel arguments
-#define X(o, f, per) o.f = f;
-        BB_DC_SHADOW_ARRAYS(X)
-#undef X
+#define XD(T, f, per) d.f = f;
+#define XE(T, f, per) E.f = f;
+        BB_DC_SHADOW_EACH(XD, XE)
+#undef XD
+#undef XE
         d.leaf_state = leaf_state;
         d.pool_g0 = g0;
     }

@@ -57,6 +57,48 @@ struct ExampleHdr { // 16 bytes, then packed state, then u32 visits[S]
     uint32_t n_children;
 };
 
+// ---- every array that has one run of elements per game slot, declared ONCE: a new one is one new row --------------------
+// A row is X(type, name, per): `per` elements per slot, in names the expanding context defines -- S = G::S, MP = G::MAXPATH,
+// PS = the policy stride (G::A for DragonChess, else G::S), ANC = the ancestor stride (max_plies + 2) * (DragonChess ? 2 : 1).
+// TreeDev's pointer members, the allocation and the slot-range views (engine.hip) and the persistent kernels' LDS shadows
+// (mega2.hip.h, mega_dc.hip.h) are generated from the rows.  The lists are the runs of arrays between TreeDev's other members,
+// in its order: TreeDev is an argument of every kernel, and moving a member changes SGPR counts and spills of a dozen of them.
+// Macros B / Q / R: kept in LDS by both persistent kernels / the Connect4 queue kernel only / the same in its REC form only.
+#define BB_SLOTS_TREE(B, Q, R) /* per-slot tree state */                                                                    \
+    B(int32_t, root, 1) B(int32_t, root_N, 1) B(int32_t, n_nodes, 1) B(int32_t, ply, 1) B(int32_t, sims_left, 1)           \
+    B(int32_t, pend_leaf, 1) B(int32_t, pend_expand, 1) B(int32_t, path_len, 1)                                            \
+    B(int32_t, game_lid, 1) /* local game index played in this slot, -1 idle */                                            \
+    B(int32_t, sim_serial, 1) B(float, root_W, 1)                                                                          \
+    B(int8_t, root_pp, 1) /* Player of the root's parent state, 0 = root has no parent */                                  \
+    B(uint32_t, path, MP) /* node<<6 | player<<4 | action */                                                               \
+    /* what the descent saw of every edge of the recorded path (persistent kernel, level-stepped tree waves): the backup is  \
+       then stores only -- N + 1, W + v, Q, sum + 1, sqrt -- instead of a read-modify-write round trip per simulation */    \
+    R(int32_t, path_N, MP) R(int32_t, path_all, MP) /* child.Plays of the chosen edge, sum(ChildPlays) of its node */      \
+    R(float, path_W, MP)                            /* child.Value of the chosen edge */                                   \
+    Q(int32_t, leaf_flags, 1) /* flags word of the posted leaf | LEAF_RECORDED (0: posted by a kernel that records nothing) */
+#define BB_SLOTS_ANC(X) /* with track_anc */                                                                                \
+    /* [max_plies + 2] node<<6 | player<<4 | action, top-most first.  DragonChess (dc_anc_edge): TWO PLANES of n_slots such  \
+       runs, nodes then edges -- ANC is its element count per slot, no stride: a slot-range view of it would be wrong */   \
+    X(uint32_t, anc, ANC)                                                                                                   \
+    X(int32_t, anc_len, 1) X(int32_t, top_N, 1) /* top_N: Plays of the top-most ancestor (it has no parent edge for them) */
+#define BB_SLOTS_MAILBOX(B, Q) /* evaluator mailboxes, next to leaf_state */                                                \
+    B(uint32_t, leaf_game_id, 1) B(int32_t, leaf_serial, 1) B(float, eval_value, 1) Q(float, eval_policy, PS)              \
+    B(uint64_t, evals, 1) /* leaves handed to the evaluator */                                                             \
+    B(uint64_t, ctr, 8)   /* sims, sum_depth, nodes, terminal, games, plies, overflow, examples */
+#define BB_SLOTS_OUT(X) /* bb_sample_moves outputs (device staging) */                                                      \
+    X(int32_t, out_action, 1) X(int32_t, out_root_plays, 1) X(int32_t, out_child_plays, S)                                 \
+    X(float, out_root_winrate, 1) X(float, out_child_value, S)
+#define BB_SLOTS_RESUME(X) X(int32_t, resume_cur, 1) X(int32_t, resume_depth, 1) /* descent parked by the level budget (-1: none) */
+#define BB_SLOTS_POST(X) X(int, post_slot, 1) /* slots of the posted leaves, in arrival order */
+#define BB_ROW_NONE(...)
+#define BB_SLOT_ARRAYS(X) BB_SLOTS_TREE(X, X, X) BB_SLOTS_ANC(X) BB_SLOTS_MAILBOX(X, X) BB_SLOTS_OUT(X) BB_SLOTS_RESUME(X) BB_SLOTS_POST(X)
+#define BB_SLOT_SHADOWED(X) BB_SLOTS_TREE(X, BB_ROW_NONE, BB_ROW_NONE) BB_SLOTS_MAILBOX(X, BB_ROW_NONE) // by both persistent kernels
+// The persistent kernels' side of a row: the LDS copy is a member of the same name, GW slots long; n of them exist from slot g0 on.
+#define BB_SLOT_POINTER(T, f, per) T *f; // [n_slots][per]
+#define BB_SHADOW_MEMBER(T, f, per) T f[GW * (per)];
+#define BB_SHADOW_LOAD(o, f, per) for (int i = threadIdx.x; i < n * (per); i += nthreads) f[i] = o.f[(size_t)g0 * (per) + i];
+#define BB_SHADOW_STORE(o, f, per) for (int i = threadIdx.x; i < n * (per); i += nthreads) o.f[(size_t)g0 * (per) + i] = f[i];
+
 struct TreeDev {
     // configuration
     int n_slots, node_cap, sims_per_move, max_plies, kind, max_depth, evaluator, priors_ones;
@@ -65,49 +107,26 @@ struct TreeDev {
     double c_puct;
     uint64_t seed, salt;
     uint32_t first_game_id;
-    // per-slot tree state
-    int32_t *root, *root_N, *n_nodes, *ply, *sims_left, *pend_leaf, *pend_expand, *path_len;
-    int32_t *game_lid; // local game index played in this slot, -1 idle
-    int32_t *sim_serial;
-    float *root_W;
-    int8_t *root_pp; // Player of the root's parent state, 0 = root has no parent
-    uint32_t *path;  // [n_slots][MAXPATH]  node<<6 | player<<4 | action
-    // what the descent saw of every edge of the recorded path (persistent kernel, level-stepped tree waves): the backup is
-    // then stores only -- N + 1, W + v, Q, sum + 1, sqrt -- instead of a read-modify-write round trip per simulation
-    int32_t *path_N, *path_all; // [n_slots][MAXPATH]  child.Plays of the chosen edge, sum(ChildPlays) of its node
-    float *path_W;              // [n_slots][MAXPATH]  child.Value of the chosen edge
-    int32_t *leaf_flags;        // [n_slots] flags word of the posted leaf | LEAF_RECORDED (0: posted by a kernel that records nothing)
+    BB_SLOTS_TREE(BB_SLOT_POINTER, BB_SLOT_POINTER, BB_SLOT_POINTER)
     // MCTS.ResetRoot (MCTS.py:214-225) walks Root back to its top-most ancestor, and _backProp (:238-258) recurses through every
     // ancestor above the current root, so the statistics found there include every later simulation.  With track_anc (the
     // FindMove front end's engines) a slot keeps the chain of (node, player, action) edges from the first root down to the
     // current one, every backup also walks it, and bb_reset_roots puts the root back at its top.
     int track_anc;
-    uint32_t *anc;      // [n_slots][max_plies + 2]  node<<6 | player<<4 | action, top-most first
-    int32_t *anc_len;   // [n_slots]
-    int32_t *top_N;     // [n_slots] Plays of the top-most ancestor (it has no parent edge to keep them in)
-    // evaluator mailboxes
-    void *leaf_state;       // [n_slots] packed state of the pending leaf
-    uint32_t *leaf_game_id; // [n_slots]
-    int32_t *leaf_serial;   // [n_slots]
-    float *eval_value;      // [n_slots]
-    float *eval_policy;     // [n_slots][S]
-    uint64_t *evals;        // [n_slots] leaves handed to the evaluator
-    uint64_t *ctr;          // [n_slots][8]: sims, sum_depth, nodes, terminal, games, plies, overflow, examples
-    void *nodes;            // [n_slots][node_cap]
-    // self-play
-    int n_games_target;
+    BB_SLOTS_ANC(BB_SLOT_POINTER)
+    void *leaf_state; // [n_slots] packed state of the pending leaf
+    BB_SLOTS_MAILBOX(BB_SLOT_POINTER, BB_SLOT_POINTER)
+    void *nodes; // [n_slots][node_cap]
+    int n_games_target; // self-play
     double temp;
     uint8_t *examples; // [max_games][max_plies+1][example_bytes]
     int32_t *game_hdr; // [max_games][4]: n_examples, winner, plies, done
     int example_bytes;
-    // bb_sample_moves outputs (device staging)
-    int32_t *out_action, *out_root_plays, *out_child_plays;
-    float *out_root_winrate, *out_child_value;
+    BB_SLOTS_OUT(BB_SLOT_POINTER)
     const double *in_u; // optional uniforms
-    // asynchronous self-play (k_tree_async): resumable descents + compacted leaf list
-    int32_t *resume_cur, *resume_depth; // [n_slots] descent parked by the level budget (-1: none)
-    int *post_count;                    // [4] leaves posted in round r -> post_count[r & 3]
-    int *post_slot;                     // [n_slots] slots of the posted leaves, in arrival order
+    BB_SLOTS_RESUME(BB_SLOT_POINTER) // asynchronous self-play (k_tree_async): resumable descents (shadowed by the queue kernel) + leaf list
+    int *post_count; // [4] leaves posted in round r -> post_count[r & 3]; per view, not per slot
+    BB_SLOTS_POST(BB_SLOT_POINTER)
     int level_budget;                   // tree levels one launch may descend per game
     // a TreeDev may be a VIEW of a slot range (pointers pre-offset): pipelined self-play runs two views on two streams
     int slot_offset;                    // first slot of this view in the engine

@@ -44,10 +44,11 @@ struct alignas(16) DCEdge {
 };
 static_assert(sizeof(DCEdge) == 32, "DragonChess edge record is half a cache line");
 
+#define BB_DC_SLOT_ARRAYS(X) /* DragonChess's own per-slot arrays, rows as in tree.hip.h; its persistent kernel shadows both */ \
+    X(int32_t, used, 1) /* allocation cursor */ X(uint32_t, path_edge, MP) /* absolute edge index | player << 30 */
 struct DCEdges { // per-slot edge pool, stride edge_cap
     DCEdge *e;
-    int32_t *used; // [n_slots] allocation cursor
-    uint32_t *path_edge; // [n_slots][MAXPATH] absolute edge index | player << 30
+    BB_DC_SLOT_ARRAYS(BB_SLOT_POINTER)
     int edge_cap;
     int noise_on;
     float alpha, eps;
