@@ -46,6 +46,24 @@ CASES = [  # (game, H, W, C, F, R, D, A)
     ("ttt", 3, 3, 3, 16, 4, 16, 9),
     ("dc", 8, 8, 17, 16, 2, 16, 4032),
     ("c4wide", 6, 7, 3, 64, 2, 16, 7),
+    # value-head widths away from 16 (eval.dense: 1 .. 64) and block counts 0 and 5: dense_2 is the 64-slot pairwise tree
+    # (tree_sum64) over D products -- one slot, an odd count, one past a row of 16, one past 32, all 64 -- and the tower
+    # is absent / longer than any 16-filter case above.  tests/test_gpu_net_shapes.py holds the kernels to this oracle.
+    ("c4-D1-R0", 6, 7, 3, 16, 0, 1, 7),
+    ("c4-D5-R5", 6, 7, 3, 16, 5, 5, 7),
+    ("c4-D17-R0", 6, 7, 3, 16, 0, 17, 7),
+    ("c4-D17-R5", 6, 7, 3, 16, 5, 17, 7),
+    ("c4-D33-R5", 6, 7, 3, 16, 5, 33, 7),
+    ("c4-D64-R0", 6, 7, 3, 16, 0, 64, 7),
+    ("c4-D64-R5", 6, 7, 3, 16, 5, 64, 7),
+    ("ttt-D1-R5", 3, 3, 3, 16, 5, 1, 9),
+    ("ttt-D5-R0", 3, 3, 3, 16, 0, 5, 9),
+    ("ttt-D17-R5", 3, 3, 3, 16, 5, 17, 9),
+    ("ttt-D33-R0", 3, 3, 3, 16, 0, 33, 9),
+    ("ttt-D33-R5", 3, 3, 3, 16, 5, 33, 9),
+    ("ttt-D64-R0", 3, 3, 3, 16, 0, 64, 9),
+    ("ttt-D64-R5", 3, 3, 3, 16, 5, 64, 9),
+    ("dc-D40-R1", 8, 8, 17, 16, 1, 40, 4032),
 ]
 
 
