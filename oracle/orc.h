@@ -103,8 +103,12 @@ typedef struct {
 } orc_cfg;
 
 typedef struct {
-    uint64_t sims, evals, sum_depth, nodes, terminal_leaves;
+    uint64_t sims, evals, sum_depth, nodes, terminal_leaves; /* nodes: Node.__init__ calls (AddChildren builds every child) */
     int max_depth_seen;
+    uint32_t max_rollout_steps;      /* the longest rollout of the search, in plies (ORC_EVAL_ROLLOUT) */
+    uint64_t rollouts_without_moves; /* rollouts that met a position without a legal move (scored 0.5, see sample_value) */
+    uint64_t nodes_reached;          /* nodes below a root that a descent or MoveRoot reached for the first time: what the HIP
+                                        engine, which builds a child when it is first selected, counts as created */
 } orc_stats;
 
 typedef struct orc_search orc_search;

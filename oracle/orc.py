@@ -55,7 +55,9 @@ class Cfg(C.Structure):
 
 class Stats(C.Structure):
     _fields_ = [("sims", C.c_uint64), ("evals", C.c_uint64), ("sum_depth", C.c_uint64),
-                ("nodes", C.c_uint64), ("terminal_leaves", C.c_uint64), ("max_depth_seen", C.c_int)]
+                ("nodes", C.c_uint64), ("terminal_leaves", C.c_uint64), ("max_depth_seen", C.c_int),
+                ("max_rollout_steps", C.c_uint32), ("rollouts_without_moves", C.c_uint64),
+                ("nodes_reached", C.c_uint64)]
 
 
 def build(force=False):

@@ -213,6 +213,12 @@ static orc_node *node_new(orc_search *s, const orc_state *st) { /* Node.__init__
     return n;
 }
 
+/* First time a search reaches a node below its root: the node gets its place in the order of first visits (orc_node.visit). */
+static void node_reach(orc_search *s, orc_node *n) {
+    n->visit = s->visit_next++;
+    s->stats.nodes_reached++;
+}
+
 /* evaluator front: value in [-1,1] for the side to move + getPolicy()-shaped vector */
 static void evaluate(orc_search *s, const orc_node *n, float *value, float *policy) {
     const orc_cfg *c = &s->cfg;
@@ -350,6 +356,12 @@ static double sample_value(orc_search *s, orc_node *leaf, const float *net_value
             orc_game_legal(c->game, &r, legal);
             int n = 0;
             for (int a = 0; a < s->d.A; a++) n += legal[a] == 1.0;
+            if (n == 0) { /* np.random.choice over an empty set raises in the reference; here, as in the HIP engine, the
+                           * rollout ends and scores 0.5 (deviations).  DragonChess only: both kings on the board
+                           * and the side to move without a pseudo-legal move. */
+                s->stats.rollouts_without_moves++;
+                break;
+            }
             uint32_t x[4];
             orc_philox(c->seed, s->game_id, s->sim_serial, TAG_ROLL, step++, x);
             int pick = (int)(((uint64_t)x[0] * (uint64_t)n) >> 32);
@@ -360,7 +372,8 @@ static double sample_value(orc_search *s, orc_node *leaf, const float *net_value
             orc_game_apply(c->game, &r, action);
             winner = orc_game_winner(c->game, &r, action);
         }
-        return winner == 0 ? 0.5 : (double)(player == winner);
+        if (step > s->stats.max_rollout_steps) s->stats.max_rollout_steps = step; /* (no ply cap here: the tests bound it) */
+        return winner <= 0 ? 0.5 : (double)(player == winner);
     }
     float value;
     if (net_value) value = *net_value;
@@ -415,20 +428,23 @@ static void run_sim(orc_search *s) {
             int k = select_puct(s, node);
             last_action = node->act[k];
             node = node->ch[k];
-            if (node->visit < 0) node->visit = s->visit_next++;
+            if (node->visit < 0) node_reach(s, node);
             depth++;
         }
     } else { /* FixedMCTS._findLeaf, FixedMCTS.py:21-34 */
         for (int it = 0; it < c->max_depth; it++) {
             if (!node->has_children) {
-                if (orc_game_winner(c->game, &node->st, last_action) >= 0) break;
+                if (orc_game_winner(c->game, &node->st, last_action) >= 0) {
+                    s->stats.terminal_leaves++;
+                    break;
+                }
                 add_children(s, node, NULL);
             }
             if (node->nlegal == 0) break;
             int k = select_puct(s, node);
             last_action = node->act[k];
             node = node->ch[k];
-            if (node->visit < 0) node->visit = s->visit_next++;
+            if (node->visit < 0) node_reach(s, node);
             depth++;
         }
     }
@@ -469,7 +485,9 @@ int orc_find_move(orc_search *s, const orc_state *st, double temp, int play_limi
         all += (double)r->ch[k]->N;
     }
     int act;
-    if (temp == 0.0) {
+    if (r->nlegal == 0) {
+        return -3; /* no child to choose from: argmax / choice over nothing (the engine answers BB_ERR_NAN) */
+    } else if (temp == 0.0) {
         act = r->act[select_puct(s, r)];
     } else {
         if (u < 0.0) u = orc_u53(s->cfg.seed, s->game_id, ply);
@@ -503,7 +521,7 @@ int orc_move_root(orc_search *s, const orc_state *st) { /* MCTS._moveRoot, MCTS.
     for (int k = 0; k < s->root->nlegal; k++)
         if (orc_game_equal(s->cfg.game, &s->root->ch[k]->st, st)) {
             s->root = s->root->ch[k];
-            if (s->root->visit < 0) s->root->visit = s->visit_next++; /* a move no simulation ever tried */
+            if (s->root->visit < 0) node_reach(s, s->root); /* a move no simulation ever tried */
             return 1;
         }
     return 0;

@@ -127,18 +127,18 @@ def _oracle_arena(orc, og, cfgs, sims, first, temp, draw):
     return np.array(result)
 
 
-@pytest.mark.parametrize("key,temp", [("c4", 0), ("ttt", 0), ("c4", 1.0), ("ttt_rollout", 0)])
+@pytest.mark.parametrize("key,temp", [("c4", 0), ("ttt", 0), ("c4", 1.0), ("ttt_rollout", 0), ("c4_rollout", 0)])
 def test_batched_arena_equals_two_searcher_oracle(orc, key, temp):
     """TestModelsBatched against the oracle's own two-searcher game loop, game by game: hash-evaluator DynamicMCTS with
     different salts / exploration rates on the two sides (exact), at temp 0 (PUCT argmax move) and temp 1 (sampled
-    moves, same uniforms); and DynamicMCTS against the rollout FixedMCTS that TestGood uses."""
+    moves, same uniforms); and DynamicMCTS against the rollout FixedMCTS that TestGood uses, on TicTacToe and on Connect4."""
     game = TicTacToe.BoardState if key.startswith("ttt") else Connect4.BoardState
     og = 1 if key.startswith("ttt") else 0
     first = np.array([True, False, False, True, True, False, True, False, False, True, True])
     sims = (30, 20)
     p1 = _HashPlayer(game, 11, explorationRate=0.85, playLimit=sims[0])
     cfg1 = orc.make_cfg(og, evaluator=orc.EVAL_HASH, salt=11, c_puct=0.85, seed=77)
-    if key == "ttt_rollout":
+    if key.endswith("_rollout"):
         p2 = _RolloutFixed(game, maxDepth=10, explorationRate=0.85, playLimit=sims[1])
         cfg2 = orc.make_cfg(og, kind=orc.FIXED, max_depth=10, evaluator=orc.EVAL_ROLLOUT, c_puct=0.85, seed=77)
     else:

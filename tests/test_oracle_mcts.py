@@ -95,3 +95,71 @@ def test_edge_cases(orc):
     s = orc.Search(cfg)
     s.find_move(st, 1.0, 1, u=0.5)
     assert s.stats().nodes == 22
+
+
+# ---- the rollout evaluator (MCTS.SampleValue, MCTS.py:360-383): what tests/test_gpu_rollout.py relies on ------------------
+from tests import rollout_cases as RC  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(RC.SELFPLAY))
+def test_rollout_selfplay_stays_clear_of_cap_and_stalemate(orc, name):
+    """The configurations and seeds the GPU comparison uses: no rollout reaches the HIP engine's 2048-ply cap or a position
+    without a legal move -- the two places where engine and oracle score 0.5 where the reference would go on or raise -- and
+    every move of every game ran exactly sims-per-move rollouts."""
+    _key, _fixed, _depth, sims, n_games, _slots, max_plies = RC.SELFPLAY[name]
+    games = RC.oracle_selfplay(orc, name)
+    assert len(games) == n_games
+    for o in games:
+        RC.assert_rollouts_decided(o["stats"])
+        assert 2 <= o["n"] <= max_plies + 1
+        assert o["stats"].sims == (o["n"] - 1) * sims
+        assert o["stats"].max_rollout_steps > 0 and o["stats"].nodes_reached <= o["stats"].nodes
+
+
+def test_rollout_stats_count_steps(orc):
+    """max_rollout_steps is the number of moves the longest rollout played: from TicTacToe's empty board with one
+    simulation (DynamicMCTS: the root is the leaf) a rollout plays 5 to 9 moves; Connect4 7 to 42."""
+    for game, lo, hi in ((RC.ORC_GAME["ttt"], 5, 9), (RC.ORC_GAME["c4"], 7, 42)):
+        seen = set()
+        for gid in range(40):
+            s = orc.Search(orc.make_cfg(game, evaluator=orc.EVAL_ROLLOUT, seed=RC.SEED), gid)
+            with pytest.raises(ValueError):  # one simulation on a fresh root: 0 / 0
+                s.find_move(orc.new_state(game), 1.0, 1, u=0.5)
+            st = s.stats()
+            assert st.sims == 1 and st.rollouts_without_moves == 0 and lo <= st.max_rollout_steps <= hi
+            seen.add(st.max_rollout_steps)
+        assert len(seen) > 1
+
+
+@pytest.mark.parametrize("fixed", [False, True])
+def test_rollout_without_a_legal_move_scores_half(orc, fixed):
+    """DragonChess, both kings present, the side to move has no pseudo-legal move: the reference's np.random.choice would
+    raise; the oracle (like the HIP engine) ends the rollout with 0.5 and treats the node as a leaf.  Every simulation
+    terminates and backs up exactly 0.5."""
+    stuck, forced, after = (RC.orc_state(orc, p) for p in (RC.STUCK_ROOK, RC.FORCED, RC.STUCK_AFTER_FORCED))
+    for st in (stuck, after):
+        assert orc.legal(orc.DC, st).sum() == 0 and orc.winner(orc.DC, st) is None
+    assert np.flatnonzero(orc.legal(orc.DC, forced)).tolist() == [RC.FORCED_ACTION] and orc.winner(orc.DC, forced) is None
+    nxt = forced.copy()
+    assert orc.apply(orc.DC, nxt, RC.FORCED_ACTION) == 0
+    assert bytes(nxt) == bytes(after)
+    cfg = RC.oracle_cfg(orc, "dc", fixed, 3)
+    # reached as the only child of the root
+    s = orc.Search(cfg, 5)
+    r = s.find_move(forced, 0, 4)
+    assert r["action"] == RC.FORCED_ACTION and r["root_plays"] == 4
+    assert r["plays"].sum() == r["plays"][RC.FORCED_ACTION] == (4 if fixed else 3)  # (DynamicMCTS: the first leaf is the root)
+    assert r["winrates"][RC.FORCED_ACTION] == 0.5
+    st = s.stats()
+    assert (st.sims, st.rollouts_without_moves, st.max_rollout_steps) == (4, 4, 0 if fixed else 1)
+    # ... and as the root itself: it keeps its statistics, gets no children, and there is no move to choose
+    assert s.move_root(r["next"]) == 1
+    with pytest.raises(ValueError):
+        s.find_move(after, 0, 4)
+    st = s.stats()
+    assert (st.sims, st.rollouts_without_moves, st.sum_depth) == (8, 8, 4 if fixed else 3)
+    s2 = orc.Search(cfg, 6)
+    with pytest.raises(ValueError):
+        s2.find_move(stuck, 0, 4)
+    st = s2.stats()
+    assert (st.sims, st.rollouts_without_moves, st.max_rollout_steps, st.sum_depth) == (4, 4, 0, 0)
