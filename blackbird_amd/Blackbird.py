@@ -152,7 +152,8 @@ def _side_to_move(game, packed):
 
 
 def GenerateTrainingSamples(model, nGames, temp):
-    """Blackbird.py:219-268.  Raises ValueError if nGames <= 0."""
+    """Blackbird.py:219-268.  Raises ValueError if nGames <= 0.  With model.KeepDeviceExamples the run's records also stay on
+    the GPU for TrainWithDeviceExamples (not under a time limit: _timed_selfplay leaves no engine records)."""
     if nGames <= 0:
         raise ValueError('Use a positive integer for number of games.')
     game_cls = model.Game
@@ -236,6 +237,9 @@ def GenerateTrainingSamples(model, nGames, temp):
     finally:
         if ctx is not None:
             ctx.__exit__(None, None, None)
+    if getattr(model, 'KeepDeviceExamples', False):  # every game has finished: a snapshot of the run's records stays on the GPU
+        from .training import DeviceExamples
+        model._kept_examples.append((model.Version, DeviceExamples.from_engine(eng, 'cuda:%d' % eng.cfg.device)))
 
 
 def TrainWithExamples(model, batchSize, learningRate, epochs=1, teacher=None, model_override=None,
@@ -252,6 +256,39 @@ def TrainWithExamples(model, batchSize, learningRate, epochs=1, teacher=None, mo
                     np.vstack([b.MctsPolicy for b in batch]), learningRate, teacher)
     model.Version += 1
     model.Conn.PutModel(model.Game.GameType, model.Name, model.Version)
+
+
+def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=None):
+    """TrainWithExamples (Blackbird.py:271-312) on examples that never left the GPU: `examples` (a training.DeviceExamples),
+    or else what GenerateTrainingSamples kept for the model's current Version (model.KeepDeviceExamples).  The same steps
+    in the same order -- the epoch's order drawn from numpy's generator as there (the same seed visits the same examples in
+    the same batches), one optimiser step per batch --, but a batch is formed on the device (bb_examples_to_batch) and the
+    trained weights are exported and handed to the engines once, after the last batch, not after every one.  `epochs` is
+    accepted and ignored, as in the reference.  Raises ValueError when there is nothing to train from."""
+    from .training import epoch_order
+    model.SampleValue.cache_clear()
+    model.GetPriors.cache_clear()
+    if examples is None:
+        examples = model.KeptDeviceExamples()
+    if examples is None or len(examples) == 0:
+        raise ValueError('no device examples for %s version %d: pass `examples`, or set KeepDeviceExamples before '
+                         'GenerateTrainingSamples' % (model.Name, model.Version))
+    order = examples.index_tensor(epoch_order(len(examples), batchSize))
+    nBatches = len(order) // batchSize
+    if nBatches:
+        trainer = model._trainer_for(examples.info.C)
+        for i in range(nBatches):
+            boards, value, policy = examples._batch(order[i * batchSize:(i + 1) * batchSize])
+            trainer.step_tensors(boards, value, policy, learningRate)
+        bad = examples.bad()  # (one look per epoch: it waits for the GPU)
+        if bad:
+            raise _lib.BlackbirdHipError('%d malformed example records were met in training' % bad)
+        model._weights = trainer.export()
+        model._weights_changed()
+        model.batchCount += nBatches
+    model.Version += 1
+    model.Conn.PutModel(model.Game.GameType, model.Name, model.Version)
+    model._kept_examples = [(v, ex) for v, ex in model._kept_examples if v >= model.Version]
 
 
 def TestModelsBatched(model1, model2, temp, numTests, **kw):
@@ -313,6 +350,11 @@ class Model(MCTS, Network):
         self._saveName = '%s_%s' % (name, self.Version)
         self._batch_engine = None
         self._games_played = 0  # self-play games this model has started: the next run's first global game id
+        # opt-in: GenerateTrainingSamples also keeps each run's finished records on the GPU (training.DeviceExamples), with
+        # the Version they were played by, for TrainWithDeviceExamples; sqlite receives every game either way.  Runs under a
+        # time limit (mcts.timeLimit: _timed_selfplay) search in lock step and leave no engine records: nothing is kept
+        self.KeepDeviceExamples = False
+        self._kept_examples = []
         MCTS.__init__(self, **mctsConfig)
         factory = None
         if networkConfig != {}:
@@ -323,6 +365,12 @@ class Model(MCTS, Network):
     def LastVersion(self):
         """Blackbird.py:347-348: a second Model built from the same arguments (it loads the last saved version)."""
         return type(self)(self.Game, self.Name, self.MCTSConfig, self.NetworkConfig, self.TensorflowConfig)
+
+    def KeptDeviceExamples(self):
+        """The device examples kept for the current Version (all runs together), or None."""
+        from .training import DeviceExamples
+        mine = [ex for v, ex in self._kept_examples if v == self.Version]
+        return DeviceExamples.cat(mine) if mine else None
 
     # ---- engine plumbing -----------------------------------------------------------------------------------
     def _make_engine(self, game_id, n_slots, sims, **kw):

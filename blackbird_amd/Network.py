@@ -71,21 +71,26 @@ class Network:
         _v, _l, p = eng.net_eval(planes=state.astype(np.int8), noise=eng._noise_calls)  # fresh draw per call
         return p[0]
 
-    def train(self, state, eval, policy, learningRate=0.01, teacher=None):
-        """Network.py:66-84 (see blackbird_amd/training.py for the loss)."""
+    def _trainer_for(self, in_planes):
+        """The optimiser over this network's weights, created on first use (optimiser kind from NetworkConfig, the graph's
+        alpha and epsilon) and kept, with its slots, until other weights are loaded."""
         from .training import Trainer
-        if teacher is not None:
-            # the reference's teacher branch (NetworkFactory.py:205-218) calls the removed tf.log and cannot run; refusing
-            # is better than silently training without the term
-            raise NotImplementedError('policy distillation from a teacher (hasTeacher) is not supported')
-        state = np.asarray(state)
-        self._ensure_weights(state.shape[-1])
+        self._ensure_weights(in_planes)
         if self._trainer is None:
             cfg = getattr(self._constructor, 'NetworkConfig', None) or {}
             self._trainer = Trainer(self._weights, alpha=self.alpha, epsilon=self.epsilon,
                                     optimizer=(cfg.get('training') or {}).get('optimizer', 'adam'),
                                     momentum=(cfg.get('training') or {}).get('momentum', 0.9))
-        self._trainer.step(state, eval, policy, learningRate)
+        return self._trainer
+
+    def train(self, state, eval, policy, learningRate=0.01, teacher=None):
+        """Network.py:66-84 (see blackbird_amd/training.py for the loss)."""
+        if teacher is not None:
+            # the reference's teacher branch (NetworkFactory.py:205-218) calls the removed tf.log and cannot run; refusing
+            # is better than silently training without the term
+            raise NotImplementedError('policy distillation from a teacher (hasTeacher) is not supported')
+        state = np.asarray(state)
+        self._trainer_for(state.shape[-1]).step(state, eval, policy, learningRate)
         self._weights = self._trainer.export()
         self._weights_changed()
         self.batchCount += 1

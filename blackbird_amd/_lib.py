@@ -25,6 +25,7 @@ EXPORTS = (
     "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked",
     "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
+    "bb_examples_to_batch",
 )
 
 
@@ -115,6 +116,7 @@ def lib():
     L.bb_node_edges.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp, vp]
     L.bb_examples_fetch_games.argtypes = [vp, ip, vp, vp, ip, vp, vp]
     L.bb_examples_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp)]
+    L.bb_examples_to_batch.argtypes = [ip, ip, vp, ip, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name != "bb_last_error":
             getattr(L, name).restype = C.c_int
@@ -266,6 +268,15 @@ def example_dtype(game):
     dt = np.dtype(fields)
     assert dt.itemsize == gi.example_bytes, (dt.itemsize, gi.example_bytes)
     return dt
+
+
+def examples_to_batch(game, n_records, records, n, index=None, boards=None, policy=None, value=None, bad=None, stream=0):
+    """bb_examples_to_batch: rows `index[0..n)` (None: 0..n-1) of the device records -> float32 boards [n,H,W,C], policy
+    [n,A], value [n] and the int32 count of rejected rows.  Every argument after `n` is a DEVICE address (an int, e.g.
+    torch.Tensor.data_ptr(); None/0 = absent) on the current device; `stream` a hipStream_t handle.  Asynchronous."""
+    check(lib().bb_examples_to_batch(int(game), int(n_records), C.c_void_p(records or None), int(n), C.c_void_p(index or None),
+                                     C.c_void_p(boards or None), C.c_void_p(policy or None), C.c_void_p(value or None),
+                                     C.c_void_p(bad or None), C.c_void_p(stream or None)))
 
 
 def fit_slots(game, n_slots, sims_per_move, *, mcts_kind=MCTS_DYNAMIC, max_depth=10, max_plies=None, max_games=None,

@@ -13,6 +13,7 @@
 #include "tree_dc.hip.h"
 #include "mega2.hip.h"
 #include "mega_dc.hip.h"
+#include "examples.hip.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -1804,6 +1805,26 @@ extern "C" int bb_examples_device(bb_engine *e, void **ptr_out, uint64_t *bytes_
     if (bytes_out) *bytes_out = (uint64_t)e->cfg.max_games * (uint64_t)(e->cfg.max_plies + 1) * (uint64_t)e->info.example_bytes;
     if (record_bytes_out) *record_bytes_out = (uint64_t)e->info.example_bytes;
     if (game_hdr_out) *game_hdr_out = e->dev.game_hdr;
+    return BB_OK;
+}
+
+extern "C" int bb_examples_to_batch(int game, int n_records, const void *records, int n, const int64_t *index, float *boards_out,
+                                    float *policy_out, float *value_out, int32_t *bad_out, void *stream) {
+    if (n == 0) return BB_OK; // an empty batch is a no-op
+    if (n < 0 || n_records < 0 || !records || (!boards_out && !policy_out && !value_out)) return fail(BB_ERR_ARG, "bad arguments");
+    if (((uintptr_t)records | (uintptr_t)boards_out | (uintptr_t)policy_out) % 16)
+        return fail(BB_ERR_ARG, "records, boards_out and policy_out are accessed in 16-byte units");
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t *rec = (const uint8_t *)records;
+    GAME_SWITCH(game, {
+        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
+            k_dc_examples_to_batch<<<n, 256, 0, st>>>(n_records, rec, index, boards_out, policy_out, value_out, bad_out);
+        else
+            k_examples_to_batch<G><<<nblk((size_t)n * (G::H * G::W * G::C + G::A + 1)), 256, 0, st>>>(
+                n_records, rec, n, index, boards_out, policy_out, value_out, bad_out);
+        break;
+    });
+    HIPCHK(hipGetLastError());
     return BB_OK;
 }
 

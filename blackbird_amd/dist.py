@@ -8,7 +8,8 @@ maximum (RCCL has no all-gather-v).  torch.distributed is used for the collectiv
 On the GPU the records never visit the host on their way out: `engine_records_device` wraps the engine's example
 store (bb_examples_device) as a torch tensor without copying, compacts the finished games' records on the device,
 and `allgather_bytes` hands that tensor to RCCL; only the gathered result is brought to the host, by whoever consumes it
-(the sqlite sink, the training set)."""
+(the sqlite sink) -- or not at all: training.DeviceExamples(game, tensor) accepts the tensor `allgather_engine_examples`
+returns as it is and forms training batches from it on the device (bb_examples_to_batch; Blackbird.TrainWithDeviceExamples)."""
 import numpy as np
 
 GAME_ID_STRIDE = 50_000_000  # global game ids of rank r start at r * GAME_ID_STRIDE
@@ -85,7 +86,8 @@ def allgather_store(store, hdr):
 def allgather_engine_examples(eng, device, dtype=None):
     """Epoch-end exchange for one engine per rank: device records -> RCCL all-gather -> (device tensor [N, record_bytes]
     of every rank's records in rank order, per-rank record counts).  With `dtype` (Engine example dtype) the result is
-    also returned as a host structured array for host-side consumers."""
+    also returned as a host structured array for host-side consumers.  The device tensor is what training.DeviceExamples
+    wraps: DeviceExamples(eng.game, out) trains from every rank's records without a host copy."""
     rec = engine_records_device(eng, device)
     rb = rec.shape[1] if rec.dim() == 2 else int(eng.examples_device()[2])
     flat, sizes = allgather_bytes(rec)

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 import torch.nn.functional as Fn
 
+from . import _lib
 from . import weights as W
 
 
@@ -100,6 +101,14 @@ class Trainer:
         lossParam = torch.stack(l2).mean()
         return lossEvaluation + lossPolicy + lossParam, (lossEvaluation, lossPolicy, lossParam)
 
+    def _gradients_tensors(self, boards, evalLabel, policyLabel, noise=None):
+        """The tensor-level core of `gradients`, `step` and `step_tensors`: float32 tensors on the trainer's device in,
+        (loss, its three terms, {variable: gradient}) out as tensors -- nothing is brought to the host."""
+        total, parts = self.loss(boards, evalLabel, policyLabel, noise)
+        names = list(self.params)
+        gs = torch.autograd.grad(total, [self.params[k] for k in names])
+        return total.detach(), [p.detach() for p in parts], dict(zip(names, gs))
+
     def gradients(self, state, eval, policy, noise=None):
         """Loss, its three terms and d loss / d variable for one batch (what optimizer.minimize(loss) differentiates).
         noise: the A Beta(alpha, 1-alpha) draws of the graph's Dirichlet node, or None to draw them."""
@@ -108,13 +117,19 @@ class Trainer:
         pl = torch.tensor(np.asarray(policy, dtype=np.float32), device=self.device)
         if noise is not None:
             noise = torch.tensor(np.asarray(noise, dtype=np.float32), device=self.device)
-        total, parts = self.loss(boards, ev, pl, noise)
-        names = list(self.params)
-        gs = torch.autograd.grad(total, [self.params[k] for k in names])
-        return float(total.detach()), [float(p.detach()) for p in parts], dict(zip(names, gs))
+        total, parts, grads = self._gradients_tensors(boards, ev, pl, noise)
+        return float(total), [float(p) for p in parts], grads
 
     def step(self, state, eval, policy, learningRate, noise=None):
         total, parts, grads = self.gradients(state, eval, policy, noise)
+        self._apply(grads, float(learningRate))
+        return total, parts
+
+    def step_tensors(self, boards, evalLabel, policyLabel, learningRate, noise=None):
+        """`step` for a batch that is already on the trainer's device as float32 tensors (boards [B,H,W,C], evalLabel [B],
+        policyLabel [B,A], noise [A] or None): no host copy on the way in, and the loss and its terms come back as
+        tensors, so the call does not wait for the GPU."""
+        total, parts, grads = self._gradients_tensors(boards, evalLabel.reshape(-1), policyLabel, noise)
         self._apply(grads, float(learningRate))
         return total, parts
 
@@ -122,3 +137,97 @@ class Trainer:
         out = {k: v.detach().cpu().numpy().copy() for k, v in self.params.items()}
         out.update({k: v.cpu().numpy().copy() for k, v in self.consts.items()})
         return out
+
+
+def epoch_order(n, batchSize):
+    """The order in which an epoch visits `n` examples in whole batches: TrainWithExamples' draw (Blackbird.py:292-293),
+    consuming numpy's global generator exactly as it does -- the same numpy seed gives the same batches on the host
+    path and on the device path."""
+    return np.random.choice(n, n - n % batchSize, replace=False)
+
+
+class DeviceExamples:
+    """Self-play example records that stay on the GPU: a game id and a uint8 tensor [N, example_bytes] in the layout of
+    bb_examples_fetch.  `batch` turns any selection of them into the three float32 tensors the loss takes
+    (bb_examples_to_batch: one HIP launch on torch's current stream, nothing staged through the host).
+
+    The records may come from one engine (`from_engine`), from the host (`from_records`) or from every rank:
+    DeviceExamples(game, dist.allgather_engine_examples(eng, device)[0]) takes the all-gathered tensor as it is."""
+
+    def __init__(self, game, records):
+        gi = _lib.game_info(game)
+        if records.dtype != torch.uint8 or records.dim() != 2 or records.shape[1] != gi.example_bytes:
+            raise ValueError('records: a uint8 tensor [N, %d] is expected, got %s %r'
+                             % (gi.example_bytes, records.dtype, tuple(records.shape)))
+        self.game, self.info = game, gi
+        self.records = records.contiguous()
+        self._bad = torch.zeros(1, dtype=torch.int32, device=records.device)
+
+    @classmethod
+    def from_engine(cls, eng, device):
+        """A snapshot of the finished games' records of `eng`, in (game, ply) order.  dist.engine_records_device compacts
+        the engine's store into a tensor of its own; the clone makes the snapshot independent of how it does so -- the
+        store is written again by the next bb_selfplay_begin."""
+        from . import dist
+        return cls(eng.game, dist.engine_records_device(eng, device).clone())
+
+    @classmethod
+    def from_records(cls, game, records, device):
+        """From a host structured array (Engine.fetch_examples / fetch_games, _lib.example_dtype)."""
+        raw = np.ascontiguousarray(records).view(np.uint8).reshape(len(records), -1)
+        return cls(game, torch.from_numpy(raw.copy()).to(torch.device(device)))
+
+    @classmethod
+    def cat(cls, parts):
+        """The records of several sets of one game, in list order; the count of rejected rows carries over."""
+        parts = list(parts)
+        if not parts or any(p.game != parts[0].game for p in parts):
+            raise ValueError('cat needs at least one DeviceExamples, all of one game')
+        out = cls(parts[0].game, torch.cat([p.records for p in parts]))
+        for p in parts:
+            out._bad += p._bad.to(out._bad.device)
+        return out
+
+    def __len__(self):
+        return int(self.records.shape[0])
+
+    def index_tensor(self, index):
+        """`index` (int64 tensor or anything numpy takes) as an int64 tensor on the records' device, range-checked:
+        every entry must name one of the len(self) records."""
+        if torch.is_tensor(index):
+            idx = index.to(device=self.records.device, dtype=torch.int64).reshape(-1)
+            wrong = bool(((idx < 0) | (idx >= len(self))).any()) if idx.numel() else False
+        else:
+            host = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+            wrong = bool(((host < 0) | (host >= len(self))).any())
+            idx = torch.from_numpy(host).to(self.records.device)
+        if wrong:
+            raise IndexError('example index out of range [0, %d)' % len(self))
+        return idx.contiguous()
+
+    def batch(self, index=None):
+        """(boards [n,H,W,C], value [n], policy [n,A]) of the records `index` names (None: all, in order), fresh float32
+        tensors on the records' device: what TrainWithExamples stacks per batch, in Network.train's argument order."""
+        return self._batch(None if index is None else self.index_tensor(index))
+
+    def _batch(self, idx):
+        """`batch` for an index tensor that index_tensor returned (or a slice of one)."""
+        gi, dev = self.info, self.records.device
+        n = len(self) if idx is None else int(idx.numel())
+        boards = torch.empty((n, gi.H, gi.W, gi.C), dtype=torch.float32, device=dev)
+        value = torch.empty((n,), dtype=torch.float32, device=dev)
+        policy = torch.empty((n, gi.A), dtype=torch.float32, device=dev)
+        if n == 0:
+            return boards, value, policy
+        if dev.type != 'cuda':
+            raise _lib.BlackbirdHipError('DeviceExamples.batch runs on the GPU only (records on %s)' % dev)
+        with torch.cuda.device(dev):
+            _lib.examples_to_batch(self.game, len(self), self.records.data_ptr(), n,
+                                   None if idx is None else idx.data_ptr(), boards.data_ptr(), policy.data_ptr(),
+                                   value.data_ptr(), self._bad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return boards, value, policy
+
+    def bad(self):
+        """Rows that bb_examples_to_batch rejected (and wrote as zeros) since this object was made: malformed records.
+        Waits for the GPU -- look at it once per epoch, not once per batch."""
+        return int(self._bad.item())

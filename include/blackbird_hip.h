@@ -301,6 +301,27 @@ int bb_examples_fetch_games(bb_engine *e, int n, const int32_t *game_ids, void *
 int bb_examples_device(bb_engine *e, void **records_out, uint64_t *bytes_out, uint64_t *record_bytes_out,
                        int32_t **game_hdr_out);
 
+/* ---- training batches from example records, on the device ------------------------------------ */
+/* What TrainWithExamples stacks per batch (Blackbird.py:300-308: AsInputArray planes, the MCTS policy, z), after the float32
+ * conversion of the loss's inputs -- formed where the records are, with nothing staged through the host.  Stateless; ALL
+ * pointers are device memory of the calling thread's current device, and the launch is asynchronous on `stream` (a hipStream_t;
+ * 0 = the default stream).
+ *   records  [n_records][example_bytes], the bb_examples_fetch layout: the engine's own store (bb_examples_device), a compacted
+ *            copy or an all-gathered tensor.  16-byte aligned.
+ *   index    [n] record of every batch row, in output order; NULL = records 0..n-1.
+ * Row k, from record r = records[index[k]] (any single output may be NULL, not all three):
+ *   boards_out[k][H][W][C] float32: the AsInputArray planes of r's state (bb_game_encode's values);
+ *   policy_out[k][A]       float32: (float)((double)visits_a / (double)total) -- divided in double, rounded once --, all zeros
+ *                          when total == 0 (the terminal example).  Dense games: entry a from visits[a], a < A (the spare
+ *                          slots A..S-1 are ignored); DragonChess: zeros except entry action[j] from visits[j], j < n_children;
+ *   value_out[k]           float32: r.z.
+ *   boards_out and policy_out 16-byte aligned.
+ * A row is written as all zeros, and *bad_out (when non-NULL) incremented by one per such row, if index[k] is outside
+ * [0, n_records), if n_children > S, or if a compact action[j] >= A: malformed input never becomes an out-of-bounds access.
+ * n == 0: BB_OK, nothing touched (GPU or not).  n < 0, records NULL, every output NULL, a misaligned pointer: BB_ERR_ARG. */
+int bb_examples_to_batch(int game, int n_records, const void *records, int n, const int64_t *index, float *boards_out,
+                         float *policy_out, float *value_out, int32_t *bad_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

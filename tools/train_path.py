@@ -1,0 +1,93 @@
+"""From finished self-play games to a trained network, both ways, timed: python tools/train_path.py [--games N]
+[--play-limit P] [--batch B] [--lr LR]
+
+N Connect4 games at PlayLimit P are played once (Model.KeepDeviceExamples on, so that sqlite and the GPU hold the same
+examples); then one epoch over them is trained twice with the same batch size:
+
+  host path    what Blackbird.TrainWithExamples does: Conn.GetGames + ExampleState.FromSerialized per example (decode),
+               then np.vstack per batch + Model.train, which exports the weights and reloads the engines after every batch
+  device path  Blackbird.TrainWithDeviceExamples on the kept records: bb_examples_to_batch + Trainer.step_tensors per
+               batch, one export and one reload at the end
+
+and the bare DeviceExamples.batch calls of that epoch alone.  Every timed region ends in a device synchronise; one training
+step is run before any of them (the first step pays for the library's kernel selection).  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from blackbird_amd import Blackbird, Connect4  # noqa: E402
+from blackbird_amd.training import epoch_order  # noqa: E402
+
+CFG = {"blocks": 4, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
+       "policy": {"dirichlet": {"alpha": 0.2, "epsilon": 0.3}}, "training": {"optimizer": "adam"}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=2048)
+    ap.add_argument("--play-limit", type=int, default=32)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    os.chdir(tempfile.mkdtemp())  # the sqlite file and the saved networks of this run
+    np.random.seed(a.seed)
+    model = Blackbird.Model(Connect4.BoardState, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, CFG)
+    model.KeepDeviceExamples = True
+    Blackbird.GenerateTrainingSamples(model, 64, 1.0)  # warm-up run (its examples are trained on too)
+    t = time.time()
+    Blackbird.GenerateTrainingSamples(model, a.games, 1.0)
+    selfplay_s = time.time() - t
+    kept = model.KeptDeviceExamples()
+    n, B = len(kept), a.batch
+    boards, value, policy = (x.cpu().numpy() for x in kept.batch(np.arange(min(B, n))))
+    model.train(boards, value, policy, a.lr)  # warm-up step
+    torch.cuda.synchronize()
+
+    # bare batches of one epoch
+    order = kept.index_tensor(epoch_order(n, B))
+    torch.cuda.synchronize()
+    t = time.time()
+    for i in range(len(order) // B):
+        kept._batch(order[i * B:(i + 1) * B])
+    torch.cuda.synchronize()
+    batch_s = time.time() - t
+
+    # host path: TrainWithExamples, statement by statement, with a clock after the decode
+    t = time.time()
+    states = model.Conn.GetGames(model.Name, model.Version)
+    examples = [Blackbird.ExampleState.FromSerialized(s) for s in states]
+    decode_s = time.time() - t
+    assert len(examples) == n, (len(examples), n)
+    horder = np.random.choice(len(examples), len(examples) - (len(examples) % B), replace=False)
+    examples = [examples[i] for i in horder]
+    for i in range(len(examples) // B):
+        b = examples[i * B:(i + 1) * B]
+        model.train(np.vstack([e.Board for e in b]), np.hstack([e.MctsEval for e in b]),
+                    np.vstack([e.MctsPolicy for e in b]), a.lr)
+    torch.cuda.synchronize()
+    host_s = time.time() - t
+
+    # device path
+    t = time.time()
+    Blackbird.TrainWithDeviceExamples(model, B, a.lr, examples=kept)
+    torch.cuda.synchronize()
+    device_s = time.time() - t
+
+    print(json.dumps({"tool": "train_path", "game": "connect4", "games": a.games, "warmup_games": 64, "play_limit": a.play_limit,
+                      "examples": n, "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
+                      "host_path_s": round(host_s, 3), "host_decode_s": round(decode_s, 3),
+                      "device_path_s": round(device_s, 3), "device_batches_only_s": round(batch_s, 4),
+                      "host_over_device": round(host_s / device_s, 2)}))
+
+
+if __name__ == "__main__":
+    main()
