@@ -1,8 +1,9 @@
 """Mirror of /root/reference/src/Network.py:9-112.  getEvaluation/getPolicy run the fused HIP
 tower (bb_net_eval) on the int8 planes AsInputArray returns; weights live in an .npz with the
 reference's TensorFlow variable names instead of a TF checkpoint.  train() is the step right after
-the hot path: PyTorch-ROCm optimiser over the same parameters, then the new
-weights are pushed back into the engine."""
+the hot path: PyTorch-ROCm optimiser over the same parameters (or, with
+NetworkConfig['training']['backend'] = 'hip', the HIP training kernels), then the new weights are
+pushed back into the engine."""
 import os
 
 import numpy as np
@@ -74,13 +75,20 @@ class Network:
     def _trainer_for(self, in_planes):
         """The optimiser over this network's weights, created on first use (optimiser kind from NetworkConfig, the graph's
         alpha and epsilon) and kept, with its slots, until other weights are loaded."""
-        from .training import Trainer
+        from . import training
         self._ensure_weights(in_planes)
         if self._trainer is None:
-            cfg = getattr(self._constructor, 'NetworkConfig', None) or {}
-            self._trainer = Trainer(self._weights, alpha=self.alpha, epsilon=self.epsilon,
-                                    optimizer=(cfg.get('training') or {}).get('optimizer', 'adam'),
-                                    momentum=(cfg.get('training') or {}).get('momentum', 0.9))
+            cfg = (getattr(self._constructor, 'NetworkConfig', None) or {}).get('training') or {}
+            backend = cfg.get('backend', 'torch')
+            if backend not in ('torch', 'hip'):
+                raise ValueError("NetworkConfig['training']['backend'] is 'torch' or 'hip', got %r" % (backend,))
+            if backend == 'hip' and not training.hip_trainer_supports(self._weights):
+                raise ValueError("NetworkConfig['training']['backend'] = 'hip' covers %s; this network has shape "
+                                 "(planes, filters, blocks, dense, actions) = %r.  Use the 'torch' backend for it."
+                                 % (training.HIP_TRAINER_LIMITS, W.infer_shape(self._weights)))
+            make = training.HipTrainer if backend == 'hip' else training.Trainer
+            self._trainer = make(self._weights, alpha=self.alpha, epsilon=self.epsilon,
+                                 optimizer=cfg.get('optimizer', 'adam'), momentum=cfg.get('momentum', 0.9))
         return self._trainer
 
     def train(self, state, eval, policy, learningRate=0.01, teacher=None):

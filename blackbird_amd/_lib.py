@@ -17,6 +17,8 @@ MCTS_DYNAMIC, MCTS_FIXED = 0, 1
 EVAL_HASH, EVAL_NET, EVAL_ROLLOUT = 0, 1, 2
 NET_FORM_AUTO, NET_FORM_F32, NET_FORM_SPLIT = 0, 1, 2   # bb_config.net_form
 LAUNCH_AUTO, LAUNCH_LOCKSTEP, LAUNCH_ROUNDS = 0, 1, 2    # bb_config.launch
+OPT_ADAM, OPT_MOMENTUM, OPT_SGD = 0, 1, 2                # bb_train_config.optimizer
+TRAIN_PARAMS, TRAIN_GRADS, TRAIN_SLOT_M, TRAIN_SLOT_V, TRAIN_NOISE = 0, 1, 2, 3, 4   # bb_trainer_read
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NAN, ERR_CAPACITY, ERR_WEIGHTS = 0, -1, -2, -3, -4, -5, -6
 
 EXPORTS = (
@@ -26,6 +28,7 @@ EXPORTS = (
     "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
     "bb_examples_to_batch",
+    "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_param_count", "bb_trainer_read",
 )
 
 
@@ -56,6 +59,11 @@ class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("sims", "sum_depth", "nodes", "terminal_leaves", "games_finished",
                                            "plies", "overflow", "examples", "evals",
                                            "eval_cache_hits", "eval_cache_probes")]
+
+
+class TrainConfig(C.Structure):
+    _fields_ = [("game", C.c_int32), ("optimizer", C.c_int32), ("max_batch", C.c_int32), ("device", C.c_int32),
+                ("momentum", C.c_float), ("alpha", C.c_float), ("epsilon", C.c_float), ("seed", C.c_uint64)]
 
 
 class BlackbirdHipError(RuntimeError):
@@ -117,6 +125,11 @@ def lib():
     L.bb_examples_fetch_games.argtypes = [vp, ip, vp, vp, ip, vp, vp]
     L.bb_examples_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp)]
     L.bb_examples_to_batch.argtypes = [ip, ip, vp, ip, vp, vp, vp, vp, vp, vp]
+    L.bb_trainer_create.argtypes = [C.POINTER(TrainConfig), C.POINTER(NetWeights), C.POINTER(vp)]
+    L.bb_trainer_destroy.argtypes = [vp]
+    L.bb_trainer_step.argtypes = [vp, ip, vp, vp, vp, vp, C.c_double, ip, vp, vp]
+    L.bb_trainer_param_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.bb_trainer_read.argtypes = [vp, ip, vp, C.c_int64]
     for name in EXPORTS:
         if name != "bb_last_error":
             getattr(L, name).restype = C.c_int
@@ -277,6 +290,57 @@ def examples_to_batch(game, n_records, records, n, index=None, boards=None, poli
     check(lib().bb_examples_to_batch(int(game), int(n_records), C.c_void_p(records or None), int(n), C.c_void_p(index or None),
                                      C.c_void_p(boards or None), C.c_void_p(policy or None), C.c_void_p(value or None),
                                      C.c_void_p(bad or None), C.c_void_p(stream or None)))
+
+
+def net_weights(H, W, flat):
+    """(bb_net_weights, the arrays it points into) for a dict from blackbird_amd.weights.flatten(); the shape fields are
+    taken from the arrays, so a network outside what an entry point supports reaches that entry point's own checks."""
+    w = NetWeights()
+    k0 = flat["conv0_k"]
+    w.H, w.W, w.C, w.F = int(H), int(W), k0.shape[2], k0.shape[3]
+    w.R, w.D, w.A = flat["blk_k"].shape[0], flat["v_d1_k"].shape[0], flat["p_d_b"].shape[0]
+    keep = {}
+    for name, _t in NetWeights._fields_[7:]:
+        keep[name] = np.ascontiguousarray(flat[name], dtype=np.float32)
+        setattr(w, name, keep[name].ctypes.data_as(_FP))
+    return w, keep
+
+
+def trainer_create(game, flat, H, W, optimizer, max_batch, device=0, momentum=0.9, alpha=0.2, epsilon=0.3, seed=0):
+    """bb_trainer_create: a bb_trainer handle (c_void_p) over the weights `flat` (weights.flatten()) of an H x W game."""
+    cfg = TrainConfig(game=int(game), optimizer=int(optimizer), max_batch=int(max_batch), device=int(device),
+                      momentum=float(momentum), alpha=float(alpha), epsilon=float(epsilon), seed=int(seed) & (2 ** 64 - 1))
+    w, _keep = net_weights(H, W, flat)
+    h = C.c_void_p()
+    check(lib().bb_trainer_create(C.byref(cfg), C.byref(w), C.byref(h)))
+    return h
+
+
+def trainer_destroy(h):
+    if h is not None and h.value:
+        lib().bb_trainer_destroy(h)
+
+
+def trainer_step(h, n, boards, value, policy, noise=None, lr=0.0, apply=True, loss_out=None, stream=0):
+    """bb_trainer_step: boards, value, policy, noise, loss_out are DEVICE addresses (ints; None/0 = absent).  Asynchronous."""
+    check(lib().bb_trainer_step(h, int(n), C.c_void_p(boards or None), C.c_void_p(value or None), C.c_void_p(policy or None),
+                                C.c_void_p(noise or None), float(lr), int(bool(apply)), C.c_void_p(loss_out or None),
+                                C.c_void_p(stream or None)))
+
+
+def trainer_param_count(h):
+    n = C.c_int64()
+    check(lib().bb_trainer_param_count(h, C.byref(n)))
+    return n.value
+
+
+def trainer_read(h, what, count=None):
+    """bb_trainer_read: a flat float32 array (count: the parameter count, or A for TRAIN_NOISE, when None)."""
+    if count is None:
+        count = trainer_param_count(h)
+    out = np.zeros(int(count), dtype=np.float32)
+    check(lib().bb_trainer_read(h, int(what), ptr(out), int(count)))
+    return out
 
 
 def fit_slots(game, n_slots, sims_per_move, *, mcts_kind=MCTS_DYNAMIC, max_depth=10, max_plies=None, max_games=None,

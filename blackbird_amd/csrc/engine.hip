@@ -14,6 +14,7 @@
 #include "mega2.hip.h"
 #include "mega_dc.hip.h"
 #include "examples.hip.h"
+#include "train.hip.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -1825,6 +1826,212 @@ extern "C" int bb_examples_to_batch(int game, int n_records, const void *records
         break;
     });
     HIPCHK(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- the training step (train.hip.h) ----------------------------------------------------------------------------------
+struct bb_trainer {
+    bb_train_config cfg;
+    TrainLayout lay;
+    int A, P, C;
+    size_t lds_bytes;
+    float *prm, *slot_m, *slot_v, *grads, *slabs, *le, *lp, *loss;
+    uint8_t *kind;
+    TrainAux *aux;
+    uint64_t calls; // steps made so far, gradient-only ones included: the counter of the noise stream
+    int64_t t;      // updates applied so far: AdamOptimizer's beta powers
+};
+
+static TrainLayout train_layout(int C, int R, int D, int A) {
+    TrainLayout l = {};
+    int o = 0;
+    auto take = [&](int n) { int at = o; o += n; return at; };
+    const int F = BB_TRAIN_F;
+    l.R = R; l.D = D;
+    l.conv0_k = take(9 * C * F); l.conv0_b = take(F); l.conv0_bn = take(4 * F);
+    l.blk_k = take(R * 2 * 9 * F * F); l.blk_b = take(R * 2 * F); l.blk_bn = take(R * 2 * 4 * F);
+    l.v_conv_k = take(F); l.v_conv_b = take(1); l.v_bn = take(4);
+    l.v_d1_k = take(D); l.v_d1_b = take(D); l.v_d2_k = take(D); l.v_d2_b = take(1);
+    l.p_conv_k = take(2 * F); l.p_conv_b = take(2); l.p_bn = take(8); l.p_d_k = take(2 * A); l.p_d_b = take(A);
+    l.count = o;
+    l.n_l2 = 12 + 6 * R; // kernel, gamma, beta of 1 + 2R tower convs and of the two head convs; dense_1, dense_2, policy kernels
+    return l;
+}
+
+static void trainer_free(bb_trainer *t) {
+    void *ps[] = {t->prm, t->slot_m, t->slot_v, t->grads, t->slabs, t->le, t->lp, t->loss, t->kind, t->aux};
+    for (void *p : ps)
+        if (p) (void)hipFree(p);
+    delete t;
+}
+
+template <class G>
+static int trainer_lds(bb_trainer *t) {
+    t->lds_bytes = (size_t)train_lds_floats<G>(t->lay.R) * sizeof(float);
+    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
+    return BB_OK;
+}
+
+static int trainer_alloc(bb_trainer *t, const bb_net_weights *w) {
+    const TrainLayout &l = t->lay;
+    const size_t cb = (size_t)l.count * sizeof(float), slab_b = cb * (size_t)t->cfg.max_batch;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (slab_b + 8 * cb > free_b - free_b / 16)
+        return fail(BB_ERR_CAPACITY, "%d gradient slabs of %zu bytes do not fit the %zu free bytes of device %d", t->cfg.max_batch, cb,
+                    free_b, t->cfg.device);
+    HIPCHK(hipMalloc(&t->prm, cb));
+    HIPCHK(hipMalloc(&t->slot_m, cb));
+    HIPCHK(hipMalloc(&t->slot_v, cb));
+    HIPCHK(hipMalloc(&t->grads, cb));
+    HIPCHK(hipMalloc(&t->slabs, slab_b));
+    HIPCHK(hipMalloc(&t->le, (size_t)t->cfg.max_batch * sizeof(float)));
+    HIPCHK(hipMalloc(&t->lp, (size_t)t->cfg.max_batch * sizeof(float)));
+    HIPCHK(hipMalloc(&t->loss, 4 * sizeof(float)));
+    HIPCHK(hipMalloc(&t->kind, (size_t)l.count));
+    HIPCHK(hipMalloc(&t->aux, sizeof(TrainAux)));
+    HIPCHK(hipMemset(t->slot_m, 0, cb));
+    HIPCHK(hipMemset(t->slot_v, 0, cb));
+    HIPCHK(hipMemset(t->grads, 0, cb));
+    HIPCHK(hipMemset(t->loss, 0, 4 * sizeof(float)));
+    HIPCHK(hipMemset(t->aux, 0, sizeof(TrainAux)));
+    // variable kinds: 1 trainable and in the L2 mean, 2 trainable bias, 0 moving statistics
+    std::vector<uint8_t> kind((size_t)l.count, 1);
+    auto mark = [&](int at, int n, uint8_t k) { std::fill(kind.begin() + at, kind.begin() + at + n, k); };
+    const int F = BB_TRAIN_F, R = l.R, D = l.D;
+    mark(l.conv0_b, F, 2); mark(l.blk_b, R * 2 * F, 2); mark(l.v_conv_b, 1, 2); mark(l.v_d1_b, D, 2); mark(l.v_d2_b, 1, 2);
+    mark(l.p_conv_b, 2, 2); mark(l.p_d_b, t->A, 2);
+    mark(l.conv0_bn + 2 * F, 2 * F, 0);
+    for (int i = 0; i < 2 * R; i++) mark(l.blk_bn + i * 4 * F + 2 * F, 2 * F, 0);
+    mark(l.v_bn + 2, 2, 0); mark(l.p_bn + 4, 4, 0);
+    HIPCHK(hipMemcpy(t->kind, kind.data(), kind.size(), hipMemcpyHostToDevice));
+    const struct { int at, n; const float *src; } parts[] = {
+        {l.conv0_k, 9 * t->C * F, w->conv0_k}, {l.conv0_b, F, w->conv0_b}, {l.conv0_bn, 4 * F, w->conv0_bn},
+        {l.blk_k, R * 2 * 9 * F * F, w->blk_k}, {l.blk_b, R * 2 * F, w->blk_b}, {l.blk_bn, R * 2 * 4 * F, w->blk_bn},
+        {l.v_conv_k, F, w->v_conv_k}, {l.v_conv_b, 1, w->v_conv_b}, {l.v_bn, 4, w->v_bn}, {l.v_d1_k, D, w->v_d1_k},
+        {l.v_d1_b, D, w->v_d1_b}, {l.v_d2_k, D, w->v_d2_k}, {l.v_d2_b, 1, w->v_d2_b}, {l.p_conv_k, 2 * F, w->p_conv_k},
+        {l.p_conv_b, 2, w->p_conv_b}, {l.p_bn, 8, w->p_bn}, {l.p_d_k, 2 * t->A, w->p_d_k}, {l.p_d_b, t->A, w->p_d_b}};
+    for (const auto &p : parts)
+        if (p.n) HIPCHK(hipMemcpy(t->prm + p.at, p.src, (size_t)p.n * sizeof(float), hipMemcpyDefault));
+    if (t->cfg.game == BB_GAME_CONNECT4) return trainer_lds<Connect4>(t);
+    return trainer_lds<TicTacToe>(t);
+}
+
+extern "C" int bb_trainer_create(const bb_train_config *cfg, const bb_net_weights *w, bb_trainer **out) {
+    if (!cfg || !w || !out) return fail(BB_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (cfg->game != BB_GAME_CONNECT4 && cfg->game != BB_GAME_TICTACTOE)
+        return fail(BB_ERR_ARG, "the HIP trainer covers Connect4 and TicTacToe, not game %d", cfg->game);
+    bb_game_info gi;
+    bb_game_info_get(cfg->game, &gi);
+    if (w->H != gi.H || w->W != gi.W || w->C != gi.C || w->A != gi.A)
+        return fail(BB_ERR_ARG, "weights are for a %dx%dx%d/%d network, game needs %dx%dx%d/%d", w->H, w->W, w->C, w->A, gi.H, gi.W,
+                    gi.C, gi.A);
+    if (w->F != BB_TRAIN_F || w->R < 0 || w->R > 9 || w->D < 1 || w->D > 64)
+        return fail(BB_ERR_ARG, "the HIP trainer covers 16 filters, 0..9 blocks and a dense width of 1..64; got %d filters, %d blocks, "
+                    "dense %d", w->F, w->R, w->D);
+    if (cfg->optimizer != BB_OPT_ADAM && cfg->optimizer != BB_OPT_MOMENTUM && cfg->optimizer != BB_OPT_SGD)
+        return fail(BB_ERR_ARG, "unknown optimizer %d", cfg->optimizer);
+    if (cfg->max_batch <= 0 || cfg->max_batch > (1 << 20)) return fail(BB_ERR_ARG, "max_batch %d out of range", cfg->max_batch);
+    if (!(cfg->epsilon >= 0.f && cfg->epsilon <= 1.f) || (cfg->epsilon != 0.f && !(cfg->alpha > 0.f && cfg->alpha < 1.f)))
+        return fail(BB_ERR_ARG, "epsilon must lie in [0, 1] and alpha in (0, 1)");
+    const float *need[] = {w->conv0_k, w->conv0_b, w->conv0_bn, w->v_conv_k, w->v_conv_b, w->v_bn, w->v_d1_k, w->v_d1_b, w->v_d2_k,
+                           w->v_d2_b, w->p_conv_k, w->p_conv_b, w->p_bn, w->p_d_k, w->p_d_b};
+    for (const float *p : need)
+        if (!p) return fail(BB_ERR_ARG, "a weight block is missing");
+    if (w->R > 0 && (!w->blk_k || !w->blk_b || !w->blk_bn)) return fail(BB_ERR_ARG, "a weight block is missing");
+    const int ndev = bb_device_count();
+    if (ndev <= 0) return fail(BB_ERR_HIP, "no HIP device available (this library has no CPU fallback)");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(BB_ERR_ARG, "device %d out of range", cfg->device);
+    int prev = 0;
+    HIPCHK(hipGetDevice(&prev));
+    HIPCHK(hipSetDevice(cfg->device));
+    bb_trainer *t = new bb_trainer();
+    t->cfg = *cfg;
+    t->A = gi.A; t->P = gi.H * gi.W; t->C = gi.C;
+    t->lay = train_layout(gi.C, w->R, w->D, gi.A);
+    const int rc = trainer_alloc(t, w);
+    (void)hipSetDevice(prev);
+    if (rc) {
+        const std::string keep = g_err;
+        trainer_free(t);
+        g_err = keep;
+        return rc;
+    }
+    *out = t;
+    return BB_OK;
+}
+
+extern "C" int bb_trainer_destroy(bb_trainer *t) {
+    if (!t) return BB_OK;
+    int prev = 0;
+    const bool ok = hipGetDevice(&prev) == hipSuccess && hipSetDevice(t->cfg.device) == hipSuccess;
+    if (ok) (void)hipDeviceSynchronize();
+    trainer_free(t);
+    if (ok) (void)hipSetDevice(prev);
+    return BB_OK;
+}
+
+extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const float *value, const float *policy, const float *noise,
+                               double lr, int apply, float *loss_out, void *stream) {
+    if (!t) return fail(BB_ERR_ARG, "null trainer");
+    if (n <= 0 || n > t->cfg.max_batch) return fail(BB_ERR_ARG, "a batch of %d examples; the trainer takes 1..%d (max_batch)", n, t->cfg.max_batch);
+    if (!boards || !value || !policy) return fail(BB_ERR_ARG, "boards, value and policy are required");
+    if (((uintptr_t)boards | (uintptr_t)value | (uintptr_t)policy | (uintptr_t)noise | (uintptr_t)loss_out) % sizeof(float))
+        return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
+    if (!std::isfinite(lr)) return fail(BB_ERR_ARG, "the learning rate is not finite");
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev != t->cfg.device) return fail(BB_ERR_ARG, "the trainer lives on device %d, the current device is %d", t->cfg.device, dev);
+    hipStream_t st = (hipStream_t)stream;
+    const TrainLayout &l = t->lay;
+    const float eps = t->cfg.epsilon;
+    k_train_prep<<<1, BB_TRAIN_THREADS, 0, st>>>(t->A, n, l.count, l.n_l2, t->prm, t->kind, policy, noise, eps, t->cfg.alpha, t->cfg.seed,
+                                                 t->calls, t->aux);
+    t->calls++;
+    if (t->cfg.game == BB_GAME_CONNECT4)
+        k_train_grad<Connect4><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, boards, value, n, eps, t->slabs, t->le, t->lp);
+    else
+        k_train_grad<TicTacToe><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, boards, value, n, eps, t->slabs, t->le, t->lp);
+    float rate = (float)lr;
+    if (apply) {
+        t->t++;
+        if (t->cfg.optimizer == BB_OPT_ADAM) // AdamOptimizer's lr_t (beta1 0.9, beta2 0.999)
+            rate = (float)(lr * std::sqrt(1.0 - std::pow(0.999, (double)t->t)) / (1.0 - std::pow(0.9, (double)t->t)));
+    }
+    k_train_apply<<<nblk((size_t)l.count, BB_TRAIN_THREADS) + 1, BB_TRAIN_THREADS, 0, st>>>(
+        l.count, n, l.n_l2, t->slabs, t->kind, t->prm, t->slot_m, t->slot_v, t->grads, t->cfg.optimizer, rate, t->cfg.momentum,
+        apply != 0, t->le, t->lp, t->aux, t->loss, loss_out);
+    HIPCHK(hipGetLastError());
+    return BB_OK;
+}
+
+extern "C" int bb_trainer_param_count(bb_trainer *t, int64_t *count_out) {
+    if (!t || !count_out) return fail(BB_ERR_ARG, "null argument");
+    *count_out = t->lay.count;
+    return BB_OK;
+}
+
+extern "C" int bb_trainer_read(bb_trainer *t, int what, float *host_out, int64_t count) {
+    if (!t || !host_out) return fail(BB_ERR_ARG, "null argument");
+    const float *src = nullptr;
+    int64_t want = t->lay.count;
+    switch (what) {
+    case BB_TRAIN_PARAMS: src = t->prm; break;
+    case BB_TRAIN_GRADS: src = t->grads; break;
+    case BB_TRAIN_SLOT_M: src = t->slot_m; break;
+    case BB_TRAIN_SLOT_V: src = t->slot_v; break;
+    case BB_TRAIN_NOISE: src = t->aux->noise; want = t->A; break;
+    default: return fail(BB_ERR_ARG, "unknown selector %d", what);
+    }
+    if (count != want) return fail(BB_ERR_ARG, "count %lld, expected %lld", (long long)count, (long long)want);
+    int prev = 0;
+    HIPCHK(hipGetDevice(&prev));
+    HIPCHK(hipSetDevice(t->cfg.device));
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(host_out, src, (size_t)want * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipSetDevice(prev);
+    if (e != hipSuccess) return fail(BB_ERR_HIP, "reading the trainer failed: %s", hipGetErrorString(e));
     return BB_OK;
 }
 

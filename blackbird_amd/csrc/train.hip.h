@@ -1,0 +1,523 @@
+// train.hip.h -- one optimiser step of Network.train (NetworkFactory.py:185-245) for the 16-filter networks of the dense
+// games, as three launches (bb_trainer_step):
+//   k_train_prep   one workgroup: the step's Beta noise (caller's, or A Philox draws keyed by seed and step count), the
+//                  batch-wide label sum L[a] = sum_j label_j[a], log S of the policy normalisation, and the L2 loss term
+//   k_train_grad   one workgroup per example: forward with every layer's post-activation and normalised conv output in
+//                  LDS, the example's loss pieces, backward, and the gradient of every trainable variable into the
+//                  workgroup's own slab in HBM
+//   k_train_apply  per parameter element: the slabs summed in example order, + v / N for the non-bias variables, the
+//                  TF1 optimiser update in place; its last workgroup reduces the loss terms
+// The batch couples the examples in two places only, and neither reaches a gradient across examples: policy / policy.sum()
+// divides by S = B (1 - eps) + B eps sum(noise), which holds no weight (softmax rows sum to 1), and
+// -mean(log(policy) @ label^T) = -(1 / B^2) sum_i sum_a log policy_i[a] L[a].
+// No float atomics: every sum has its order written down here, so the same steps give the same bits.
+// The flat parameter vector is bb_net_weights' fields back to back (TrainLayout); a batch-norm block is [4][n] = gamma,
+// beta, moving_mean, moving_variance, and the moving statistics are constants (kind 0: no gradient, no update).
+// float32 throughout, every fused multiply-add explicit (-ffp-contract=off); the loss sums are taken in double.
+#pragma once
+#include "games.hip.h"
+#include "rng.hip.h"
+
+#define BB_TRAIN_F 16            // filters
+#define BB_TRAIN_WROW 17         // row stride of a staged conv kernel: [tap*CIN + ci][f], read along f (forward, weight
+                                 // gradient) and along ci (input gradient) -- an odd stride keeps both off one bank
+#define BB_TRAIN_SMALL 896       // floats of the head scratch (TrainSmall)
+#define BB_TRAIN_THREADS 256
+
+struct TrainLayout {
+    int R, D;
+    int conv0_k, conv0_b, conv0_bn, blk_k, blk_b, blk_bn, v_conv_k, v_conv_b, v_bn, v_d1_k, v_d1_b, v_d2_k, v_d2_b, p_conv_k,
+        p_conv_b, p_bn, p_d_k, p_d_b, count;
+    int n_l2; // trainable variables whose name does not contain `bias`: the N of the L2 mean
+};
+
+struct TrainAux {
+    float noise[16]; // the step's noise (zeros when epsilon == 0)
+    float L[16];     // sum over the batch of the policy labels
+    float logS;      // log of the batch-wide normaliser
+    float l2;        // lossParam
+};
+
+__device__ __forceinline__ float tr_bn_inv(float var) { return 1.0f / sqrtf(var + 1e-3f); }
+
+// ---- k_train_prep ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_prep(int A, int n, int count, int n_l2, const float *params,
+                                                                const uint8_t *kind, const float *policy, const float *noise_in,
+                                                                float eps, float alpha, uint64_t seed, uint64_t calls, TrainAux *aux) {
+    __shared__ double s_sq[BB_TRAIN_THREADS];
+    __shared__ float s_part[BB_TRAIN_THREADS];
+    __shared__ float s_noise[16];
+    const int tid = threadIdx.x;
+    if (tid < 16) {
+        float z = 0.f;
+        if (tid < A && eps != 0.f)
+            z = noise_in ? noise_in[tid] : bb_beta_noise(seed, (uint32_t)calls, (uint32_t)(calls >> 32), (uint32_t)tid, alpha);
+        s_noise[tid] = z;
+        aux->noise[tid] = z;
+    }
+    { // L[a]: 16 strided partial sums per action, then those in order
+        const int a = tid & 15, c = tid >> 4;
+        float acc = 0.f;
+        if (a < A)
+            for (int j = c; j < n; j += 16) acc += policy[(size_t)j * A + a];
+        s_part[tid] = acc;
+    }
+    double sq = 0.0;
+    for (int i = tid; i < count; i += BB_TRAIN_THREADS)
+        if (kind[i] == 1) sq += (double)params[i] * (double)params[i];
+    s_sq[tid] = sq;
+    __syncthreads();
+    for (int w = BB_TRAIN_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) s_sq[tid] += s_sq[tid + w];
+        __syncthreads();
+    }
+    if (tid < 16) {
+        float acc = 0.f;
+        for (int c = 0; c < 16; c++) acc += s_part[c * 16 + tid];
+        aux->L[tid] = tid < A ? acc : 0.f;
+    }
+    if (tid == 0) {
+        float sn = 0.f;
+        for (int a = 0; a < A; a++) sn += s_noise[a];
+        const float S = (float)n * (1.0f - eps) + (float)n * eps * sn;
+        aux->logS = logf(S);
+        aux->l2 = (float)(0.5 * s_sq[0] / (double)n_l2);
+    }
+}
+
+// ---- pieces of k_train_grad -------------------------------------------------------------------------------------------
+struct TrainSmall { // offsets into the head scratch
+    static constexpr int brd = 0, vn = 128, vy = 192, pn = 256, py = 384, dvy = 512, dpy = 576, hbuf = 704, tmp = 768, lg = 832,
+                         dlg = 848, misc = 864; // misc: 0 svy, 1..2 spy, 3 dz
+};
+static_assert(TrainSmall::misc + 16 <= BB_TRAIN_SMALL, "head scratch");
+
+// a conv kernel [9*CIN][16] into LDS rows of BB_TRAIN_WROW, each column times scale[f] (gamma / sqrt(var + eps)) when SCALED
+template <int CIN, bool SCALED>
+__device__ __forceinline__ void tr_stage(float *wst, const float *k, const float *bn, int tid) {
+    const int f = tid & 15;
+    float s = 1.f;
+    if constexpr (SCALED) s = bn[f] * tr_bn_inv(bn[3 * BB_TRAIN_F + f]);
+    for (int row = tid >> 4; row < 9 * CIN; row += BB_TRAIN_THREADS / 16) {
+        const float w = k[row * BB_TRAIN_F + f];
+        wst[row * BB_TRAIN_WROW + f] = SCALED ? w * s : w;
+    }
+}
+
+// conv 3x3 SAME + bias, inference batch norm, (+ residual), ReLU.  Thread (f = tid & 15, pg = tid >> 4) owns the pixels
+// pg, pg + 16, ...; the sum over (tap, ci) is one fmaf chain in that order, padding skipped.
+template <class G, int CIN>
+__device__ __forceinline__ void tr_conv_fwd(const float *X, const float *wst, const float *bias, const float *bn, const float *res,
+                                            float *nrm, float *act, int tid) {
+    constexpr int P = G::H * G::W, NP = (P + 15) / 16;
+    const int f = tid & 15, pg = tid >> 4;
+    float acc[NP];
+    int pr[NP], pc[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+        const int p = pg + 16 * k;
+        acc[k] = 0.f;
+        pr[k] = p / G::W;
+        pc[k] = p % G::W;
+    }
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) {
+        const int dy = tap / 3 - 1, dx = tap % 3 - 1;
+        bool ok[NP];
+        int q[NP];
+#pragma unroll
+        for (int k = 0; k < NP; k++) {
+            const int r = pr[k] + dy, c = pc[k] + dx;
+            ok[k] = pg + 16 * k < P && r >= 0 && r < G::H && c >= 0 && c < G::W;
+            q[k] = ok[k] ? r * G::W + c : 0;
+        }
+        if constexpr (CIN % 4 == 0) {
+#pragma unroll
+            for (int c4 = 0; c4 < CIN / 4; c4++) {
+                float w[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) w[j] = wst[(tap * CIN + 4 * c4 + j) * BB_TRAIN_WROW + f];
+#pragma unroll
+                for (int k = 0; k < NP; k++)
+                    if (ok[k]) {
+                        const float4 x = ((const float4 *)(X + q[k] * CIN))[c4];
+                        acc[k] = __builtin_fmaf(x.x, w[0], acc[k]);
+                        acc[k] = __builtin_fmaf(x.y, w[1], acc[k]);
+                        acc[k] = __builtin_fmaf(x.z, w[2], acc[k]);
+                        acc[k] = __builtin_fmaf(x.w, w[3], acc[k]);
+                    }
+            }
+        } else {
+#pragma unroll
+            for (int ci = 0; ci < CIN; ci++) {
+                const float w = wst[(tap * CIN + ci) * BB_TRAIN_WROW + f];
+#pragma unroll
+                for (int k = 0; k < NP; k++)
+                    if (ok[k]) acc[k] = __builtin_fmaf(X[q[k] * CIN + ci], w, acc[k]);
+            }
+        }
+    }
+    const float b = bias[f], g = bn[f], be = bn[BB_TRAIN_F + f], mu = bn[2 * BB_TRAIN_F + f], inv = tr_bn_inv(bn[3 * BB_TRAIN_F + f]);
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+        const int p = pg + 16 * k;
+        if (p < P) {
+            const float xh = ((acc[k] + b) - mu) * inv;
+            float y = __builtin_fmaf(g, xh, be);
+            if (res) y += res[p * BB_TRAIN_F + f];
+            nrm[p * BB_TRAIN_F + f] = xh;
+            act[p * BB_TRAIN_F + f] = fmaxf(y, 0.f);
+        }
+    }
+}
+
+// gradient of a conv's input: dX[q][ci] = sum_tap sum_f dy[q - off(tap)][f] * wst[tap][ci][f] (wst already holds the
+// batch-norm scale).  Thread (ci = tid & 15, pg).  MASKED: out = act_mask > 0 ? dX : 0; else out += dX.
+template <class G, bool MASKED>
+__device__ __forceinline__ void tr_conv_dx(const float *dy, const float *wst, const float *act_mask, float *out, int tid) {
+    constexpr int P = G::H * G::W, NP = (P + 15) / 16;
+    const int ci = tid & 15, pg = tid >> 4;
+    float acc[NP];
+    int pr[NP], pc[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+        const int p = pg + 16 * k;
+        acc[k] = 0.f;
+        pr[k] = p / G::W;
+        pc[k] = p % G::W;
+    }
+#pragma unroll
+    for (int tap = 0; tap < 9; tap++) {
+        const int oy = tap / 3 - 1, ox = tap % 3 - 1;
+        bool ok[NP];
+        int q[NP];
+#pragma unroll
+        for (int k = 0; k < NP; k++) {
+            const int r = pr[k] - oy, c = pc[k] - ox; // the output pixel this tap fed from here
+            ok[k] = pg + 16 * k < P && r >= 0 && r < G::H && c >= 0 && c < G::W;
+            q[k] = ok[k] ? r * G::W + c : 0;
+        }
+#pragma unroll
+        for (int f4 = 0; f4 < BB_TRAIN_F / 4; f4++) {
+            float w[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) w[j] = wst[(tap * BB_TRAIN_F + ci) * BB_TRAIN_WROW + 4 * f4 + j];
+#pragma unroll
+            for (int k = 0; k < NP; k++)
+                if (ok[k]) {
+                    const float4 d = ((const float4 *)(dy + q[k] * BB_TRAIN_F))[f4];
+                    acc[k] = __builtin_fmaf(d.x, w[0], acc[k]);
+                    acc[k] = __builtin_fmaf(d.y, w[1], acc[k]);
+                    acc[k] = __builtin_fmaf(d.z, w[2], acc[k]);
+                    acc[k] = __builtin_fmaf(d.w, w[3], acc[k]);
+                }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+        const int p = pg + 16 * k;
+        if (p < P) {
+            const int e = p * BB_TRAIN_F + ci;
+            if (MASKED)
+                out[e] = act_mask[e] > 0.f ? acc[k] : 0.f;
+            else
+                out[e] += acc[k];
+        }
+    }
+}
+
+// gradients of one conv layer's variables from dy (gradient at the batch-norm output, ReLU mask applied):
+//   kernel[tap][ci][f] = scale[f] * sum_p X[p + off(tap)][ci] dy[p][f]   thread (f = tid & 15, ci = tid >> 4), p ascending
+//   gamma[f] = sum_p dy xhat, beta[f] = sum_p dy, bias[f] = scale[f] * beta[f]                       threads 0..15
+template <class G, int CIN>
+__device__ __forceinline__ void tr_conv_dw(const float *X, const float *dy, const float *nrm, const float *bn, float *slab_k,
+                                           float *slab_b, float *slab_bn, int tid) {
+    constexpr int P = G::H * G::W;
+    const int f = tid & 15, ci = tid >> 4;
+    const float s = bn[f] * tr_bn_inv(bn[3 * BB_TRAIN_F + f]);
+    if (ci < CIN) {
+        float acc[9];
+#pragma unroll
+        for (int t = 0; t < 9; t++) acc[t] = 0.f;
+        for (int r = 0; r < G::H; r++)
+            for (int c = 0; c < G::W; c++) {
+                const float d = dy[(r * G::W + c) * BB_TRAIN_F + f];
+#pragma unroll
+                for (int t = 0; t < 9; t++) {
+                    const int rr = r + t / 3 - 1, cc = c + t % 3 - 1;
+                    if (rr >= 0 && rr < G::H && cc >= 0 && cc < G::W)
+                        acc[t] = __builtin_fmaf(X[(rr * G::W + cc) * CIN + ci], d, acc[t]);
+                }
+            }
+#pragma unroll
+        for (int t = 0; t < 9; t++) slab_k[(t * CIN + ci) * BB_TRAIN_F + f] = acc[t] * s;
+    }
+    if (tid < BB_TRAIN_F) {
+        float dg = 0.f, db = 0.f;
+        for (int p = 0; p < P; p++) {
+            const float d = dy[p * BB_TRAIN_F + f];
+            dg = __builtin_fmaf(d, nrm[p * BB_TRAIN_F + f], dg);
+            db += d;
+        }
+        slab_bn[f] = dg;
+        slab_bn[BB_TRAIN_F + f] = db;
+        slab_b[f] = db * s;
+    }
+}
+
+// LDS floats of k_train_grad for R blocks
+template <class G>
+__host__ __device__ constexpr int train_lds_floats(int R) {
+    return (2 * (2 * R + 1) + 2) * G::H * G::W * BB_TRAIN_F + 9 * BB_TRAIN_F * BB_TRAIN_WROW + BB_TRAIN_SMALL;
+}
+
+// ---- k_train_grad: one workgroup per example ---------------------------------------------------------------------------
+template <class G>
+__global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay, const float *__restrict__ prm, const TrainAux *__restrict__ aux,
+                                                                const float *__restrict__ boards, const float *__restrict__ value,
+                                                                int n, float eps, float *__restrict__ slabs, float *__restrict__ le_out,
+                                                                float *__restrict__ lp_out) {
+    constexpr int P = G::H * G::W, C = G::C, A = G::A, F = BB_TRAIN_F, LF = P * F;
+    static_assert(P <= 64 && P * C <= 128 && A <= 16 && 2 * P <= 128, "head scratch sizes");
+    using S = TrainSmall;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    if (b >= n) return;
+    const int R = lay.R, D = lay.D, NL = 2 * R + 1;
+    float *act = lds, *nrm = act + NL * LF, *gA = nrm + NL * LF, *gB = gA + LF, *wst = gB + LF, *sm = wst + 9 * F * BB_TRAIN_WROW;
+    float *slab = slabs + (size_t)b * lay.count;
+
+    // ---- forward: tower ----
+    for (int i = tid; i < P * C; i += BB_TRAIN_THREADS) sm[S::brd + i] = boards[(size_t)b * P * C + i];
+    tr_stage<C, false>(wst, prm + lay.conv0_k, nullptr, tid);
+    __syncthreads();
+    tr_conv_fwd<G, C>(sm + S::brd, wst, prm + lay.conv0_b, prm + lay.conv0_bn, nullptr, nrm, act, tid);
+    __syncthreads();
+    for (int l = 1; l < NL; l++) { // layer l: conv_{1,2} of block (l-1)/2; conv_2 adds the block's input
+        tr_stage<F, false>(wst, prm + lay.blk_k + (l - 1) * 9 * F * F, nullptr, tid);
+        __syncthreads();
+        tr_conv_fwd<G, F>(act + (l - 1) * LF, wst, prm + lay.blk_b + (l - 1) * F, prm + lay.blk_bn + (l - 1) * 4 * F,
+                          (l & 1) ? nullptr : act + (l - 2) * LF, nrm + l * LF, act + l * LF, tid);
+        __syncthreads();
+    }
+    const float *x = act + (NL - 1) * LF;
+
+    // ---- forward: heads ----
+    const float v_s = prm[lay.v_bn] * tr_bn_inv(prm[lay.v_bn + 3]);
+    if (tid < P) { // value/convolution (1x1, one filter), batch norm, ReLU
+        float acc = 0.f;
+        for (int f = 0; f < F; f++) acc = __builtin_fmaf(x[tid * F + f], prm[lay.v_conv_k + f], acc);
+        const float xh = ((acc + prm[lay.v_conv_b]) - prm[lay.v_bn + 2]) * tr_bn_inv(prm[lay.v_bn + 3]);
+        sm[S::vn + tid] = xh;
+        sm[S::vy + tid] = fmaxf(__builtin_fmaf(prm[lay.v_bn], xh, prm[lay.v_bn + 1]), 0.f);
+    } else if (tid >= 64 && tid < 64 + 2 * P) { // policy/convolution (1x1, two filters)
+        const int e = tid - 64, p = e >> 1, j = e & 1;
+        float acc = 0.f;
+        for (int f = 0; f < F; f++) acc = __builtin_fmaf(x[p * F + f], prm[lay.p_conv_k + f * 2 + j], acc);
+        const float xh = ((acc + prm[lay.p_conv_b + j]) - prm[lay.p_bn + 4 + j]) * tr_bn_inv(prm[lay.p_bn + 6 + j]);
+        sm[S::pn + e] = xh;
+        sm[S::py + e] = fmaxf(__builtin_fmaf(prm[lay.p_bn + j], xh, prm[lay.p_bn + 2 + j]), 0.f);
+    }
+    __syncthreads();
+    if (tid < D) { // value/dense_1 on every square, summed over the squares, ReLU
+        const float k1 = prm[lay.v_d1_k + tid], b1 = prm[lay.v_d1_b + tid];
+        float acc = 0.f;
+        for (int p = 0; p < P; p++) acc += __builtin_fmaf(sm[S::vy + p], k1, b1);
+        sm[S::hbuf + tid] = fmaxf(acc, 0.f);
+    } else if (tid >= 64 && tid < 64 + A) { // policy/policy on every square, summed
+        const int a = tid - 64;
+        const float k0 = prm[lay.p_d_k + a], k1 = prm[lay.p_d_k + A + a], pb = prm[lay.p_d_b + a];
+        float acc = 0.f;
+        for (int p = 0; p < P; p++)
+            acc += __builtin_fmaf(sm[S::py + 2 * p + 1], k1, __builtin_fmaf(sm[S::py + 2 * p], k0, pb));
+        sm[S::lg + a] = acc;
+    } else if (tid >= 128 && tid < 131) { // sums over the squares the dense gradients need
+        const int j = tid - 128;
+        float acc = 0.f;
+        for (int p = 0; p < P; p++) acc += j == 0 ? sm[S::vy + p] : sm[S::py + 2 * p + (j - 1)];
+        sm[S::misc + j] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) { // value, softmax, the example's loss pieces, d loss / d (pre-tanh value, logits)
+        float z = prm[lay.v_d2_b];
+        for (int d = 0; d < D; d++) z = __builtin_fmaf(sm[S::hbuf + d], prm[lay.v_d2_k + d], z);
+        const float val = tanhf(z), diff = val - value[b];
+        le_out[b] = diff * diff;
+        sm[S::misc + 3] = 2.0f * diff * (1.0f - val * val) / (float)n;
+        float mx = sm[S::lg];
+        for (int a = 1; a < A; a++) mx = fmaxf(mx, sm[S::lg + a]);
+        float e[A], sum = 0.f;
+        for (int a = 0; a < A; a++) {
+            e[a] = expf(sm[S::lg + a] - mx);
+            sum += e[a];
+        }
+        float lp = 0.f, t = 0.f, r[A];
+        for (int a = 0; a < A; a++) {
+            e[a] = e[a] / sum; // softmax
+            const float q = __builtin_fmaf(eps, aux->noise[a], (1.0f - eps) * e[a]), La = aux->L[a];
+            if (La != 0.f) lp = __builtin_fmaf(La, logf(q) - aux->logS, lp);
+            r[a] = q > 0.f ? (1.0f - eps) * e[a] / q : 0.f;
+            t = __builtin_fmaf(La, r[a], t);
+        }
+        lp_out[b] = lp;
+        const float inv_n2 = 1.0f / ((float)n * (float)n);
+        for (int a = 0; a < A; a++) sm[S::dlg + a] = -inv_n2 * (aux->L[a] * r[a] - e[a] * t);
+    }
+    __syncthreads();
+
+    // ---- backward: heads ----
+    const float dz = sm[S::misc + 3];
+    if (tid < D) {
+        const float h = sm[S::hbuf + tid], dh = h > 0.f ? dz * prm[lay.v_d2_k + tid] : 0.f;
+        slab[lay.v_d2_k + tid] = dz * h;
+        slab[lay.v_d1_k + tid] = dh * sm[S::misc];
+        slab[lay.v_d1_b + tid] = dh * (float)P;
+        sm[S::tmp + tid] = dh * prm[lay.v_d1_k + tid];
+    } else if (tid >= 64 && tid < 64 + A) {
+        const int a = tid - 64;
+        const float dl = sm[S::dlg + a];
+        slab[lay.p_d_b + a] = dl * (float)P;
+        slab[lay.p_d_k + a] = dl * sm[S::misc + 1];
+        slab[lay.p_d_k + A + a] = dl * sm[S::misc + 2];
+    } else if (tid == 128) {
+        slab[lay.v_d2_b] = dz;
+    }
+    __syncthreads();
+    if (tid < P) { // every square's value-head activation gets the same gradient, through its own ReLU
+        float g1 = 0.f;
+        for (int d = 0; d < D; d++) g1 += sm[S::tmp + d];
+        sm[S::dvy + tid] = sm[S::vy + tid] > 0.f ? g1 : 0.f;
+    } else if (tid >= 64 && tid < 64 + 2 * P) {
+        const int e = tid - 64, j = e & 1;
+        float g = 0.f;
+        for (int a = 0; a < A; a++) g = __builtin_fmaf(sm[S::dlg + a], prm[lay.p_d_k + j * A + a], g);
+        sm[S::dpy + e] = sm[S::py + e] > 0.f ? g : 0.f;
+    }
+    __syncthreads();
+    const float p_s0 = prm[lay.p_bn] * tr_bn_inv(prm[lay.p_bn + 6]), p_s1 = prm[lay.p_bn + 1] * tr_bn_inv(prm[lay.p_bn + 7]);
+    if (tid == 0) {
+        float dg = 0.f, db = 0.f;
+        for (int p = 0; p < P; p++) {
+            dg = __builtin_fmaf(sm[S::dvy + p], sm[S::vn + p], dg);
+            db += sm[S::dvy + p];
+        }
+        slab[lay.v_bn] = dg;
+        slab[lay.v_bn + 1] = db;
+        slab[lay.v_conv_b] = db * v_s;
+    } else if (tid < 3) {
+        const int j = tid - 1;
+        float dg = 0.f, db = 0.f;
+        for (int p = 0; p < P; p++) {
+            dg = __builtin_fmaf(sm[S::dpy + 2 * p + j], sm[S::pn + 2 * p + j], dg);
+            db += sm[S::dpy + 2 * p + j];
+        }
+        slab[lay.p_bn + j] = dg;
+        slab[lay.p_bn + 2 + j] = db;
+        slab[lay.p_conv_b + j] = db * (j ? p_s1 : p_s0);
+    } else if (tid >= 16 && tid < 32) {
+        const int f = tid - 16;
+        float acc = 0.f;
+        for (int p = 0; p < P; p++) acc = __builtin_fmaf(sm[S::dvy + p], x[p * F + f], acc);
+        slab[lay.v_conv_k + f] = acc * v_s;
+    } else if (tid >= 32 && tid < 64) {
+        const int e = tid - 32, f = e >> 1, j = e & 1;
+        float acc = 0.f;
+        for (int p = 0; p < P; p++) acc = __builtin_fmaf(sm[S::dpy + 2 * p + j], x[p * F + f], acc);
+        slab[lay.p_conv_k + e] = acc * (j ? p_s1 : p_s0);
+    }
+    for (int e = tid; e < LF; e += BB_TRAIN_THREADS) { // gradient at the tower's output
+        const int p = e / F, f = e % F;
+        float g = (sm[S::dvy + p] * v_s) * prm[lay.v_conv_k + f];
+        g = __builtin_fmaf(sm[S::dpy + 2 * p] * p_s0, prm[lay.p_conv_k + 2 * f], g);
+        g = __builtin_fmaf(sm[S::dpy + 2 * p + 1] * p_s1, prm[lay.p_conv_k + 2 * f + 1], g);
+        gA[e] = g;
+    }
+    __syncthreads();
+
+    // ---- backward: tower.  gA: gradient at the current block's output ----
+    for (int i = R - 1; i >= 0; i--) {
+        const int l1 = 1 + 2 * i, l2 = 2 + 2 * i; // layers of conv_1 and conv_2; the block's input is layer l1 - 1
+        const float *k1 = prm + lay.blk_k + (l1 - 1) * 9 * F * F, *k2 = prm + lay.blk_k + (l2 - 1) * 9 * F * F;
+        const float *bn1 = prm + lay.blk_bn + (l1 - 1) * 4 * F, *bn2 = prm + lay.blk_bn + (l2 - 1) * 4 * F;
+        // through the block's last ReLU: this is the gradient at batch_norm_2's output and at the skip connection
+        for (int e = tid; e < LF; e += BB_TRAIN_THREADS) gA[e] = act[l2 * LF + e] > 0.f ? gA[e] : 0.f;
+        tr_stage<F, true>(wst, k2, bn2, tid);
+        __syncthreads();
+        tr_conv_dw<G, F>(act + l1 * LF, gA, nrm + l2 * LF, bn2, slab + lay.blk_k + (l2 - 1) * 9 * F * F, slab + lay.blk_b + (l2 - 1) * F,
+                         slab + lay.blk_bn + (l2 - 1) * 4 * F, tid);
+        tr_conv_dx<G, true>(gA, wst, act + l1 * LF, gB, tid);
+        __syncthreads();
+        tr_stage<F, true>(wst, k1, bn1, tid);
+        tr_conv_dw<G, F>(act + (l1 - 1) * LF, gB, nrm + l1 * LF, bn1, slab + lay.blk_k + (l1 - 1) * 9 * F * F,
+                         slab + lay.blk_b + (l1 - 1) * F, slab + lay.blk_bn + (l1 - 1) * 4 * F, tid);
+        __syncthreads();
+        tr_conv_dx<G, false>(gB, wst, nullptr, gA, tid);
+        __syncthreads();
+    }
+    for (int e = tid; e < LF; e += BB_TRAIN_THREADS) gA[e] = act[e] > 0.f ? gA[e] : 0.f;
+    __syncthreads();
+    tr_conv_dw<G, C>(sm + S::brd, gA, nrm, prm + lay.conv0_bn, slab + lay.conv0_k, slab + lay.conv0_b, slab + lay.conv0_bn, tid);
+}
+
+// ---- k_train_apply ---------------------------------------------------------------------------------------------------
+// One thread per parameter element: slabs summed b = 0 .. n-1, the L2 part, the update.  The workgroup after the last
+// element reduces the loss pieces: loss[4] = total, evaluation, policy, parameter term.
+__global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_apply(int count, int n, int n_l2, const float *__restrict__ slabs,
+                                                                 const uint8_t *__restrict__ kind, float *__restrict__ prm,
+                                                                 float *__restrict__ slot_m, float *__restrict__ slot_v, float *__restrict__ grads,
+                                                                 int opt, float lr, float momentum, int apply, const float *le,
+                                                                 const float *lp, const TrainAux *aux, float *loss, float *loss_out) {
+    const int tid = threadIdx.x;
+    if (blockIdx.x == gridDim.x - 1) {
+        __shared__ double s_e[BB_TRAIN_THREADS], s_p[BB_TRAIN_THREADS];
+        double e = 0.0, p = 0.0;
+        for (int i = tid; i < n; i += BB_TRAIN_THREADS) {
+            e += (double)le[i];
+            p += (double)lp[i];
+        }
+        s_e[tid] = e;
+        s_p[tid] = p;
+        __syncthreads();
+        for (int w = BB_TRAIN_THREADS / 2; w > 0; w >>= 1) {
+            if (tid < w) {
+                s_e[tid] += s_e[tid + w];
+                s_p[tid] += s_p[tid + w];
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const float l_e = (float)(s_e[0] / (double)n), l_p = (float)(-s_p[0] / ((double)n * (double)n)), l_w = aux->l2;
+            const float total = l_e + l_p + l_w;
+            loss[0] = total; loss[1] = l_e; loss[2] = l_p; loss[3] = l_w;
+            if (loss_out) {
+                loss_out[0] = total; loss_out[1] = l_e; loss_out[2] = l_p; loss_out[3] = l_w;
+            }
+        }
+        return;
+    }
+    const int i = blockIdx.x * BB_TRAIN_THREADS + tid;
+    if (i >= count) return;
+    const int kd = kind[i];
+    if (kd == 0) {
+        grads[i] = 0.f;
+        return;
+    }
+    float g = 0.f;
+    for (int b = 0; b < n; b++) g += slabs[(size_t)b * count + i];
+    const float p = prm[i];
+    if (kd == 1) g += p / (float)n_l2;
+    grads[i] = g;
+    if (!apply) return;
+    if (opt == BB_OPT_ADAM) { // lr is lr_t = lr sqrt(1 - b2^t) / (1 - b1^t); epsilon outside the bias correction (TF1)
+        const float m = __builtin_fmaf(g, 0.1f, slot_m[i] * 0.9f), v = __builtin_fmaf(g * g, 0.001f, slot_v[i] * 0.999f);
+        slot_m[i] = m;
+        slot_v[i] = v;
+        prm[i] = p - (lr * m) / (sqrtf(v) + 1e-8f);
+    } else if (opt == BB_OPT_MOMENTUM) {
+        const float m = __builtin_fmaf(momentum, slot_m[i], g);
+        slot_m[i] = m;
+        prm[i] = p - lr * m;
+    } else {
+        prm[i] = p - lr * g;
+    }
+}

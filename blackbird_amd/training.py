@@ -139,6 +139,108 @@ class Trainer:
         return out
 
 
+HIP_TRAINER_LIMITS = 'Connect4 or TicTacToe, 16 filters, 0 to 9 blocks, a dense width of 1 to 64'
+_GAME_BY_PLANES = {(7, 3): (_lib.GAME_CONNECT4, 6, 7), (9, 3): (_lib.GAME_TICTACTOE, 3, 3)}   # (A, C) -> game, H, W
+_OPTIMIZERS = {'adam': _lib.OPT_ADAM, 'momentum': _lib.OPT_MOMENTUM, 'sgd': _lib.OPT_SGD}
+
+
+def hip_trainer_supports(weights):
+    """Whether `weights` (TF-named dict) is a network the HIP training kernels cover (HIP_TRAINER_LIMITS)."""
+    C, F, R, D, A = W.infer_shape(weights)
+    return (A, C) in _GAME_BY_PLANES and F == 16 and 0 <= R <= 9 and 1 <= D <= 64
+
+
+class HipTrainer:
+    """`Trainer` with the step as HIP kernels of libblackbird_hip.so (bb_trainer_*, csrc/train.hip.h): the same loss, the
+    same optimiser rules, the same interface -- chosen with NetworkConfig['training']['backend'] = 'hip'.  Parameters,
+    optimiser slots and gradients live in the library's own device buffers; `export` reads the parameters back.  Covers
+    HIP_TRAINER_LIMITS; anything else raises ValueError.  `seed` keys the Beta noise a step draws when none is given
+    (None: from numpy's generator, as the engines do); `max_batch` bounds the examples of one step."""
+
+    def __init__(self, weights, alpha=0.2, epsilon=0.3, optimizer='adam', momentum=0.9, device=None, seed=None, max_batch=1024):
+        self.device = torch.device(device or 'cuda')
+        if self.device.type != 'cuda':
+            raise _lib.BlackbirdHipError('HipTrainer runs on the GPU only (device %s)' % self.device)
+        self.alpha, self.epsilon = float(alpha), float(epsilon)
+        self.C, self.F, self.R, self.D, self.A = W.infer_shape(weights)
+        if not hip_trainer_supports(weights):
+            raise ValueError('the hip training backend covers %s; got %d input planes, %d actions, %d filters, %d blocks, '
+                             'dense %d' % (HIP_TRAINER_LIMITS, self.C, self.A, self.F, self.R, self.D))
+        if optimizer not in _OPTIMIZERS:   # (Trainer treats any other name as sgd; the kernels are asked by number)
+            optimizer = 'sgd'
+        self.kind, self.momentum = optimizer, float(momentum)
+        self.game, self.H, self.Wd = _GAME_BY_PLANES[(self.A, self.C)]
+        self.max_batch = int(max_batch)
+        if seed is None:
+            from .MCTS import _seed_from_numpy
+            seed = _seed_from_numpy()
+        self._index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._h = _lib.trainer_create(self.game, W.flatten(weights), self.H, self.Wd, _OPTIMIZERS[optimizer], self.max_batch,
+                                      device=self._index, momentum=self.momentum, alpha=self.alpha, epsilon=self.epsilon,
+                                      seed=seed)
+        self.count = _lib.trainer_param_count(self._h)
+
+    def close(self):
+        h, self._h = getattr(self, '_h', None), None
+        _lib.trainer_destroy(h)
+
+    __del__ = close
+
+    def _f32(self, x, shape):
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32)))
+        t = t.to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
+        return t
+
+    def _launch(self, boards, evalLabel, policyLabel, noise, lr, apply):
+        """One bb_trainer_step on torch's current stream; returns the device tensor [4] of the loss and its terms."""
+        n = int(policyLabel.shape[0]) if hasattr(policyLabel, 'shape') else len(policyLabel)
+        boards = self._f32(boards, (n, self.H, self.Wd, self.C))
+        ev = self._f32(evalLabel, (n,))
+        pl = self._f32(policyLabel, (n, self.A))
+        nz = None if noise is None else self._f32(noise, (self.A,))
+        loss = torch.empty(4, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.trainer_step(self._h, n, boards.data_ptr(), ev.data_ptr(), pl.data_ptr(), None if nz is None else nz.data_ptr(),
+                              lr, apply, loss.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        for t in (boards, ev, pl, nz):     # the launch is asynchronous: the inputs stay alive until the stream has used them
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return loss
+
+    def _named(self, what):
+        return W.unflatten(_lib.trainer_read(self._h, what), self.C, self.F, self.R, self.D, self.A)
+
+    def gradients(self, state, eval, policy, noise=None):
+        """Loss, its three terms (floats) and {TF variable name: d loss / d variable} of one batch; no update."""
+        loss = self._launch(np.asarray(state), np.asarray(eval).reshape(-1), np.asarray(policy), noise, 0.0, False).cpu().numpy()
+        grads = {k: torch.from_numpy(v).to(self.device) for k, v in self._named(_lib.TRAIN_GRADS).items()
+                 if not (k.endswith('moving_mean') or k.endswith('moving_variance'))}
+        return float(loss[0]), [float(x) for x in loss[1:]], grads
+
+    def step(self, state, eval, policy, learningRate, noise=None):
+        loss = self._launch(np.asarray(state), np.asarray(eval).reshape(-1), np.asarray(policy), noise, float(learningRate),
+                            True).cpu().numpy()
+        return float(loss[0]), [float(x) for x in loss[1:]]
+
+    def step_tensors(self, boards, evalLabel, policyLabel, learningRate, noise=None):
+        """`step` for float32 tensors already on the trainer's device: launched on torch's current stream, not waited for;
+        the loss and its terms come back as device tensors."""
+        loss = self._launch(boards, evalLabel, policyLabel, noise, float(learningRate), True)
+        return loss[0], [loss[1], loss[2], loss[3]]
+
+    def last_noise(self):
+        """The noise of the last step (given or drawn), read back from the device."""
+        return _lib.trainer_read(self._h, _lib.TRAIN_NOISE, self.A)
+
+    def slots(self):
+        """(m, v) as TF-named dicts: Adam's moments, or Momentum's accumulator and zeros."""
+        drop = lambda d: {k: v for k, v in d.items() if not (k.endswith('moving_mean') or k.endswith('moving_variance'))}  # noqa: E731
+        return drop(self._named(_lib.TRAIN_SLOT_M)), drop(self._named(_lib.TRAIN_SLOT_V))
+
+    def export(self):
+        return self._named(_lib.TRAIN_PARAMS)
+
+
 def epoch_order(n, batchSize):
     """The order in which an epoch visits `n` examples in whole batches: TrainWithExamples' draw (Blackbird.py:292-293),
     consuming numpy's global generator exactly as it does -- the same numpy seed gives the same batches on the host

@@ -127,6 +127,52 @@ def flatten(w):
     return out
 
 
+def flat_fields(C, F, R, D, A):
+    """(bb_net_weights field, shape) in the struct's order: how bb_trainer_read lays one flat vector out."""
+    return [("conv0_k", (3, 3, C, F)), ("conv0_b", (F,)), ("conv0_bn", (4, F)), ("blk_k", (R, 2, 3, 3, F, F)),
+            ("blk_b", (R, 2, F)), ("blk_bn", (R, 2, 4, F)), ("v_conv_k", (F,)), ("v_conv_b", (1,)), ("v_bn", (4, 1)),
+            ("v_d1_k", (D,)), ("v_d1_b", (D,)), ("v_d2_k", (D,)), ("v_d2_b", (1,)), ("p_conv_k", (F, 2)), ("p_conv_b", (2,)),
+            ("p_bn", (4, 2)), ("p_d_k", (2, A)), ("p_d_b", (A,))]
+
+
+def unflatten(vec, C, F, R, D, A):
+    """The inverse of flatten() for one flat float32 vector in flat_fields' order: the TF-named dict, fresh arrays."""
+    vec = np.asarray(vec)
+    blocks, at = {}, 0
+    for name, shape in flat_fields(C, F, R, D, A):
+        n = int(np.prod(shape))
+        blocks[name] = vec[at:at + n].reshape(shape)
+        at += n
+    assert at == vec.size, (at, vec.size)
+    w = {}
+
+    def bn(prefix, block):
+        for i, f in enumerate(BN_FIELDS):
+            w[f"{prefix}/{f}"] = block[i].copy()
+
+    w["resTower/conv_block/conv/kernel"] = blocks["conv0_k"].copy()
+    w["resTower/conv_block/conv/bias"] = blocks["conv0_b"].copy()
+    bn("resTower/conv_block/batch_norm", blocks["conv0_bn"])
+    for i in range(R):
+        for j in (1, 2):
+            w[f"resTower/block_{i}/conv_{j}/kernel"] = blocks["blk_k"][i, j - 1].copy()
+            w[f"resTower/block_{i}/conv_{j}/bias"] = blocks["blk_b"][i, j - 1].copy()
+            bn(f"resTower/block_{i}/batch_norm_{j}", blocks["blk_bn"][i, j - 1])
+    w["value/convolution/kernel"] = blocks["v_conv_k"].reshape(1, 1, F, 1).copy()
+    w["value/convolution/bias"] = blocks["v_conv_b"].copy()
+    bn("value/batch_norm", blocks["v_bn"])
+    w["value/dense_1/kernel"] = blocks["v_d1_k"].reshape(1, D).copy()
+    w["value/dense_1/bias"] = blocks["v_d1_b"].copy()
+    w["value/dense_2/kernel"] = blocks["v_d2_k"].reshape(D, 1).copy()
+    w["value/dense_2/bias"] = blocks["v_d2_b"].copy()
+    w["policy/convolution/kernel"] = blocks["p_conv_k"].reshape(1, 1, F, 2).copy()
+    w["policy/convolution/bias"] = blocks["p_conv_b"].copy()
+    bn("policy/batch_norm", blocks["p_bn"])
+    w["policy/policy/kernel"] = blocks["p_d_k"].copy()
+    w["policy/policy/bias"] = blocks["p_d_b"].copy()
+    return w
+
+
 def save_npz(path, w):
     np.savez(path, **{k.replace("/", "."): v for k, v in w.items()})
 

@@ -322,6 +322,43 @@ int bb_examples_device(bb_engine *e, void **records_out, uint64_t *bytes_out, ui
 int bb_examples_to_batch(int game, int n_records, const void *records, int n, const int64_t *index, float *boards_out,
                          float *policy_out, float *value_out, int32_t *bad_out, void *stream);
 
+/* ---- the training step as HIP kernels (opt-in; the default trainer is PyTorch's autograd) --------- */
+/* One step of Network.train (Network.py:66-84; loss and optimiser NetworkFactory.py:185-245) for the dense games (Connect4,
+ * TicTacToe) with 16 filters, 0..9 blocks and a dense width of 1..64: three launches (csrc/train.hip.h) -- the step's noise,
+ * label sum and L2 term; one workgroup per example (forward, loss pieces, backward, the gradients of every trainable variable
+ * into the example's own slab); per parameter element the slabs summed in example order, + v / N for the non-bias variables,
+ * and the TF1 update (Adam with epsilon outside the bias correction, Momentum, GradientDescent) in place.  No float atomics:
+ * the same steps give the same bits.  Batch norm is in inference mode: the moving statistics are constants. */
+enum { BB_OPT_ADAM = 0, BB_OPT_MOMENTUM = 1, BB_OPT_SGD = 2 };
+enum { BB_TRAIN_PARAMS = 0, BB_TRAIN_GRADS = 1, BB_TRAIN_SLOT_M = 2, BB_TRAIN_SLOT_V = 3, BB_TRAIN_NOISE = 4 };
+typedef struct {
+    int32_t game;      /* BB_GAME_CONNECT4 | BB_GAME_TICTACTOE */
+    int32_t optimizer; /* BB_OPT_* */
+    int32_t max_batch; /* examples per step at most: one gradient slab each is allocated */
+    int32_t device;    /* HIP device ordinal */
+    float momentum;    /* BB_OPT_MOMENTUM */
+    float alpha, epsilon; /* the graph's Beta(alpha, 1-alpha) noise and its weight (NetworkFactory.py:176-182); epsilon 0: none */
+    uint64_t seed;     /* Philox key of the noise drawn on the device; the counter is the number of steps made so far */
+} bb_train_config;
+typedef struct bb_trainer bb_trainer;
+/* w: the initial weights (host or device memory).  BB_ERR_ARG for a game, a shape, an optimiser or a max_batch outside the scope
+ * above -- checked before any device call; BB_ERR_HIP without a GPU; BB_ERR_CAPACITY if the slabs do not fit the free memory. */
+int bb_trainer_create(const bb_train_config *cfg, const bb_net_weights *w, bb_trainer **out);
+int bb_trainer_destroy(bb_trainer *t);
+/* boards [n][H][W][C], value [n], policy [n][A], noise [A] or NULL: float32 DEVICE pointers of the trainer's device, which must
+ * be the calling thread's current one; loss_out: device float[4] = total, evaluation, policy, parameter term, or NULL.
+ * noise == NULL and epsilon != 0: A Beta(alpha, 1-alpha) values are drawn (readable afterwards, BB_TRAIN_NOISE).
+ * apply = 0 computes loss and gradients only.  lr: the learning rate.  Asynchronous on stream (a hipStream_t; 0 = the default).
+ * BB_ERR_ARG: n <= 0, n > max_batch, a required pointer NULL, any pointer not 4-byte aligned. */
+int bb_trainer_step(bb_trainer *t, int n, const float *boards, const float *value, const float *policy,
+                    const float *noise, double lr, int apply, float *loss_out, void *stream);
+int bb_trainer_param_count(bb_trainer *t, int64_t *count_out);
+/* what = BB_TRAIN_PARAMS | GRADS | SLOT_M | SLOT_V: host_out[count] flat float32, bb_net_weights' fields back to back in their
+ * order (the moving statistics included for PARAMS, zero for the others), count = bb_trainer_param_count; SLOT_M is Adam's first
+ * moment or Momentum's accumulator, SLOT_V Adam's second moment.  BB_TRAIN_NOISE: the last step's noise, count = A.
+ * Synchronises the device.  BB_ERR_ARG for any other `what` or count. */
+int bb_trainer_read(bb_trainer *t, int what, float *host_out, int64_t count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,10 +8,14 @@ examples); then one epoch over them is trained twice with the same batch size:
                then np.vstack per batch + Model.train, which exports the weights and reloads the engines after every batch
   device path  Blackbird.TrainWithDeviceExamples on the kept records: bb_examples_to_batch + Trainer.step_tensors per
                batch, one export and one reload at the end
+  hip path     the same epoch through TrainWithDeviceExamples with NetworkConfig['training']['backend'] = 'hip' (the
+               training step as HIP kernels, bb_trainer_step), on a second model built from the same saved weights
 
 and the bare DeviceExamples.batch calls of that epoch alone.  Every timed region ends in a device synchronise; one training
-step is run before any of them (the first step pays for the library's kernel selection).  Prints one JSON line."""
+step is run before any of them, per trainer (the first step pays for the library's kernel selection).  Prints one JSON
+line."""
 import argparse
+import copy
 import json
 import os
 import sys
@@ -49,7 +53,13 @@ def main():
     kept = model.KeptDeviceExamples()
     n, B = len(kept), a.batch
     boards, value, policy = (x.cpu().numpy() for x in kept.batch(np.arange(min(B, n))))
+    # the second model: the weights the first one saved when it was made, the hip backend
+    hip_cfg = copy.deepcopy(CFG)
+    hip_cfg["training"]["backend"] = "hip"
+    hip_model = Blackbird.Model(Connect4.BoardState, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, hip_cfg)
+    assert all(np.array_equal(hip_model._weights[k], model._weights[k]) for k in model._weights)
     model.train(boards, value, policy, a.lr)  # warm-up step
+    hip_model.train(boards, value, policy, a.lr)
     torch.cuda.synchronize()
 
     # bare batches of one epoch
@@ -82,11 +92,18 @@ def main():
     torch.cuda.synchronize()
     device_s = time.time() - t
 
+    # hip path: the same epoch (the same examples, an order drawn the same way) with the step as HIP kernels
+    t = time.time()
+    Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept)
+    torch.cuda.synchronize()
+    hip_s = time.time() - t
+
     print(json.dumps({"tool": "train_path", "game": "connect4", "games": a.games, "warmup_games": 64, "play_limit": a.play_limit,
                       "examples": n, "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
                       "host_path_s": round(host_s, 3), "host_decode_s": round(decode_s, 3),
                       "device_path_s": round(device_s, 3), "device_batches_only_s": round(batch_s, 4),
-                      "host_over_device": round(host_s / device_s, 2)}))
+                      "host_over_device": round(host_s / device_s, 2), "hip_path_s": round(hip_s, 3),
+                      "device_over_hip": round(device_s / hip_s, 2)}))
 
 
 if __name__ == "__main__":
