@@ -22,7 +22,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 static thread_local std::string g_err;
@@ -90,16 +89,80 @@ struct DevBuf {
 
 static inline int nblk(size_t n, int per = 256) { return (int)((n + per - 1) / per); }
 
+// ---- launch tables ---------------------------------------------------------------------------------------------
+// THE place that knows which kernel a game family launches for a step of the lock-step engine, and on what grid: the primary template
+// for the dense-action games (G::S lanes per slot; gpw games per wave in the tree step), the specialisation for DragonChess (one
+// wave per slot, and the edge pool E that the dense family ignores).  Every member is exactly one launch, of 256-thread blocks (the
+// node view: one wave).  The entry points below check, stage, call one member and copy back: none names a k_dc_* lock-step kernel or
+// sizes a grid for one, and a new lock-step kernel's launch goes here, in both halves -- never into an entry point.
+template <class G>
+struct Launch {
+    using State = typename G::State;
+    static void legal(int n, const State *s, uint8_t *out) { k_game_legal<G><<<nblk(n), 256>>>(n, s, out); }
+    static void encode(int n, const State *s, int8_t *out) { k_game_encode<G><<<nblk((size_t)n * G::H * G::W), 256>>>(n, s, out); }
+    static void tree_step(const TreeDev &d, const DCEdges &, hipStream_t st) { k_tree_step<G><<<nblk((size_t)((d.n_slots + d.gpw - 1) / d.gpw) * 64), 256, 0, st>>>(d); }
+    static void tree_apply(const TreeDev &d, const DCEdges &, hipStream_t st) { k_tree_apply<G><<<nblk((size_t)d.n_slots * G::S), 256, 0, st>>>(d); }
+    static void hash(hipStream_t st, int n, const State *s, const uint32_t *game_id, uint64_t salt, int salt_per_game, uint32_t first_game_id, float *value, float *policy, int pstride) {
+        k_hash_eval<G><<<nblk(n), 256, 0, st>>>(n, s, game_id, salt, salt_per_game, first_game_id, value, policy, pstride);
+    }
+    static void rollout(const TreeDev &d, const DCEdges &, hipStream_t st) {
+        k_rollout<G><<<nblk(d.n_slots), 256, 0, st>>>(d.n_slots, (const State *)d.leaf_state, d.leaf_game_id, d.sim_serial, d.pend_leaf, d.seed, d.eval_value);
+    }
+    static void sample(const TreeDev &d, const DCEdges &, hipStream_t st, double temp, int32_t *) { k_sample<G><<<nblk((size_t)d.n_slots * G::S), 256, 0, st>>>(d, temp); }
+    static void move_roots(const TreeDev &d, const DCEdges &, hipStream_t st, const int32_t *actions) { k_move_roots<G><<<nblk((size_t)d.n_slots * G::S), 256, 0, st>>>(d, actions); }
+    static void set_roots(const TreeDev &d, const DCEdges &, hipStream_t st, int n, const int32_t *slots, const State *s, const uint32_t *game_ids) {
+        k_set_roots<G><<<nblk(n), 256, 0, st>>>(d, n, slots, s, game_ids);
+    }
+    static void reset_roots(const TreeDev &d, const DCEdges &, hipStream_t st) { k_reset_roots<G><<<nblk(d.n_slots), 256, 0, st>>>(d); }
+    static void get_roots(const TreeDev &d, const DCEdges &, hipStream_t st, State *out) { k_get_roots<G><<<nblk(d.n_slots), 256, 0, st>>>(d, out); }
+    static void node_edges(const TreeDev &d, const DCEdges &, hipStream_t st, int slot, int node, int32_t *, int32_t *child, int32_t *plays, float *value,
+                           State *state, int32_t *info) { // (slot i is action i: no action list; info word 1 is the legal mask)
+        k_node_view<G><<<1, 64, 0, st>>>(d, slot, node, child, plays, value, state, info);
+    }
+    static void selfplay_begin(const TreeDev &d, const DCEdges &, hipStream_t st) { k_selfplay_begin<G><<<nblk(d.n_slots), 256, 0, st>>>(d); }
+    static void selfplay_move(const TreeDev &d, const DCEdges &, hipStream_t st) { k_selfplay_move<G><<<nblk((size_t)d.n_slots * G::S), 256, 0, st>>>(d); }
+    static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, float *boards, float *policy, float *value, int32_t *bad) {
+        k_examples_to_batch<G><<<nblk((size_t)n * (G::H * G::W * G::C + G::A + 1)), 256, 0, st>>>(n_records, rec, n, index, boards, policy, value, bad);
+    }
+};
+template <>
+struct Launch<DragonChess> {
+    using State = DCState;
+    static void legal(int n, const State *s, uint8_t *out) { k_dc_legal<<<nblk((size_t)n * 64), 256>>>(n, s, out); }
+    static void encode(int n, const State *s, int8_t *out) { k_dc_encode<<<nblk((size_t)n * 64), 256>>>(n, s, out); }
+    static void tree_step(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_tree_step<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
+    static void tree_apply(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_tree_apply<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
+    static void hash(hipStream_t st, int n, const State *s, const uint32_t *game_id, uint64_t salt, int salt_per_game, uint32_t first_game_id, float *value, float *policy, int pstride) {
+        k_dc_hash_eval<<<nblk((size_t)n * 64), 256, 0, st>>>(n, s, game_id, salt, salt_per_game, first_game_id, value, policy, pstride);
+    }
+    static void rollout(const TreeDev &d, const DCEdges &, hipStream_t st) {
+        k_dc_rollout<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d.n_slots, (const State *)d.leaf_state, d.leaf_game_id, d.sim_serial, d.pend_leaf, d.seed, d.eval_value);
+    }
+    static void sample(const TreeDev &d, const DCEdges &E, hipStream_t st, double temp, int32_t *child_action) { k_dc_sample<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E, temp, child_action); }
+    static void move_roots(const TreeDev &d, const DCEdges &E, hipStream_t st, const int32_t *actions) { k_dc_move_roots<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E, actions); }
+    static void set_roots(const TreeDev &d, const DCEdges &E, hipStream_t st, int n, const int32_t *slots, const State *s, const uint32_t *game_ids) {
+        k_dc_set_roots<<<nblk(n), 256, 0, st>>>(d, E, n, slots, s, game_ids);
+    }
+    static void reset_roots(const TreeDev &d, const DCEdges &, hipStream_t st) { k_dc_reset_roots<<<nblk(d.n_slots), 256, 0, st>>>(d); }
+    static void get_roots(const TreeDev &d, const DCEdges &, hipStream_t st, State *out) { k_dc_get_roots<<<nblk(d.n_slots), 256, 0, st>>>(d, out); }
+    static void node_edges(const TreeDev &d, const DCEdges &E, hipStream_t st, int slot, int node, int32_t *action, int32_t *child, int32_t *plays, float *value,
+                           State *state, int32_t *info) {
+        k_dc_node_edges<<<1, 64, 0, st>>>(d, E, slot, node, action, child, plays, value, state, info);
+    }
+    static void selfplay_begin(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_selfplay_begin<<<nblk(d.n_slots), 256, 0, st>>>(d, E); }
+    static void selfplay_move(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_selfplay_move<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
+    static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, float *boards, float *policy, float *value, int32_t *bad) {
+        k_dc_examples_to_batch<<<n, 256, 0, st>>>(n_records, rec, index, boards, policy, value, bad);
+    }
+};
+
 // ---- stateless batched game ops ------------------------------------------------------------------
 template <class G>
 static int game_legal(int n, const void *states, uint8_t *out) {
     DevBuf ds, dout;
     if (ds.alloc((size_t)n * sizeof(typename G::State)) || dout.alloc((size_t)n * G::A)) return BB_ERR_HIP;
     HIPCHK(hipMemcpy(ds.p, states, (size_t)n * sizeof(typename G::State), hipMemcpyDefault));
-    if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-        k_dc_legal<<<nblk((size_t)n * 64), 256>>>(n, (const DCState *)ds.p, (uint8_t *)dout.p);
-    else
-        k_game_legal<G><<<nblk(n), 256>>>(n, (const typename G::State *)ds.p, (uint8_t *)dout.p);
+    Launch<G>::legal(n, (const typename G::State *)ds.p, (uint8_t *)dout.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, dout.p, (size_t)n * G::A, hipMemcpyDefault));
     return BB_OK;
@@ -136,10 +199,7 @@ static int game_encode(int n, const void *states, int8_t *out) {
     DevBuf ds, dout;
     if (ds.alloc((size_t)n * sizeof(typename G::State)) || dout.alloc(ob)) return BB_ERR_HIP;
     HIPCHK(hipMemcpy(ds.p, states, (size_t)n * sizeof(typename G::State), hipMemcpyDefault));
-    if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-        k_dc_encode<<<nblk((size_t)n * 64), 256>>>(n, (const DCState *)ds.p, (int8_t *)dout.p);
-    else
-        k_game_encode<G><<<nblk((size_t)n * G::H * G::W), 256>>>(n, (const typename G::State *)ds.p, (int8_t *)dout.p);
+    Launch<G>::encode(n, (const typename G::State *)ds.p, (int8_t *)dout.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(out, dout.p, ob, hipMemcpyDefault));
     return BB_OK;
@@ -152,31 +212,30 @@ static int game_encode(int n, const void *states, int8_t *out) {
     case BB_GAME_DRAGONCHESS: { using G = DragonChess; __VA_ARGS__; }            \
     default: return fail(BB_ERR_ARG, "unknown game %d", game);                   \
     }
-#define GAME_SWITCH_ALL GAME_SWITCH
 
 extern "C" int bb_game_legal(int game, int n, const void *states, uint8_t *legal_out) {
     if (n == 0) return BB_OK; // an empty batch is a no-op
     if (n < 0 || !states || !legal_out) return fail(BB_ERR_ARG, "bad arguments");
-    GAME_SWITCH_ALL(game, return game_legal<G>(n, states, legal_out));
+    GAME_SWITCH(game, return game_legal<G>(n, states, legal_out));
 }
 extern "C" int bb_game_apply(int game, int n, void *states, const int32_t *actions, int32_t *status_out) {
     if (n == 0) return BB_OK;
     if (n < 0 || !states || !actions) return fail(BB_ERR_ARG, "bad arguments");
-    GAME_SWITCH_ALL(game, return game_apply<G>(n, states, actions, status_out));
+    GAME_SWITCH(game, return game_apply<G>(n, states, actions, status_out));
 }
 extern "C" int bb_game_winner(int game, int n, const void *states, const int32_t *prev, int8_t *winner_out) {
     if (n == 0) return BB_OK;
     if (n < 0 || !states || !winner_out) return fail(BB_ERR_ARG, "bad arguments");
-    GAME_SWITCH_ALL(game, return game_winner<G>(n, states, prev, winner_out));
+    GAME_SWITCH(game, return game_winner<G>(n, states, prev, winner_out));
 }
 extern "C" int bb_game_encode(int game, int n, const void *states, int8_t *planes_out) {
     if (n == 0) return BB_OK;
     if (n < 0 || !states || !planes_out) return fail(BB_ERR_ARG, "bad arguments");
-    GAME_SWITCH_ALL(game, return game_encode<G>(n, states, planes_out));
+    GAME_SWITCH(game, return game_encode<G>(n, states, planes_out));
 }
 extern "C" int bb_game_initial(int game, void *state_out) {
     if (!state_out) return fail(BB_ERR_ARG, "null out");
-    GAME_SWITCH_ALL(game, {
+    GAME_SWITCH(game, {
         typename G::State s = G::initial();
         memcpy(state_out, &s, sizeof s);
         return BB_OK;
@@ -275,6 +334,8 @@ static int dalloc(bb_engine *e, T *&p, size_t count, bool zero = true) {
     return 0;
 }
 
+template <class G> struct NodeOf { using type = DenseNode<G>; }; // a node of the family's pool
+template <> struct NodeOf<DragonChess> { using type = DCNode; };
 #define SLOT_EXTENTS(G, max_plies) /* what the rows of BB_SLOT_ARRAYS (tree.hip.h) are written in */ \
     constexpr size_t S = G::S, MP = G::MAXPATH, PS = G::GID == BB_GAME_DRAGONCHESS ? G::A : G::S; \
     const size_t ANC = (size_t)((max_plies) + 2) * (G::GID == BB_GAME_DRAGONCHESS ? 2 : 1)
@@ -285,7 +346,7 @@ static int engine_alloc(bb_engine *e) {
     const bb_config &c = e->cfg;
     size_t n = (size_t)c.n_slots;
     constexpr bool DC = G::GID == BB_GAME_DRAGONCHESS;
-    constexpr size_t NODE_BYTES = DC ? sizeof(DCNode) : sizeof(DenseNode<typename std::conditional<DC, Connect4, G>::type>);
+    constexpr size_t NODE_BYTES = sizeof(typename NodeOf<G>::type);
     e->node_bytes = NODE_BYTES;
     SLOT_EXTENTS(G, c.max_plies);
     bool bad = false;
@@ -386,7 +447,7 @@ static long node_capacity_of(const bb_config *cfg) {
 template <class G>
 static void pool_bytes(const bb_config *cfg, size_t *per_slot, size_t *fixed) {
     constexpr bool DC = G::GID == BB_GAME_DRAGONCHESS;
-    constexpr size_t NODE_BYTES = DC ? sizeof(DCNode) : sizeof(DenseNode<typename std::conditional<DC, Connect4, G>::type>);
+    constexpr size_t NODE_BYTES = sizeof(typename NodeOf<G>::type);
     const size_t cap = (size_t)node_capacity_of(cfg);
     size_t ps = cap * NODE_BYTES;
     if (DC) ps += cap * 24 * sizeof(DCEdge) + (size_t)G::MAXPATH * 4;
@@ -1117,12 +1178,7 @@ static int hash_eval(bb_engine *e, int n, const void *states, float *value, floa
     if (ds.alloc((size_t)n * sizeof(typename G::State)) || dv.alloc((size_t)n * 4) || dp.alloc((size_t)n * G::A * 4))
         return BB_ERR_HIP;
     HIPCHK(hipMemcpy(ds.p, states, (size_t)n * sizeof(typename G::State), hipMemcpyDefault));
-    if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-        k_dc_hash_eval<<<nblk((size_t)n * 64), 256, 0, e->stream>>>(n, (const DCState *)ds.p, nullptr, e->cfg.hash_salt, 0, 0,
-                                                                      (float *)dv.p, (float *)dp.p, G::A);
-    else
-        k_hash_eval<G><<<nblk(n), 256, 0, e->stream>>>(n, (const typename G::State *)ds.p, nullptr, e->cfg.hash_salt, 0, 0,
-                                                       (float *)dv.p, (float *)dp.p, G::A);
+    Launch<G>::hash(e->stream, n, (const typename G::State *)ds.p, nullptr, e->cfg.hash_salt, 0, 0, (float *)dv.p, (float *)dp.p, G::A);
     HIPCHK(hipGetLastError());
     HIPCHK(sync_all(e));
     if (value) HIPCHK(hipMemcpy(value, dv.p, (size_t)n * 4, hipMemcpyDefault));
@@ -1138,9 +1194,6 @@ extern "C" int bb_hash_eval(bb_engine *e, int n, const void *states, float *valu
 }
 
 // ---- simulation loop ---------------------------------------------------------------------------------
-template <class G>
-static int launch_eval_inner(bb_engine *e);
-
 // bb_timing_enable: `launch` between a pair of HIP events on `st` while the pool has one left: every time_every-th of the evaluator
 // launches (the rounds count their first view's only and never time the second's), each of the persistent launches.
 enum { TIME_NEVER, TIME_SAMPLED, TIME_EACH };
@@ -1158,34 +1211,21 @@ static int timed_launch(bb_engine *e, hipStream_t st, int which, F launch) {
 }
 
 template <class G>
-static int launch_eval(bb_engine *e) { return timed_launch(e, e->stream, TIME_SAMPLED, [&] { return launch_eval_inner<G>(e); }); }
-
-template <class G>
 static int launch_eval_inner(bb_engine *e) {
     TreeDev &d = e->dev;
     int n = d.n_slots;
     const typename G::State *ls = (const typename G::State *)d.leaf_state;
+    constexpr bool DC = G::GID == BB_GAME_DRAGONCHESS;
+    constexpr int PS = DC ? G::A : G::S; // floats of a slot's eval_policy row (SLOT_EXTENTS)
     switch (d.evaluator) {
     case BB_EVAL_HASH:
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-            k_dc_hash_eval<<<nblk((size_t)n * 64), 256, 0, e->stream>>>(n, ls, d.leaf_game_id, d.salt, d.salt_per_game,
-                                                                          d.first_game_id, d.eval_value, d.eval_policy, G::A);
-        else
-            k_hash_eval<G><<<nblk(n), 256, 0, e->stream>>>(n, ls, d.leaf_game_id, d.salt, d.salt_per_game, d.first_game_id,
-                                                           d.eval_value, d.eval_policy, G::S);
+        Launch<G>::hash(e->stream, n, ls, d.leaf_game_id, d.salt, d.salt_per_game, d.first_game_id, d.eval_value, d.eval_policy, PS);
         break;
     case BB_EVAL_NET:
         // (a wide game's prior noise is mixed in at expansion, over the legal moves only: tree_dc.hip.h)
-        return launch_net<G>(e, n, ls, nullptr, d.leaf_game_id, d.leaf_serial, (G::GID == BB_GAME_DRAGONCHESS) ? 0 : e->cfg.noise_on,
-                             d.eval_value, nullptr, d.eval_policy, (G::GID == BB_GAME_DRAGONCHESS) ? G::A : G::S, e->stream);
-    case BB_EVAL_ROLLOUT:
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-            k_dc_rollout<<<nblk((size_t)n * 64), 256, 0, e->stream>>>(n, ls, d.leaf_game_id, d.sim_serial, d.pend_leaf, d.seed,
-                                                                        d.eval_value);
-        else
-            k_rollout<G><<<nblk(n), 256, 0, e->stream>>>(n, ls, d.leaf_game_id, d.sim_serial, d.pend_leaf, d.seed,
-                                                         d.eval_value);
-        break;
+        return launch_net<G>(e, n, ls, nullptr, d.leaf_game_id, d.leaf_serial, DC ? 0 : e->cfg.noise_on, d.eval_value, nullptr, d.eval_policy,
+                             PS, e->stream);
+    case BB_EVAL_ROLLOUT: Launch<G>::rollout(d, e->edges, e->stream); break;
     default: return fail(BB_ERR_ARG, "unknown evaluator %d", d.evaluator);
     }
     HIPCHK(hipGetLastError());
@@ -1193,17 +1233,14 @@ static int launch_eval_inner(bb_engine *e) {
 }
 
 template <class G>
+static int launch_eval(bb_engine *e) { return timed_launch(e, e->stream, TIME_SAMPLED, [&] { return launch_eval_inner<G>(e); }); }
+
+template <class G>
 static int run_sims(bb_engine *e, int sims) {
-    TreeDev &d = e->dev;
-    int tb = nblk((size_t)((d.n_slots + d.gpw - 1) / d.gpw) * 64);
     for (int s = 0; s < sims; s++) {
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-            k_dc_tree_step<<<nblk((size_t)d.n_slots * 64), 256, 0, e->stream>>>(d, e->edges);
-        else
-            k_tree_step<G><<<tb, 256, 0, e->stream>>>(d);
+        Launch<G>::tree_step(e->dev, e->edges, e->stream);
         HIPCHK(hipGetLastError());
-        int rc = launch_eval<G>(e);
-        if (rc) return rc;
+        if (int rc = launch_eval<G>(e)) return rc;
     }
     return BB_OK;
 }
@@ -1222,12 +1259,8 @@ static int set_roots(bb_engine *e, int n, const int32_t *slots, const void *stat
     HIPCHK(hipMemcpy(ds.p, states, (size_t)n * sizeof(typename G::State), hipMemcpyDefault));
     if (slots) HIPCHK(hipMemcpy(dsl.p, slots, (size_t)n * 4, hipMemcpyDefault));
     if (gids) HIPCHK(hipMemcpy(dg.p, gids, (size_t)n * 4, hipMemcpyDefault));
-    if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-        k_dc_set_roots<<<nblk(n), 256, 0, e->stream>>>(e->dev, e->edges, n, slots ? (const int32_t *)dsl.p : nullptr,
-                                                         (const DCState *)ds.p, gids ? (const uint32_t *)dg.p : nullptr);
-    else
-        k_set_roots<G><<<nblk(n), 256, 0, e->stream>>>(e->dev, n, slots ? (const int32_t *)dsl.p : nullptr,
-                                                       (const typename G::State *)ds.p, gids ? (const uint32_t *)dg.p : nullptr);
+    Launch<G>::set_roots(e->dev, e->edges, e->stream, n, slots ? (const int32_t *)dsl.p : nullptr, (const typename G::State *)ds.p,
+                         gids ? (const uint32_t *)dg.p : nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(sync_all(e));
     return BB_OK;
@@ -1249,14 +1282,11 @@ static int run_sims_api(bb_engine *e, int sims, const uint8_t *mask) {
         if (dm.alloc((size_t)e->dev.n_slots)) return BB_ERR_HIP;
         HIPCHK(hipMemcpyAsync(dm.p, mask, (size_t)e->dev.n_slots, hipMemcpyDefault, e->stream));
     }
+    k_add_sims<<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev, sims, mask ? (const uint8_t *)dm.p : nullptr);
     GAME_SWITCH(e->cfg.game, {
-        k_add_sims<typename std::conditional<G::GID == BB_GAME_DRAGONCHESS, Connect4, G>::type><<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev, sims, mask ? (const uint8_t *)dm.p : nullptr);
         rc = run_sims<G>(e, sims);
         if (rc) return rc;
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-            k_dc_tree_apply<<<nblk((size_t)e->dev.n_slots * 64), 256, 0, e->stream>>>(e->dev, e->edges);
-        else
-            k_tree_apply<G><<<nblk((size_t)e->dev.n_slots * G::S), 256, 0, e->stream>>>(e->dev);
+        Launch<G>::tree_apply(e->dev, e->edges, e->stream);
         HIPCHK(hipGetLastError());
         if (mask) HIPCHK(sync_all(e)); // the mask buffer is freed on return
         return BB_OK;
@@ -1275,16 +1305,9 @@ static int sample_moves(bb_engine *e, double temp, const double *u, int32_t *act
                         int32_t *cact, int32_t *cplays, float *cval) {
     TreeDev d = e->dev;
     size_t n = (size_t)d.n_slots;
-    if (u) {
-        HIPCHK(hipMemcpyAsync(e->d_u, u, n * 8, hipMemcpyDefault, e->stream));
-        d.in_u = e->d_u;
-    } else {
-        d.in_u = nullptr;
-    }
-    if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-        k_dc_sample<<<nblk(n * 64), 256, 0, e->stream>>>(d, e->edges, temp, e->d_child_action);
-    else
-        k_sample<G><<<nblk(n * G::S), 256, 0, e->stream>>>(d, temp);
+    if (u) HIPCHK(hipMemcpyAsync(e->d_u, u, n * 8, hipMemcpyDefault, e->stream));
+    d.in_u = u ? e->d_u : nullptr;
+    Launch<G>::sample(d, e->edges, e->stream, temp, e->d_child_action);
     HIPCHK(hipGetLastError());
     HIPCHK(sync_all(e));
     if (action) HIPCHK(hipMemcpy(action, d.out_action, n * 4, hipMemcpyDefault));
@@ -1292,7 +1315,7 @@ static int sample_moves(bb_engine *e, double temp, const double *u, int32_t *act
     if (rp) HIPCHK(hipMemcpy(rp, d.out_root_plays, n * 4, hipMemcpyDefault));
     if (cplays) HIPCHK(hipMemcpy(cplays, d.out_child_plays, n * G::S * 4, hipMemcpyDefault));
     if (cval) HIPCHK(hipMemcpy(cval, d.out_child_value, n * G::S * 4, hipMemcpyDefault));
-    if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
+    if constexpr (G::GID == BB_GAME_DRAGONCHESS) { // its kernel lists the actions of the root's edges
         if (cact) HIPCHK(hipMemcpy(cact, e->d_child_action, n * G::S * 4, hipMemcpyDefault));
     } else if (cact) { // dense games: slot i is action i
         std::vector<int32_t> ca(n * G::S);
@@ -1317,10 +1340,7 @@ extern "C" int bb_move_roots(bb_engine *e, const int32_t *actions) {
     HIPCHK(hipSetDevice(e->cfg.device));
     HIPCHK(hipMemcpyAsync(e->d_actions, actions, (size_t)e->dev.n_slots * 4, hipMemcpyDefault, e->stream));
     GAME_SWITCH(e->cfg.game, {
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-            k_dc_move_roots<<<nblk((size_t)e->dev.n_slots * 64), 256, 0, e->stream>>>(e->dev, e->edges, e->d_actions);
-        else
-            k_move_roots<G><<<nblk((size_t)e->dev.n_slots * G::S), 256, 0, e->stream>>>(e->dev, e->d_actions);
+        Launch<G>::move_roots(e->dev, e->edges, e->stream, e->d_actions);
         HIPCHK(hipGetLastError());
         HIPCHK(sync_all(e));
         return BB_OK;
@@ -1331,24 +1351,43 @@ extern "C" int bb_reset_roots(bb_engine *e) {
     if (!e) return fail(BB_ERR_ARG, "null engine");
     if (!e->dev.track_anc) return fail(BB_ERR_STATE, "this engine does not keep the ancestors of its roots (bb_config.track_ancestors)");
     HIPCHK(hipSetDevice(e->cfg.device));
+    if (e->cfg.game == BB_GAME_DRAGONCHESS) {
+        // a slot whose chain outgrew its max_plies + 2 entries cannot find its top-most ancestor (tree_dc.hip.h DC_ANC_BROKEN)
+        std::vector<int32_t> na((size_t)e->dev.n_slots);
+        HIPCHK(sync_all(e));
+        HIPCHK(hipMemcpy(na.data(), e->dev.anc_len, na.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t g = 0; g < na.size(); g++)
+            if (na[g] < 0)
+                return fail(BB_ERR_CAPACITY, "slot %zu moved its root more than max_plies + 2 times (max_plies %d) since the tree "
+                                             "was primed: its ancestors were not all kept", g, e->cfg.max_plies);
+    }
     GAME_SWITCH(e->cfg.game, {
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
-            // a slot whose chain outgrew its max_plies + 2 entries cannot find its top-most ancestor (tree_dc.hip.h DC_ANC_BROKEN)
-            std::vector<int32_t> na((size_t)e->dev.n_slots);
-            HIPCHK(sync_all(e));
-            HIPCHK(hipMemcpy(na.data(), e->dev.anc_len, na.size() * 4, hipMemcpyDeviceToHost));
-            for (size_t g = 0; g < na.size(); g++)
-                if (na[g] < 0)
-                    return fail(BB_ERR_CAPACITY, "slot %zu moved its root more than max_plies + 2 times (max_plies %d) since the tree "
-                                                 "was primed: its ancestors were not all kept", g, e->cfg.max_plies);
-            k_dc_reset_roots<<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev);
-        } else {
-            k_reset_roots<G><<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev);
-        }
+        Launch<G>::reset_roots(e->dev, e->edges, e->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(sync_all(e));
         return BB_OK;
     });
+}
+
+// One node of a slot's tree, staged on the device and copied out; action_out only where the family's kernel lists actions
+template <class G>
+static int node_fetch(bb_engine *e, int slot, int node, int32_t *action_out, int32_t *child_node_out, int32_t *child_plays_out,
+                      float *child_value_out, void *state_out, int32_t *info_out) {
+    constexpr int S = G::S;
+    DevBuf da, dc, dp, dv, ds, di;
+    if ((action_out && da.alloc(S * 4)) || dc.alloc(S * 4) || dp.alloc(S * 4) || dv.alloc(S * 4) || ds.alloc(sizeof(typename G::State)) || di.alloc(16))
+        return BB_ERR_HIP;
+    Launch<G>::node_edges(e->dev, e->edges, e->stream, slot, node, (int32_t *)da.p, (int32_t *)dc.p, (int32_t *)dp.p, (float *)dv.p,
+                          (typename G::State *)ds.p, (int32_t *)di.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(sync_all(e));
+    HIPCHK(hipMemcpy(child_node_out, dc.p, S * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(child_plays_out, dp.p, S * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(child_value_out, dv.p, S * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(state_out, ds.p, sizeof(typename G::State), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(info_out, di.p, 12, hipMemcpyDeviceToHost));
+    if (action_out) HIPCHK(hipMemcpy(action_out, da.p, S * 4, hipMemcpyDeviceToHost));
+    return BB_OK;
 }
 
 extern "C" int bb_node_view(bb_engine *e, int slot, int node, int32_t *child_node_out, int32_t *child_plays_out, float *child_value_out,
@@ -1357,25 +1396,9 @@ extern "C" int bb_node_view(bb_engine *e, int slot, int node, int32_t *child_nod
         return fail(BB_ERR_ARG, "bad arguments");
     if (node >= e->dev.node_cap) return fail(BB_ERR_ARG, "node %d out of range", node);
     HIPCHK(hipSetDevice(e->cfg.device));
-    GAME_SWITCH(e->cfg.game, {
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
-            return fail(BB_ERR_ARG, "node views exist for the dense-action games");
-        } else {
-            DevBuf dc, dp, dv, ds, di;
-            if (dc.alloc(G::S * 4) || dp.alloc(G::S * 4) || dv.alloc(G::S * 4) || ds.alloc(sizeof(typename G::State)) || di.alloc(16)) return BB_ERR_HIP;
-            HIPCHK(sync_all(e));
-            k_node_view<G><<<1, 64, 0, e->stream>>>(e->dev, slot, node, (int32_t *)dc.p, (int32_t *)dp.p, (float *)dv.p,
-                                                    (typename G::State *)ds.p, (int32_t *)di.p);
-            HIPCHK(hipGetLastError());
-            HIPCHK(sync_all(e));
-            HIPCHK(hipMemcpy(child_node_out, dc.p, G::S * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(child_plays_out, dp.p, G::S * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(child_value_out, dv.p, G::S * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(state_out, ds.p, sizeof(typename G::State), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(info_out, di.p, 12, hipMemcpyDeviceToHost));
-            return BB_OK;
-        }
-    });
+    if (e->cfg.game == BB_GAME_DRAGONCHESS) return fail(BB_ERR_ARG, "node views exist for the dense-action games");
+    HIPCHK(sync_all(e));
+    GAME_SWITCH(e->cfg.game, return node_fetch<G>(e, slot, node, nullptr, child_node_out, child_plays_out, child_value_out, state_out, info_out));
 }
 
 extern "C" int bb_node_edges(bb_engine *e, int slot, int node, int32_t *child_action_out, int32_t *child_node_out,
@@ -1389,29 +1412,13 @@ extern "C" int bb_node_edges(bb_engine *e, int slot, int node, int32_t *child_ac
     HIPCHK(hipMemcpy(&nn, e->dev.n_nodes + slot, 4, hipMemcpyDeviceToHost));
     if (node >= nn) return fail(BB_ERR_ARG, "node %d is not in slot %d's tree (%d nodes)", node, slot, nn);
     GAME_SWITCH(e->cfg.game, {
-        constexpr int S = G::S;
-        DevBuf da, dc, dp, dv, ds, di;
-        if (da.alloc(S * 4) || dc.alloc(S * 4) || dp.alloc(S * 4) || dv.alloc(S * 4) || ds.alloc(sizeof(typename G::State)) || di.alloc(16))
-            return BB_ERR_HIP;
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-            k_dc_node_edges<<<1, 64, 0, e->stream>>>(e->dev, e->edges, slot, node, (int32_t *)da.p, (int32_t *)dc.p, (int32_t *)dp.p,
-                                                     (float *)dv.p, (DCState *)ds.p, (int32_t *)di.p);
-        else
-            k_node_view<G><<<1, 64, 0, e->stream>>>(e->dev, slot, node, (int32_t *)dc.p, (int32_t *)dp.p, (float *)dv.p,
-                                                    (typename G::State *)ds.p, (int32_t *)di.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(sync_all(e));
-        HIPCHK(hipMemcpy(child_node_out, dc.p, S * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(child_plays_out, dp.p, S * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(child_value_out, dv.p, S * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(state_out, ds.p, sizeof(typename G::State), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(info_out, di.p, 12, hipMemcpyDeviceToHost));
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
-            HIPCHK(hipMemcpy(child_action_out, da.p, S * 4, hipMemcpyDeviceToHost));
-        } else { // slot i is action i; the node view's info word 1 is the legal mask
+        constexpr bool DC = G::GID == BB_GAME_DRAGONCHESS;
+        if (int rc = node_fetch<G>(e, slot, node, DC ? child_action_out : nullptr, child_node_out, child_plays_out, child_value_out, state_out, info_out))
+            return rc;
+        if constexpr (!DC) { // slot i is action i; the node view's info word 1 is the legal mask
             const uint32_t legal = (uint32_t)info_out[1];
             int cnt = 0;
-            for (int i = 0; i < S; i++) {
+            for (int i = 0; i < G::S; i++) {
                 const bool on = i < G::A && ((legal >> i) & 1u);
                 child_action_out[i] = on ? i : -1;
                 if (!on) {
@@ -1434,10 +1441,7 @@ extern "C" int bb_get_root_states(bb_engine *e, void *states_out) {
         DevBuf ds;
         size_t bytes = (size_t)e->dev.n_slots * sizeof(typename G::State);
         if (ds.alloc(bytes)) return BB_ERR_HIP;
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-            k_dc_get_roots<<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev, (DCState *)ds.p);
-        else
-            k_get_roots<G><<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev, (typename G::State *)ds.p);
+        Launch<G>::get_roots(e->dev, e->edges, e->stream, (typename G::State *)ds.p);
         HIPCHK(hipGetLastError());
         HIPCHK(sync_all(e));
         HIPCHK(hipMemcpy(states_out, ds.p, bytes, hipMemcpyDefault));
@@ -1455,12 +1459,10 @@ extern "C" int bb_set_sims_per_move(bb_engine *e, int sims) {
     e->sims_now = sims;
     e->dev.sims_per_move = sims;
     for (int v = 0; v < e->n_views; v++) e->view[v].sims_per_move = sims;
-    GAME_SWITCH(e->cfg.game, {
-        k_add_sims<typename std::conditional<G::GID == BB_GAME_DRAGONCHESS, Connect4, G>::type><<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev, sims); // slots waiting for their next move
-        HIPCHK(hipGetLastError());
-        HIPCHK(sync_all(e));
-        return BB_OK;
-    });
+    k_add_sims<<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev, sims); // slots waiting for their next move
+    HIPCHK(hipGetLastError());
+    HIPCHK(sync_all(e));
+    return BB_OK;
 }
 
 extern "C" int bb_set_rng_stream(bb_engine *e, uint64_t seed, uint32_t first_game_id) {
@@ -1504,14 +1506,14 @@ extern "C" int bb_selfplay_begin(bb_engine *e, int n_games, double temp) {
     e->vround[0] = e->vround[1] = 0;
     e->miss_next[0] = e->miss_next[1] = 0;
     GAME_SWITCH(e->cfg.game, {
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS) {
-            k_dc_selfplay_begin<<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev, e->edges);
+        if constexpr (G::GID == BB_GAME_DRAGONCHESS) { // one view (make_views), never played through the rounds
+            Launch<G>::selfplay_begin(e->dev, e->edges, e->stream);
         } else {
             for (int v = 0; v < e->n_views; v++) {
                 e->view[v].n_games_target = n_games;
                 e->view[v].temp = temp;
                 e->view[v].sims_per_move = e->sims_now;
-                k_selfplay_begin<G><<<nblk(e->view[v].n_slots), 256, 0, e->vstream[v]>>>(e->view[v]);
+                Launch<G>::selfplay_begin(e->view[v], e->edges, e->vstream[v]);
             }
         }
         HIPCHK(hipGetLastError());
@@ -1649,12 +1651,8 @@ extern "C" int bb_selfplay_step(bb_engine *e, int plies) {
             return mode == PLAY_QUEUE ? selfplay_queue<G>(e, plies * e->sims_now) : selfplay_rounds_async<G>(e, plies * e->sims_now);
         }
         for (int p = 0; p < plies; p++) { // PLAY_LOCKSTEP
-            int rc = run_sims<G>(e, e->sims_now);
-            if (rc) return rc;
-            if constexpr (DC)
-                k_dc_selfplay_move<<<nblk((size_t)e->dev.n_slots * 64), 256, 0, e->stream>>>(e->dev, e->edges);
-            else
-                k_selfplay_move<G><<<nblk((size_t)e->dev.n_slots * G::S), 256, 0, e->stream>>>(e->dev);
+            if (int rc = run_sims<G>(e, e->sims_now)) return rc;
+            Launch<G>::selfplay_move(e->dev, e->edges, e->stream);
             HIPCHK(hipGetLastError());
         }
         return BB_OK;
@@ -1817,14 +1815,7 @@ extern "C" int bb_examples_to_batch(int game, int n_records, const void *records
         return fail(BB_ERR_ARG, "records, boards_out and policy_out are accessed in 16-byte units");
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *rec = (const uint8_t *)records;
-    GAME_SWITCH(game, {
-        if constexpr (G::GID == BB_GAME_DRAGONCHESS)
-            k_dc_examples_to_batch<<<n, 256, 0, st>>>(n_records, rec, index, boards_out, policy_out, value_out, bad_out);
-        else
-            k_examples_to_batch<G><<<nblk((size_t)n * (G::H * G::W * G::C + G::A + 1)), 256, 0, st>>>(
-                n_records, rec, n, index, boards_out, policy_out, value_out, bad_out);
-        break;
-    });
+    GAME_SWITCH(game, Launch<G>::examples_to_batch(st, n_records, rec, n, index, boards_out, policy_out, value_out, bad_out); break);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }

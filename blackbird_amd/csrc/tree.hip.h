@@ -849,7 +849,6 @@ __global__ void __launch_bounds__(256) k_set_roots(TreeDev d, int n, const int32
     d.sims_left[g] = 0;
 }
 
-template <class G>
 __global__ void __launch_bounds__(256) k_add_sims(TreeDev d, int sims, const uint8_t *mask = nullptr) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.n_slots) return;
