@@ -129,6 +129,11 @@ class MCTS(object):
     _KIND = _lib.MCTS_DYNAMIC
     _EVALUATOR = _lib.EVAL_ROLLOUT
     _MAX_NODES = 1 << 20
+    # How the engines behind FindMove / ResetRoot / Children and the arena run their simulations (bb_config.launch):
+    # 'lockstep' -- one tree + one evaluator launch per simulation -- or 'wave', the opt-in: one launch per run_sims call, a wave
+    # per game (Connect4 / TicTacToe with the hash evaluator or a 16-filter network; any other engine searches lock-step and
+    # Engine.run_sims_structure() says so).  The same trees bit for bit either way.
+    SearchLaunch = 'lockstep'
 
     def __init__(self, explorationRate, timeLimit=None, playLimit=None, **kwargs):
         self.TimeLimit = timeLimit
@@ -144,7 +149,16 @@ class MCTS(object):
     def _max_depth(self):
         return 1
 
+    def _search_launch(self):
+        """bb_config.launch of a search engine, from SearchLaunch ('lockstep' leaves the engine's default alone)."""
+        if self.SearchLaunch == 'lockstep':
+            return _lib.LAUNCH_AUTO
+        if self.SearchLaunch == 'wave':
+            return _lib.LAUNCH_WAVE
+        raise ValueError("SearchLaunch must be 'lockstep' or 'wave', not {!r}".format(self.SearchLaunch))
+
     def _make_engine(self, game_id, n_slots, sims, **kw):
+        kw.setdefault('launch', self._search_launch())
         return _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
                            max_depth=self._max_depth(), evaluator=self._EVALUATOR, c_puct=float(self.ExplorationRate),
                            seed=_seed_from_numpy(), **kw)

@@ -16,7 +16,7 @@ GAME_CONNECT4, GAME_TICTACTOE, GAME_DRAGONCHESS = 0, 1, 2
 MCTS_DYNAMIC, MCTS_FIXED = 0, 1
 EVAL_HASH, EVAL_NET, EVAL_ROLLOUT = 0, 1, 2
 NET_FORM_AUTO, NET_FORM_F32, NET_FORM_SPLIT = 0, 1, 2   # bb_config.net_form
-LAUNCH_AUTO, LAUNCH_LOCKSTEP, LAUNCH_ROUNDS = 0, 1, 2    # bb_config.launch
+LAUNCH_AUTO, LAUNCH_LOCKSTEP, LAUNCH_ROUNDS, LAUNCH_WAVE = 0, 1, 2, 3    # bb_config.launch (LAUNCH_WAVE: the search API in one launch)
 OPT_ADAM, OPT_MOMENTUM, OPT_SGD = 0, 1, 2                # bb_train_config.optimizer
 TRAIN_PARAMS, TRAIN_GRADS, TRAIN_SLOT_M, TRAIN_SLOT_V, TRAIN_NOISE = 0, 1, 2, 3, 4   # bb_trainer_read
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NAN, ERR_CAPACITY, ERR_WEIGHTS = 0, -1, -2, -3, -4, -5, -6
@@ -24,7 +24,7 @@ OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NAN, ERR_CAPACITY, ERR_WEIGHTS = 0, -1, -2,
 EXPORTS = (
     "bb_game_info_get", "bb_last_error", "bb_device_count", "bb_game_legal", "bb_game_apply", "bb_game_winner",
     "bb_game_encode", "bb_game_initial", "bb_create", "bb_destroy", "bb_load_weights", "bb_get_counters",
-    "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked",
+    "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked", "bb_run_sims_structure",
     "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
     "bb_examples_to_batch",
@@ -111,6 +111,7 @@ def lib():
     L.bb_set_roots.argtypes = [vp, ip, vp, vp, vp]
     L.bb_run_sims.argtypes = [vp, ip]
     L.bb_run_sims_masked.argtypes = [vp, ip, vp]
+    L.bb_run_sims_structure.argtypes = [vp, C.POINTER(C.c_int32)]
     L.bb_sample_moves.argtypes = [vp, C.c_double, vp, vp, vp, vp, vp, vp, vp]
     L.bb_move_roots.argtypes = [vp, vp]
     L.bb_get_root_states.argtypes = [vp, vp]
@@ -365,7 +366,7 @@ class Engine:
                  noise_on=False, alpha=0.2, epsilon=0.3, device=0, salt_per_game=False, node_capacity=0,
                  net_form=0, launch=0, general_net=False, track_ancestors=False):
         """net_form: NET_FORM_AUTO / NET_FORM_F32 / NET_FORM_SPLIT (bb_config.net_form); launch: LAUNCH_AUTO / LAUNCH_LOCKSTEP /
-        LAUNCH_ROUNDS (bb_config.launch); general_net: a 16-filter network through the launch-per-layer kernels."""
+        LAUNCH_ROUNDS / LAUNCH_WAVE (bb_config.launch; LAUNCH_WAVE is the search API's opt-in: run_sims_structure); general_net: a 16-filter network through the launch-per-layer kernels."""
         self.game = game
         self.info = game_info(game)
         if max_plies is None:
@@ -499,6 +500,13 @@ class Engine:
             mask = np.ascontiguousarray(mask, dtype=np.uint8)
             assert mask.shape[0] == self.n_slots
             check(lib().bb_run_sims_masked(self.h, int(sims), ptr(mask)))
+
+    def run_sims_structure(self):
+        """bb_run_sims_structure: LAUNCH_LOCKSTEP or LAUNCH_WAVE -- what run_sims launches for this engine as it stands (after
+        load_weights): an engine that asked for LAUNCH_WAVE and cannot have it says so here, never silently."""
+        out = C.c_int32(-1)
+        check(lib().bb_run_sims_structure(self.h, C.byref(out)))
+        return out.value
 
     def sample_moves(self, temp, u=None):
         n, S = self.n_slots, self.info.S

@@ -13,6 +13,7 @@
 #include "tree_dc.hip.h"
 #include "mega2.hip.h"
 #include "mega_dc.hip.h"
+#include "search_wave.hip.h"
 #include "examples.hip.h"
 #include "train.hip.h"
 
@@ -102,6 +103,14 @@ struct Launch {
     static void encode(int n, const State *s, int8_t *out) { k_game_encode<G><<<nblk((size_t)n * G::H * G::W), 256>>>(n, s, out); }
     static void tree_step(const TreeDev &d, const DCEdges &, hipStream_t st) { k_tree_step<G><<<nblk((size_t)((d.n_slots + d.gpw - 1) / d.gpw) * 64), 256, 0, st>>>(d); }
     static void tree_apply(const TreeDev &d, const DCEdges &, hipStream_t st) { k_tree_apply<G><<<nblk((size_t)d.n_slots * G::S), 256, 0, st>>>(d); }
+    // BB_LAUNCH_WAVE: `sims` steps of tree_step + the evaluator, and tree_apply, as one launch with a wave per slot (search_wave.hip.h);
+    // x3 with operands: the 16-filter network, else the hash evaluator.  false: this family has no such kernel.
+    static bool search_wave(const TreeDev &d, const DCEdges &, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int noise) {
+        const int blocks = (d.n_slots + SW_WAVES - 1) / SW_WAVES;
+        if (x3.w0) k_search_wave<G, true><<<blocks, 64 * SW_WAVES, 0, st>>>(d, nd, x3, sims, noise);
+        else k_search_wave<G, false><<<blocks, 64 * SW_WAVES, 0, st>>>(d, nd, x3, sims, 0);
+        return true;
+    }
     static void hash(hipStream_t st, int n, const State *s, const uint32_t *game_id, uint64_t salt, int salt_per_game, uint32_t first_game_id, float *value, float *policy, int pstride) {
         k_hash_eval<G><<<nblk(n), 256, 0, st>>>(n, s, game_id, salt, salt_per_game, first_game_id, value, policy, pstride);
     }
@@ -132,6 +141,7 @@ struct Launch<DragonChess> {
     static void encode(int n, const State *s, int8_t *out) { k_dc_encode<<<nblk((size_t)n * 64), 256>>>(n, s, out); }
     static void tree_step(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_tree_step<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
     static void tree_apply(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_tree_apply<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
+    static bool search_wave(const TreeDev &, const DCEdges &, hipStream_t, int, const NetDev &, const NetX3 &, int) { return false; } // (search_structure never sends the wide game here)
     static void hash(hipStream_t st, int n, const State *s, const uint32_t *game_id, uint64_t salt, int salt_per_game, uint32_t first_game_id, float *value, float *policy, int pstride) {
         k_dc_hash_eval<<<nblk((size_t)n * 64), 256, 0, st>>>(n, s, game_id, salt, salt_per_game, first_game_id, value, policy, pstride);
     }
@@ -550,7 +560,7 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
     }
     e->tune.launch_steps = env_int("BB_LAUNCH_STEPS", 64);
     e->tune.queue_limit_s = env_int("BB_QUEUE_LIMIT_S", 30);
-    if (cfg->launch < 0 || cfg->launch > BB_LAUNCH_ROUNDS || cfg->net_form < 0 || cfg->net_form > BB_NET_FORM_SPLIT) {
+    if (cfg->launch < 0 || cfg->launch > BB_LAUNCH_WAVE || cfg->net_form < 0 || cfg->net_form > BB_NET_FORM_SPLIT) {
         delete e;
         return fail(BB_ERR_ARG, "bad bb_config.launch / net_form");
     }
@@ -1272,6 +1282,24 @@ extern "C" int bb_set_roots(bb_engine *e, int n, const int32_t *slots, const voi
     GAME_SWITCH(e->cfg.game, return set_roots<G>(e, n, slots, states, game_ids));
 }
 
+// The structure bb_run_sims / bb_run_sims_masked search through at this moment -- the ONE place that reads launch / game / evaluator /
+// the loaded network for this: BB_LAUNCH_WAVE where the engine asked for it and k_search_wave exists for what it is (a dense game
+// with the hash evaluator, or with a 16-filter network in the split-operand form), else the lock-step loop.  bb_run_sims_structure
+// reports it, so an engine that asked and was refused is visible.
+static int search_structure(const bb_engine *e) {
+    if (e->cfg.launch != BB_LAUNCH_WAVE || e->cfg.game == BB_GAME_DRAGONCHESS) return BB_LAUNCH_LOCKSTEP;
+    if (e->cfg.evaluator == BB_EVAL_HASH) return BB_LAUNCH_WAVE;
+    if (e->cfg.evaluator == BB_EVAL_NET && e->has_weights && !e->general_net && e->x3.w0) return BB_LAUNCH_WAVE;
+    return BB_LAUNCH_LOCKSTEP;
+}
+
+extern "C" int bb_run_sims_structure(bb_engine *e, int32_t *out) {
+    if (!e || !out) return fail(BB_ERR_ARG, "null argument");
+    if (int rc = check_eval(e)) return rc;
+    *out = search_structure(e);
+    return BB_OK;
+}
+
 static int run_sims_api(bb_engine *e, int sims, const uint8_t *mask) {
     if (!e || sims <= 0) return fail(BB_ERR_ARG, "Not enough information to decide a stop time."); // MCTS.py:181-182
     int rc = check_eval(e);
@@ -1283,10 +1311,21 @@ static int run_sims_api(bb_engine *e, int sims, const uint8_t *mask) {
         HIPCHK(hipMemcpyAsync(dm.p, mask, (size_t)e->dev.n_slots, hipMemcpyDefault, e->stream));
     }
     k_add_sims<<<nblk(e->dev.n_slots), 256, 0, e->stream>>>(e->dev, sims, mask ? (const uint8_t *)dm.p : nullptr);
+    const bool wave = search_structure(e) == BB_LAUNCH_WAVE;
     GAME_SWITCH(e->cfg.game, {
-        rc = run_sims<G>(e, sims);
-        if (rc) return rc;
-        Launch<G>::tree_apply(e->dev, e->edges, e->stream);
+        if (wave) { // every simulation of every slot, and the last leaf's apply, in one launch
+            const bool net = e->cfg.evaluator == BB_EVAL_NET;
+            rc = timed_launch(e, e->stream, TIME_EACH, [&]() -> int {
+                if (!Launch<G>::search_wave(e->dev, e->edges, e->stream, sims, e->net, net ? e->x3 : NetX3{nullptr, nullptr, nullptr, nullptr, nullptr}, e->cfg.noise_on))
+                    return fail(BB_ERR_STATE, "no one-launch search for this game");
+                return BB_OK;
+            });
+            if (rc) return rc;
+        } else {
+            rc = run_sims<G>(e, sims);
+            if (rc) return rc;
+            Launch<G>::tree_apply(e->dev, e->edges, e->stream);
+        }
         HIPCHK(hipGetLastError());
         if (mask) HIPCHK(sync_all(e)); // the mask buffer is freed on return
         return BB_OK;

@@ -1,0 +1,64 @@
+// search_wave.hip.h -- the search API (bb_run_sims / bb_run_sims_masked) in ONE launch: one wave per game slot.
+//
+// The lock-step search is a host loop of two launches per simulation (k_tree_step, then the evaluator over every slot): a
+// lone FindMove position pays 2 x 800 launches per move, and so does every ply of an arena however few games it plays.
+// The slots share nothing, so here a wave keeps its slot for the whole call, as k_dc_selfplay_fused does for DragonChess
+// self-play (mega_dc.hip.h): phase_apply -> phase_select -> the evaluator for its own leaf -> ..., and after the last
+// simulation the pending evaluation is applied (what Launch<G>::tree_apply does for the lock-step loop), so nothing
+// outlives the launch.  No wave waits for another: no spin, no cross-wave synchronisation, every loop is bounded by `sims`.
+//
+// Per slot this is exactly the lock-step sequence of operations, from the same device functions -- phase_apply /
+// phase_select (tree.hip.h: backup_path with the ancestor walk of track_anc engines, terminal leaves, a full node pool ->
+// the overflow counter, slots without sims_left), then what k_hash_eval or k_net_x3 do for one slot: net_body_x3 on the leaf in
+// the slot's mailbox with the prior noise keyed (game id, node serial, action) -- so trees, counters and sampled moves are
+// the lock-step ones bit for bit (tests/test_gpu_search_wave.py).  One difference nobody can observe: the lock-step
+// evaluator launch also rewrites the mailboxes of slots that posted nothing; here an idle slot's mailbox is left alone.
+//
+// The tree phases run on lanes 0 .. S-1, the network on all 64; what decides whether the network runs is made
+// wave-uniform (readfirstlane), so net_body_x3 is never entered with part of the wave masked off.  TreeDev stays a kernel
+// argument (SGPRs) and every helper is inlined: an out-of-line callee would take it by reference from scratch.
+#pragma once
+#include "eval.hip.h"
+#include "net_x3.hip.h"
+#include "tree.hip.h"
+
+#define SW_WAVES 4 // waves (= slots) per workgroup: four waves' activations (X3Geom::WAVE_BYTES each) as in k_net_x3, one wave per SIMD
+
+// what k_hash_eval does for position g of the leaf mailbox: every lane forms the hash, lane a writes action a
+template <class G>
+__device__ __forceinline__ void sw_hash_eval(const TreeDev &d, int g, int lane) {
+    const typename G::State st = ((const typename G::State *)d.leaf_state)[g];
+    const uint64_t sl = d.salt + (d.salt_per_game ? (uint64_t)(d.leaf_game_id[g] - d.first_game_id) : 0ull);
+    const uint64_t z = hash_state<G>(st, sl);
+    if (lane == 0) d.eval_value[g] = bb_hash_value(z);
+    if (lane < G::A) d.eval_policy[(size_t)g * G::S + lane] = bb_hash_policy(z, lane);
+}
+
+// NET: the 16-filter network in the split-operand form (x3.w0 set); else the hash evaluator.
+template <class G, bool NET>
+__global__ void __launch_bounds__(64 * SW_WAVES) k_search_wave(TreeDev d, NetDev nd, NetX3 x3, int sims, int noise) {
+    using XG = X3Geom<G>;
+    constexpr int S = G::S;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[NET ? SW_WAVES * XG::WAVE_BYTES : 16];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * SW_WAVES + wave;
+    if (g >= d.n_slots) return; // (whole waves leave: nothing below synchronises the workgroup)
+    const bool tree_lane = lane < S;
+    for (int s = 0; s < sims; s++) { // the lock-step loop's `sims` steps, for this slot
+        if (tree_lane) {
+            phase_apply<G>(d, g, lane);
+            __threadfence_block();
+            phase_select<G>(d, g, lane);
+        }
+        __threadfence_block(); // lane 0's mailbox stores before the other lanes' loads
+        // (uniform) no leaf posted: the slot is idle, masked out or out of simulations, and every further step is a no-op
+        if (__builtin_amdgcn_readfirstlane(d.pend_leaf[g]) < 0) break;
+        if constexpr (NET)
+            net_body_x3<G, false>(nd, x3, g + 1, g, nullptr, lds + wave * XG::WAVE_BYTES, (const typename G::State *)d.leaf_state, nullptr,
+                                  d.leaf_game_id, d.leaf_serial, noise, d.eval_value, nullptr, d.eval_policy, S, true);
+        else
+            sw_hash_eval<G>(d, g, lane);
+        __threadfence_block(); // the evaluation is in the mailbox before phase_apply reads it
+    }
+    if (tree_lane) phase_apply<G>(d, g, lane); // the last simulation's evaluation (no-op without a pending leaf)
+}

@@ -131,7 +131,8 @@ typedef struct {
     int32_t net_form;      /* BB_NET_FORM_*: the arithmetic of the conv tower (Network.getEvaluation/getPolicy, Network.py:48-64).
                               0 = AUTO: the fastest form that meets the 1e-5 bound (the split-operand form wherever it exists) */
     int32_t launch;        /* BB_LAUNCH_*: launch structure of bb_selfplay_step; 0 = AUTO (persistent kernels where the network
-                              fits them).  The others exist for parity checks: every structure gives the same bits */
+                              fits them).  The others exist for parity checks: every structure gives the same bits.
+                              BB_LAUNCH_WAVE is the one value that concerns bb_run_sims instead (opt-in, bb_run_sims_structure) */
     int32_t general_net;   /* 1: run a 16-filter network through the launch-per-layer kernels of wider networks (parity checks) */
     int32_t track_ancestors; /* 1: keep, per slot, the chain of edges from the first root to the current one (at most
                               max_plies + 2 of them) and back every simulation of bb_run_sims up through it, as the reference's
@@ -148,6 +149,8 @@ typedef struct {
 #define BB_LAUNCH_AUTO 0
 #define BB_LAUNCH_LOCKSTEP 1 /* one tree + one evaluator launch per simulation, one move launch per ply */
 #define BB_LAUNCH_ROUNDS 2   /* asynchronous rounds: k_tree_async + a compacted network launch (dense games) */
+#define BB_LAUNCH_WAVE 3     /* bb_run_sims / bb_run_sims_masked in ONE launch, one wave per slot (bb_run_sims_structure says where it
+                                applies); bb_selfplay_step treats it as BB_LAUNCH_LOCKSTEP */
 
 typedef struct bb_engine bb_engine;
 
@@ -232,6 +235,15 @@ int bb_run_sims(bb_engine *e, int sims);
  * untouched.  This is what a batched arena needs (Blackbird.py:177-216, TestModels: two searchers share the games and
  * each one only searches the positions where it is to move). */
 int bb_run_sims_masked(bb_engine *e, int sims, const uint8_t *mask);
+/* Which launch structure bb_run_sims / bb_run_sims_masked use for this engine as it stands: *out = BB_LAUNCH_LOCKSTEP (one tree
+ * + one evaluator launch per simulation of _runMCTS, MCTS.py:284-303) or BB_LAUNCH_WAVE (one launch per call: a wave keeps its
+ * slot and runs _findLeaf / the evaluator / _backProp, MCTS.py:238-258, 305-334, for its own leaf, simulation after
+ * simulation -- the same trees bit for bit).  BB_LAUNCH_WAVE is what an engine created with bb_config.launch = BB_LAUNCH_WAVE
+ * gets when its game is Connect4 or TicTacToe and its evaluator is BB_EVAL_HASH, or BB_EVAL_NET with a 16-filter network in
+ * the split-operand form (bb_net_form 2); every other engine (DragonChess, rollouts, wide networks, BB_NET_FORM_F32, general_net)
+ * searches lock-step whatever it asked for, and says so here.  Read it after bb_load_weights: a network evaluator without
+ * weights answers BB_ERR_WEIGHTS. */
+int bb_run_sims_structure(bb_engine *e, int32_t *out);
 /* After bb_run_sims: Root statistics + the move _selectAction(exploring=False) picks (MCTS.py:335-338).
  * u[n_slots] uniforms in [0,1) for np.random.choice's law, or NULL to draw Philox(seed, game_id, ply).
  * Outputs per slot (S = bb_game_info.S): action (or BB_ERR_NAN), root_winrate = Root.WinRate(),
