@@ -131,8 +131,9 @@ class MCTS(object):
     _MAX_NODES = 1 << 20
     # How the engines behind FindMove / ResetRoot / Children and the arena run their simulations (bb_config.launch):
     # 'lockstep' -- one tree + one evaluator launch per simulation -- or 'wave', the opt-in: one launch per run_sims call, a wave
-    # per game (Connect4 / TicTacToe with the hash evaluator or a 16-filter network; any other engine searches lock-step and
-    # Engine.run_sims_structure() says so).  The same trees bit for bit either way.
+    # per game (Connect4 / TicTacToe with the hash evaluator or a 16-filter network, DragonChess with a 16-filter network of at
+    # most 8 blocks; any other engine searches lock-step and Engine.run_sims_structure() says so).  The same trees bit for bit
+    # either way.
     SearchLaunch = 'lockstep'
 
     def __init__(self, explorationRate, timeLimit=None, playLimit=None, **kwargs):

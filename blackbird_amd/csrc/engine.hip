@@ -14,6 +14,7 @@
 #include "mega2.hip.h"
 #include "mega_dc.hip.h"
 #include "search_wave.hip.h"
+#include "search_wave_dc.hip.h"
 #include "examples.hip.h"
 #include "train.hip.h"
 
@@ -141,7 +142,13 @@ struct Launch<DragonChess> {
     static void encode(int n, const State *s, int8_t *out) { k_dc_encode<<<nblk((size_t)n * 64), 256>>>(n, s, out); }
     static void tree_step(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_tree_step<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
     static void tree_apply(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_tree_apply<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
-    static bool search_wave(const TreeDev &, const DCEdges &, hipStream_t, int, const NetDev &, const NetX3 &, int) { return false; } // (search_structure never sends the wide game here)
+    // (search_structure sends the wide game here with a 16-filter split-operand network that fits the kernel's LDS, and nothing else;
+    // its prior noise is mixed in at expansion: E.noise_on)
+    static bool search_wave(const TreeDev &d, const DCEdges &E, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int) {
+        if (!x3.w0 || nd.R > DC_RMAX || nd.head_floats > DC_HEAD_FLOATS) return false;
+        k_dc_search_wave<<<(d.n_slots + SW_WAVES - 1) / SW_WAVES, 64 * SW_WAVES, 0, st>>>(d, E, nd, x3, sims);
+        return true;
+    }
     static void hash(hipStream_t st, int n, const State *s, const uint32_t *game_id, uint64_t salt, int salt_per_game, uint32_t first_game_id, float *value, float *policy, int pstride) {
         k_dc_hash_eval<<<nblk((size_t)n * 64), 256, 0, st>>>(n, s, game_id, salt, salt_per_game, first_game_id, value, policy, pstride);
     }
@@ -1283,13 +1290,17 @@ extern "C" int bb_set_roots(bb_engine *e, int n, const int32_t *slots, const voi
 }
 
 // The structure bb_run_sims / bb_run_sims_masked search through at this moment -- the ONE place that reads launch / game / evaluator /
-// the loaded network for this: BB_LAUNCH_WAVE where the engine asked for it and k_search_wave exists for what it is (a dense game
-// with the hash evaluator, or with a 16-filter network in the split-operand form), else the lock-step loop.  bb_run_sims_structure
-// reports it, so an engine that asked and was refused is visible.
+// the loaded network for this: BB_LAUNCH_WAVE where the engine asked for it and a one-launch kernel exists for what it is (a dense
+// game with the hash evaluator, or any game with a 16-filter network in the split-operand form -- for DragonChess one that also fits
+// k_dc_search_wave's LDS, the test selfplay_structure applies to the self-play kernel), else the lock-step loop.
+// bb_run_sims_structure reports it, so an engine that asked and was refused is visible.
 static int search_structure(const bb_engine *e) {
-    if (e->cfg.launch != BB_LAUNCH_WAVE || e->cfg.game == BB_GAME_DRAGONCHESS) return BB_LAUNCH_LOCKSTEP;
-    if (e->cfg.evaluator == BB_EVAL_HASH) return BB_LAUNCH_WAVE;
-    if (e->cfg.evaluator == BB_EVAL_NET && e->has_weights && !e->general_net && e->x3.w0) return BB_LAUNCH_WAVE;
+    if (e->cfg.launch != BB_LAUNCH_WAVE) return BB_LAUNCH_LOCKSTEP;
+    const bool dc = e->cfg.game == BB_GAME_DRAGONCHESS;
+    if (e->cfg.evaluator == BB_EVAL_HASH && !dc) return BB_LAUNCH_WAVE;
+    if (e->cfg.evaluator == BB_EVAL_NET && e->has_weights && !e->general_net && e->x3.w0 &&
+        (!dc || (e->net.R <= DC_RMAX && e->net.head_floats <= DC_HEAD_FLOATS)))
+        return BB_LAUNCH_WAVE;
     return BB_LAUNCH_LOCKSTEP;
 }
 

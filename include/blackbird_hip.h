@@ -150,7 +150,8 @@ typedef struct {
 #define BB_LAUNCH_LOCKSTEP 1 /* one tree + one evaluator launch per simulation, one move launch per ply */
 #define BB_LAUNCH_ROUNDS 2   /* asynchronous rounds: k_tree_async + a compacted network launch (dense games) */
 #define BB_LAUNCH_WAVE 3     /* bb_run_sims / bb_run_sims_masked in ONE launch, one wave per slot (bb_run_sims_structure says where it
-                                applies); bb_selfplay_step treats it as BB_LAUNCH_LOCKSTEP */
+                                applies: Connect4, TicTacToe, and DragonChess with a 16-filter network of at most 8 blocks);
+                                bb_selfplay_step treats it as BB_LAUNCH_LOCKSTEP */
 
 typedef struct bb_engine bb_engine;
 
@@ -239,10 +240,11 @@ int bb_run_sims_masked(bb_engine *e, int sims, const uint8_t *mask);
  * + one evaluator launch per simulation of _runMCTS, MCTS.py:284-303) or BB_LAUNCH_WAVE (one launch per call: a wave keeps its
  * slot and runs _findLeaf / the evaluator / _backProp, MCTS.py:238-258, 305-334, for its own leaf, simulation after
  * simulation -- the same trees bit for bit).  BB_LAUNCH_WAVE is what an engine created with bb_config.launch = BB_LAUNCH_WAVE
- * gets when its game is Connect4 or TicTacToe and its evaluator is BB_EVAL_HASH, or BB_EVAL_NET with a 16-filter network in
- * the split-operand form (bb_net_form 2); every other engine (DragonChess, rollouts, wide networks, BB_NET_FORM_F32, general_net)
- * searches lock-step whatever it asked for, and says so here.  Read it after bb_load_weights: a network evaluator without
- * weights answers BB_ERR_WEIGHTS. */
+ * gets when its evaluator is BB_EVAL_NET with a 16-filter network in the split-operand form (bb_net_form 2) -- for DragonChess
+ * one of at most 8 residual blocks, what its kernel keeps in LDS -- or when its game is Connect4 or TicTacToe and its evaluator
+ * is BB_EVAL_HASH; every other engine (DragonChess with BB_EVAL_HASH or a deeper tower, rollouts, wide networks, BB_NET_FORM_F32,
+ * general_net) searches lock-step whatever it asked for, and says so here.  Read it after bb_load_weights: a network evaluator
+ * without weights answers BB_ERR_WEIGHTS. */
 int bb_run_sims_structure(bb_engine *e, int32_t *out);
 /* After bb_run_sims: Root statistics + the move _selectAction(exploring=False) picks (MCTS.py:335-338).
  * u[n_slots] uniforms in [0,1) for np.random.choice's law, or NULL to draw Philox(seed, game_id, ply).
