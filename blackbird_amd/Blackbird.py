@@ -375,6 +375,7 @@ class Model(MCTS, Network):
     # ---- engine plumbing -----------------------------------------------------------------------------------
     def _make_engine(self, game_id, n_slots, sims, **kw):
         kw.setdefault('launch', self._search_launch())
+        self._search_cache_kw(kw)
         return _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
                            evaluator=_lib.EVAL_NET, c_puct=float(self.ExplorationRate), noise_on=True,
                            alpha=float(self.alpha), epsilon=float(self.epsilon),
@@ -406,8 +407,9 @@ class Model(MCTS, Network):
             eng = self._batch_engine = None
         if eng is None:
             n_slots, _per_slot = _lib.fit_slots(self.Game.GAME_ID, want, int(self.PlayLimit), max_games=n_games)
-            # (self-play keeps its own launch structure: SearchLaunch is about the search API's engines)
-            eng = self._make_engine(self.Game.GAME_ID, n_slots, self.PlayLimit, max_games=n_games, launch=_lib.LAUNCH_AUTO)
+            # (self-play keeps its own launch structure: SearchLaunch / SearchEvalCache are about the search API's engines)
+            eng = self._make_engine(self.Game.GAME_ID, n_slots, self.PlayLimit, max_games=n_games, launch=_lib.LAUNCH_AUTO,
+                                    search_cache=False)
             eng.load_weights(W.flatten(self._ensure_weights(eng.info.C)))
             eng._want = want
             self._batch_engine = eng

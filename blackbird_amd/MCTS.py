@@ -135,6 +135,10 @@ class MCTS(object):
     # most 8 blocks; any other engine searches lock-step and Engine.run_sims_structure() says so).  The same trees bit for bit
     # either way.
     SearchLaunch = 'lockstep'
+    # With SearchLaunch = 'wave': those engines also probe the evaluation cache before the network and store what they evaluate
+    # (bb_config.search_cache; network engines of Connect4 and DragonChess, nothing happens elsewhere).  The same trees bit for
+    # bit, fewer tower runs: Engine.counters() reports eval_cache_hits / eval_cache_probes.  Self-play engines are not concerned.
+    SearchEvalCache = False
 
     def __init__(self, explorationRate, timeLimit=None, playLimit=None, **kwargs):
         self.TimeLimit = timeLimit
@@ -158,8 +162,17 @@ class MCTS(object):
             return _lib.LAUNCH_WAVE
         raise ValueError("SearchLaunch must be 'lockstep' or 'wave', not {!r}".format(self.SearchLaunch))
 
+    def _search_cache_kw(self, kw):
+        """search_cache=True for a search engine when SearchEvalCache is set (left out otherwise: the engine's default)."""
+        if not isinstance(self.SearchEvalCache, bool):
+            raise ValueError("SearchEvalCache must be True or False, not {!r}".format(self.SearchEvalCache))
+        if self.SearchEvalCache:
+            kw.setdefault('search_cache', True)
+        return kw
+
     def _make_engine(self, game_id, n_slots, sims, **kw):
         kw.setdefault('launch', self._search_launch())
+        self._search_cache_kw(kw)
         return _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
                            max_depth=self._max_depth(), evaluator=self._EVALUATOR, c_puct=float(self.ExplorationRate),
                            seed=_seed_from_numpy(), **kw)

@@ -52,7 +52,8 @@ class Config(C.Structure):
                 ("max_games", C.c_int32), ("c_puct", C.c_double), ("seed", C.c_uint64), ("hash_salt", C.c_uint64),
                 ("first_game_id", C.c_uint32), ("noise_on", C.c_int32), ("alpha", C.c_float), ("epsilon", C.c_float),
                 ("device", C.c_int32), ("salt_per_game", C.c_int32), ("node_capacity", C.c_int32),
-                ("net_form", C.c_int32), ("launch", C.c_int32), ("general_net", C.c_int32), ("track_ancestors", C.c_int32)]
+                ("net_form", C.c_int32), ("launch", C.c_int32), ("general_net", C.c_int32), ("track_ancestors", C.c_int32),
+                ("search_cache", C.c_int32)]
 
 
 class Counters(C.Structure):
@@ -364,9 +365,11 @@ class Engine:
     def __init__(self, game, n_slots, sims_per_move, *, mcts_kind=MCTS_DYNAMIC, max_depth=10, evaluator=EVAL_NET,
                  c_puct=0.85, max_plies=None, max_games=None, seed=1234, hash_salt=0, first_game_id=0,
                  noise_on=False, alpha=0.2, epsilon=0.3, device=0, salt_per_game=False, node_capacity=0,
-                 net_form=0, launch=0, general_net=False, track_ancestors=False):
+                 net_form=0, launch=0, general_net=False, track_ancestors=False, search_cache=False):
         """net_form: NET_FORM_AUTO / NET_FORM_F32 / NET_FORM_SPLIT (bb_config.net_form); launch: LAUNCH_AUTO / LAUNCH_LOCKSTEP /
-        LAUNCH_ROUNDS / LAUNCH_WAVE (bb_config.launch; LAUNCH_WAVE is the search API's opt-in: run_sims_structure); general_net: a 16-filter network through the launch-per-layer kernels."""
+        LAUNCH_ROUNDS / LAUNCH_WAVE (bb_config.launch; LAUNCH_WAVE is the search API's opt-in: run_sims_structure); general_net: a 16-filter network through the launch-per-layer kernels;
+        search_cache: run_sims probes and fills the engine's evaluation cache where it searches in one launch with a network
+        (bb_config.search_cache: same trees, fewer tower runs; bb_create refuses anything but 0 / 1)."""
         self.game = game
         self.info = game_info(game)
         if max_plies is None:
@@ -376,7 +379,7 @@ class Engine:
                      seed=seed, hash_salt=hash_salt, first_game_id=first_game_id, noise_on=int(noise_on), alpha=alpha,
                      epsilon=epsilon, device=device, salt_per_game=int(salt_per_game), node_capacity=node_capacity,
                      net_form=int(net_form), launch=int(launch), general_net=int(bool(general_net)),
-                     track_ancestors=int(bool(track_ancestors)))
+                     track_ancestors=int(bool(track_ancestors)), search_cache=int(search_cache))
         self.cfg = cfg
         self.h = C.c_void_p()
         self.n_slots = n_slots

@@ -105,9 +105,17 @@ struct Launch {
     static void tree_step(const TreeDev &d, const DCEdges &, hipStream_t st) { k_tree_step<G><<<nblk((size_t)((d.n_slots + d.gpw - 1) / d.gpw) * 64), 256, 0, st>>>(d); }
     static void tree_apply(const TreeDev &d, const DCEdges &, hipStream_t st) { k_tree_apply<G><<<nblk((size_t)d.n_slots * G::S), 256, 0, st>>>(d); }
     // BB_LAUNCH_WAVE: `sims` steps of tree_step + the evaluator, and tree_apply, as one launch with a wave per slot (search_wave.hip.h);
-    // x3 with operands: the 16-filter network, else the hash evaluator.  false: this family has no such kernel.
-    static bool search_wave(const TreeDev &d, const DCEdges &, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int noise) {
+    // x3 with operands: the 16-filter network, else the hash evaluator.  cache (run_sims_api: bb_config.search_cache on an engine that
+    // owns a table): the network's instantiation that probes and fills d.eval_cache, for a game with a one-word key.
+    // false: this family has no such kernel.
+    static bool search_wave(const TreeDev &d, const DCEdges &, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int noise, bool cache) {
         const int blocks = (d.n_slots + SW_WAVES - 1) / SW_WAVES;
+        if constexpr (G::CACHE_KEY) {
+            if (x3.w0 && cache && d.eval_cache) {
+                k_search_wave<G, true, true><<<blocks, 64 * SW_WAVES, 0, st>>>(d, nd, x3, sims, noise);
+                return true;
+            }
+        }
         if (x3.w0) k_search_wave<G, true><<<blocks, 64 * SW_WAVES, 0, st>>>(d, nd, x3, sims, noise);
         else k_search_wave<G, false><<<blocks, 64 * SW_WAVES, 0, st>>>(d, nd, x3, sims, 0);
         return true;
@@ -144,9 +152,11 @@ struct Launch<DragonChess> {
     static void tree_apply(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_tree_apply<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
     // (search_structure sends the wide game here with a 16-filter split-operand network that fits the kernel's LDS, and nothing else;
     // its prior noise is mixed in at expansion: E.noise_on)
-    static bool search_wave(const TreeDev &d, const DCEdges &E, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int) {
+    static bool search_wave(const TreeDev &d, const DCEdges &E, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int, bool cache) {
         if (!x3.w0 || nd.R > DC_RMAX || nd.head_floats > DC_HEAD_FLOATS) return false;
-        k_dc_search_wave<<<(d.n_slots + SW_WAVES - 1) / SW_WAVES, 64 * SW_WAVES, 0, st>>>(d, E, nd, x3, sims);
+        const int blocks = (d.n_slots + SW_WAVES - 1) / SW_WAVES;
+        if (cache && d.eval_cache) k_dc_search_wave_cached<<<blocks, 64 * SW_WAVES, 0, st>>>(d, E, nd, x3, sims);
+        else k_dc_search_wave<<<blocks, 64 * SW_WAVES, 0, st>>>(d, E, nd, x3, sims);
         return true;
     }
     static void hash(hipStream_t st, int n, const State *s, const uint32_t *game_id, uint64_t salt, int salt_per_game, uint32_t first_game_id, float *value, float *policy, int pstride) {
@@ -433,17 +443,22 @@ static void make_views(bb_engine *e) {
 // probes it in the persistent kernel (mega2.hip.h) and in the
 // asynchronous rounds that any other network or BB_LAUNCH_ROUNDS runs as (eval_probe.hip.h); DragonChess in its
 // one-wave-per-game kernel (mega_dc.hip.h, 128-byte entries; default 2^24: 2 GiB, ~16 M positions against the ~0.4 M a ply
-// of 1024 games evaluates, next to pools of ~190 GB).  The lock-step search does not.  BB_EVAL_CACHE=0 turns it off,
+// of 1024 games evaluates, next to pools of ~190 GB).  The search API (bb_run_sims / bb_run_sims_masked) probes it in its one-launch
+// structure when the engine asks for both (bb_config.launch = BB_LAUNCH_WAVE with search_cache = 1, a network evaluator, Connect4 or
+// DragonChess: search_wave.hip.h, search_wave_dc.hip.h) -- such an engine plays self-play in lock-step, so without search_cache it owns
+// no table, as before; the lock-step search never probes.  BB_EVAL_CACHE=0 turns it off,
 // BB_EVAL_CACHE_LOG2 sizes it -- tuning knobs, read from the environment at bb_create / bb_fit_slots.
 static size_t eval_cache_entry_bytes(const bb_config *cfg) { return cfg->game == BB_GAME_DRAGONCHESS ? 128 : 64; }
 static int eval_cache_log2_of(const bb_config *cfg) {
     // THE rule of who owns a table: a configuration whose structure probes one.  (TicTacToe has no key: games.hip.h CACHE_KEY.)
     const bool c4 = cfg->game == BB_GAME_CONNECT4;
-    switch (selfplay_plan(cfg)) {
+    const bool search_probes = cfg->search_cache == 1 && cfg->launch == BB_LAUNCH_WAVE && cfg->evaluator == BB_EVAL_NET &&
+                               (c4 || cfg->game == BB_GAME_DRAGONCHESS); // (whether the loaded network has a one-launch search: search_structure)
+    if (!search_probes) switch (selfplay_plan(cfg)) {
     case PLAY_DC_FUSED: break;                                                // mega_dc.hip.h
     case PLAY_QUEUE: if (!c4) return 0; break;                                // mega2.hip.h, and the rounds of a network that does not fit it
     case PLAY_ROUNDS: if (!c4 || cfg->evaluator != BB_EVAL_NET) return 0; break; // eval_probe.hip.h (the hash evaluator's rounds probe nothing)
-    default: return 0;                                                        // the lock-step search does not
+    default: return 0;                                                        // lock-step self-play does not
     }
     const char *on = getenv("BB_EVAL_CACHE"), *lg = getenv("BB_EVAL_CACHE_LOG2");
     if (on && atoi(on) == 0) return 0;
@@ -483,6 +498,7 @@ static int check_config(const bb_config *cfg) {
     if (cfg->mcts_kind == BB_MCTS_FIXED && cfg->max_depth <= 0)
         return fail(BB_ERR_ARG, "MaxDepth for MCTS must be > 0."); // FixedMCTS.py:15-16
     if (cfg->sims_per_move < 0 || cfg->max_plies <= 0) return fail(BB_ERR_ARG, "bad sims_per_move/max_plies");
+    if (cfg->search_cache != 0 && cfg->search_cache != 1) return fail(BB_ERR_ARG, "bb_config.search_cache must be 0 or 1");
     int ndev = bb_device_count();
     if (ndev <= 0) return fail(BB_ERR_HIP, "no HIP device available (this library has no CPU fallback)");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(BB_ERR_ARG, "device %d out of range", cfg->device);
@@ -1327,7 +1343,8 @@ static int run_sims_api(bb_engine *e, int sims, const uint8_t *mask) {
         if (wave) { // every simulation of every slot, and the last leaf's apply, in one launch
             const bool net = e->cfg.evaluator == BB_EVAL_NET;
             rc = timed_launch(e, e->stream, TIME_EACH, [&]() -> int {
-                if (!Launch<G>::search_wave(e->dev, e->edges, e->stream, sims, e->net, net ? e->x3 : NetX3{nullptr, nullptr, nullptr, nullptr, nullptr}, e->cfg.noise_on))
+                if (!Launch<G>::search_wave(e->dev, e->edges, e->stream, sims, e->net, net ? e->x3 : NetX3{nullptr, nullptr, nullptr, nullptr, nullptr}, e->cfg.noise_on,
+                                            e->cfg.search_cache != 0))
                     return fail(BB_ERR_STATE, "no one-launch search for this game");
                 return BB_OK;
             });

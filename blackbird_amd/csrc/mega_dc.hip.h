@@ -34,10 +34,12 @@ __device__ __attribute__((noinline)) void dc_fused_tree(const TreeDev &d_, const
 // the leaf back from d.evals, which counts tower runs (the select phase counted the leaf when it posted it).  The probe
 // cannot start earlier: the tree phases are out-of-line functions, and a call returns only once its memory requests are
 // back.  Both network forms call it first thing (dc_fused_net, dc_fused_net_x3); net_body / net_body_x3 are unchanged.
-__device__ __forceinline__ int dc_fused_probe(const TreeDev &d, int g, DCHeadLocal *hl, int lane) {
+// (dc_leaf_probe / dc_leaf_store: the same for a leaf the caller names -- `leaf` in LDS -- which is how the one-launch search,
+// search_wave_dc.hip.h, whose mailbox stays in HBM, shares them.)
+__device__ __forceinline__ int dc_leaf_probe(const TreeDev &d, const DCState *leaf, int g, DCHeadLocal *hl, int lane) {
     const EvalCache c = {(u32x4 *)d.eval_cache, d.eval_cache_log2};
     if (!c.tab) return -1;
-    const DCKey key = DragonChess::cache_key_wave(as_lds((const DCState *)d.leaf_state)[g], lane);
+    const DCKey key = DragonChess::cache_key_wave(*leaf, lane);
     if (key.none()) return -1;
     const uint64_t tag = key.tag();
     WideHead h;
@@ -49,13 +51,19 @@ __device__ __forceinline__ int dc_fused_probe(const TreeDev &d, int g, DCHeadLoc
     __threadfence_block();
     return 1;
 }
+__device__ __forceinline__ int dc_fused_probe(const TreeDev &d, int g, DCHeadLocal *hl, int lane) {
+    return dc_leaf_probe(d, &as_lds((const DCState *)d.leaf_state)[g], g, hl, lane);
+}
 // A miss: the entry of the evaluation just made, fire and forget (the key again from the leaf: nothing of the probe is
 // held in registers through the network).
-__device__ __forceinline__ void dc_fused_store(const TreeDev &d, int g, const DCHeadLocal *hl, int lane) {
+__device__ __forceinline__ void dc_leaf_store(const TreeDev &d, const DCState *leaf, const DCHeadLocal *hl, int lane) {
     const EvalCache c = {(u32x4 *)d.eval_cache, d.eval_cache_log2};
-    const DCKey key = DragonChess::cache_key_wave(as_lds((const DCState *)d.leaf_state)[g], lane);
+    const DCKey key = DragonChess::cache_key_wave(*leaf, lane);
     const uint64_t tag = key.tag();
     dc_eval_cache_put(dc_eval_cache_entry(c, tag), key, tag, hl->h, lane);
+}
+__device__ __forceinline__ void dc_fused_store(const TreeDev &d, int g, const DCHeadLocal *hl, int lane) {
+    dc_leaf_store(d, &as_lds((const DCState *)d.leaf_state)[g], hl, lane);
 }
 
 // The network for the wave's own leaf.  Nothing 4032-wide leaves the wave: the policy head is reduced to (R0, R1, max,

@@ -35,15 +35,26 @@ __device__ __forceinline__ void sw_hash_eval(const TreeDev &d, int g, int lane) 
 }
 
 // NET: the 16-filter network in the split-operand form (x3.w0 set); else the hash evaluator.
-template <class G, bool NET>
+// CACHE (bb_config.search_cache, an engine that owns a table; Connect4 with NET): the leaf's entry of the engine's evaluation cache
+// (net.hip.h) is requested before the network's prologue and tested after it, as in the persistent self-play kernel (mega2.hip.h).  A
+// hit runs only dense_prior_tail on the cached value and pre-noise priors, with the node's own noise key (game id, node serial,
+// action), so it leaves in the mailbox the bits the tower would have; a miss stores from head_one into the way the probe picked.
+// d.evals keeps counting tower runs: phase_select counted the leaf when it posted it, a hit takes it back.  The wave counts its
+// probes and hits in registers and adds them to the engine's counters once, from one lane.  Two waves that evaluate one position at
+// the same time both miss and both store the same bits (the entry protocol of net.hip.h): nobody waits for anybody.
+template <class G, bool NET, bool CACHE = false>
 __global__ void __launch_bounds__(64 * SW_WAVES) k_search_wave(TreeDev d, NetDev nd, NetX3 x3, int sims, int noise) {
     using XG = X3Geom<G>;
     constexpr int S = G::S;
+    static_assert(!CACHE || (NET && G::CACHE_KEY), "the evaluation cache: the network's evaluations of a game with a one-word key");
     __shared__ __attribute__((aligned(16))) unsigned char lds[NET ? SW_WAVES * XG::WAVE_BYTES : 16];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int g = blockIdx.x * SW_WAVES + wave;
     if (g >= d.n_slots) return; // (whole waves leave: nothing below synchronises the workgroup)
     const bool tree_lane = lane < S;
+    unsigned n_probes = 0, n_hits = 0; // (CACHE) this wave's call
+    (void)n_probes;
+    (void)n_hits;
     for (int s = 0; s < sims; s++) { // the lock-step loop's `sims` steps, for this slot
         if (tree_lane) {
             phase_apply<G>(d, g, lane);
@@ -53,7 +64,17 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_search_wave(TreeDev d, NetDev
         __threadfence_block(); // lane 0's mailbox stores before the other lanes' loads
         // (uniform) no leaf posted: the slot is idle, masked out or out of simulations, and every further step is a no-op
         if (__builtin_amdgcn_readfirstlane(d.pend_leaf[g]) < 0) break;
-        if constexpr (NET)
+        if constexpr (CACHE) {
+            int probe = -1;
+            net_body_x3<G, false, false, true>(nd, x3, g + 1, g, nullptr, lds + wave * XG::WAVE_BYTES, (const typename G::State *)d.leaf_state, nullptr,
+                                               d.leaf_game_id, d.leaf_serial, noise, d.eval_value, nullptr, d.eval_policy, S, true, nullptr,
+                                               EvalCache{(u32x4 *)d.eval_cache, d.eval_cache_log2}, &probe);
+            n_probes += probe >= 0;
+            if (probe > 0) {
+                n_hits++;
+                if (lane == 0) d.evals[g] -= 1;
+            }
+        } else if constexpr (NET)
             net_body_x3<G, false>(nd, x3, g + 1, g, nullptr, lds + wave * XG::WAVE_BYTES, (const typename G::State *)d.leaf_state, nullptr,
                                   d.leaf_game_id, d.leaf_serial, noise, d.eval_value, nullptr, d.eval_policy, S, true);
         else
@@ -61,4 +82,10 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_search_wave(TreeDev d, NetDev
         __threadfence_block(); // the evaluation is in the mailbox before phase_apply reads it
     }
     if (tree_lane) phase_apply<G>(d, g, lane); // the last simulation's evaluation (no-op without a pending leaf)
+    if constexpr (CACHE) {
+        if (lane == 0 && n_probes && d.eval_cache_ctr) {
+            atomicAdd(&d.eval_cache_ctr[0], (unsigned long long)n_hits);
+            atomicAdd(&d.eval_cache_ctr[1], (unsigned long long)n_probes);
+        }
+    }
 }

@@ -3,8 +3,8 @@
 // What search_wave.hip.h is for the dense games, in the shape k_dc_selfplay_fused (mega_dc.hip.h) gives the wide one: a wave keeps its
 // slot for the whole call -- dc_phase_apply (with the ancestor walk: FindMove engines track their ancestors) -> dc_phase_select -> the
 // network for its own leaf on the bf16 matrix pipe -> ..., `sims` times, then the pending evaluation is applied (what k_dc_tree_apply
-// does for the lock-step loop), so nothing outlives the launch.  No move kernel, no pool of simulations, no evaluation-cache probe
-// (search engines own no table).  Nothing 4032-wide leaves the wave: the policy head is reduced to five numbers (WideHead) in LDS and
+// does for the lock-step loop), so nothing outlives the launch.  No move kernel, no pool of simulations; the evaluation-cache probe is
+// the CACHE instantiation (bb_config.search_cache, below).  Nothing 4032-wide leaves the wave: the policy head is reduced to five numbers (WideHead) in LDS and
 // the expansion forms the priors of the legal moves only, from the head weights in LDS -- the same operations on the same inputs
 // as the 16 KB row k_net_x3 writes and dc_expand gathers from, so the same bits (tests/test_gpu_search_wave_dc.py; the self-play
 // kernel is held to that by tests/test_gpu_mcts.py).  No wave waits for another: no spin, every loop is bounded by `sims`.
@@ -59,9 +59,29 @@ __device__ __forceinline__ void dc_sw_net(const NetDev &nd_, const NetX3 &x3_, c
                                           DragonChess::A, true, &hl->h);
     __threadfence_block();
 }
+// The same behind the evaluation cache (bb_config.search_cache, an engine that owns a table; what dc_fused_net_x3 is to the
+// self-play kernel): the leaf's entry is probed first, with the key formed from the wave's LDS copy of the leaf (dc_leaf_probe,
+// mega_dc.hip.h).  A hit puts the cached WideHead in hl->h, takes the leaf back from d.evals and skips the network; a miss stores
+// the WideHead the network leaves.  The entry is pre-noise, as in self-play: a wide game's prior noise is mixed in at expansion.
+// Returns what dc_leaf_probe does: -1 no probe (a state without a key), 0 miss, 1 hit.
+__device__ __forceinline__ int dc_sw_net_cached(const NetDev &nd_, const NetX3 &x3_, const TreeDev &d_, int g, const DCState *leaf, const int *slot,
+                                                float *nl, DCHeadLocal *hl) {
+    const TreeDev &d = *as_lds(&d_);
+    const DCState *mine = as_lds(leaf) + *as_lds(slot);
+    const int lane = threadIdx.x & 63;
+    const int probe = dc_leaf_probe(d, mine, g, as_lds(hl), lane);
+    if (probe > 0) return probe;
+    dc_sw_net(nd_, x3_, leaf, slot, nl, hl);
+    if (probe == 0) {
+        dc_leaf_store(d, mine, as_lds(hl), lane);
+        __threadfence_block();
+    }
+    return probe;
+}
 
 // host: 16-filter network in the split-operand form, nd.R <= DC_RMAX, nd.head_floats <= DC_HEAD_FLOATS (search_structure)
-__global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave(TreeDev d_arg, DCEdges E_arg, NetDev nd_arg, NetX3 x3_arg, int sims) {
+template <bool CACHE>
+__device__ __forceinline__ void dc_search_wave_body(const TreeDev &d_arg, const DCEdges &E_arg, const NetDev &nd_arg, const NetX3 &x3_arg, int sims) {
     // the tree's scratch (the 4032-float policy image) and the network's activations are never live together
     constexpr int TREE_BYTES = DC_LDS_FLOATS * 4, NET_BYTES = X3Geom<DragonChess>::WAVE_BYTES_PP;
     constexpr int WAVE_BYTES = ((TREE_BYTES > NET_BYTES ? TREE_BYTES : NET_BYTES) + 15) / 16 * 16;
@@ -103,10 +123,32 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave(TreeDev d_arg,
     // (no leaf is pending on entry: every entry point that searches -- this kernel, the lock-step loop, the self-play structures --
     // applies its last evaluation before it returns)
     bool pending = false;
+    [[maybe_unused]] unsigned n_probes = 0, n_hits = 0; // (CACHE) this wave's call: one counter update at the end
     for (int s = 0; s < sims; s++) { // the lock-step loop's `sims` steps, for this slot
         pending = dc_sw_tree(s_d, s_E, g, lane, tl, hl, &s_leaf[wv]) >= 0;
         if (!pending) break; // (uniform) no game or no simulations left: every further step is a no-op (see the head of this file)
-        dc_sw_net(s_nd, s_x3, s_leaf, &myslot[wv], tl, hl);
+        if constexpr (CACHE) {
+            const int probe = dc_sw_net_cached(s_nd, s_x3, s_d, g, s_leaf, &myslot[wv], tl, hl);
+            n_probes += probe >= 0;
+            n_hits += probe > 0;
+        } else
+            dc_sw_net(s_nd, s_x3, s_leaf, &myslot[wv], tl, hl);
     }
     if (pending) dc_sw_apply(s_d, s_E, g, lane, tl, hl); // the last simulation's evaluation
+    if constexpr (CACHE) {
+        if (lane == 0 && n_probes && d_arg.eval_cache_ctr) {
+            atomicAdd(&d_arg.eval_cache_ctr[0], (unsigned long long)n_hits);
+            atomicAdd(&d_arg.eval_cache_ctr[1], (unsigned long long)n_probes);
+        }
+    }
+}
+// (Two kernels that call the same out-of-line phases: beside the second one, the first is compiled with one spilled scalar register
+// where alone it has none; every other figure of it is unchanged.  Copies of the phases per kernel -- plain or as template instances --
+// cost both kernels two accumulator registers and 8 bytes of scratch instead.)
+__global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave(TreeDev d_arg, DCEdges E_arg, NetDev nd_arg, NetX3 x3_arg, int sims) {
+    dc_search_wave_body<false>(d_arg, E_arg, nd_arg, x3_arg, sims);
+}
+// ... behind the evaluation cache (bb_config.search_cache, an engine that owns a table)
+__global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave_cached(TreeDev d_arg, DCEdges E_arg, NetDev nd_arg, NetX3 x3_arg, int sims) {
+    dc_search_wave_body<true>(d_arg, E_arg, nd_arg, x3_arg, sims);
 }

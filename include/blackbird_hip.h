@@ -138,6 +138,12 @@ typedef struct {
                               max_plies + 2 of them) and back every simulation of bb_run_sims up through it, as the reference's
                               _backProp does (MCTS.py:238-258) -- what MCTS.ResetRoot (:214-225) needs.  Every game; DragonChess
                               self-play refuses such an engine (BB_ERR_STATE) */
+    int32_t search_cache;  /* 1: bb_run_sims / bb_run_sims_masked probe the engine's evaluation cache before the network, answer hits
+                              from it and store misses -- where they search through BB_LAUNCH_WAVE with a network (bb_run_sims_structure)
+                              and the game has a cache key (Connect4, DragonChess); the engine then owns a table (sized by
+                              BB_EVAL_CACHE_LOG2, none with BB_EVAL_CACHE=0), cleared at every bb_load_weights.  Trees, moves and node rows are
+                              unchanged bit for bit; only the evals / eval_cache_* counters differ.  Everywhere else the flag is
+                              accepted and nothing is probed.  0 (default): no probe.  Any other value: BB_ERR_ARG */
 } bb_config;
 
 /* bb_config.net_form */
@@ -151,7 +157,8 @@ typedef struct {
 #define BB_LAUNCH_ROUNDS 2   /* asynchronous rounds: k_tree_async + a compacted network launch (dense games) */
 #define BB_LAUNCH_WAVE 3     /* bb_run_sims / bb_run_sims_masked in ONE launch, one wave per slot (bb_run_sims_structure says where it
                                 applies: Connect4, TicTacToe, and DragonChess with a 16-filter network of at most 8 blocks);
-                                bb_selfplay_step treats it as BB_LAUNCH_LOCKSTEP */
+                                bb_selfplay_step treats it as BB_LAUNCH_LOCKSTEP.  With bb_config.search_cache that launch also
+                                probes the evaluation cache */
 
 typedef struct bb_engine bb_engine;
 
@@ -164,9 +171,10 @@ typedef struct {
     uint64_t plies;           /* moves played in self-play */
     uint64_t overflow;        /* simulations cut short by pool/path limits (must be 0) */
     uint64_t examples;        /* examples stored */
-    uint64_t evals;           /* network tower runs (< sims when known terminal values are reused; evaluation-cache hits not included) */
-    uint64_t eval_cache_hits;   /* evaluations served by the evaluation cache: Connect4 self-play in the persistent kernel and in asynchronous rounds (any network, BB_LAUNCH_ROUNDS), one-wave-per-game DragonChess self-play; the lock-step search (bb_run_sims) does not probe */
-    uint64_t eval_cache_probes; /* evaluations that looked it up: hits + the tower runs among them */
+    uint64_t evals;           /* network tower runs (< sims when known terminal values are reused; evaluation-cache hits not included,
+                                 in self-play and in a bb_run_sims that probes alike) */
+    uint64_t eval_cache_hits;   /* evaluations served by the evaluation cache: Connect4 self-play in the persistent kernel and in asynchronous rounds (any network, BB_LAUNCH_ROUNDS), one-wave-per-game DragonChess self-play, and the one-launch search (bb_run_sims with BB_LAUNCH_WAVE and bb_config.search_cache); the lock-step search does not probe */
+    uint64_t eval_cache_probes; /* evaluations that looked it up: hits + the tower runs among them (a search that probes: probes == evals + hits) */
 } bb_counters;
 
 /* bb_create fails with BB_ERR_CAPACITY (before allocating anything) when the pools of cfg->n_slots games -- sized for the

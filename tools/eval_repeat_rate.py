@@ -11,7 +11,15 @@ shared by 4096 concurrent Connect4 games / 1024 DragonChess games).
              plays ~30 plies a minute there, so --plies caps every game (default 40).  The noise is drawn for the legal
              moves only (the priors are renormalised over them anyway; only their rounding differs from the oracle's own).
 
-usage: python tools/eval_repeat_rate.py [games] [sims] [--game c4|dc] [--plies N]
+  --search: the search API instead (bb_config.search_cache: the evaluation cache of the one-launch search).  The share of ALL
+             leaf evaluations (a node evaluated again counts again: the search probes every leaf it posts) whose position was
+             evaluated before, in two cases: ONE GAME played through by FindMove with tree reuse, table empty at the first
+             move (game 0 alone), and an ARENA of `games` games (default 64) from the start position on one table.  The
+             oracle plays each game move by move with tree reuse, which is FindMove + MoveRoot; its arena stand-in is one
+             network playing both sides, where a real arena has two engines that each search every other ply with a table
+             of their own -- a real side sees fewer of a game's positions, so its share is at most the one reported.
+
+usage: python tools/eval_repeat_rate.py [games] [sims] [--game c4|dc] [--plies N] [--search]
 """
 import argparse
 import ctypes as C
@@ -38,7 +46,10 @@ def main():
     ap.add_argument("sims", type=int, nargs="?", default=None)
     ap.add_argument("--game", choices=sorted(GAMES), default="c4")
     ap.add_argument("--plies", type=int, default=None, help="ply cap of every game")
+    ap.add_argument("--search", action="store_true", help="the search API: one FindMove game, and an arena of `games` games")
     args = ap.parse_args()
+    if args.search and len([x for x in sys.argv[1:] if not x.startswith("-") and x.isdigit()]) == 0:
+        args.games = 64
     game, H, Wd, Cc, A, sims, plies = GAMES[args.game]
     sims = args.sims or sims
     plies = args.plies or plies
@@ -88,6 +99,11 @@ def main():
         print("game %3d: %3d plies, %5d first visits, repeats: same game %.3f, with the %d earlier games %.3f"
               % (g, o["n"] - 1, n, same / max(n, 1), g, shared / max(n, 1)), flush=True)
     a = np.array(rows, dtype=np.float64)
+    if args.search:
+        print("search API, %s at %d simulations: one FindMove game (%d evaluations) repeat share %.3f; arena of %d games on one "
+              "table (%d evaluations) repeat share %.3f"
+              % (args.game, sims, a[0, 3], a[0, 4] / max(a[0, 3], 1), args.games, a[:, 3].sum(), a[:, 4].sum() / a[:, 3].sum()))
+        return
     print("all %d games: first visits / simulations %.3f, repeats: same game %.3f, shared table %.3f; "
           "every evaluation (first visits or not): %d, repeats %.3f"
           % (args.games, a[:, 0].sum() / max(sims_total, 1), a[:, 1].sum() / a[:, 0].sum(), a[:, 2].sum() / a[:, 0].sum(),
