@@ -17,6 +17,7 @@
 #include "search_wave_dc.hip.h"
 #include "examples.hip.h"
 #include "train.hip.h"
+#include "net_pack.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -694,39 +695,15 @@ extern "C" int bb_synchronize(bb_engine *e) {
     return BB_OK;
 }
 
-// ---- weights: fold BN, swizzle into MFMA operand order, upload ---------------------------------------
-static void bn_fold(const float *bn, int F, float *scale, float *shift) {
-    for (int f = 0; f < F; f++) {
-        float g = bn[0 * F + f], b = bn[1 * F + f], m = bn[2 * F + f], v = bn[3 * F + f];
-        float s = g / sqrtf(v + 1e-3f); // tf.layers.batch_normalization default epsilon
-        float t = m * s;
-        scale[f] = s;
-        shift[f] = b - t;
-    }
+// ---- weights: pack on the host (net_pack.h), keep or reallocate the operand buffers, upload ---------------------------
+static_assert(GNET_X3_BLOCK * 2 == GX3_PAIR_B, "net_pack.h and gnet_x3.hip.h must agree on the tower's weight block");
+template <class T>
+static int upload(void *dst, const std::vector<T> &v) {
+    if (!v.empty()) HIPCHK(hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return BB_OK;
 }
 
-
-// ---- general-F network (gnet.hip.h): operand layouts, buffers, launch sequence -----------------------------------
-// ---- operands of net_x3.hip.h: every weight as three bf16 planes (w = w1 + w2 + w3 exactly), in A-operand lane order ----
-static uint16_t bf16_rne(float v) {
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static float bf16_value(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-static void bf16_split3(float v, uint16_t out[3]) {
-    out[0] = bf16_rne(v);
-    float r = v - bf16_value(out[0]);
-    out[1] = bf16_rne(r);
-    r = r - bf16_value(out[1]);
-    out[2] = bf16_rne(r);
-}
+// ---- general-F network (gnet.hip.h): buffers, weights, launch sequence -------------------------------------------------
 template <class G>
 static int gnet_reserve(bb_engine *e, int n) {
     using GG = GNetGeom<G>;
@@ -748,38 +725,12 @@ static int gnet_reserve(bb_engine *e, int n) {
     return BB_OK;
 }
 
-static int load_general_weights(bb_engine *e, const bb_net_weights *w) {
+// img: pack_f32 at F / 16 filter blocks
+static int load_general_weights(bb_engine *e, const bb_net_weights *w, const NetF32 &img) {
     const int F = w->F, C = w->C, R = w->R, NCB = F / 16;
-    const int steps0 = (9 * C + 3) / 4;
-    std::vector<float> w0((size_t)NCB * steps0 * 64), wt((size_t)2 * R * NCB * 9 * NCB * 64 * 4), epi((size_t)(1 + 2 * R) * NCB * 48);
-    for (int fb = 0; fb < NCB; fb++)
-        for (int s = 0; s < steps0; s++)
-            for (int lane = 0; lane < 64; lane++) {
-                int f = lane & 15, j = lane >> 4, k = 4 * s + j;
-                w0[((size_t)fb * steps0 + s) * 64 + lane] = k < 9 * C ? w->conv0_k[(size_t)k * F + 16 * fb + f] : 0.f;
-            }
-    for (int l = 0; l < 2 * R; l++)
-        for (int fb = 0; fb < NCB; fb++)
-            for (int cb = 0; cb < NCB; cb++)
-                for (int tap = 0; tap < 9; tap++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int r = 0; r < 4; r++) {
-                            int f = lane & 15, j = lane >> 4, c = 16 * cb + 4 * j + r;
-                            wt[((((((size_t)l * NCB + fb) * NCB + cb) * 9 + tap) * 64) + lane) * 4 + r] =
-                                w->blk_k[(((size_t)l * 9 + tap) * F + c) * F + 16 * fb + f];
-                        }
-    std::vector<float> sc(F), sh(F);
-    for (int l = 0; l < 1 + 2 * R; l++) {
-        const float *b = l == 0 ? w->conv0_b : w->blk_b + (size_t)(l - 1) * F;
-        const float *bn = l == 0 ? w->conv0_bn : w->blk_bn + (size_t)(l - 1) * 4 * F;
-        bn_fold(bn, F, sc.data(), sh.data());
-        for (int fb = 0; fb < NCB; fb++) {
-            float *o = &epi[((size_t)l * NCB + fb) * 48];
-            memcpy(o, b + 16 * fb, 64);
-            memcpy(o + 16, sc.data() + 16 * fb, 64);
-            memcpy(o + 32, sh.data() + 16 * fb, 64);
-        }
-    }
+    // the tower layers' operands as three bf16 planes (gnet_x3.hip.h); BB_NET_FORM_F32 keeps the float32-MFMA layers
+    const bool want3 = R > 0 && e->cfg.net_form != BB_NET_FORM_F32;
+    const std::vector<uint16_t> x = want3 ? pack_gnet_x3(w, NCB) : std::vector<uint16_t>();
     GNetDev &g = e->gnet;
     // weights are reloaded after every training step: keep the device buffers (operands and activation scratch) when
     // the network shape is unchanged instead of allocating new ones each time
@@ -791,48 +742,22 @@ static int load_general_weights(bb_engine *e, const bb_net_weights *w) {
         g.NCB = NCB;
         g.R = R;
         e->gnet_C = C;
-        if (dalloc(e, d_w0, w0.size(), false) || dalloc(e, d_wt, wt.size(), false) || dalloc(e, d_epi, epi.size(), false))
+        if (dalloc(e, d_w0, img.w0.size(), false) || dalloc(e, d_wt, img.wt.size(), false) || dalloc(e, d_epi, img.epi.size(), false))
             return BB_ERR_HIP;
     }
     HIPCHK(sync_all(e));
-    HIPCHK(hipMemcpy(d_w0, w0.data(), w0.size() * 4, hipMemcpyHostToDevice));
-    if (!wt.empty()) HIPCHK(hipMemcpy(d_wt, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_epi, epi.data(), epi.size() * 4, hipMemcpyHostToDevice));
+    if (upload(d_w0, img.w0) || upload(d_wt, img.wt) || upload(d_epi, img.epi)) return BB_ERR_HIP;
     g.w0 = d_w0;
     g.wt = (const f32x4 *)d_wt;
     g.epi = d_epi;
-    // the tower layers' operands as three bf16 planes (gnet_x3.hip.h); BB_NET_FORM_F32 keeps the float32-MFMA layers
-    const bool want3 = R > 0 && e->cfg.net_form != BB_NET_FORM_F32;
     if (want3) {
-        static const int slice_taps[4][2] = {{0, 1}, {3, 4}, {6, 7}, {2, 5}};
-        const size_t per = GX3_PAIR_B / 2; // uint16 elements per (fb, cb) block
-        std::vector<uint16_t> x((size_t)2 * R * NCB * NCB * per);
-        uint16_t h[3];
-        for (int l = 0; l < 2 * R; l++)
-            for (int fb = 0; fb < NCB; fb++)
-                for (int cb = 0; cb < NCB; cb++) {
-                    uint16_t *o = x.data() + (((size_t)l * NCB + fb) * NCB + cb) * per;
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int f = lane & 15, gg = lane >> 4;
-                        for (int sl = 0; sl < 4; sl++)
-                            for (int i = 0; i < 8; i++) {
-                                int tap = slice_taps[sl][gg >> 1], c = 16 * cb + 8 * (gg & 1) + i;
-                                bf16_split3(w->blk_k[(((size_t)l * 9 + tap) * F + c) * F + 16 * fb + f], h);
-                                for (int q = 0; q < 3; q++) o[(((size_t)sl * 3 + q) * 64 + lane) * 8 + i] = h[q];
-                            }
-                        for (int i = 0; i < 4; i++) {
-                            bf16_split3(w->blk_k[(((size_t)l * 9 + 8) * F + 16 * cb + 4 * gg + i) * F + 16 * fb + f], h);
-                            for (int q = 0; q < 3; q++) o[(size_t)4 * 3 * 64 * 8 + ((size_t)q * 64 + lane) * 4 + i] = h[q];
-                        }
-                    }
-                }
         unsigned char *d_x = (unsigned char *)e->gx3.wt;
         if (!d_x || x.size() * 2 != e->gx3_bytes) {
             if (dalloc(e, d_x, x.size() * 2 + 16, false)) return BB_ERR_HIP;
             e->gx3_bytes = x.size() * 2;
             g.cap = 0; // (the activation buffers of the other form are re-reserved on the next launch)
         }
-        HIPCHK(hipMemcpy(d_x, x.data(), x.size() * 2, hipMemcpyHostToDevice));
+        if (upload(d_x, x)) return BB_ERR_HIP;
         e->gx3.wt = d_x;
     } else {
         if (e->gx3.wt) g.cap = 0;
@@ -862,141 +787,44 @@ static int launch_gnet(bb_engine *e, int n_max, const int *n_ptr, const int *slo
         if (g.act[1]) g.act[1] += (size_t)buf_offset * pos_floats; // (not allocated when the tower layers run in the split-operand form)
     }
     k_gnet_input<G><<<nblk((size_t)n_max * GG::HW), 256, 0, st>>>(g, n_max, n_ptr, slot_list, states, planes);
-    if (e->gx3.wt) { // tower layers on the bf16 matrix pipe (gnet_x3.hip.h); first conv in float32 MFMA, writing the split form
-        GNetX3 gx = e->gx3;
+    GNetX3 gx = e->gx3; // wt != nullptr: tower layers on the bf16 matrix pipe (gnet_x3.hip.h); first conv in float32 MFMA, writing the split form
+    if (gx.wt) {
         const size_t pos_bytes = (size_t)g.NCB * GG::SLOTS * 96;
         gx.act3[0] += (size_t)buf_offset * pos_bytes;
         gx.act3[1] += (size_t)buf_offset * pos_bytes;
-        const int L = 2 * g.R;
-        if ((long)n_max * g.NCB <= 2048 && !n_ptr) { // small batch: one position x one filter block per wave
-            const int ppw = g.NCB >= 4 ? 4 : (g.NCB >= 2 ? 2 : 1);
-            dim3 grid((n_max + 4 / ppw - 1) / (4 / ppw), (g.NCB + ppw - 1) / ppw);
-            k_gnet_conv<G, true, 1, 1><<<grid, 256, 0, st>>>(g, 0, n_max, n_ptr, nullptr, g.act[0], 0, ppw, gx.act3[0]);
-            for (int l = 0; l < L; l++) {
-                if (l + 1 < L) k_gnet_conv_x3<G, 1, 1, false><<<grid, 256, 0, st>>>(g, gx, 1 + l, n_max, n_ptr, gx.act3[l & 1], gx.act3[(l & 1) ^ 1], nullptr, l & 1, ppw);
-                else k_gnet_conv_x3<G, 1, 1, true><<<grid, 256, 0, st>>>(g, gx, 1 + l, n_max, n_ptr, gx.act3[l & 1], gx.act3[(l & 1) ^ 1], g.act[0], l & 1, ppw);
-            }
-        } else {
-            constexpr int FBW3 = 4;
-            const int fgroups = (g.NCB + FBW3 - 1) / FBW3;               // groups of 4 filter blocks
-            const int gpw = fgroups >= 4 ? 4 : (fgroups >= 2 ? 2 : 1);   // ... per workgroup
-            const int groups = (n_max + GG::PPB - 1) / GG::PPB;          // groups of PPB positions
-            dim3 grid((groups + 4 / gpw - 1) / (4 / gpw), (fgroups + gpw - 1) / gpw);
-            {
-                const int pairs = (g.NCB + GN_FBW - 1) / GN_FBW;
-                const int ppw = pairs >= 4 ? 4 : (pairs >= 2 ? 2 : 1);
-                dim3 grid0((groups + 4 / ppw - 1) / (4 / ppw), (pairs + ppw - 1) / ppw);
-                k_gnet_conv<G, true><<<grid0, 256, 0, st>>>(g, 0, n_max, n_ptr, nullptr, g.act[0], 0, ppw, gx.act3[0]);
-            }
-            for (int l = 0; l < L; l++) {
-                if (l + 1 < L) k_gnet_conv_x3<G, GG::PPB, FBW3, false><<<grid, 256, 0, st>>>(g, gx, 1 + l, n_max, n_ptr, gx.act3[l & 1], gx.act3[(l & 1) ^ 1], nullptr, l & 1, gpw);
-                else k_gnet_conv_x3<G, GG::PPB, FBW3, true><<<grid, 256, 0, st>>>(g, gx, 1 + l, n_max, n_ptr, gx.act3[l & 1], gx.act3[(l & 1) ^ 1], g.act[0], l & 1, gpw);
-            }
-        }
-    } else
-    if ((long)n_max * g.NCB <= 2048 && !n_ptr) {
-        // small batch: one position x one filter block per wave (latency of a lone evaluation: 40 layers x ~25 us
-        // instead of x ~170 us at 256 filters)
-        const int ppw = g.NCB >= 4 ? 4 : (g.NCB >= 2 ? 2 : 1);
-        dim3 grid((n_max + 4 / ppw - 1) / (4 / ppw), (g.NCB + ppw - 1) / ppw);
-        k_gnet_conv<G, true, 1, 1><<<grid, 256, 0, st>>>(g, 0, n_max, n_ptr, nullptr, g.act[0], 0, ppw);
-        for (int l = 0; l < 2 * g.R; l++)
-            k_gnet_conv<G, false, 1, 1><<<grid, 256, 0, st>>>(g, 1 + l, n_max, n_ptr, g.act[l & 1], g.act[(l & 1) ^ 1], l & 1, ppw);
+    }
+    // small batch: one position x one filter block per wave (latency of a lone evaluation: 40 layers x ~25 us
+    // instead of x ~170 us at 256 filters)
+    const bool small = (long)n_max * g.NCB <= 2048 && !n_ptr;
+    constexpr int FBW3 = 4;
+    // a workgroup's four waves take `per` neighbours along y (filter blocks, or groups of FBW of them) and 4 / per along x
+    // (positions, or groups of PPB of them)
+    const int nx = small ? n_max : (n_max + GG::PPB - 1) / GG::PPB;
+    auto cut = [&](int fbw, int &per) {
+        const int ny = small ? g.NCB : (g.NCB + fbw - 1) / fbw;
+        per = ny >= 4 ? 4 : (ny >= 2 ? 2 : 1);
+        return dim3((nx + 4 / per - 1) / (4 / per), (ny + per - 1) / per);
+    };
+    int per0, per;
+    const dim3 grid0 = cut(GN_FBW, per0), grid = cut(gx.wt ? FBW3 : GN_FBW, per); // first convolution, tower
+    auto *conv0 = small ? k_gnet_conv<G, true, 1, 1> : k_gnet_conv<G, true>;
+    conv0<<<grid0, 256, 0, st>>>(g, 0, n_max, n_ptr, nullptr, g.act[0], 0, per0, gx.wt ? gx.act3[0] : nullptr);
+    const int L = 2 * g.R;
+    if (gx.wt) {
+        auto *mid = small ? k_gnet_conv_x3<G, 1, 1, false> : k_gnet_conv_x3<G, GG::PPB, FBW3, false>;
+        auto *last = small ? k_gnet_conv_x3<G, 1, 1, true> : k_gnet_conv_x3<G, GG::PPB, FBW3, true>; // writes float32, for the heads
+        for (int l = 0; l < L; l++)
+            (l + 1 < L ? mid : last)<<<grid, 256, 0, st>>>(g, gx, 1 + l, n_max, n_ptr, gx.act3[l & 1], gx.act3[(l & 1) ^ 1],
+                                                           l + 1 < L ? nullptr : g.act[0], l & 1, per);
     } else {
-    const int pairs = (g.NCB + GN_FBW - 1) / GN_FBW;
-    const int ppw = pairs >= 4 ? 4 : (pairs >= 2 ? 2 : 1); // filter-block pairs per workgroup
-    const int groups = (n_max + GG::PPB - 1) / GG::PPB;    // groups of PPB positions
-    dim3 grid((groups + 4 / ppw - 1) / (4 / ppw), (pairs + ppw - 1) / ppw);
-    k_gnet_conv<G, true><<<grid, 256, 0, st>>>(g, 0, n_max, n_ptr, nullptr, g.act[0], 0, ppw);
-    for (int l = 0; l < 2 * g.R; l++)
-        k_gnet_conv<G, false><<<grid, 256, 0, st>>>(g, 1 + l, n_max, n_ptr, g.act[l & 1], g.act[(l & 1) ^ 1], l & 1, ppw);
+        auto *conv = small ? k_gnet_conv<G, false, 1, 1> : k_gnet_conv<G, false>;
+        for (int l = 0; l < L; l++)
+            conv<<<grid, 256, 0, st>>>(g, 1 + l, n_max, n_ptr, g.act[l & 1], g.act[(l & 1) ^ 1], l & 1, per, nullptr);
     }
     k_gnet_heads<G><<<(n_max + 3) / 4, 256, 0, st>>>(g, e->net, n_max, n_ptr, slot_list, g.act[0], game_id, serial, noise, value,
                                                      logits, policy, pstride, store, planes ? nullptr : states);
     HIPCHK(hipGetLastError());
     return BB_OK;
-}
-
-// w0:   narrow input: [plane][lane][8] (taps 2g, 2g + 1 x 4 input planes), then ONE operand [lane][8] for tap 8: lane group 0
-//       = [w1 | w2] (4 input planes each), group 1 = [w3 | 0], groups 2, 3 zero -- against B = [x | x] that is all three planes
-//       of the tap in one K = 32 product.  Wide input (DragonChess): [tap][plane][lane][8], lane group g = input planes 8g .. 8g + 7
-// wt12: per layer [slice 0..3][plane 0..1][lane][8] (slices = taps (0,1), (3,4), (6,7), (2,5); lane group g: tap g >> 1 of the
-//       slice, channels 8 (g & 1) .. + 7) then tap 8: [plane 0..1][channel half][filter][8] (what both halves of the lane groups read)
-// wt3:  per layer [slice][lane][8] (the third plane alone) then [lane][8] = tap 8's operand [w1 | w3]: lane groups 0, 1 plane 1,
-//       groups 2, 3 plane 3, channels 8 (g & 1) .. + 7
-// wt8:  per layer [3][lane][8]: tap 8's three A operands [w1|w1], [w2|w2], [w1|w3] as 64-lane images (PP form)
-// (tap 8 = three K = 32 products on plane-concatenated operands: [w1|w1].[x1;x2] + [w2|w2].[x1;x2] + [w1|w3].[x3;x1], net_x3.hip.h)
-// wh:   [3][lane][8]: the head convolutions as a 16-filter K = 16 layer -- filter 0 = value conv, 4 and 8 = policy conv, the rest
-//       zero (so that lane groups 0, 1, 2 of the result each hold ONE head's activation) -- in the three operands of tap 8
-static void pack_x3(const bb_net_weights *w, std::vector<uint16_t> &w0, std::vector<uint16_t> &wt12, std::vector<uint16_t> &wt3,
-                    std::vector<uint16_t> &wt8, std::vector<uint16_t> &wh) {
-    const int F = 16, C = w->C, R = w->R;
-    const bool wide = C > 4; // DragonChess: one K = 32 slice per tap, lane group g = input planes 8g .. 8g + 7
-    w0.assign(wide ? (size_t)9 * 3 * 64 * 8 : (size_t)(3 * 64 * 8 + 64 * 8), 0);
-    const size_t per12 = 4 * 2 * 64 * 8 + 2 * 32 * 8, per3 = 4 * 64 * 8 + 64 * 8;
-    wt12.assign((size_t)2 * R * per12, 0);
-    wt3.assign((size_t)2 * R * per3, 0);
-    wt8.assign((size_t)2 * R * 3 * 64 * 8, 0);
-    uint16_t h[3];
-    for (int lane = 0; wide && lane < 64; lane++) {
-        const int f = lane & 15, g = lane >> 4;
-        for (int tap = 0; tap < 9; tap++)
-            for (int i = 0; i < 8; i++) {
-                int ch = 8 * g + i;
-                bf16_split3(ch < C ? w->conv0_k[((size_t)tap * C + ch) * F + f] : 0.f, h);
-                for (int q = 0; q < 3; q++) w0[(((size_t)tap * 3 + q) * 64 + lane) * 8 + i] = h[q];
-            }
-    }
-    for (int lane = 0; !wide && lane < 64; lane++) {
-        const int f = lane & 15, g = lane >> 4;
-        for (int i = 0; i < 8; i++) {
-            int tap = 2 * g + (i >> 2), ch = i & 3;
-            bf16_split3(ch < C ? w->conv0_k[((size_t)tap * C + ch) * F + f] : 0.f, h);
-            for (int q = 0; q < 3; q++) w0[((size_t)q * 64 + lane) * 8 + i] = h[q];
-        }
-        for (int i = 0; i < 8 && g < 2; i++) { // tap 8: k slot i of lane group g = plane 2g + (i >> 2) of input plane i & 3
-            const int q = 2 * g + (i >> 2), ch = i & 3;
-            if (q > 2) continue;
-            bf16_split3(ch < C ? w->conv0_k[((size_t)8 * C + ch) * F + f] : 0.f, h);
-            w0[(size_t)3 * 64 * 8 + (size_t)lane * 8 + i] = h[q];
-        }
-    }
-    wh.assign((size_t)3 * 64 * 8, 0);
-    for (int lane = 0; lane < 64; lane++) {
-        const int f = lane & 15, g = lane >> 4;
-        const int head = f == 0 ? 0 : f == 4 ? 1 : f == 8 ? 2 : -1; // filter rows 0, 4, 8: the first result register of lane groups 0, 1, 2
-        for (int i = 0; i < 8 && head >= 0; i++) {
-            const int ch = 8 * (g & 1) + i;
-            bf16_split3(head == 0 ? w->v_conv_k[ch] : w->p_conv_k[(size_t)ch * 2 + (head - 1)], h);
-            wh[((size_t)0 * 64 + lane) * 8 + i] = h[0];
-            wh[((size_t)1 * 64 + lane) * 8 + i] = h[1];
-            wh[((size_t)2 * 64 + lane) * 8 + i] = g < 2 ? h[0] : h[2];
-        }
-    }
-    static const int slice_taps[4][2] = {{0, 1}, {3, 4}, {6, 7}, {2, 5}};
-    for (int l = 0; l < 2 * R; l++) {
-        uint16_t *o12 = wt12.data() + (size_t)l * per12, *o3 = wt3.data() + (size_t)l * per3;
-        for (int lane = 0; lane < 64; lane++) {
-            const int f = lane & 15, g = lane >> 4;
-            for (int sl = 0; sl < 4; sl++)
-                for (int i = 0; i < 8; i++) {
-                    int tap = slice_taps[sl][g >> 1], ch = 8 * (g & 1) + i;
-                    bf16_split3(w->blk_k[(((size_t)l * 9 + tap) * F + ch) * F + f], h);
-                    for (int q = 0; q < 2; q++) o12[(((size_t)sl * 2 + q) * 64 + lane) * 8 + i] = h[q];
-                    o3[((size_t)sl * 64 + lane) * 8 + i] = h[2];
-                }
-            for (int i = 0; i < 8; i++) { // tap 8, channels 8 (g & 1) .. + 7
-                bf16_split3(w->blk_k[(((size_t)l * 9 + 8) * F + (8 * (g & 1) + i)) * F + f], h);
-                if (g < 2)
-                    for (int q = 0; q < 2; q++) o12[(size_t)4 * 2 * 64 * 8 + (((size_t)q * 2 + g) * 16 + f) * 8 + i] = h[q];
-                const uint16_t a3 = g < 2 ? h[0] : h[2];
-                o3[(size_t)4 * 64 * 8 + (size_t)lane * 8 + i] = a3;
-                wt8[(((size_t)l * 3 + 0) * 64 + lane) * 8 + i] = h[0];
-                wt8[(((size_t)l * 3 + 1) * 64 + lane) * 8 + i] = h[1];
-                wt8[(((size_t)l * 3 + 2) * 64 + lane) * 8 + i] = a3;
-            }
-        }
-    }
 }
 
 extern "C" int bb_load_weights(bb_engine *e, const bb_net_weights *w) {
@@ -1011,106 +839,55 @@ extern "C" int bb_load_weights(bb_engine *e, const bb_net_weights *w) {
     HIPCHK(hipSetDevice(e->cfg.device));
     // no evaluation outlives the weights (or the network form) it was made with
     if (e->eval_cache_bytes) HIPCHK(hipMemsetAsync(e->dev.eval_cache, 0, e->eval_cache_bytes, e->stream));
-    const int F = w->F, C = w->C, R = w->R, D = w->D, A = w->A;
-    const int steps0 = (9 * C + 3) / 4;
+    const int F = w->F, C = w->C, R = w->R;
     e->general_net = F != 16 || e->cfg.general_net != 0;
+    // operands of the fused single-wave tower (net.hip.h): the one-block image; a wider network leaves them zero
+    const NetF32 img = F == 16 ? pack_f32(w, 1) : NetF32(C, R, 1);
     if (e->general_net) {
-        int rc = load_general_weights(e, w);
+        int rc = load_general_weights(e, w, F == 16 ? img : pack_f32(w, F / 16));
         if (rc) return rc;
     }
-    std::vector<float> w0((size_t)steps0 * 64), wt((size_t)2 * R * 9 * 64 * 4), epi((size_t)(1 + 2 * R) * 48);
-    if (F == 16) // operands of the fused single-wave tower (net.hip.h)
-    for (int s = 0; s < steps0; s++)
-        for (int lane = 0; lane < 64; lane++) {
-            int f = lane & 15, j = lane >> 4, k = 4 * s + j;
-            w0[(size_t)s * 64 + lane] = k < 9 * C ? w->conv0_k[(size_t)k * F + f] : 0.f;
-        }
-    if (F == 16)
-    for (int l = 0; l < 2 * R; l++)
-        for (int tap = 0; tap < 9; tap++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int r = 0; r < 4; r++) {
-                    int f = lane & 15, j = lane >> 4, c = 4 * j + r;
-                    wt[(((size_t)l * 9 + tap) * 64 + lane) * 4 + r] = w->blk_k[(((size_t)l * 9 + tap) * F + c) * F + f];
-                }
-    for (int l = 0; F == 16 && l < 1 + 2 * R; l++) {
-        const float *b = l == 0 ? w->conv0_b : w->blk_b + (size_t)(l - 1) * F;
-        const float *bn = l == 0 ? w->conv0_bn : w->blk_bn + (size_t)(l - 1) * 4 * F;
-        memcpy(&epi[(size_t)l * 48], b, F * sizeof(float));
-        bn_fold(bn, F, &epi[(size_t)l * 48 + 16], &epi[(size_t)l * 48 + 32]);
-    }
-    std::vector<float> head;
+    const NetHead head = pack_head(w);
+    // the bf16-pipe form of the same network (every game, 16 filters); BB_NET_FORM_F32 keeps the float32 MFMA path
+    const bool want3 = F == 16 && C <= 32 && !e->general_net && e->cfg.net_form != BB_NET_FORM_F32;
+    const NetX3Image x = want3 ? pack_x3(w) : NetX3Image();
     NetDev &nd = e->net;
-    auto push = [&](const float *p, int n) {
-        int off = (int)head.size();
-        head.insert(head.end(), p, p + n);
-        while (head.size() % 4) head.push_back(0.f);
-        return off;
-    };
-    float v3[3], p6[6], s1, t1, s2[2], t2[2];
-    bn_fold(w->v_bn, 1, &s1, &t1);
-    bn_fold(w->p_bn, 2, s2, t2);
-    v3[0] = w->v_conv_b[0]; v3[1] = s1; v3[2] = t1;
-    p6[0] = w->p_conv_b[0]; p6[1] = w->p_conv_b[1]; p6[2] = s2[0]; p6[3] = s2[1]; p6[4] = t2[0]; p6[5] = t2[1];
-    nd.off_vk = push(w->v_conv_k, F);
-    nd.off_v3 = push(v3, 3);
-    nd.off_d1k = push(w->v_d1_k, D);
-    nd.off_d1b = push(w->v_d1_b, D);
-    nd.off_d2k = push(w->v_d2_k, D);
-    nd.off_d2b = push(w->v_d2_b, 1);
-    nd.off_pk = push(w->p_conv_k, 2 * F);
-    nd.off_p6 = push(p6, 6);
-    nd.off_pdk = push(w->p_d_k, 2 * A);
-    nd.off_pdb = push(w->p_d_b, A);
-    nd.head_floats = (int)head.size();
     // (weights are reloaded after every training step: the operand buffers are reused while their sizes stay the same)
     float *d_w0 = (float *)nd.w0, *d_wt = (float *)nd.wt, *d_epi = (float *)nd.epi, *d_head = (float *)nd.head;
-    const size_t sizes[4] = {w0.size(), wt.size(), epi.size(), head.size()};
+    const size_t sizes[4] = {img.w0.size(), img.wt.size(), img.epi.size(), head.v.size()};
     if (!d_w0 || memcmp(sizes, e->net_sizes, sizeof(sizes)) != 0) {
-        if (dalloc(e, d_w0, w0.size(), false) || dalloc(e, d_wt, wt.size(), false) || dalloc(e, d_epi, epi.size(), false) ||
-            dalloc(e, d_head, head.size(), false))
+        if (dalloc(e, d_w0, sizes[0], false) || dalloc(e, d_wt, sizes[1], false) || dalloc(e, d_epi, sizes[2], false) ||
+            dalloc(e, d_head, sizes[3], false))
             return BB_ERR_HIP;
         memcpy(e->net_sizes, sizes, sizeof(sizes));
     }
     HIPCHK(sync_all(e));
-    HIPCHK(hipMemcpy(d_w0, w0.data(), w0.size() * 4, hipMemcpyHostToDevice));
-    if (!wt.empty()) HIPCHK(hipMemcpy(d_wt, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_epi, epi.data(), epi.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_head, head.data(), head.size() * 4, hipMemcpyHostToDevice));
-    // the bf16-pipe form of the same network (every game, 16 filters); BB_NET_FORM_F32 keeps the float32 MFMA path
-    {
-        const bool want = F == 16 && C <= 32 && !e->general_net && e->cfg.net_form != BB_NET_FORM_F32;
-        if (want) {
-            std::vector<uint16_t> xw0, xw12, xw3, xw8, xwh;
-            pack_x3(w, xw0, xw12, xw3, xw8, xwh);
-            const size_t b0 = xw0.size() * 2, b12 = xw12.size() * 2, b3 = xw3.size() * 2, b8 = xw8.size() * 2, bh = xwh.size() * 2,
-                         bytes = b0 + b12 + b3 + b8 + bh;
-            unsigned char *d_x = (unsigned char *)e->x3.w0;
-            if (!d_x || bytes != e->x3_bytes) {
-                if (dalloc(e, d_x, bytes + 16, false)) return BB_ERR_HIP;
-                e->x3_bytes = bytes;
-            }
-            HIPCHK(hipMemcpy(d_x, xw0.data(), b0, hipMemcpyHostToDevice));
-            if (b12) HIPCHK(hipMemcpy(d_x + b0, xw12.data(), b12, hipMemcpyHostToDevice));
-            if (b3) HIPCHK(hipMemcpy(d_x + b0 + b12, xw3.data(), b3, hipMemcpyHostToDevice));
-            if (b8) HIPCHK(hipMemcpy(d_x + b0 + b12 + b3, xw8.data(), b8, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d_x + b0 + b12 + b3 + b8, xwh.data(), bh, hipMemcpyHostToDevice));
-            e->x3.w0 = d_x;
-            e->x3.wt12 = d_x + b0;
-            e->x3.wt3 = d_x + b0 + b12;
-            e->x3.wt8 = d_x + b0 + b12 + b3;
-            e->x3.wh = d_x + b0 + b12 + b3 + b8;
-        } else {
-            e->x3.w0 = e->x3.wt12 = e->x3.wt3 = e->x3.wt8 = e->x3.wh = nullptr;
+    if (upload(d_w0, img.w0) || upload(d_wt, img.wt) || upload(d_epi, img.epi) || upload(d_head, head.v)) return BB_ERR_HIP;
+    if (want3) { // one buffer, the five images back to back
+        const std::vector<uint16_t> *part[5] = {&x.w0, &x.wt12, &x.wt3, &x.wt8, &x.wh};
+        size_t at[6] = {0};
+        for (int i = 0; i < 5; i++) at[i + 1] = at[i] + part[i]->size() * 2;
+        unsigned char *d_x = (unsigned char *)e->x3.w0;
+        if (!d_x || at[5] != e->x3_bytes) {
+            if (dalloc(e, d_x, at[5] + 16, false)) return BB_ERR_HIP;
+            e->x3_bytes = at[5];
         }
+        for (int i = 0; i < 5; i++)
+            if (upload(d_x + at[i], *part[i])) return BB_ERR_HIP;
+        e->x3 = NetX3{d_x + at[0], d_x + at[1], d_x + at[2], d_x + at[3], d_x + at[4]};
+    } else {
+        e->x3 = NetX3{nullptr, nullptr, nullptr, nullptr, nullptr};
     }
     nd.R = R;
-    nd.D = D;
-    nd.A = A;
+    nd.D = w->D;
+    nd.A = w->A;
     nd.w0 = d_w0;
     nd.wt = (const f32x4 *)d_wt;
     nd.epi = d_epi;
     nd.head = d_head;
+    nd.head_floats = (int)head.v.size();
+    nd.off_vk = head.off_vk; nd.off_v3 = head.off_v3; nd.off_d1k = head.off_d1k; nd.off_d1b = head.off_d1b; nd.off_d2k = head.off_d2k;
+    nd.off_d2b = head.off_d2b; nd.off_pk = head.off_pk; nd.off_p6 = head.off_p6; nd.off_pdk = head.off_pdk; nd.off_pdb = head.off_pdb;
     nd.seed = e->cfg.seed;
     nd.alpha = e->cfg.alpha;
     nd.eps = e->cfg.epsilon;

@@ -41,7 +41,7 @@
 //   plane of each pair, groups 2,3 the second): 27 MFMAs per tile and layer instead of 30 with zero-extended K = 16 operands.
 //   Products are accumulated in ONE order in both forms (single buffer / PP): per slice w3 x1, w2 x1, w1 x1, w2 x2, w1 x2,
 //   w1 x3, then the tap-8 products in the order above reversed -- so all launch structures give the same bits.
-//   Weights: pre-split and pre-swizzled on the host into the A-operand lane order (engine.hip: pack_x3); planes 1 and 2 may
+//   Weights: pre-split and pre-swizzled on the host into the A-operand lane order (net_pack.h: pack_x3); planes 1 and 2 may
 //   live in the caller's LDS, plane 3 always streams from L2 a layer ahead.
 //   Callers: k_net_x3 (bb_net_eval, lock-step and asynchronous-round search), k_selfplay_queue (mega2.hip.h),
 //   k_dc_selfplay_fused (mega_dc.hip.h); the per-layer launches of wider networks use the same split in gnet_x3.hip.h.
@@ -716,7 +716,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
     // the spatial sums: lane (g = 0, nn) holds the three head activations of column nn of every tile.  (Round 2 formed them
     // on the vector ALUs from a float32 copy of the last layer: 48 fmas and four 16-byte reads per pixel, 2.0 k cycles.)
     const float *hp = PP ? as_lds(nd.head) : nd.head; // (the one-wave-per-game kernel keeps the head parameters in its LDS)
-    // Filter rows 0, 4 and 8 of the operand are the value conv and the two policy convs (engine.hip pack_x3), so lane group g
+    // Filter rows 0, 4 and 8 of the operand are the value conv and the two policy convs (net_pack.h pack_x3), so lane group g
     // (< 3) finds the activation of head g in the FIRST result register: one accumulator per lane, and the three spatial sums
     // are ONE row-wise reduction -- rows 0, 1, 2 of the wave -- instead of three wave reductions.  (Same bits as three
     // pooled_sum calls on a value that is zero outside row 0: the other rows only ever added exact zeros.)
