@@ -376,6 +376,7 @@ class Model(MCTS, Network):
     def _make_engine(self, game_id, n_slots, sims, **kw):
         kw.setdefault('launch', self._search_launch())
         self._search_cache_kw(kw)
+        self._search_rollouts()   # (checks the switch; a Model's engines evaluate with the network and are not concerned)
         return _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
                            evaluator=_lib.EVAL_NET, c_puct=float(self.ExplorationRate), noise_on=True,
                            alpha=float(self.alpha), epsilon=float(self.epsilon),

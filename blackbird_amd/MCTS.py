@@ -132,13 +132,17 @@ class MCTS(object):
     # How the engines behind FindMove / ResetRoot / Children and the arena run their simulations (bb_config.launch):
     # 'lockstep' -- one tree + one evaluator launch per simulation -- or 'wave', the opt-in: one launch per run_sims call, a wave
     # per game (Connect4 / TicTacToe with the hash evaluator or a 16-filter network, DragonChess with a 16-filter network of at
-    # most 8 blocks; any other engine searches lock-step and Engine.run_sims_structure() says so).  The same trees bit for bit
-    # either way.
+    # most 8 blocks, the rollout evaluator of every game with SearchRollouts below; any other engine searches lock-step and
+    # Engine.run_sims_structure() says so).  The same trees bit for bit either way.
     SearchLaunch = 'lockstep'
     # With SearchLaunch = 'wave': those engines also probe the evaluation cache before the network and store what they evaluate
     # (bb_config.search_cache; network engines of Connect4 and DragonChess, nothing happens elsewhere).  The same trees bit for
     # bit, fewer tower runs: Engine.counters() reports eval_cache_hits / eval_cache_probes.  Self-play engines are not concerned.
     SearchEvalCache = False
+    # With SearchLaunch = 'wave': the engines of the rollout evaluator (FixedMCTS, plain DynamicMCTS: every searcher that is not a
+    # Model) search in one launch as well -- the playout of a leaf runs in its slot's own wave (bb_search_rollouts).  The same
+    # trees bit for bit.  Model engines are not concerned.
+    SearchRollouts = False
 
     def __init__(self, explorationRate, timeLimit=None, playLimit=None, **kwargs):
         self.TimeLimit = timeLimit
@@ -170,12 +174,22 @@ class MCTS(object):
             kw.setdefault('search_cache', True)
         return kw
 
+    def _search_rollouts(self):
+        """Whether a search engine of this searcher is to take bb_search_rollouts: 'wave', SearchRollouts, the rollout evaluator."""
+        if not isinstance(self.SearchRollouts, bool):
+            raise ValueError("SearchRollouts must be True or False, not {!r}".format(self.SearchRollouts))
+        return self.SearchRollouts and self.SearchLaunch == 'wave' and self._EVALUATOR == _lib.EVAL_ROLLOUT
+
     def _make_engine(self, game_id, n_slots, sims, **kw):
         kw.setdefault('launch', self._search_launch())
         self._search_cache_kw(kw)
-        return _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
-                           max_depth=self._max_depth(), evaluator=self._EVALUATOR, c_puct=float(self.ExplorationRate),
-                           seed=_seed_from_numpy(), **kw)
+        rollouts = self._search_rollouts()
+        engine = _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
+                             max_depth=self._max_depth(), evaluator=self._EVALUATOR, c_puct=float(self.ExplorationRate),
+                             seed=_seed_from_numpy(), **kw)
+        if rollouts:
+            engine.search_rollouts(True)
+        return engine
 
     def _ensure_engine(self, state):
         if self._engine is None or self._engine.game != state.GAME_ID:

@@ -98,6 +98,11 @@ static inline int nblk(size_t n, int per = 256) { return (int)((n + per - 1) / p
 // wave per slot, and the edge pool E that the dense family ignores).  Every member is exactly one launch, of 256-thread blocks (the
 // node view: one wave).  The entry points below check, stage, call one member and copy back: none names a k_dc_* lock-step kernel or
 // sizes a grid for one, and a new lock-step kernel's launch goes here, in both halves -- never into an entry point.
+// (measurement switch of tools/search_latency.py: the dense games' one-launch rollout with lane 0 alone doing the playout)
+static bool rollout_plain() {
+    static const bool plain = [] { const char *v = getenv("BB_SW_ROLLOUT_PLAIN"); return v && v[0] == '1'; }();
+    return plain;
+}
 template <class G>
 struct Launch {
     using State = typename G::State;
@@ -111,6 +116,11 @@ struct Launch {
     // false: this family has no such kernel.
     static bool search_wave(const TreeDev &d, const DCEdges &, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int noise, bool cache) {
         const int blocks = (d.n_slots + SW_WAVES - 1) / SW_WAVES;
+        if (d.evaluator == BB_EVAL_ROLLOUT) { // (bb_search_rollouts)
+            if (rollout_plain()) k_search_wave_rollout<G, false><<<blocks, 64 * SW_WAVES, 0, st>>>(d, sims);
+            else k_search_wave_rollout<G, true><<<blocks, 64 * SW_WAVES, 0, st>>>(d, sims);
+            return true;
+        }
         if constexpr (G::CACHE_KEY) {
             if (x3.w0 && cache && d.eval_cache) {
                 k_search_wave<G, true, true><<<blocks, 64 * SW_WAVES, 0, st>>>(d, nd, x3, sims, noise);
@@ -154,6 +164,10 @@ struct Launch<DragonChess> {
     // (search_structure sends the wide game here with a 16-filter split-operand network that fits the kernel's LDS, and nothing else;
     // its prior noise is mixed in at expansion: E.noise_on)
     static bool search_wave(const TreeDev &d, const DCEdges &E, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int, bool cache) {
+        if (d.evaluator == BB_EVAL_ROLLOUT) { // (bb_search_rollouts)
+            k_dc_search_wave_rollout<<<(d.n_slots + SW_WAVES - 1) / SW_WAVES, 64 * SW_WAVES, 0, st>>>(d, E, sims);
+            return true;
+        }
         if (!x3.w0 || nd.R > DC_RMAX || nd.head_floats > DC_HEAD_FLOATS) return false;
         const int blocks = (d.n_slots + SW_WAVES - 1) / SW_WAVES;
         if (cache && d.eval_cache) k_dc_search_wave_cached<<<blocks, 64 * SW_WAVES, 0, st>>>(d, E, nd, x3, sims);
@@ -294,6 +308,7 @@ struct bb_engine {
     NetX3 x3 = {nullptr, nullptr, nullptr, nullptr, nullptr}; // 16-filter network of a dense game on the bf16 matrix pipe (net_x3.hip.h); null: float32 MFMA path
     size_t x3_bytes = 0;
     bool has_weights = false;
+    bool search_rollouts = false; // bb_search_rollouts: a BB_EVAL_ROLLOUT engine with launch = BB_LAUNCH_WAVE searches in one launch
     int net_F = 0, net_C = 0;
     bool general_net = false; // F != 16 (or BB_GNET=1): one implicit-GEMM launch per conv layer (gnet.hip.h)
     GNetDev gnet = {};
@@ -1086,15 +1101,23 @@ extern "C" int bb_set_roots(bb_engine *e, int n, const int32_t *slots, const voi
 // the loaded network for this: BB_LAUNCH_WAVE where the engine asked for it and a one-launch kernel exists for what it is (a dense
 // game with the hash evaluator, or any game with a 16-filter network in the split-operand form -- for DragonChess one that also fits
 // k_dc_search_wave's LDS, the test selfplay_structure applies to the self-play kernel), else the lock-step loop.
+// The rollout evaluator has a one-launch kernel for every game and is sent there only after bb_search_rollouts(e, 1).
 // bb_run_sims_structure reports it, so an engine that asked and was refused is visible.
 static int search_structure(const bb_engine *e) {
     if (e->cfg.launch != BB_LAUNCH_WAVE) return BB_LAUNCH_LOCKSTEP;
     const bool dc = e->cfg.game == BB_GAME_DRAGONCHESS;
     if (e->cfg.evaluator == BB_EVAL_HASH && !dc) return BB_LAUNCH_WAVE;
+    if (e->cfg.evaluator == BB_EVAL_ROLLOUT && e->search_rollouts) return BB_LAUNCH_WAVE; // (every game, both mcts_kinds)
     if (e->cfg.evaluator == BB_EVAL_NET && e->has_weights && !e->general_net && e->x3.w0 &&
         (!dc || (e->net.R <= DC_RMAX && e->net.head_floats <= DC_HEAD_FLOATS)))
         return BB_LAUNCH_WAVE;
     return BB_LAUNCH_LOCKSTEP;
+}
+
+extern "C" int bb_search_rollouts(bb_engine *e, int on) {
+    if (!e || (on != 0 && on != 1)) return fail(BB_ERR_ARG, "bb_search_rollouts: an engine and 0 or 1");
+    e->search_rollouts = on != 0; // (read by search_structure, for BB_EVAL_ROLLOUT engines only)
+    return BB_OK;
 }
 
 extern "C" int bb_run_sims_structure(bb_engine *e, int32_t *out) {

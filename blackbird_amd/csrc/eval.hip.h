@@ -77,22 +77,17 @@ __global__ void __launch_bounds__(256) k_hash_eval(int n, const typename G::Stat
 }
 
 // ---- MCTS.SampleValue rollouts (MCTS.py:360-383): one thread per leaf --------------------------
+// One playout from `s` by one thread: uniform draws over the legal moves in ascending order, keyed (game id, simulation serial,
+// 'ROLL', step); the value is for leaf.State.PreviousPlayer (MCTS.py:302).  A leaf that is already decided draws nothing.
 template <class G>
-__global__ void __launch_bounds__(256) k_rollout(int n, const typename G::State *st, const uint32_t *game_id,
-                                                 const int32_t *sim_serial, const int32_t *pend_leaf, uint64_t seed,
-                                                 float *value) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (pend_leaf && pend_leaf[i] < 0) return;
-    typename G::State s = st[i];
-    int player = gs_prev(s); // value is for leaf.State.PreviousPlayer (MCTS.py:302)
+__device__ __forceinline__ float rollout_value(typename G::State s, uint64_t seed, uint32_t game_id, uint32_t serial) {
+    int player = gs_prev(s);
     int w = G::winner(s, -1);
     uint32_t step = 0;
-    uint32_t serial = (uint32_t)(sim_serial[i] - 1); // sim_serial was advanced when the leaf was posted
     while (w < 0) {
         uint32_t m = G::legal_mask(s);
         int cnt = __popc(m);
-        Philox4 r = philox4x32_10(seed, game_id[i], serial, BB_TAG_ROLL, step++);
+        Philox4 r = philox4x32_10(seed, game_id, serial, BB_TAG_ROLL, step++);
         int pick = (int)(((uint64_t)r.x[0] * (uint64_t)cnt) >> 32);
         int a = 0;
         for (int k = 0; k < G::A; k++)
@@ -103,7 +98,18 @@ __global__ void __launch_bounds__(256) k_rollout(int n, const typename G::State 
         G::apply(s, a);
         w = G::winner(s, a);
     }
-    value[i] = w == 0 ? 0.5f : (player == w ? 1.0f : 0.0f);
+    return w == 0 ? 0.5f : (player == w ? 1.0f : 0.0f);
+}
+
+template <class G>
+__global__ void __launch_bounds__(256) k_rollout(int n, const typename G::State *st, const uint32_t *game_id,
+                                                 const int32_t *sim_serial, const int32_t *pend_leaf, uint64_t seed,
+                                                 float *value) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (pend_leaf && pend_leaf[i] < 0) return;
+    // (sim_serial was advanced when the leaf was posted)
+    value[i] = rollout_value<G>(st[i], seed, game_id[i], (uint32_t)(sim_serial[i] - 1));
 }
 
 // ---- DragonChess batched kernels ---------------------------------------------------------------------

@@ -89,3 +89,66 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_search_wave(TreeDev d, NetDev
         }
     }
 }
+
+// ---- the rollout evaluator (BB_EVAL_ROLLOUT: MCTS.SampleValue, what k_rollout does for one slot) ----------------------------------
+// The playout of rollout_value (eval.hip.h) by a whole wave.  Its Philox calls are the bulk of the arithmetic and do not depend on the
+// position: a playout of a dense game has at most H*W steps, so lane k computes step k's draw once, up front, and the serial play
+// loop takes step k's draw from lane k.  The position is wave-uniform (scalar registers), so the loop is scalar arithmetic plus one
+// v_readlane per step.  The same draws on the same positions in the same order as rollout_value: the same value, bit for bit.
+template <class G>
+__device__ __forceinline__ float rollout_value_wave(typename G::State s, uint64_t seed, uint32_t game_id, uint32_t serial, int lane) {
+    static_assert(G::H * G::W <= 64, "one lane per step of the longest playout");
+    s.p1 = ((uint64_t)__builtin_amdgcn_readfirstlane((int)(s.p1 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)s.p1);
+    s.p2 = ((uint64_t)__builtin_amdgcn_readfirstlane((int)(s.p2 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)s.p2);
+    const int player = gs_prev(s);
+    int w = G::winner(s, -1);
+    if (w < 0) { // (uniform) a leaf that is already decided draws nothing
+        const uint32_t draw = philox4x32_10(seed, game_id, serial, BB_TAG_ROLL, (uint32_t)lane).x[0];
+        for (int step = 0; w < 0 && step < G::H * G::W; step++) { // (every step puts a stone on the board)
+            const uint32_t m = G::legal_mask(s);
+            const int cnt = __popc(m);
+            const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)draw, step);
+            int pick = (int)(((uint64_t)r0 * (uint64_t)cnt) >> 32);
+            uint32_t mm = m;
+            for (; pick > 0; pick--) mm &= mm - 1; // the pick-th legal move in ascending order
+            const int a = mm ? __builtin_ctz(mm) : 0;
+            G::apply(s, a);
+            w = G::winner(s, a);
+        }
+    }
+    return w == 0 ? 0.5f : (player == w ? 1.0f : 0.0f);
+}
+
+// k_search_wave with the rollout evaluator: phase_apply -> phase_select -> the playout of the leaf in the slot's mailbox -> ..., and
+// the last simulation's apply.  A kernel of its own, so the hash and network instantiations above are compiled as they were; no LDS.
+// The draws are keyed (game id, sim_serial - 1, 'ROLL', step) with sim_serial read after phase_select has advanced it -- what
+// k_rollout reads in the lock-step loop -- so the trees are the lock-step ones bit for bit (tests/test_gpu_search_wave_rollout.py).
+// LANES: rollout_value_wave; else lane 0 runs rollout_value, literally k_rollout's thread (the form the other was measured against).
+template <class G, bool LANES>
+__global__ void __launch_bounds__(64 * SW_WAVES) k_search_wave_rollout(TreeDev d, int sims) {
+    constexpr int S = G::S;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * SW_WAVES + wave;
+    if (g >= d.n_slots) return; // (whole waves leave: nothing here synchronises the workgroup)
+    const bool tree_lane = lane < S;
+    for (int s = 0; s < sims; s++) {
+        if (tree_lane) {
+            phase_apply<G>(d, g, lane);
+            __threadfence_block();
+            phase_select<G>(d, g, lane);
+        }
+        __threadfence_block(); // lane 0's mailbox stores before the other lanes' loads
+        if (__builtin_amdgcn_readfirstlane(d.pend_leaf[g]) < 0) break; // (uniform) nothing posted: every further step is a no-op
+        const typename G::State st = ((const typename G::State *)d.leaf_state)[g];
+        const uint32_t gid = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.leaf_game_id[g]);
+        const uint32_t serial = (uint32_t)(__builtin_amdgcn_readfirstlane(d.sim_serial[g]) - 1);
+        if constexpr (LANES) {
+            const float v = rollout_value_wave<G>(st, d.seed, gid, serial, lane);
+            if (lane == 0) d.eval_value[g] = v;
+        } else {
+            if (lane == 0) d.eval_value[g] = rollout_value<G>(st, d.seed, gid, serial);
+        }
+        __threadfence_block(); // the value is in the mailbox before phase_apply reads it
+    }
+    if (tree_lane) phase_apply<G>(d, g, lane); // the last simulation's evaluation (no-op without a pending leaf)
+}

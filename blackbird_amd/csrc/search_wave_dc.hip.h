@@ -152,3 +152,57 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave(TreeDev d_arg,
 __global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave_cached(TreeDev d_arg, DCEdges E_arg, NetDev nd_arg, NetX3 x3_arg, int sims) {
     dc_search_wave_body<true>(d_arg, E_arg, nd_arg, x3_arg, sims);
 }
+
+// ---- the rollout evaluator (BB_EVAL_ROLLOUT) ------------------------------------------------------------------------------------------
+// The same loop with dc_rollout_wave (tree_dc.hip.h: the body of k_dc_rollout) in the network's place: dc_phase_apply<false, true> ->
+// dc_phase_select -> the playout of the leaf in the slot's mailbox -> ..., then the last apply.  Uniform priors are set at expansion
+// (d.priors_ones), the value travels through d.eval_value[g] as in the lock-step loop (no DCHeadLocal), and the draws are keyed (game
+// id, sim_serial - 1, 'ROLL', step) with sim_serial read after dc_phase_select has advanced it: what k_dc_rollout reads, so the same
+// trees bit for bit (tests/test_gpu_search_wave_rollout.py).  None of the network's LDS: the tree's per-wave scratch and the
+// descriptor copies only.  The phases are out of line and instances of this kernel alone (COPY = 1).
+// Returns the posted leaf (wave-uniform; < 0: none).
+__device__ __attribute__((noinline)) int dc_swr_tree(const TreeDev &d_, const DCEdges &E_, int g, int lane, float *tl) {
+    const TreeDev &d = *as_lds(&d_);
+    const DCEdges &E = *as_lds(&E_);
+    tl = as_lds(tl);
+    dc_phase_apply<false, true, 1>(d, E, g, lane, tl);
+    __threadfence_block();
+    dc_phase_select<false, 1>(d, E, g, lane, tl);
+    __threadfence_block(); // lane 0's mailbox stores before the other lanes' loads
+    return __builtin_amdgcn_readfirstlane(as_global(d.pend_leaf)[g]);
+}
+__device__ __attribute__((noinline)) void dc_swr_apply(const TreeDev &d_, const DCEdges &E_, int g, int lane, float *tl) {
+    const TreeDev &d = *as_lds(&d_);
+    const DCEdges &E = *as_lds(&E_);
+    dc_phase_apply<false, true, 1>(d, E, g, lane, as_lds(tl));
+    __threadfence_block();
+}
+__device__ __attribute__((noinline)) void dc_swr_rollout(const TreeDev &d_, int g, int lane) {
+    const TreeDev &d = *as_lds(&d_);
+    const uint32_t gid = (uint32_t)__builtin_amdgcn_readfirstlane((int)as_global(d.leaf_game_id)[g]);
+    const uint32_t serial = (uint32_t)(__builtin_amdgcn_readfirstlane(as_global(d.sim_serial)[g]) - 1);
+    const float v = dc_rollout_wave(as_global((const DCState *)d.leaf_state) + g, gid, serial, d.seed, lane);
+    if (lane == 0) as_global(d.eval_value)[g] = v;
+    __threadfence_block(); // the value is in the mailbox before dc_phase_apply reads it
+}
+__global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave_rollout(TreeDev d_arg, DCEdges E_arg, int sims) {
+    __shared__ __attribute__((aligned(16))) float lds_all[SW_WAVES][DC_LDS_FLOATS];
+    __shared__ TreeDev s_d;
+    __shared__ DCEdges s_E;
+    if (threadIdx.x == 0) { // workgroup prologue: the one barrier of the kernel
+        s_d = d_arg;
+        s_E = E_arg;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int g = blockIdx.x * SW_WAVES + wv;
+    if (g >= d_arg.n_slots) return; // (whole waves leave: nothing below synchronises the workgroup)
+    float *tl = lds_all[wv];
+    bool pending = false; // (no leaf is pending on entry: see dc_search_wave_body)
+    for (int s = 0; s < sims; s++) {
+        pending = dc_swr_tree(s_d, s_E, g, lane, tl) >= 0;
+        if (!pending) break; // (uniform) no game or no simulations left: every further step is a no-op (see the head of this file)
+        dc_swr_rollout(s_d, g, lane);
+    }
+    if (pending) dc_swr_apply(s_d, s_E, g, lane, tl); // the last simulation's evaluation
+}

@@ -403,7 +403,9 @@ __device__ __forceinline__ uint32_t *dc_anc_edge(const TreeDev &d, int g) {
 
 // ANC: also back up through the ancestor chain when the engine keeps one.  Only the launch-per-simulation kernels
 // (k_dc_tree_step / k_dc_tree_apply, which bb_run_sims drives) are built with it; self-play refuses track_ancestors engines.
-template <bool SH = false, bool ANC = false>
+// COPY: a caller that names another value gets instances of its own, so adding it leaves the code of the existing callers as it was
+// (k_dc_search_wave_rollout, search_wave_dc.hip.h).
+template <bool SH = false, bool ANC = false, int COPY = 0>
 __device__ void dc_phase_apply(const TreeDev &d, const DCEdges &E, int g, int lane, float *lds, const DCHeadLocal *hl = nullptr) {
     static_assert(!(SH && ANC), "the ancestor chain is walked by the launch-per-simulation kernels only");
     // One wave per game and one wave per SIMD: this step is a chain of dependent HBM round trips (2-3 us each on
@@ -592,7 +594,7 @@ __device__ __forceinline__ DCEdge dc_edge_load(const DCEdge *p) {
 static_assert(offsetof(DCNode, sq) == 16 && offsetof(DCEdge, cP) == 16 && offsetof(DCEdge, act) == 24 &&
               offsetof(DCEdge, c_edges) == 26 && offsetof(DCEdge, c_off) == 28, "dc_head_load / dc_edge_load read these layouts");
 
-template <bool SH = false>
+template <bool SH = false, int COPY = 0>
 __device__ void dc_phase_select(const TreeDev &d, const DCEdges &E, int g, int lane, float *lds) {
     const int lid = dc_ctl<SH>(d.game_lid)[g], sims_left = dc_ctl<SH>(d.sims_left)[g];
     int cur = dc_ctl<SH>(d.root)[g];
@@ -1239,21 +1241,18 @@ __global__ void __launch_bounds__(256) k_dc_selfplay_move(TreeDev d, DCEdges E) 
     dc_selfplay_move_body(d, E, g, lane, lds[wv]);
 }
 
-// MCTS.SampleValue rollouts for DragonChess: one wave per leaf (lane = from-square), capped at 2048 plies
-__global__ void __launch_bounds__(256) k_dc_rollout(int n, const DCState *st, const uint32_t *game_id, const int32_t *sim_serial,
-                                                    const int32_t *pend_leaf, uint64_t seed, float *value) {
-    int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-    if (i >= n) return;
-    if (pend_leaf && pend_leaf[i] < 0) return;
-    DCState s = st[i];
+// MCTS.SampleValue rollouts for DragonChess, one wave per leaf (lane = from-square): a playout from *st, capped at 2048 plies; a
+// position without a legal move, like the cap, scores 0.5.  Draws keyed (game id, simulation serial, 'ROLL', step).  Every lane
+// returns the value (for the leaf's previous player).  Shared by k_dc_rollout and the one-launch search (search_wave_dc.hip.h).
+__device__ __forceinline__ float dc_rollout_wave(const DCState *st, uint32_t game_id, uint32_t serial, uint64_t seed, int lane) {
+    DCState s = *st;
     int player = s.prev;
     int w = DragonChess::winner(s, -1);
-    uint32_t serial = (uint32_t)(sim_serial[i] - 1);
     for (uint32_t step = 0; w < 0 && step < 2048; step++) {
         uint64_t m = DragonChess::targets(s, lane);
         int cnt = bb_popc64(m), pre = wave_excl_scan_i(cnt, lane), total = wave_sum_i(cnt);
         if (total == 0) break;
-        Philox4 r = philox4x32_10(seed, game_id[i], serial, BB_TAG_ROLL, step);
+        Philox4 r = philox4x32_10(seed, game_id, serial, BB_TAG_ROLL, step);
         int pick = (int)(((uint64_t)r.x[0] * (uint64_t)total) >> 32);
         int a = -1;
         if (pick >= pre && pick < pre + cnt) {
@@ -1266,5 +1265,14 @@ __global__ void __launch_bounds__(256) k_dc_rollout(int n, const DCState *st, co
         DragonChess::apply(s, a);
         w = DragonChess::winner(s, a);
     }
-    if (lane == 0) value[i] = w <= 0 ? 0.5f : (player == w ? 1.0f : 0.0f);
+    return w <= 0 ? 0.5f : (player == w ? 1.0f : 0.0f);
+}
+
+__global__ void __launch_bounds__(256) k_dc_rollout(int n, const DCState *st, const uint32_t *game_id, const int32_t *sim_serial,
+                                                    const int32_t *pend_leaf, uint64_t seed, float *value) {
+    int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (i >= n) return;
+    if (pend_leaf && pend_leaf[i] < 0) return;
+    const float v = dc_rollout_wave(st + i, game_id[i], (uint32_t)(sim_serial[i] - 1), seed, lane);
+    if (lane == 0) value[i] = v;
 }

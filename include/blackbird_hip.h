@@ -156,7 +156,8 @@ typedef struct {
 #define BB_LAUNCH_LOCKSTEP 1 /* one tree + one evaluator launch per simulation, one move launch per ply */
 #define BB_LAUNCH_ROUNDS 2   /* asynchronous rounds: k_tree_async + a compacted network launch (dense games) */
 #define BB_LAUNCH_WAVE 3     /* bb_run_sims / bb_run_sims_masked in ONE launch, one wave per slot (bb_run_sims_structure says where it
-                                applies: Connect4, TicTacToe, and DragonChess with a 16-filter network of at most 8 blocks);
+                                applies: Connect4, TicTacToe, and DragonChess with a 16-filter network of at most 8 blocks; the
+                                rollout evaluator of every game after bb_search_rollouts(e, 1));
                                 bb_selfplay_step treats it as BB_LAUNCH_LOCKSTEP.  With bb_config.search_cache that launch also
                                 probes the evaluation cache */
 
@@ -250,10 +251,18 @@ int bb_run_sims_masked(bb_engine *e, int sims, const uint8_t *mask);
  * simulation -- the same trees bit for bit).  BB_LAUNCH_WAVE is what an engine created with bb_config.launch = BB_LAUNCH_WAVE
  * gets when its evaluator is BB_EVAL_NET with a 16-filter network in the split-operand form (bb_net_form 2) -- for DragonChess
  * one of at most 8 residual blocks, what its kernel keeps in LDS -- or when its game is Connect4 or TicTacToe and its evaluator
- * is BB_EVAL_HASH; every other engine (DragonChess with BB_EVAL_HASH or a deeper tower, rollouts, wide networks, BB_NET_FORM_F32,
- * general_net) searches lock-step whatever it asked for, and says so here.  Read it after bb_load_weights: a network evaluator
+ * is BB_EVAL_HASH, or when its evaluator is BB_EVAL_ROLLOUT and bb_search_rollouts(e, 1) was called; every other engine (DragonChess
+ * with BB_EVAL_HASH or a deeper tower, rollouts without that call, wide networks, BB_NET_FORM_F32, general_net) searches lock-step whatever it asked for, and says so here.  Read it after bb_load_weights: a network evaluator
  * without weights answers BB_ERR_WEIGHTS. */
 int bb_run_sims_structure(bb_engine *e, int32_t *out);
+/* Opt-in for BB_EVAL_ROLLOUT engines (MCTS.SampleValue, MCTS.py:360-383: FixedMCTS, plain DynamicMCTS), called after bb_create:
+ * on = 1 lets an engine created with bb_config.launch = BB_LAUNCH_WAVE search through BB_LAUNCH_WAVE as well -- tree descent, the
+ * random playout of the leaf and the backup in the slot's own wave, every game and both mcts_kinds, the same trees bit for bit
+ * (the playout's draws are keyed by game id, simulation serial and step, not by who computes them).  on = 0 (the state after
+ * bb_create): such an engine searches lock-step.  bb_run_sims_structure reports the result.  On an engine with another evaluator or
+ * another launch value the call is accepted and changes nothing; self-play is not concerned.  BB_ERR_ARG: null engine, or `on`
+ * other than 0 / 1. */
+int bb_search_rollouts(bb_engine *e, int on);
 /* After bb_run_sims: Root statistics + the move _selectAction(exploring=False) picks (MCTS.py:335-338).
  * u[n_slots] uniforms in [0,1) for np.random.choice's law, or NULL to draw Philox(seed, game_id, ply).
  * Outputs per slot (S = bb_game_info.S): action (or BB_ERR_NAN), root_winrate = Root.WinRate(),

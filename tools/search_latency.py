@@ -19,8 +19,14 @@ position to the end, table cold at the first move) and a WHOLE ARENA of `--games
 networks; DragonChess, whose games outlast the arena's node pools at 400 simulations: the same loop for `--plies` plies), and
 reports the share of leaf evaluations the cache answered (eval_cache_hits / eval_cache_probes of the engines).
 
+`--evaluator rollout` measures the searchers of the rollout evaluator instead (MCTS.SearchRollouts): `FixedMCTS(maxDepth=--depth)`
+or, with `--kind dynamic`, a plain DynamicMCTS, on the same two figures at the same simulation counts -- lock-step against wave in
+this build, against the other checkout's lock-step with `--tree`, and for a dense game against `wave_plain`: the wave kernel whose
+lane 0 alone plays the leaf out (BB_SW_ROLLOUT_PLAIN=1) instead of the lane-parallel draws.
+
 usage: python tools/search_latency.py [--game c4|dc] [--rounds 5] [--sims 800|400] [--games 64] [--reps 20] [--tree other/checkout]
        python tools/search_latency.py --cache [--game c4|dc] [--rounds 5] [--sims ..] [--games 64] [--plies 40] [--tree other/checkout]
+       python tools/search_latency.py --evaluator rollout [--game c4|dc] [--kind fixed|dynamic] [--depth 10] [--rounds 5] [--reps 20] [--tree ..]
 """
 import argparse
 import json
@@ -77,6 +83,50 @@ def child(a):
     eng.close()
     print(json.dumps({"run": a.child, "game": a.game, "tree": a.tree or "-", "structure": structure, "findmove_ms": statistics.median(find),
                       "findmove_min_ms": min(find), "arena_ply_ms": statistics.median(ply), "arena_ply_min_ms": min(ply)}))
+
+
+def child_rollout(a):
+    """One run of the --evaluator rollout leg; a.child is 'lockstep', 'wave' or 'wave_plain' (the environment makes the difference)."""
+    sys.path.insert(0, os.path.abspath(a.tree) if a.tree else ROOT)
+    import numpy as np
+    from blackbird_amd import Connect4, DragonChess, _lib
+    from blackbird_amd.DynamicMCTS import DynamicMCTS
+    from blackbird_amd.FixedMCTS import FixedMCTS
+    from blackbird_amd.MCTS import MCTS
+    if not a.tree:   # (another checkout searches the way it always did)
+        MCTS.SearchLaunch = "lockstep" if a.child == "lockstep" else "wave"
+        MCTS.SearchRollouts = a.child != "lockstep"
+    np.random.seed(0)
+    cls, game_id, plies = (DragonChess.BoardState, _lib.GAME_DRAGONCHESS, 64) if a.game == "dc" else (Connect4.BoardState, _lib.GAME_CONNECT4, 43)
+    if a.kind == "fixed":
+        m = FixedMCTS(maxDepth=a.depth, explorationRate=0.85, playLimit=a.sims)
+    else:
+        m = DynamicMCTS(explorationRate=0.85, playLimit=a.sims)
+    start = cls()
+    find = []
+    for k in range(3 + a.reps):   # (three heat-up calls: code objects, clocks)
+        m.DropRoot()
+        t = time.perf_counter()
+        m.FindMove(start, 1.0)   # (ends in bb_sample_moves, which synchronises)
+        if k >= 3:
+            find.append((time.perf_counter() - t) * 1e3)
+    structure = m._engine.run_sims_structure() if hasattr(m._engine, "run_sims_structure") else None
+    eng = m._make_engine(game_id, a.games, a.sims, node_capacity=a.sims * plies * m._max_depth() + 64)   # (arena._Searcher's sizing)
+    states = np.repeat(_lib.game_initial(game_id), a.games, axis=0)
+    mask = np.ones(a.games, dtype=np.uint8)
+    ply = []
+    for k in range(3 + max(a.reps // 2, 3)):
+        eng.set_roots(states, game_ids=np.arange(a.games))
+        t = time.perf_counter()
+        eng.run_sims(a.sims, mask=mask)
+        eng.sample_moves(1.0, np.full(a.games, 0.5))
+        if k >= 3:
+            ply.append((time.perf_counter() - t) * 1e3)
+    assert eng.counters()["overflow"] == 0
+    eng.close()
+    print(json.dumps({"run": a.child, "game": a.game, "kind": a.kind, "tree": a.tree or "-", "structure": structure,
+                      "findmove_ms": statistics.median(find), "findmove_min_ms": min(find), "arena_ply_ms": statistics.median(ply),
+                      "arena_ply_min_ms": min(ply)}))
 
 
 def child_cache(a):
@@ -188,8 +238,10 @@ def main_cache(a):
 
 def run(a, which, tree=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", which, "--game", a.game, "--sims", str(a.sims), "--games", str(a.games),
-           "--reps", str(a.reps), "--plies", str(a.plies)] + (["--tree", tree] if tree else []) + (["--cache"] if a.cache else [])
-    out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout, check=True).stdout.decode()
+           "--reps", str(a.reps), "--plies", str(a.plies), "--evaluator", a.evaluator, "--kind", a.kind, "--depth", str(a.depth)]
+    cmd += (["--tree", tree] if tree else []) + (["--cache"] if a.cache else [])
+    env = dict(os.environ, BB_SW_ROLLOUT_PLAIN="1" if which == "wave_plain" else "0")
+    out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout, check=True, env=env).stdout.decode()
     r = json.loads(out.strip().splitlines()[-1])
     print(json.dumps(r), flush=True)
     return r
@@ -206,6 +258,9 @@ def main():
     p.add_argument("--timeout", type=int, default=240, help="seconds one measurement process may take")
     p.add_argument("--cache", action="store_true", help="the evaluation cache of the one-launch search: whole game, whole arena")
     p.add_argument("--plies", type=int, default=None, help="--cache: cap on the plies of the whole game (default: 43 for c4, 40 for dc)")
+    p.add_argument("--evaluator", choices=["net", "rollout"], default="net", help="rollout: FixedMCTS / DynamicMCTS instead of a Model")
+    p.add_argument("--kind", choices=["fixed", "dynamic"], default="fixed", help="--evaluator rollout: the searcher")
+    p.add_argument("--depth", type=int, default=10, help="--evaluator rollout --kind fixed: maxDepth")
     p.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
     if a.sims is None:
@@ -213,17 +268,21 @@ def main():
     if a.plies is None:
         a.plies = 40 if a.game == "dc" else 43
     if a.child:
-        return child_cache(a) if a.cache else child(a)
+        return child_cache(a) if a.cache else child_rollout(a) if a.evaluator == "rollout" else child(a)
     if a.cache:
         return main_cache(a)
     run(a, "lockstep")   # heat-up, not counted
-    runs = {"lockstep": [], "wave": [], "other_lockstep": []}
+    runs = {"lockstep": [], "wave": [], "wave_plain": [], "other_lockstep": []}
     for _ in range(a.rounds):
         runs["lockstep"].append(run(a, "lockstep"))
         runs["wave"].append(run(a, "wave"))
+        if a.evaluator == "rollout" and a.game != "dc":   # (DragonChess has one form: its playout is a wave's already)
+            runs["wave_plain"].append(run(a, "wave_plain"))
         if a.tree:
             runs["other_lockstep"].append(run(a, "lockstep", a.tree))
     res = {"game": a.game, "sims": a.sims, "games": a.games, "rounds": a.rounds}
+    if a.evaluator == "rollout":
+        res.update(evaluator="rollout", kind=a.kind, depth=a.depth if a.kind == "fixed" else None)
     for name, rs in runs.items():
         for key in ("findmove_ms", "arena_ply_ms"):
             v = [r[key] for r in rs]
