@@ -24,7 +24,7 @@ OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NAN, ERR_CAPACITY, ERR_WEIGHTS = 0, -1, -2,
 EXPORTS = (
     "bb_game_info_get", "bb_last_error", "bb_device_count", "bb_game_legal", "bb_game_apply", "bb_game_winner",
     "bb_game_encode", "bb_game_initial", "bb_create", "bb_destroy", "bb_load_weights", "bb_get_counters",
-    "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked", "bb_run_sims_structure", "bb_search_rollouts",
+    "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked", "bb_run_sims_structure", "bb_search_rollouts", "bb_selfplay_rollouts",
     "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
     "bb_examples_to_batch",
@@ -114,6 +114,7 @@ def lib():
     L.bb_run_sims_masked.argtypes = [vp, ip, vp]
     L.bb_run_sims_structure.argtypes = [vp, C.POINTER(C.c_int32)]
     L.bb_search_rollouts.argtypes = [vp, ip]
+    L.bb_selfplay_rollouts.argtypes = [vp, ip]
     L.bb_sample_moves.argtypes = [vp, C.c_double, vp, vp, vp, vp, vp, vp, vp]
     L.bb_move_roots.argtypes = [vp, vp]
     L.bb_get_root_states.argtypes = [vp, vp]
@@ -516,6 +517,11 @@ class Engine:
         """bb_search_rollouts: let a rollout engine created with launch=LAUNCH_WAVE search in one launch as well (the same trees
         bit for bit; run_sims_structure() reports it).  Accepted and without effect on any other engine."""
         check(lib().bb_search_rollouts(self.h, int(bool(on))))
+
+    def selfplay_rollouts(self, on=True):
+        """bb_selfplay_rollouts: let a rollout engine play selfplay_step in one launch per call, a wave per slot (the same
+        records, headers and counters byte for byte; selfplay_mode() reports 6).  Accepted and without effect on any other engine."""
+        check(lib().bb_selfplay_rollouts(self.h, int(bool(on))))
 
     def sample_moves(self, temp, u=None):
         n, S = self.n_slots, self.info.S

@@ -15,6 +15,7 @@
 #include "mega_dc.hip.h"
 #include "search_wave.hip.h"
 #include "search_wave_dc.hip.h"
+#include "selfplay_wave.hip.h"
 #include "examples.hip.h"
 #include "train.hip.h"
 #include "net_pack.h"
@@ -150,6 +151,11 @@ struct Launch {
     }
     static void selfplay_begin(const TreeDev &d, const DCEdges &, hipStream_t st) { k_selfplay_begin<G><<<nblk(d.n_slots), 256, 0, st>>>(d); }
     static void selfplay_move(const TreeDev &d, const DCEdges &, hipStream_t st) { k_selfplay_move<G><<<nblk((size_t)d.n_slots * G::S), 256, 0, st>>>(d); }
+    // PLAY_WAVE_ROLLOUT: `plies` times (`sims` steps of tree_step + rollout, then selfplay_move) as one launch with a wave per slot
+    // (selfplay_wave.hip.h); move = 0: `sims` steps of one ply and no move
+    static void selfplay_wave_rollout(const TreeDev &d, const DCEdges &, hipStream_t st, int plies, int sims, int move) {
+        k_selfplay_wave_rollout<G><<<(d.n_slots + SW_WAVES - 1) / SW_WAVES, 64 * SW_WAVES, 0, st>>>(d, plies, sims, move);
+    }
     static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, float *boards, float *policy, float *value, int32_t *bad) {
         k_examples_to_batch<G><<<nblk((size_t)n * (G::H * G::W * G::C + G::A + 1)), 256, 0, st>>>(n_records, rec, n, index, boards, policy, value, bad);
     }
@@ -193,6 +199,9 @@ struct Launch<DragonChess> {
     }
     static void selfplay_begin(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_selfplay_begin<<<nblk(d.n_slots), 256, 0, st>>>(d, E); }
     static void selfplay_move(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_selfplay_move<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
+    static void selfplay_wave_rollout(const TreeDev &d, const DCEdges &E, hipStream_t st, int plies, int sims, int move) {
+        k_dc_selfplay_wave_rollout<<<(d.n_slots + SW_WAVES - 1) / SW_WAVES, 64 * SW_WAVES, 0, st>>>(d, E, plies, sims, move);
+    }
     static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, float *boards, float *policy, float *value, int32_t *bad) {
         k_dc_examples_to_batch<<<n, 256, 0, st>>>(n_records, rec, index, boards, policy, value, bad);
     }
@@ -286,8 +295,9 @@ extern "C" int bb_game_initial(int game, void *state_out) {
 
 // ---- engine ----------------------------------------------------------------------------------------
 // The launch structures of self-play (bb_selfplay_mode's values): lock-step launches per simulation (run_sims); dense games:
-// k_tree_async rounds + evaluator; persistent per-CU kernel with an LDS work queue (mega2.hip.h); DragonChess: mega_dc.hip.h
-enum { PLAY_LOCKSTEP = 0, PLAY_ROUNDS = 1, PLAY_QUEUE = 3, PLAY_DC_FUSED = 5 };
+// k_tree_async rounds + evaluator; persistent per-CU kernel with an LDS work queue (mega2.hip.h); DragonChess: mega_dc.hip.h; the
+// rollout evaluator of every game after bb_selfplay_rollouts(e, 1): one launch per step, a wave per slot (selfplay_wave.hip.h)
+enum { PLAY_LOCKSTEP = 0, PLAY_ROUNDS = 1, PLAY_QUEUE = 3, PLAY_DC_FUSED = 5, PLAY_WAVE_ROLLOUT = 6 };
 // What a configuration asks for -- the ONE place that reads mcts_kind / evaluator / launch / game for this.  (Whether the
 // network fits a persistent kernel's LDS is known only at bb_load_weights: selfplay_structure.)
 static int selfplay_plan(const bb_config *cfg) {
@@ -309,6 +319,7 @@ struct bb_engine {
     size_t x3_bytes = 0;
     bool has_weights = false;
     bool search_rollouts = false; // bb_search_rollouts: a BB_EVAL_ROLLOUT engine with launch = BB_LAUNCH_WAVE searches in one launch
+    bool selfplay_rollouts = false; // bb_selfplay_rollouts: a BB_EVAL_ROLLOUT engine plays bb_selfplay_step in one launch per call
     int net_F = 0, net_C = 0;
     bool general_net = false; // F != 16 (or BB_GNET=1): one implicit-GEMM launch per conv layer (gnet.hip.h)
     GNetDev gnet = {};
@@ -333,6 +344,7 @@ struct bb_engine {
     // kernel-tuning knobs, read from the environment ONCE in bb_create (never on the step path); not part of the API
     struct {
         int launch_steps = 64, queue_limit_s = 30;
+        int wave_rollout_sims = 0; // PLAY_WAVE_ROLLOUT: simulations per slot and launch; 0 = the game's figure (selfplay_wave_rollout)
         bool level_budget_set = false;
     } tune;
     size_t eval_cache_bytes = 0; // evaluation cache of self-play (dev.eval_cache: the persistent kernels and the asynchronous rounds), zeroed with every weight load
@@ -599,6 +611,7 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
     }
     e->tune.launch_steps = env_int("BB_LAUNCH_STEPS", 64);
     e->tune.queue_limit_s = env_int("BB_QUEUE_LIMIT_S", 30);
+    if (int v = env_int("BB_SELFPLAY_WAVE_SIMS", 0); v >= 1) e->tune.wave_rollout_sims = v; // (the tests of the launch split)
     if (cfg->launch < 0 || cfg->launch > BB_LAUNCH_WAVE || cfg->net_form < 0 || cfg->net_form > BB_NET_FORM_SPLIT) {
         delete e;
         return fail(BB_ERR_ARG, "bad bb_config.launch / net_form");
@@ -698,7 +711,15 @@ static int selfplay_structure(const bb_engine *e) {
     auto fits = [&](int rmax, int head_max) { return !e->has_weights || (!e->general_net && e->net.R <= rmax && e->net.head_floats <= head_max); };
     if (e->plan == PLAY_QUEUE && !fits(MEGA_RMAX, MEGA_HEAD_FLOATS)) return PLAY_ROUNDS;
     if (e->plan == PLAY_DC_FUSED && !fits(DC_RMAX, DC_HEAD_FLOATS)) return PLAY_LOCKSTEP;
+    // (selfplay_plan sends every rollout engine to lock-step, whatever its game, mcts_kind and launch: the opt-in replaces that)
+    if (e->cfg.evaluator == BB_EVAL_ROLLOUT && e->selfplay_rollouts) return PLAY_WAVE_ROLLOUT;
     return e->plan;
+}
+
+extern "C" int bb_selfplay_rollouts(bb_engine *e, int on) {
+    if (!e || (on != 0 && on != 1)) return fail(BB_ERR_ARG, "bb_selfplay_rollouts: an engine and 0 or 1");
+    e->selfplay_rollouts = on != 0; // (read by selfplay_structure, for BB_EVAL_ROLLOUT engines only)
+    return BB_OK;
 }
 
 extern "C" int bb_selfplay_mode(bb_engine *e) { return e ? selfplay_structure(e) : fail(BB_ERR_ARG, "null engine"); }
@@ -1444,6 +1465,44 @@ static int selfplay_dc_fused(bb_engine *e, int plies) {
     return BB_OK;
 }
 
+// PLAY_WAVE_ROLLOUT: nothing inside the kernel waits, so a launch is as long as its slowest slot's simulations, and the host bounds
+// those: at most `cap` simulations per slot and launch.  The figures are the measured costs of one simulation of a slot whose wave
+// runs alone on its SIMD (README): about 19 us for Connect4 Fixed-10 (15.8 ms per 800, TicTacToe is cheaper)
+// and about 4.3 ms for a DragonChess Dynamic simulation, nearly all of it the playout (1735 ms per 400).  65536 dense simulations
+// are then about 1.2 s, 512 DragonChess simulations about 2.2 s: launches in the low seconds -- up to twice that where two waves share a SIMD, and
+// the figure shrinks with the slot count beyond what the device holds at once (below) --, far below any watchdog and long enough that the launch cost (~10 us) is nothing.  Whole plies per launch
+// where a ply fits (cap / sims_now of them); a ply of more simulations than the cap is cut into launches of `cap` steps without
+// the move (move = 0: the leaf stays pending between them as it does between lock-step launches) and a last one with it.  Per
+// slot the sequence of operations is the same wherever the cuts fall, so the split cannot change a result.
+template <class G>
+static int selfplay_wave_rollout(bb_engine *e, int plies) {
+    const int sims = e->sims_now;
+    // (a full device holds 2 waves per SIMD of either kernel -- 189 / 228 VGPRs -- that is 2048 slots on 256 CUs; more slots run one
+    // after another inside the launch, so the figure is divided by the number of such rounds)
+    const int rounds = (e->dev.n_slots + 2047) / 2048;
+    const int dflt = (G::GID == BB_GAME_DRAGONCHESS ? 512 : 65536) / rounds;
+    const int cap = e->tune.wave_rollout_sims > 0 ? e->tune.wave_rollout_sims : dflt > 0 ? dflt : 1;
+    auto launch = [&](int n_plies, int n_sims, int move) {
+        return timed_launch(e, e->stream, TIME_EACH, [&]() -> int {
+            Launch<G>::selfplay_wave_rollout(e->dev, e->edges, e->stream, n_plies, n_sims, move);
+            HIPCHK(hipGetLastError());
+            return BB_OK;
+        });
+    };
+    if (sims > cap) { // a ply is longer than a launch
+        for (int p = 0; p < plies; p++)
+            for (int done = 0; done < sims; done += cap) {
+                const int now = sims - done < cap ? sims - done : cap;
+                if (int rc = launch(1, now, done + now == sims)) return rc;
+            }
+        return BB_OK;
+    }
+    const int per_launch = cap / (sims > 0 ? sims : 1);
+    for (int done = 0; done < plies; done += per_launch)
+        if (int rc = launch(plies - done < per_launch ? plies - done : per_launch, sims, 1)) return rc;
+    return BB_OK;
+}
+
 // PLAY_ROUNDS: per view, k_tree_async and then the evaluator over the leaves it posted
 template <class G>
 static int selfplay_rounds_async(bb_engine *e, int rounds) {
@@ -1512,6 +1571,7 @@ extern "C" int bb_selfplay_step(bb_engine *e, int plies) {
     GAME_SWITCH(e->cfg.game, {
         constexpr bool DC = G::GID == BB_GAME_DRAGONCHESS; // (selfplay_plan gives each game its own structures only)
         const int mode = selfplay_structure(e);
+        if (mode == PLAY_WAVE_ROLLOUT) return selfplay_wave_rollout<G>(e, plies);
         if constexpr (DC) {
             if (mode == PLAY_DC_FUSED) return selfplay_dc_fused(e, plies);
         } else if (mode == PLAY_QUEUE || mode == PLAY_ROUNDS) {

@@ -860,6 +860,8 @@ __global__ void __launch_bounds__(256) k_dc_tree_apply(TreeDev d, DCEdges E) {
 
 // ---- root statistics / move choice ------------------------------------------------------------------------
 // lane 0 walks the (<=144) edges: the np.random.choice law needs the sequential cumsum
+// (COPY: as for dc_phase_apply -- a caller that names another value gets instances of its own, here and in the move helpers below)
+template <int COPY = 0>
 __device__ int dc_choose_move(const TreeDev &d, const DCEdges &E, int g, int lane, double temp, double u, int &total,
                               int &edge_out) {
     DCNode *pool = (DCNode *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
@@ -984,7 +986,7 @@ __device__ __forceinline__ void dc_anc_clear(const TreeDev &d, int g) {
 
 // _moveRoot by action id (all lanes call; lane 0 writes).  ANC: push the edge taken onto the slot's ancestor chain when the
 // engine keeps one (bb_move_roots); the self-play kernels, persistent one included, are built without it.
-template <bool ANC = false>
+template <bool ANC = false, int COPY = 0>
 __device__ void dc_advance_root(const TreeDev &d, const DCEdges &E, int g, int lane, int action, DCState &new_st) {
     DCNode *pool = (DCNode *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
     DCNode *node = pool + d.root[g];
@@ -1143,6 +1145,7 @@ __global__ void __launch_bounds__(256) k_dc_selfplay_begin(TreeDev d, DCEdges E)
 }
 
 // example record: ExampleHdr, DCState, u32 visits[S], u16 action[S]
+template <int COPY = 0>
 __device__ void dc_write_example(const TreeDev &d, const DCEdges &E, int lid, int ply, const DCNode *node, const DCState &st,
                                  int g, int lane, int total, uint32_t gid, bool terminal_example) {
     constexpr int S = DragonChess::S;
@@ -1170,8 +1173,11 @@ __device__ void dc_write_example(const TreeDev &d, const DCEdges &E, int lid, in
 
 // GenerateTrainingSamples' loop body for one game (one wave): last result applied, move sampled, example written,
 // root advanced, game finished / slot handed to the next game (Blackbird.py:240-268)
+// COPY: instances of the body and of everything out of line under it for one caller alone (k_dc_selfplay_wave_rollout,
+// selfplay_wave.hip.h), so the kernels that share COPY = 0 are compiled as they were
+template <int COPY = 0>
 __device__ void dc_selfplay_move_body(const TreeDev &d, const DCEdges &E, int g, int lane, float *lds, const DCHeadLocal *hl = nullptr) {
-    dc_phase_apply(d, E, g, lane, lds, hl);
+    dc_phase_apply<false, false, COPY>(d, E, g, lane, lds, hl);
     __threadfence_block();
     int lid = d.game_lid[g];
     if (lid < 0) return;
@@ -1182,7 +1188,7 @@ __device__ void dc_selfplay_move_body(const TreeDev &d, const DCEdges &E, int g,
     int ply = d.ply[g];
     double u = bb_u53(d.seed, gid, (uint32_t)ply);
     int total, eo;
-    int act = dc_choose_move(d, E, g, lane, d.temp, u, total, eo);
+    int act = dc_choose_move<COPY>(d, E, g, lane, d.temp, u, total, eo);
     if (act < 0) {
         if (lane == 0) {
             d.game_lid[g] = -1;
@@ -1190,9 +1196,9 @@ __device__ void dc_selfplay_move_body(const TreeDev &d, const DCEdges &E, int g,
         }
         return;
     }
-    dc_write_example(d, E, lid, ply, root, st, g, lane, total, gid, false);
+    dc_write_example<COPY>(d, E, lid, ply, root, st, g, lane, total, gid, false);
     DCState ns;
-    dc_advance_root(d, E, g, lane, act, ns);
+    dc_advance_root<false, COPY>(d, E, g, lane, act, ns);
     __threadfence_block();
     ply += 1;
     int w = DragonChess::winner(ns, -1);
@@ -1205,7 +1211,7 @@ __device__ void dc_selfplay_move_body(const TreeDev &d, const DCEdges &E, int g,
         }
         return;
     }
-    dc_write_example(d, E, lid, ply, nullptr, ns, g, lane, 0, gid, true);
+    dc_write_example<COPY>(d, E, lid, ply, nullptr, ns, g, lane, 0, gid, true);
     __threadfence_block();
     for (int k = lane; k <= ply; k += 64) {
         ExampleHdr *h = (ExampleHdr *)(d.examples + ((size_t)lid * (d.max_plies + 1) + k) * d.example_bytes);

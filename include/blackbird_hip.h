@@ -206,9 +206,20 @@ int bb_timing_net(bb_engine *e, int iters, int noise, int ablate, double *ms_per
 /* Which launch structure bb_selfplay_step uses: 0 lock-step (one tree + one evaluator launch per
  * simulation), 1 asynchronous rounds, 3 persistent per-CU kernel with a work queue between its tree and network
  * waves (default for networks that fit LDS), 5 DragonChess with the 16-filter network: one wave keeps its game for a
- * whole launch -- tree step, network and move in the same wave.  (2 and 4 were launch structures that measured slower
- * and were retired.) */
+ * whole launch -- tree step, network and move in the same wave, 6 the rollout evaluator after bb_selfplay_rollouts(e, 1): one
+ * launch per bb_selfplay_step, one wave per slot -- tree step, playout, move and slot refill in the same wave.  (2 and 4 were
+ * launch structures that measured slower and were retired.) */
 int bb_selfplay_mode(bb_engine *e);
+/* Opt-in for BB_EVAL_ROLLOUT engines (MCTS.SampleValue, MCTS.py:360-383: FixedMCTS, plain DynamicMCTS), called after bb_create:
+ * on = 1 lets bb_selfplay_step play in one launch per call instead of sims_per_move x 2 + 1 launches per ply -- the wave of a
+ * slot does tree descent, playout, backup, move, example record and slot refill, for every game and both mcts_kinds, whatever
+ * bb_config.launch says.  Every slot makes exactly `plies` moves per call, and records, headers, counters and random streams are
+ * the lock-step ones byte for byte (the draws are keyed by game id, simulation serial and step, not by who computes them).  A
+ * call of many or long plies is cut into several launches on the host, which changes no result.  on = 0 (the state after
+ * bb_create): lock-step.  bb_selfplay_mode reports the result.  Independent of bb_search_rollouts (below), which concerns
+ * bb_run_sims only.  On an engine with another evaluator the call is accepted and changes nothing.  BB_ERR_ARG: null engine, or
+ * `on` other than 0 / 1. */
+int bb_selfplay_rollouts(bb_engine *e, int on);
 /* Which arithmetic the loaded network's conv tower runs in (after bb_load_weights): 0 float32 MFMA, fused 16-filter
  * tower (bit-identical to the k-ordered fmaf chain); 1 float32 MFMA, one launch per conv layer (any multiple of 16
  * filters); 2 float32 results on the bf16 matrix pipe -- every operand split exactly into three bf16 values, six MFMA
@@ -260,7 +271,7 @@ int bb_run_sims_structure(bb_engine *e, int32_t *out);
  * random playout of the leaf and the backup in the slot's own wave, every game and both mcts_kinds, the same trees bit for bit
  * (the playout's draws are keyed by game id, simulation serial and step, not by who computes them).  on = 0 (the state after
  * bb_create): such an engine searches lock-step.  bb_run_sims_structure reports the result.  On an engine with another evaluator or
- * another launch value the call is accepted and changes nothing; self-play is not concerned.  BB_ERR_ARG: null engine, or `on`
+ * another launch value the call is accepted and changes nothing; self-play is not concerned (bb_selfplay_rollouts).  BB_ERR_ARG: null engine, or `on`
  * other than 0 / 1. */
 int bb_search_rollouts(bb_engine *e, int on);
 /* After bb_run_sims: Root statistics + the move _selectAction(exploring=False) picks (MCTS.py:335-338).
