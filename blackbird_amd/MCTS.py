@@ -244,7 +244,13 @@ class MCTS(object):
             done += chunk
             self._root_sims += chunk
         if eng.counters()['overflow']:
-            raise _lib.BlackbirdHipError('search tree outgrew the node pool; raise node capacity')
+            n_legal = int(np.sum(state.LegalActions()))
+            if n_legal > eng.info.S and eng.sample_moves(0.0)['action'][0] == _lib.ERR_STATE:
+                # the engine refused to expand the root (bb_sample_moves: no tree): a node holds at most S edges
+                raise _lib.BlackbirdHipError('the position has {} legal moves; a node of the search tree holds at most '
+                                             'S = {} (bb_game_info.S)'.format(n_legal, eng.info.S))
+            raise _lib.BlackbirdHipError('search tree outgrew the node pool (raise node capacity), or reached a position '
+                                         'with more than S = {} legal moves'.format(eng.info.S))
 
         u = np.array([np.random.random_sample()]) if temp != 0 else None  # np.random.choice's one draw
         out = eng.sample_moves(temp, u)

@@ -1,6 +1,6 @@
 // tree_dc.hip.h -- node-pool MCTS for DragonChess (wide action space, compact child lists).
 //
-// A=4032 but a position has <= 137 legal moves, so a node owns a contiguous run of "edges"
+// A=4032 but a node has at most S = 144 legal moves (dc_expand refuses wider positions), so a node owns a contiguous run of "edges"
 // (action id, N, Q, W, child, c_puct*prior) in its slot's edge pool instead of a dense row.  One
 // 64-lane wave serves one game: lane = from-square during move generation, lane = edge index (mod 64)
 // during selection.  Semantics are those of tree.hip.h (same reference lines); what differs:
@@ -286,15 +286,17 @@ __device__ bool dc_expand(const TreeDev &d, const DCEdges &E, int g, DCNode *nod
     int pre = wave_excl_scan_i(cnt, lane);
     int total = wave_sum_i(cnt);
     int off = used;
-    if (off + total > E.edge_cap) return false;
+    // No node has more than S edges: every [n][S] output (k_dc_sample, k_dc_node_edges, the example records) holds a node's
+    // whole edge run.  A position with more legal moves is refused like a full edge pool -- the caller counts the
+    // simulation in `overflow` and the node stays unexpanded.
+    if (total > DragonChess::S || off + total > E.edge_cap) return false;
 #ifdef BB_STAMPS
     long long e0 = clock64(), e1 = e0, e2 = e0;
     if (priors) DST(9, e0 - x0);
 #endif
     // The moves are dealt evenly over the lanes (move j of the from-square-major enumeration -> lane j & 63): one
     // policy load, one Beta draw and one edge per lane instead of a serial loop over the busiest square's moves.
-    constexpr int MPL = 4; // moves per lane: up to 256 legal moves
-    if (total > 64 * MPL) return false;
+    constexpr int MPL = (DragonChess::S + 63) / 64; // moves per lane: total <= S
     uint16_t *mlist = (uint16_t *)lds; // compact action list, parked in the scratch until every lane has its entries
     {
         uint64_t mm = m;
@@ -934,7 +936,8 @@ __global__ void __launch_bounds__(256) k_dc_sample(TreeDev d, DCEdges E, double 
     DCNode *node = (DCNode *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap + d.root[g];
     if (node->flags & NODE_EXPANDED) {
         size_t base = (size_t)(g + d.pool_g0) * E.edge_cap + node->edge_off;
-        for (int k = lane; k < node->n_edges; k += 64) {
+        const int ne = min(node->n_edges, S); // (dc_expand keeps n_edges <= S; the row is S long whatever the node says)
+        for (int k = lane; k < ne; k += 64) {
             if (d.out_child_plays) d.out_child_plays[(size_t)g * S + k] = E.e[base + k].N;
             if (d.out_child_value) d.out_child_value[(size_t)g * S + k] = E.e[base + k].W;
             if (out_child_action) out_child_action[(size_t)g * S + k] = E.e[base + k].act;
@@ -1152,7 +1155,7 @@ __device__ void dc_write_example(const TreeDev &d, const DCEdges &E, int lid, in
     uint8_t *p = d.examples + ((size_t)lid * (d.max_plies + 1) + ply) * d.example_bytes;
     uint32_t *vis = (uint32_t *)(p + sizeof(ExampleHdr) + sizeof(DCState));
     uint16_t *act = (uint16_t *)(p + sizeof(ExampleHdr) + sizeof(DCState) + 4 * S);
-    int n = terminal_example ? 0 : node->n_edges;
+    int n = terminal_example ? 0 : min(node->n_edges, S); // (n_children never says more than the record holds)
     size_t base = terminal_example ? 0 : (size_t)(g + d.pool_g0) * E.edge_cap + node->edge_off;
     for (int k = lane; k < S; k += 64) {
         vis[k] = k < n ? (uint32_t)E.e[base + k].N : 0u;

@@ -56,7 +56,10 @@ enum {
 typedef struct {
     int32_t H, W, C;       /* AsInputArray shape [1,H,W,C] */
     int32_t A;             /* LegalMoves */
-    int32_t S;             /* child slots per node row (>= max legal moves of any position) */
+    int32_t S;             /* child slots per node row, the length of every [n][S] output.  Dense games: >= LegalMoves.
+                            * DragonChess (144): the most edges a tree node holds -- a position with more legal moves
+                            * (hand-built ones exist) is never expanded: its simulations count in `overflow`, and
+                            * bb_sample_moves answers BB_ERR_STATE for a slot whose root it is.  bb_game_* have no bound. */
     int32_t state_bytes;   /* packed state size */
     int32_t dense;         /* 1: slot i == action i; 0: compact child lists (DragonChess) */
     int32_t example_bytes; /* size of one bb_examples_fetch record */

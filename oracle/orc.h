@@ -100,6 +100,9 @@ typedef struct {
     void *cb_ctx;
     int priors_ones; /* MCTS.GetPriors default (MCTS.py:346-358): ones -> Priors = legal mask */
     orc_eval_cb2 cb2; /* ORC_EVAL_CALLBACK_KEYED */
+    int max_edges;    /* > 0: a node with more legal moves is never expanded (the HIP engine's DragonChess nodes hold 144
+                         edges): it stays a leaf, evaluated at every visit, counted in orc_stats.refused.
+                         0: no bound, the reference's behaviour */
 } orc_cfg;
 
 typedef struct {
@@ -109,6 +112,9 @@ typedef struct {
     uint64_t rollouts_without_moves; /* rollouts that met a position without a legal move (scored 0.5, see sample_value) */
     uint64_t nodes_reached;          /* nodes below a root that a descent or MoveRoot reached for the first time: what the HIP
                                         engine, which builds a child when it is first selected, counts as created */
+    uint64_t max_node_legal;         /* the most legal moves of any node the search expanded (the HIP engine's DragonChess
+                                        nodes hold at most 144 edges) */
+    uint64_t refused;                /* simulations that ended on a node wider than orc_cfg.max_edges */
 } orc_stats;
 
 typedef struct orc_search orc_search;

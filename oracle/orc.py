@@ -50,14 +50,15 @@ class Cfg(C.Structure):
     _fields_ = [("game", C.c_int), ("kind", C.c_int), ("max_depth", C.c_int), ("evaluator", C.c_int),
                 ("c_puct", C.c_double), ("salt", C.c_uint64), ("seed", C.c_uint64),
                 ("net", C.POINTER(Net)), ("noise_on", C.c_int), ("alpha", C.c_float), ("eps", C.c_float),
-                ("cb", EVAL_CB), ("cb_ctx", C.c_void_p), ("priors_ones", C.c_int), ("cb2", EVAL_CB2)]
+                ("cb", EVAL_CB), ("cb_ctx", C.c_void_p), ("priors_ones", C.c_int), ("cb2", EVAL_CB2),
+                ("max_edges", C.c_int)]
 
 
 class Stats(C.Structure):
     _fields_ = [("sims", C.c_uint64), ("evals", C.c_uint64), ("sum_depth", C.c_uint64),
                 ("nodes", C.c_uint64), ("terminal_leaves", C.c_uint64), ("max_depth_seen", C.c_int),
                 ("max_rollout_steps", C.c_uint32), ("rollouts_without_moves", C.c_uint64),
-                ("nodes_reached", C.c_uint64)]
+                ("nodes_reached", C.c_uint64), ("max_node_legal", C.c_uint64), ("refused", C.c_uint64)]
 
 
 def build(force=False):
@@ -215,12 +216,13 @@ def net_forward(w, boards, perpixel=False):
 
 # ---- search -----------------------------------------------------------------------------
 def make_cfg(game, kind=DYNAMIC, evaluator=EVAL_HASH, c_puct=0.85, max_depth=10, salt=0, seed=1234,
-             net=None, noise_on=False, alpha=0.2, eps=0.3, cb=None, priors_ones=False, cb2=None):
+             net=None, noise_on=False, alpha=0.2, eps=0.3, cb=None, priors_ones=False, cb2=None, max_edges=0):
     c = Cfg()
     c.game, c.kind, c.max_depth, c.evaluator = game, kind, max_depth, evaluator
     c.c_puct, c.salt, c.seed = c_puct, salt, seed
     c.noise_on, c.alpha, c.eps = int(noise_on), alpha, eps
     c.priors_ones = int(priors_ones)
+    c.max_edges = int(max_edges)  # > 0: nodes with more legal moves stay leaves (the engine's DragonChess S)
     if net is not None:
         c.net = C.pointer(net.c)
         c._net_keep = net

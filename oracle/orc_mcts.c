@@ -261,6 +261,7 @@ static void node_prepare(orc_search *s, orc_node *n, const float *policy) {
     int nl = 0;
     for (int a = 0; a < A; a++) nl += legal[a] == 1.0;
     n->nlegal = nl;
+    if ((uint64_t)nl > s->stats.max_node_legal) s->stats.max_node_legal = (uint64_t)nl;
     n->act = (int *)arena_alloc(s, sizeof(int) * (size_t)(nl ? nl : 1));
     n->prior = (double *)arena_alloc(s, sizeof(double) * (size_t)(nl ? nl : 1));
     int k = 0;
@@ -279,6 +280,19 @@ static void node_prepare(orc_search *s, orc_node *n, const float *policy) {
         for (k = 0; k < nl; k++) n->prior[k] = legal[n->act[k]] / tot;
     }
     n->prepared = 1;
+}
+
+/* orc_cfg.max_edges: does the node have more legal moves than a tree node may hold? */
+static int too_wide(orc_search *s, const orc_node *n) {
+    if (s->cfg.max_edges <= 0) return 0;
+    double *legal = s->tmpA;
+    orc_game_legal(s->cfg.game, &n->st, legal);
+    int nl = 0;
+    for (int a = 0; a < s->d.A; a++) nl += legal[a] == 1.0;
+    if (nl <= s->cfg.max_edges) return 0;
+    if ((uint64_t)nl > s->stats.max_node_legal) s->stats.max_node_legal = (uint64_t)nl;
+    s->stats.refused++;
+    return 1;
 }
 
 /* MCTS.AddChildren, MCTS.py:122-139 */
@@ -415,10 +429,13 @@ static void run_sim(orc_search *s) {
                     s->stats.terminal_leaves++;
                     break;
                 }
+                const int wide = too_wide(s, node);
                 if (c->evaluator != ORC_EVAL_ROLLOUT) { /* one evaluator call yields value + priors */
                     evaluate(s, node, &net_value, s->tmpP);
                     have_value = 1;
-                    add_children(s, node, s->tmpP);
+                    if (!wide) add_children(s, node, s->tmpP);
+                } else if (wide) {
+                    /* stays a leaf */
                 } else {
                     add_children(s, node, NULL);
                 }
@@ -438,6 +455,7 @@ static void run_sim(orc_search *s) {
                     s->stats.terminal_leaves++;
                     break;
                 }
+                if (too_wide(s, node)) break;
                 add_children(s, node, NULL);
             }
             if (node->nlegal == 0) break;

@@ -248,6 +248,116 @@ def gen_random_boards(key, n, seed):
     print(key, "random boards:", n)
 
 
+# ---- part 2b: hand-built DragonChess positions with 64 .. 144 legal moves, and more --------------
+# Two lone kings and freely placed pieces of the side to move (a queen in the open has ~20 moves, a mid-game position ~30 in
+# all).  Squares in algebraic notation (a1 = row 0, column 0), letters as DragonChess.letter_to_int.  "w..." positions are the
+# colour-and-rank mirror of the spec (the rules are symmetric under it), with White to move.
+_DC_QUEENS = "d4 e5 c3 f6 f3 c6 e2 d7 g4 b5".split()
+
+
+def _dc_spec(kings, n_queens, extra=""):
+    return " ".join([kings] + ["q" + s for s in _DC_QUEENS[:n_queens]] + extra.split())
+
+
+# name, spec (Black to move), mirrored?, (Player, PreviousPlayer), legal moves
+WIDE_DC = [
+    ("b64", _dc_spec("ka8 Kh1", 3, "pb2"), False, (2, 1), 64),       # the last count that fits one pass of 64 lanes
+    ("w65", _dc_spec("ka8 Kh1", 3, "pc1"), True, (1, 1), 65),        # one edge in the second pass
+    ("w83", _dc_spec("ka8 Kh1", 4), True, (1, 2), 83),               # White's first move of two
+    ("b102", _dc_spec("ka8 Kh1", 6), False, (2, 1), 102),
+    ("w114_kingcap", _dc_spec("ka8 Ke8", 7), True, (1, 1), 114),     # two king captures, both past edge 64
+    ("b128", _dc_spec("ka8 Kh1", 8, "nb1"), False, (2, 1), 128),     # two full passes
+    ("w129", _dc_spec("ka8 Kh1", 8, "na3"), True, (1, 1), 129),      # one edge in the third pass
+    ("b134_kingcap", _dc_spec("ka8 Ke8", 9), False, (2, 1), 134),    # king captures in the second and in the third pass
+    ("b142", _dc_spec("ka8 Kh1", 10), False, (2, 1), 142),
+    ("w142", _dc_spec("ka8 Kh1", 10), True, (1, 2), 142),
+    ("b144", _dc_spec("ka8 Kh1", 10, "nc1"), False, (2, 1), 144),    # == DragonChess::S, the widest node the tree holds
+    ("walk3", _dc_spec("ka8 Kh1", 9), False, (1, 1), 3),             # White's second move: each child is Black's, 131-134 wide
+]
+OVER_DC = [  # wider than the tree's node rows: the rules kernels have no such bound, the search refuses the position
+    ("w148", _dc_spec("ka8 Kh1", 10, "qb2 qg7"), True, (1, 1), 148),
+    ("b200", _dc_spec("ka8 Kh1", 10, "qb1 qg8 qh6 qa3"), False, (2, 1), 200),
+]
+
+
+def _dc_position(spec, mirrored, turn):
+    s = DragonChess.BoardState()
+    s.board = np.zeros((8, 8))
+    for tok in spec.split():
+        v, col, row = s.letter_to_int[tok[0]], "abcdefgh".index(tok[1]), int(tok[2]) - 1
+        s.board[7 - row if mirrored else row, col] = -v if mirrored else v
+    s.Player, s.PreviousPlayer = turn
+    s._white_castle_kingside = s._white_castle_queenside = s._black_castle_kingside = s._black_castle_queenside = False
+    return s
+
+
+def _dc_wide_record(positions, rng):
+    """The keys of boards_dc.npz for hand-built positions; apply_ok samples legal moves of every pass of 64 and every king
+    capture next to random (mostly illegal) actions."""
+    rec = dict(name=[], board=[], player=[], prev=[], castle=[], legal_off=[0], legal_idx=[], win_none=[], win_prev=[],
+               enc=[], apply_ok=[], n_king_captures=[], first_king_capture=[])
+    for name, spec, mirrored, turn, n_legal in positions:
+        s = _dc_position(spec, mirrored, turn)
+        la = s.LegalActions()
+        idx = np.where(la == 1)[0]
+        assert ((la == 0) | (la == 1)).all() and len(idx) == n_legal, (name, len(idx))
+        b, pl, pv, cs = state_arrays("dc", s)
+        rec["name"].append(name)
+        rec["board"].append(b.ravel())
+        rec["player"].append(pl)
+        rec["prev"].append(pv)
+        rec["castle"].append(cs)
+        rec["legal_idx"].extend(idx.tolist())
+        rec["legal_off"].append(len(rec["legal_idx"]))
+        rec["win_none"].append(wcode(s.Winner()))
+        rec["win_prev"].append([wcode(s.Winner(0))])
+        rec["enc"].append(s.AsInputArray().ravel())
+        caps = []
+        for k, a in enumerate(idx):
+            t = s.Copy()
+            t.ApplyAction(int(a))
+            if t.Winner() is not None:
+                caps.append(k)
+        rec["n_king_captures"].append(len(caps))
+        rec["first_king_capture"].append(caps[0] if caps else -1)
+        picks = [k for k in (0, 1, 62, 63, 64, 65, 126, 127, 128, 129, 142, 143, 144, 191, 192, n_legal - 2, n_legal - 1)
+                 if 0 <= k < n_legal] + caps
+        acts = [int(idx[k]) for k in sorted(set(picks))][:24]
+        acts += rng.randint(0, 4032, 32 - len(acts)).tolist()
+        ok = []
+        for a in acts:
+            t = s.Copy()
+            try:
+                t.ApplyAction(int(a))
+                tb, tp, tv, tc = state_arrays("dc", t)
+                ok.append([a, 1, tp, tv] + [int(x) for x in tc] + tb.ravel().tolist())
+            except ValueError:
+                ok.append([a, 0, 0, 0, 0, 0, 0, 0] + [0] * 64)
+        rec["apply_ok"].append(ok)
+    out = {k: np.asarray(v) for k, v in rec.items()}
+    out["enc"] = out["enc"].astype(np.int8)
+    out["board"] = out["board"].astype(np.int8)
+    return out
+
+
+def gen_wide_boards_dc(seed=24):
+    rng = np.random.RandomState(seed)
+    out = _dc_wide_record(WIDE_DC, rng)
+    out.update({"over_" + k: v for k, v in _dc_wide_record(OVER_DC, rng).items()})
+    # the children of the narrow White-to-move position are the wide interior nodes of the tree-walk tests
+    i = [p[0] for p in WIDE_DC].index("walk3")
+    s = _dc_position(*WIDE_DC[i][1:4])
+    kids = []
+    for a in np.where(s.LegalActions() == 1)[0]:
+        t = s.Copy()
+        t.ApplyAction(int(a))
+        kids.append([int(a), int(t.LegalActions().sum())])
+    out["walk_children"] = np.asarray(kids)  # [3][2]: action, legal moves of the position it leads to
+    np.savez_compressed(os.path.join(OUT, "boards_dc_wide.npz"), **out)
+    print("dc wide boards:", [len(np.where(_dc_position(*p[1:4]).LegalActions() == 1)[0]) for p in WIDE_DC + OVER_DC],
+          "walk children", kids)
+
+
 # ---- part 3: tree search under the hash evaluator ----------------------------------------
 def gen_mcts(key, tag, n_games, sims, seed, salt, temp=1.0, max_plies=10 ** 9, kind="dynamic",
              max_depth=3, c=0.85, reuse=True):
@@ -395,6 +505,7 @@ PARTS = {
                          gen_playouts("dc", 16, 13, max_plies=200)),
     "boards": lambda: (gen_random_boards("c4", 600, 21), gen_random_boards("ttt", 400, 22),
                        gen_random_boards("dc", 80, 23)),
+    "boards_dc_wide": gen_wide_boards_dc,
     "mcts": lambda: (
         gen_mcts("c4", "s2", 3, 2, 31, 100),
         gen_mcts("c4", "s50", 6, 50, 32, 200),

@@ -138,8 +138,22 @@ def _pack_dc(g):
 
 
 def test_dc_golden_random_boards(golden_dir):
+    _check_dc_boards(_load(golden_dir, "boards_dc.npz"))
+
+
+@pytest.mark.parametrize("pre", ["", "over_"], ids=["upto144", "over144"])
+def test_dc_golden_wide_boards(golden_dir, pre):
+    """Hand-built positions with 64 .. 144 legal moves, and two with 148 and 200 (more than a search-tree node holds: the rules
+    kernels have no such bound): bb_game_legal / winner / encode / apply against the reference (make_golden.py 'boards_dc_wide')."""
+    g = _load(golden_dir, "boards_dc_wide.npz")
+    g = {k[len(pre):]: g[k] for k in g.files if k.startswith(pre) and (pre or not k.startswith("over_"))}
+    n = np.diff(g["legal_off"])
+    assert (n.max() > 192) if pre else (n.max() == 144 and {64, 65, 128, 129} <= set(n.tolist()))
+    _check_dc_boards(g)
+
+
+def _check_dc_boards(g):
     game = _lib.GAME_DRAGONCHESS
-    g = _load(golden_dir, "boards_dc.npz")
     st = _pack_dc(g)
     n = st.shape[0]
     assert np.array_equal(_lib.game_legal(game, st), _legal_dense(g, n, 4032))
