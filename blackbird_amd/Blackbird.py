@@ -67,7 +67,18 @@ def _records_to_examples(game_cls, rec):
     return out
 
 
-def _timed_selfplay(model, nGames, temp):
+def _packed_starts(model, startStates):
+    """startStates (a sequence of model.Game states, or None / empty) -> packed array [n, ...] as the engine takes it, or None."""
+    if startStates is None or len(startStates) == 0:
+        return None
+    game_cls = model.Game
+    for s in startStates:
+        if not isinstance(s, game_cls):
+            raise ValueError('startStates must be %s states, got %s' % (game_cls.__name__, type(s).__name__))
+    return np.ascontiguousarray(np.concatenate([s._packed() for s in startStates], axis=0))
+
+
+def _timed_selfplay(model, nGames, temp, startStates=None):
     """GenerateTrainingSamples when the searcher has a wall-clock limit per move (mcts.timeLimit, MCTS.py:173-182, :298):
     the reference's loop (FindMove, example, MoveRoot, Winner) for all games of a wave at once through the lock-step entry
     points -- every move, all live games are searched together until `TimeLimit` seconds have passed (and no further than
@@ -83,10 +94,16 @@ def _timed_selfplay(model, nGames, temp):
     model._after_engine_created(eng)
     eng.set_rng_stream(int(np.random.randint(0, 2 ** 62, dtype=np.int64)), model._games_played)
     try:
+        starts = _packed_starts(model, startStates)
+        if starts is not None:
+            eng.selfplay_set_starts(starts)    # (for its checks: this loop primes its own roots, below)
         for first in range(0, nGames, n_slots):
             n = min(n_slots, nGames - first)
             idx = np.arange(n)
-            states = np.repeat(_lib.game_initial(game), n, axis=0)
+            if starts is None:
+                states = np.repeat(_lib.game_initial(game), n, axis=0)
+            else:                              # game k of the call starts from startStates[k % len]
+                states = starts[(first + idx) % len(starts)].copy()
             eng.set_roots(states, slots=idx, game_ids=model._games_played + first + idx)
             alive = np.ones(n_slots, dtype=bool)
             alive[n:] = False
@@ -151,15 +168,21 @@ def _side_to_move(game, packed):
     return int((int(np.asarray(packed).view(np.uint64).reshape(-1)[0]) >> 56) & 3)
 
 
-def GenerateTrainingSamples(model, nGames, temp):
+def GenerateTrainingSamples(model, nGames, temp, startStates=None):
     """Blackbird.py:219-268.  Raises ValueError if nGames <= 0.  With model.KeepDeviceExamples the run's records also stay on
-    the GPU for TrainWithDeviceExamples (not under a time limit: _timed_selfplay leaves no engine records)."""
+    the GPU for TrainWithDeviceExamples (not under a time limit: _timed_selfplay leaves no engine records).
+    startStates (beyond the reference, which starts every game from model.Game()): a sequence of model.Game states; the k-th
+    game of the call, in game-id order, starts from startStates[k % len(startStates)], its examples count plies from there and
+    its first example is that state.  None or empty: the initial position.  ValueError, with nothing stored, for a state no
+    game can start from (already over, no legal move, or a DragonChess position with more moves than a tree node holds)."""
     if nGames <= 0:
         raise ValueError('Use a positive integer for number of games.')
     game_cls = model.Game
     if model.TimeLimit is not None:
-        return _timed_selfplay(model, nGames, temp)
+        return _timed_selfplay(model, nGames, temp, startStates)
+    starts = _packed_starts(model, startStates)
     eng = model._selfplay_engine(nGames)
+    eng.selfplay_set_starts(starts)  # (None clears what an earlier call left on the engine it shares with this one)
     # every call is a fresh draw, as in the reference (new numpy choices and new graph noise each time): a new Philox
     # key from numpy's generator (advancing it) and game ids that continue where the model's last run stopped
     eng.set_rng_stream(int(np.random.randint(0, 2 ** 62, dtype=np.int64)), model._games_played)

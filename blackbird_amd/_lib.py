@@ -25,7 +25,7 @@ EXPORTS = (
     "bb_game_info_get", "bb_last_error", "bb_device_count", "bb_game_legal", "bb_game_apply", "bb_game_winner",
     "bb_game_encode", "bb_game_initial", "bb_create", "bb_destroy", "bb_load_weights", "bb_get_counters",
     "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked", "bb_run_sims_structure", "bb_search_rollouts", "bb_selfplay_rollouts",
-    "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_step",
+    "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_set_starts", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
     "bb_examples_to_batch",
     "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_param_count", "bb_trainer_read",
@@ -119,6 +119,7 @@ def lib():
     L.bb_move_roots.argtypes = [vp, vp]
     L.bb_get_root_states.argtypes = [vp, vp]
     L.bb_selfplay_begin.argtypes = [vp, ip, C.c_double]
+    L.bb_selfplay_set_starts.argtypes = [vp, ip, vp]
     L.bb_selfplay_step.argtypes = [vp, ip]
     L.bb_selfplay_done.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
     L.bb_examples_fetch.argtypes = [vp, ip, ip, vp, ip, vp, vp]
@@ -574,6 +575,19 @@ class Engine:
     def selfplay_begin(self, n_games, temp):
         check(lib().bb_selfplay_begin(self.h, int(n_games), float(temp)))
         self._n_games = int(n_games)
+
+    def selfplay_set_starts(self, states):
+        """bb_selfplay_set_starts: `states` = packed states [n, ...] (as set_roots takes them): game k of every later
+        selfplay_begin starts from states[k % n].  None or an empty array clears the table (initial positions again).  A state
+        a game cannot start from raises ValueError naming its index and the reason; the previous table then stays."""
+        n = 0 if states is None else int(np.asarray(states).shape[0])
+        if n == 0:
+            check(lib().bb_selfplay_set_starts(self.h, 0, None))
+            return
+        states = np.ascontiguousarray(states)
+        if states.nbytes != n * self.info.state_bytes:
+            raise ValueError("start states: %d bytes for %d states of %d bytes each" % (states.nbytes, n, self.info.state_bytes))
+        check(lib().bb_selfplay_set_starts(self.h, n, ptr(states)))
 
     def selfplay_step(self, plies=1):
         check(lib().bb_selfplay_step(self.h, int(plies)))

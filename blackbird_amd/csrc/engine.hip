@@ -149,6 +149,7 @@ struct Launch {
                            State *state, int32_t *info) { // (slot i is action i: no action list; info word 1 is the legal mask)
         k_node_view<G><<<1, 64, 0, st>>>(d, slot, node, child, plays, value, state, info);
     }
+    static void check_starts(hipStream_t st, int n, const State *s, uint8_t *verdict) { k_check_starts<G><<<nblk(n), 256, 0, st>>>(n, s, verdict); }
     static void selfplay_begin(const TreeDev &d, const DCEdges &, hipStream_t st) { k_selfplay_begin<G><<<nblk(d.n_slots), 256, 0, st>>>(d); }
     static void selfplay_move(const TreeDev &d, const DCEdges &, hipStream_t st) { k_selfplay_move<G><<<nblk((size_t)d.n_slots * G::S), 256, 0, st>>>(d); }
     // PLAY_WAVE_ROLLOUT: `plies` times (`sims` steps of tree_step + rollout, then selfplay_move) as one launch with a wave per slot
@@ -197,6 +198,7 @@ struct Launch<DragonChess> {
                            State *state, int32_t *info) {
         k_dc_node_edges<<<1, 64, 0, st>>>(d, E, slot, node, action, child, plays, value, state, info);
     }
+    static void check_starts(hipStream_t st, int n, const State *s, uint8_t *verdict) { k_check_starts<DragonChess><<<nblk((size_t)n * 64), 256, 0, st>>>(n, s, verdict); }
     static void selfplay_begin(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_selfplay_begin<<<nblk(d.n_slots), 256, 0, st>>>(d, E); }
     static void selfplay_move(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_selfplay_move<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
     static void selfplay_wave_rollout(const TreeDev &d, const DCEdges &E, hipStream_t st, int plies, int sims, int move) {
@@ -330,6 +332,7 @@ struct bb_engine {
     hipStream_t stream = nullptr;
     std::vector<void *> allocs;
     int n_games_target = 0;
+    StartsTable starts; // bb_selfplay_set_starts: the device copy dev.starts / view[].starts point at (starts.h); not in `allocs`
     int sims_now = 0;
     size_t node_bytes = 0;
     double *d_u = nullptr;
@@ -652,6 +655,7 @@ extern "C" int bb_destroy(bb_engine *e) {
     (void)hipSetDevice(e->cfg.device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (void *p : e->allocs) (void)hipFree(p);
+    if (e->starts.dev) (void)hipFree(e->starts.dev);
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->vstream[1]) {
         (void)hipStreamSynchronize(e->vstream[1]);
@@ -1370,6 +1374,51 @@ extern "C" int bb_set_rng_stream(bb_engine *e, uint64_t seed, uint32_t first_gam
 }
 
 // ---- self-play ----------------------------------------------------------------------------------------
+// The device side of starts_replace (starts.h) for one engine; the checks run on the engine's stream
+template <class G>
+static StartsOps starts_ops(bb_engine *e) {
+    StartsOps ops;
+    ops.ctx = e;
+    ops.alloc = [](void *, size_t bytes, void **out) -> int {
+        const hipError_t r = hipMalloc(out, bytes);
+        if (r != hipSuccess) (void)hipGetLastError();
+        return r == hipSuccess ? 0 : r == hipErrorOutOfMemory ? 1 : 2;
+    };
+    ops.upload = [](void *, void *dst, const void *src, size_t bytes) -> int { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess; };
+    ops.check = [](void *ctx, const void *dev_states, int n, uint8_t *verdict_out) -> int {
+        bb_engine *en = (bb_engine *)ctx;
+        DevBuf dv;
+        if (dv.alloc((size_t)n)) return 1;
+        Launch<G>::check_starts(en->stream, n, (const typename G::State *)dev_states, (uint8_t *)dv.p);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(en->stream) != hipSuccess) return 1;
+        return hipMemcpy(verdict_out, dv.p, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess;
+    };
+    ops.release = [](void *, void *p) { (void)hipFree(p); };
+    return ops;
+}
+
+extern "C" int bb_selfplay_set_starts(bb_engine *e, int n, const void *states) {
+    char msg[384];
+    if (starts_check_args(e != nullptr, n, states, msg, sizeof msg)) return fail(BB_ERR_ARG, "%s", msg);
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(sync_all(e)); // between runs only: nothing of the engine is in flight when the table changes
+    int rc = STARTS_DONE;
+    GAME_SWITCH(e->cfg.game, rc = starts_replace(e->starts, n, states, sizeof(typename G::State), starts_ops<G>(e), msg, sizeof msg); break);
+    switch (rc) {
+    case STARTS_DONE: break;
+    case STARTS_REFUSED: return fail(BB_ERR_ARG, "%s", msg);
+    case STARTS_NO_FIT: return fail(BB_ERR_CAPACITY, "%s", msg);
+    default: return fail(BB_ERR_HIP, "%s", msg);
+    }
+    e->dev.starts = e->starts.dev;
+    e->dev.n_starts = e->starts.n;
+    for (int v = 0; v < 2; v++) {
+        e->view[v].starts = e->starts.dev;
+        e->view[v].n_starts = e->starts.n;
+    }
+    return BB_OK;
+}
+
 extern "C" int bb_selfplay_begin(bb_engine *e, int n_games, double temp) {
     if (!e) return fail(BB_ERR_ARG, "null engine");
     if (n_games <= 0) return fail(BB_ERR_ARG, "Use a positive integer for number of games."); // Blackbird.py:235-236

@@ -18,6 +18,7 @@
 #pragma once
 #include "games.hip.h"
 #include "rng.hip.h"
+#include "starts.h"
 
 #define NODE_EXPANDED 1
 #define NODE_TERMINAL 2
@@ -143,6 +144,11 @@ struct TreeDev {
     int eval_cache_log2;
     unsigned long long *eval_cache_ctr;
     unsigned long long *stamps; // diagnostic build only (BB_STAMPS): [apply, fence, select, levels, waves]
+    // self-play start positions (bb_selfplay_set_starts): n_starts packed states, game lid starts from starts[lid % n_starts];
+    // null: G::initial().  Indexed by the engine-wide lid, so a slot-range view carries the pointer as it is.  (Last members:
+    // see the note on member order above.)
+    const void *starts;
+    int n_starts;
 };
 
 // ---- group (G::S lanes) collectives ---------------------------------------------------------
@@ -863,15 +869,38 @@ __global__ void __launch_bounds__(256) k_get_roots(TreeDev d, typename G::State 
 }
 
 // ---- self-play: begin / one move for every slot --------------------------------------------------
+// Where game `lid` of a run starts (Blackbird.py:238-251 has `state = model.Game()` here): the engine's table of start positions
+// when it has one (TreeDev::starts), else the initial position -- as for a slot without a game (lid < 0).  One lane, once per game.
+template <class G>
+__device__ __forceinline__ typename G::State start_state(const TreeDev &d, int lid) {
+    const typename G::State *t = (const typename G::State *)d.starts;
+    if (t && lid >= 0) return t[lid % d.n_starts];
+    return G::initial();
+}
+
+// bb_selfplay_set_starts: may a self-play game start from states[i]?  One BB_START_* verdict per state (starts.h), the reasons
+// looked at in their order: the game is over (Winner(None), as the self-play loop asks it), no legal move.  Dense games: one
+// thread per state.  (DragonChess: the specialisation in tree_dc.hip.h, one wave per state.)
+template <class G>
+__global__ void __launch_bounds__(256) k_check_starts(int n, const typename G::State *states, uint8_t *verdict) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const typename G::State st = states[i];
+    int v = BB_START_OK;
+    if (G::winner(st, -1) >= 0) v = BB_START_FINISHED;
+    else if (G::legal_mask(st) == 0) v = BB_START_NO_MOVE;
+    verdict[i] = (uint8_t)v;
+}
+
 template <class G>
 __global__ void __launch_bounds__(256) k_selfplay_begin(TreeDev d) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.n_slots) return;
     if (g + d.slot_offset < d.n_games_target) {
-        reset_slot<G>(d, g, g + d.slot_offset, G::initial());
+        reset_slot<G>(d, g, g + d.slot_offset, start_state<G>(d, g + d.slot_offset));
         d.sims_left[g] = d.sims_per_move;
     } else {
-        reset_slot<G>(d, g, -1, G::initial());
+        reset_slot<G>(d, g, -1, start_state<G>(d, -1));
         d.sims_left[g] = 0;
     }
 }
@@ -959,7 +988,7 @@ __device__ __forceinline__ void selfplay_move_body(const TreeDev &d, int g, int 
         c[7] += (uint64_t)(ply + 1);
         int next = lid + d.lid_stride; // this slot's next game id
         if (next < d.n_games_target) {
-            reset_slot<G>(d, g, next, G::initial());
+            reset_slot<G>(d, g, next, start_state<G>(d, next));
             d.sims_left[g] = d.sims_per_move;
         } else {
             d.game_lid[g] = -1;

@@ -1135,14 +1135,32 @@ __global__ void __launch_bounds__(256) k_dc_get_roots(TreeDev d, DCState *out) {
     out[g] = ((DCNode *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap + d.root[g])->st;
 }
 
+// k_check_starts (tree.hip.h) for DragonChess, one wave per state, lane = square: the kings by two ballots as dc_lane_apply finds
+// the winner, the legal moves counted as dc_expand counts them (occupancy by two ballots, targets_bits, a wave sum).  The third
+// reason is dc_expand's own: a root with more than S legal moves is never expanded, so no game could be played from it.
+template <>
+__global__ void __launch_bounds__(256) k_check_starts<DragonChess>(int n, const DCState *states, uint8_t *verdict) {
+    const int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (i >= n) return; // (whole waves leave)
+    const int piece = states[i].b[lane], player = states[i].player;
+    const bool bk = __ballot(piece == -1) != 0, wk = __ballot(piece == 1) != 0;
+    const uint64_t white = __ballot(piece > 0), black = __ballot(piece < 0);
+    const int total = wave_sum_i(bb_popc64(DragonChess::targets_bits(piece, player, lane, white, black)));
+    int v = BB_START_OK;
+    if (!bk || !wk) v = BB_START_FINISHED;
+    else if (total == 0) v = BB_START_NO_MOVE;
+    else if (total > DragonChess::S) v = BB_START_TOO_WIDE;
+    if (lane == 0) verdict[i] = (uint8_t)v;
+}
+
 __global__ void __launch_bounds__(256) k_dc_selfplay_begin(TreeDev d, DCEdges E) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.n_slots) return;
     if (g < d.n_games_target) {
-        dc_reset_slot(d, E, g, g, DragonChess::initial());
+        dc_reset_slot(d, E, g, g, start_state<DragonChess>(d, g));
         d.sims_left[g] = d.sims_per_move;
     } else {
-        dc_reset_slot(d, E, g, -1, DragonChess::initial());
+        dc_reset_slot(d, E, g, -1, start_state<DragonChess>(d, -1));
         d.sims_left[g] = 0;
     }
 }
@@ -1234,7 +1252,7 @@ __device__ void dc_selfplay_move_body(const TreeDev &d, const DCEdges &E, int g,
         c[7] += (uint64_t)(ply + 1);
         int next = lid + d.lid_stride;
         if (next < d.n_games_target) {
-            dc_reset_slot(d, E, g, next, DragonChess::initial());
+            dc_reset_slot(d, E, g, next, start_state<DragonChess>(d, next));
             d.sims_left[g] = d.sims_per_move;
         } else {
             d.game_lid[g] = -1;

@@ -316,6 +316,23 @@ int bb_set_rng_stream(bb_engine *e, uint64_t seed, uint32_t first_game_id);
 /* ---- batched self-play: Blackbird.GenerateTrainingSamples (Blackbird.py:219-268) ------------- */
 /* Start `n_games` games (local ids 0..n_games-1; slot g plays ids g, g+n_slots, ...). */
 int bb_selfplay_begin(bb_engine *e, int n_games, double temp);
+/* Start positions for self-play -- an extension: the reference starts every game from `model.Game()` (Blackbird.py:238-251).
+ * states: HOST memory, n packed states of the engine's game (the layout and state_bytes of bb_set_roots).  The engine copies the
+ * table to the device and owns the copy until the next call or bb_destroy.  In every later bb_selfplay_begin the game with
+ * engine-local index k (0 <= k < n_games; game id first_game_id + k) starts from states[k % n], whichever slot plays it and
+ * whichever launch structure the engine uses.  Plies count from the start position: the game's first record holds states[k % n]
+ * at ply 0, and max_plies caps the plies played from there.  Records keep their layout and the random streams their keys (move
+ * draw: seed, game id, ply; prior noise: game id, node serial; playouts as before).
+ * n == 0 clears the table (states is ignored): games start from the initial position again.  An engine that never had a table,
+ * or has none now, plays exactly as before.
+ * Every state is checked on the device before the table is swapped.  BB_ERR_ARG, with the first offending index and the reason
+ * in bb_last_error, when (1) the game is already over there (Winner() is not None), (2) it has no legal move, or (3) DragonChess:
+ * it has more than S = 144 legal moves (such a root is never expanded); the previous table then stays in force.  Anything else
+ * bb_set_roots accepts is accepted: unreachable boards, a DragonChess state in the middle of White's double move.
+ * BB_ERR_ARG before any device call: n < 0, states == NULL with n > 0, a null engine.  BB_ERR_CAPACITY: the copy does not fit.
+ * For use BETWEEN runs only: the call waits for everything the engine has queued before it swaps the table; calling it while
+ * a run started by bb_selfplay_begin is unfinished is not supported (slots refilled later would start from the new table). */
+int bb_selfplay_set_starts(bb_engine *e, int n, const void *states);
 /* Advance the self-play by `plies` moves' worth of search per active slot (a move: sims_per_move simulations, sample, record
  * the example, MoveRoot, Winner(); finished games hand their slot to the next game id).  Asynchronous.  In the lock-step and
  * rounds structures every slot makes exactly `plies` moves.  The persistent kernels hand out plies x sims_per_move tree visits

@@ -1,0 +1,183 @@
+"""Self-play from caller-given start positions (bb_selfplay_set_starts), the part that needs no GPU.
+
+The yardstick of tests/test_gpu_selfplay_starts.py is defined and pinned here: `oracle_selfplay_from` restates the loop of the
+oracle's orc_selfplay_game (oracle/orc_mcts.c; Blackbird.py:238-268) over the oracle's PUBLIC bindings -- Search.find_move with
+the keyed move draw (u = -1.0, ply = n), move_root, winner, encode, and the z rule of Blackbird.py:260-264 -- with one difference:
+the position the game starts from is an argument.  Run from the oracle's initial state it must return exactly what the committed
+orc.selfplay_game returns, for all three games; only then may the GPU tests lean on it for other starts.
+
+Also here: the entry point's argument checks (they come before any device call), the symbol in header, library and bindings,
+and the host code of the entry point (csrc/starts.h) driven by a stand-alone program over the C heap under
+AddressSanitizer + UBSan."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from blackbird_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "blackbird_amd", "csrc")
+
+
+# ---- the yardstick ---------------------------------------------------------------------------------------------------------------
+def oracle_selfplay_from(orc, cfg, game_id, start, temp, play_limit, max_plies):
+    """One self-play game of the oracle from `start` (an orc.State; not changed): the dict orc.selfplay_game returns."""
+    game = cfg.game
+    A = orc.dims(game)[3]
+    search = orc.Search(cfg, game_id)
+    search.drop_root()
+    st = start.copy()
+    boards, pi, player, actions = [], [], [], []
+    winner, n = None, 0
+    while winner is None and n < max_plies:
+        o = search.find_move(st, temp, play_limit, u=-1.0, ply=n)
+        boards.append(orc.encode(game, st)[0])   # ExampleState(..., state.AsInputArray(), player) of the state before the move
+        pi.append(o["prob"])
+        player.append(st.player)
+        actions.append(o["action"])
+        st = o["next"]
+        search.move_root(st)
+        winner = orc.winner(game, st)            # lastAction is always None (Blackbird.py:242,253)
+        n += 1
+    boards.append(orc.encode(game, st)[0])       # terminal example with pi = zeros (Blackbird.py:256-258)
+    pi.append(np.zeros(A))
+    player.append(st.player)
+    player = np.array(player, dtype=np.int8)
+    w = -1 if winner is None else int(winner)
+    z = np.zeros(n + 1, dtype=np.float32) if w <= 0 else np.where(player == w, 1.0, -1.0).astype(np.float32)  # :260-264
+    return dict(n=n + 1, boards=np.stack(boards), pi=np.stack(pi), player=player, z=z,
+                actions=np.array(actions, dtype=np.int32), winner=w, stats=search.stats())
+
+
+def orc_state_from_packed(orc, og, game, packed):
+    """One packed engine state (include/blackbird_hip.h) as the oracle's state."""
+    if game == _lib.GAME_DRAGONCHESS:
+        b, p, pv, c = _lib.unpack_dc(np.asarray(packed).view(np.uint8).reshape(1, 80))
+        return orc.state_from_arrays(og, b[0], p[0], int(pv[0]) or None, c[0])
+    b, p, pv = _lib.unpack_grid(game, np.asarray(packed).view(np.uint64).reshape(1, 2))
+    return orc.state_from_arrays(og, b[0], p[0], int(pv[0]) or None)
+
+
+@pytest.mark.parametrize("og,sims,max_plies,games", [(0, 24, 42, 4), (1, 16, 9, 6), (2, 12, 8, 3)])
+def test_yardstick_from_the_initial_state_is_the_committed_oracle(orc, og, sims, max_plies, games):
+    cfg = orc.make_cfg(og, evaluator=orc.EVAL_HASH, salt=4242, seed=99)
+    for gid in range(1000, 1000 + games):
+        want = orc.selfplay_game(cfg, gid, 1.0, sims, max_plies)
+        got = oracle_selfplay_from(orc, cfg, gid, orc.new_state(og), 1.0, sims, max_plies)
+        assert got["n"] == want["n"] and got["winner"] == want["winner"], gid
+        for k in ("boards", "pi", "player", "z", "actions"):
+            assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), (gid, k)
+        assert got["stats"].sims == want["stats"].sims and got["stats"].sum_depth == want["stats"].sum_depth, gid
+
+
+# ---- the entry point without a GPU -----------------------------------------------------------------------------------------------
+def test_argument_checks_come_before_any_device_call():
+    L = _lib.lib()
+    buf = np.zeros(16, dtype=np.uint8)
+    assert L.bb_selfplay_set_starts(None, 0, None) == _lib.ERR_ARG and "null engine" in _lib.last_error()
+    assert L.bb_selfplay_set_starts(None, 1, _lib.ptr(buf)) == _lib.ERR_ARG and "null engine" in _lib.last_error()
+    assert L.bb_selfplay_set_starts(None, -1, _lib.ptr(buf)) == _lib.ERR_ARG and "negative" in _lib.last_error()
+    assert L.bb_selfplay_set_starts(None, 2, None) == _lib.ERR_ARG and "NULL" in _lib.last_error()
+
+
+def test_symbol_in_header_library_and_bindings():
+    text = open(os.path.join(ROOT, "include", "blackbird_hip.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert re.search(r"\bint\s+bb_selfplay_set_starts\s*\(\s*bb_engine\s*\*\s*e\s*,\s*int\s+n\s*,\s*const\s+void\s*\*\s*states\s*\)", code)
+    assert "not supported" in text[text.index("Start positions for self-play"):text.index("int bb_selfplay_set_starts")]
+    assert hasattr(C.CDLL(_lib.LIB_PATH), "bb_selfplay_set_starts")
+    assert "bb_selfplay_set_starts" in _lib.EXPORTS and hasattr(_lib.Engine, "selfplay_set_starts")
+    assert _lib.lib().bb_selfplay_set_starts.argtypes == [C.c_void_p, C.c_int, C.c_void_p]
+    import inspect
+    from blackbird_amd import Blackbird
+    sig = inspect.signature(Blackbird.GenerateTrainingSamples)
+    assert list(sig.parameters) == ["model", "nGames", "temp", "startStates"] and sig.parameters["startStates"].default is None
+
+
+# ---- the host code of the entry point under a sanitizer --------------------------------------------------------------------------
+# The device is the C heap: every table is a malloc block of exactly n * state_bytes, so an access outside a table, a table freed
+# twice or never, or one used after its release stops the program (ASan; leaks are reported at exit).  The "kernel" refuses states
+# by their first byte.
+PROGRAM = r"""
+#include "starts.h"
+#include <cassert>
+#include <cstdlib>
+#include <cstring>
+struct Heap { int live = 0, fail_alloc = 0, fail_check = 0; };
+static int h_alloc(void *c, size_t bytes, void **out) {
+    Heap *h = (Heap *)c;
+    if (h->fail_alloc) return h->fail_alloc;
+    *out = malloc(bytes);
+    h->live++;
+    return 0;
+}
+static int h_upload(void *, void *dst, const void *src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
+static int h_check(void *c, const void *dev, int n, uint8_t *verdict) {
+    if (((Heap *)c)->fail_check) return 1;
+    for (int i = 0; i < n; i++) verdict[i] = ((const uint8_t *)dev)[(size_t)i * 16]; // first byte of state i = its verdict
+    return 0;
+}
+static void h_release(void *c, void *p) { free(p); ((Heap *)c)->live--; }
+int main() {
+    char msg[384];
+    assert(starts_check_args(false, -1, nullptr, msg, sizeof msg) == STARTS_BAD_ARG && strstr(msg, "negative"));
+    assert(starts_check_args(true, 3, nullptr, msg, sizeof msg) == STARTS_BAD_ARG && strstr(msg, "NULL"));
+    assert(starts_check_args(false, 0, nullptr, msg, sizeof msg) == STARTS_BAD_ARG && strstr(msg, "null engine"));
+    assert(starts_check_args(true, 0, nullptr, msg, sizeof msg) == STARTS_DONE);
+    assert(starts_check_args(true, 2, msg, msg, sizeof msg) == STARTS_DONE);
+    char tiny[8];
+    assert(starts_check_args(true, -5, nullptr, tiny, sizeof tiny) == STARTS_BAD_ARG && strlen(tiny) == 7); // truncated, terminated
+    Heap heap;
+    StartsOps ops = {&heap, h_alloc, h_upload, h_check, h_release};
+    StartsTable t;
+    uint8_t *states = (uint8_t *)malloc(5 * 16); // exactly 5 states: reading a sixth is a heap overflow
+    memset(states, 0, 5 * 16);
+    assert(starts_replace(t, 0, nullptr, 16, ops, msg, sizeof msg) == STARTS_DONE && !t.dev && t.n == 0); // clearing nothing
+    assert(starts_replace(t, 5, states, 16, ops, msg, sizeof msg) == STARTS_DONE && t.dev && t.n == 5 && heap.live == 1);
+    void *first = t.dev;
+    assert(!memcmp(first, states, 5 * 16));
+    states[3 * 16] = BB_START_NO_MOVE; // state 3 refused, and state 4 too: the first one is named
+    states[4 * 16] = BB_START_FINISHED;
+    assert(starts_replace(t, 5, states, 16, ops, msg, sizeof msg) == STARTS_REFUSED && t.dev == first && t.n == 5 && heap.live == 1);
+    assert(strstr(msg, "state 3 ") && strstr(msg, "no legal move") && strstr(msg, "reason 2"));
+    states[0] = BB_START_TOO_WIDE;
+    assert(starts_replace(t, 5, states, 16, ops, msg, sizeof msg) == STARTS_REFUSED && strstr(msg, "state 0 ") && strstr(msg, "more legal moves"));
+    states[0] = BB_START_FINISHED;
+    assert(starts_replace(t, 1, states, 16, ops, msg, sizeof msg) == STARTS_REFUSED && strstr(msg, "state 0 ") && strstr(msg, "already over"));
+    heap.fail_alloc = 1; // the copy does not fit
+    assert(starts_replace(t, 2, states + 16, 16, ops, msg, sizeof msg) == STARTS_NO_FIT && t.dev == first && heap.live == 1);
+    heap.fail_alloc = 2;
+    assert(starts_replace(t, 2, states + 16, 16, ops, msg, sizeof msg) == STARTS_DEVICE && t.dev == first && heap.live == 1);
+    heap.fail_alloc = 0;
+    heap.fail_check = 1; // the check itself fails: the fresh copy is released, the table stays
+    assert(starts_replace(t, 2, states + 16, 16, ops, msg, sizeof msg) == STARTS_DEVICE && t.dev == first && t.n == 5 && heap.live == 1);
+    heap.fail_check = 0;
+    assert(starts_replace(t, 2, states + 16, 16, ops, msg, sizeof msg) == STARTS_DONE && t.n == 2 && heap.live == 1); // a swap frees the old
+    assert(!memcmp(t.dev, states + 16, 2 * 16));
+    assert(starts_replace(t, 0, nullptr, 16, ops, msg, sizeof msg) == STARTS_DONE && !t.dev && t.n == 0 && heap.live == 0);
+    int reason = -1;
+    assert(starts_first_refused(states, 0, &reason) == -1 && reason == BB_START_OK);
+    free(states);
+    puts("starts host ok");
+    return 0;
+}
+"""
+
+
+def test_host_code_under_address_and_ub_sanitizers(tmp_path):
+    if _lib.lib().bb_device_count() > 0:
+        pytest.skip("GPU present: sanitizer builds run on machines without one")
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    src = tmp_path / "starts_host.cpp"
+    src.write_text(PROGRAM)
+    exe = str(tmp_path / "starts_host")
+    cmd = [hipcc, "-std=c++17", "-O1", "-g", "-UNDEBUG", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host",
+           "-fno-sanitize-recover=all", "-I", CSRC, "-o", exe, str(src)]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0 and "starts host ok" in r.stdout, (r.returncode, r.stdout, r.stderr[-2000:])
