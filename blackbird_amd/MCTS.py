@@ -143,6 +143,11 @@ class MCTS(object):
     # Model) search in one launch as well -- the playout of a leaf runs in its slot's own wave (bb_search_rollouts).  The same
     # trees bit for bit.  Model engines are not concerned.
     SearchRollouts = False
+    # Which loop plays the batched arena (arena.TestModelsBatched, behind TestModels and the Test* wrappers) when this searcher is
+    # its first side: 'host' -- every ply's moves are read back and applied through the batched game entry points -- or 'device',
+    # the opt-in: the whole match loop is enqueued on the GPU, both sides' searches of a ply in flight together (bb_arena_*).  A
+    # preference: against a RandomMCTS, or with a side that has only a TimeLimit, the host loop plays (arena.last_loop says which).
+    ArenaLoop = 'host'
 
     def __init__(self, explorationRate, timeLimit=None, playLimit=None, **kwargs):
         self.TimeLimit = timeLimit

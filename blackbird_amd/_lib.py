@@ -28,6 +28,7 @@ EXPORTS = (
     "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_set_starts", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
     "bb_examples_to_batch",
+    "bb_arena_create", "bb_arena_begin", "bb_arena_step", "bb_arena_status", "bb_arena_fetch", "bb_arena_destroy",
     "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_param_count", "bb_trainer_read",
 )
 
@@ -130,6 +131,12 @@ def lib():
     L.bb_examples_fetch_games.argtypes = [vp, ip, vp, vp, ip, vp, vp]
     L.bb_examples_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp)]
     L.bb_examples_to_batch.argtypes = [ip, ip, vp, ip, vp, vp, vp, vp, vp, vp]
+    L.bb_arena_create.argtypes = [vp, vp, ip, C.POINTER(vp)]
+    L.bb_arena_begin.argtypes = [vp, ip, vp, vp, C.c_double]
+    L.bb_arena_step.argtypes = [vp, ip]
+    L.bb_arena_status.argtypes = [vp, C.POINTER(ip)]
+    L.bb_arena_fetch.argtypes = [vp, vp, vp, vp, vp]
+    L.bb_arena_destroy.argtypes = [vp]
     L.bb_trainer_create.argtypes = [C.POINTER(TrainConfig), C.POINTER(NetWeights), C.POINTER(vp)]
     L.bb_trainer_destroy.argtypes = [vp]
     L.bb_trainer_step.argtypes = [vp, ip, vp, vp, vp, vp, C.c_double, ip, vp, vp]
@@ -630,3 +637,53 @@ class Engine:
         nb, rb = C.c_uint64(), C.c_uint64()
         check(lib().bb_examples_device(self.h, C.byref(p), C.byref(nb), C.byref(rb), C.byref(hdr)))
         return p.value, nb.value, rb.value, hdr.value
+
+
+class Arena:
+    """Head-to-head games of two engines on the device (bb_arena): `a` is model1, `b` model2, one game per slot index.  The
+    engines are borrowed and must stay open -- and unused by anything else -- until close()."""
+
+    def __init__(self, a, b, log_plies=0):
+        self.a, self.b = a, b
+        self.log_plies = int(log_plies)
+        self.n_games = 0
+        self.h = C.c_void_p()
+        check(lib().bb_arena_create(a.h, b.h, self.log_plies, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h.value:
+            lib().bb_arena_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    def begin(self, first, temp, start_states=None):
+        """first: bool [n_games], a moves first in game i; start_states: packed states [n_games, ...] or None (initial position)."""
+        first = np.ascontiguousarray(first, dtype=np.uint8)
+        n = int(first.shape[0])
+        if start_states is not None:
+            start_states = np.ascontiguousarray(start_states)
+            if start_states.nbytes != n * self.a.info.state_bytes:
+                raise ValueError("start states: %d bytes for %d games of %d bytes each" % (start_states.nbytes, n, self.a.info.state_bytes))
+        check(lib().bb_arena_begin(self.h, n, ptr(first), ptr(start_states), float(temp)))
+        self.n_games = n
+
+    def step(self, plies=1):
+        check(lib().bb_arena_step(self.h, int(plies)))
+
+    def status(self):
+        """Waits; the number of games still running.  Raises BlackbirdHipError when a tree outgrew its node pool, ValueError when a
+        game stopped on NaN probabilities."""
+        alive = C.c_int()
+        check(lib().bb_arena_status(self.h, C.byref(alive)))
+        return alive.value
+
+    def fetch(self):
+        """dict(result int8 [n], plies int32 [n], moves int32 [n, log_plies] (-1 padded), states (packed) [n, ...])."""
+        n = self.n_games
+        out = dict(result=np.zeros(n, np.int8), plies=np.zeros(n, np.int32), moves=np.full((n, self.log_plies), -1, np.int32))
+        states = np.zeros((n, self.a.info.state_bytes), dtype=np.uint8)
+        check(lib().bb_arena_fetch(self.h, ptr(out["result"]), ptr(out["plies"]), ptr(out["moves"]) if self.log_plies else None,
+                                   ptr(states)))
+        out["states"] = states.view(STATE_DTYPE[self.a.game])
+        return out

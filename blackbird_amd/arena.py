@@ -8,7 +8,15 @@ touched, as in the reference, where a model only searches on its own turns), and
 
 Per game the sequence (FindMove on my turns, MoveRoot after every move) is the reference's; what differs from a serial
 run is only the order in which random numbers are consumed across games, so results are identical for deterministic
-settings (temp = 0, no prior noise) and identically distributed otherwise (tests/test_gpu_arena.py)."""
+settings (temp = 0, no prior noise) and identically distributed otherwise (tests/test_gpu_arena.py).
+
+Two loops play this.  'host' (the default) is the loop written out in TestModelsBatched below: every ply it reads each side's
+moves back and applies them through the batched game entry points.  'device' (opt-in: `loop='device'`, or the class attribute
+MCTS.ArenaLoop as a preference) hands the same sequence to the engine library's arena (`_lib.Arena`, bb_arena_*): the games'
+states, turns and results stay on the GPU, both sides' searches of a ply are in flight together, and the host looks at the
+result once every few plies.  Per game it is the same sequence of operations, with the moves drawn from the engines' own
+Philox streams (as `sample_moves(temp, None)` does), so `uniforms=` belongs to the host loop only; a RandomMCTS side and a side
+that has only a wall-clock budget are played by the host loop too."""
 import random
 from time import time
 
@@ -55,7 +63,54 @@ class _Searcher(object):
             self.engine = None
 
 
-def TestModelsBatched(model1, model2, temp, numTests, playLimit=None, first=None, uniforms=None):
+last_loop = None   # which loop the last TestModelsBatched call played through: 'host' or 'device'
+_STEP_PLIES = 8    # device loop: plies enqueued between two looks at the result
+
+
+def _device_loop_obstacle(model1, model2, playLimit, uniforms):
+    """Why the device loop cannot play this match (a string), or None."""
+    if uniforms is not None:
+        return 'uniforms= belongs to the host loop: the device loop draws from the engines\' own streams'
+    for name, m in (('model1', model1), ('model2', model2)):
+        if isinstance(m, RandomMCTS):
+            return '%s is a RandomMCTS, which the host loop plays' % name
+        if playLimit is None and getattr(m, 'PlayLimit', None) is None and getattr(m, 'TimeLimit', None) is not None:
+            return '%s has only a TimeLimit and no playLimit: a wall-clock budget is the host loop\'s' % name
+    return None
+
+
+def _choose_loop(model1, model2, playLimit, uniforms, loop):
+    """'host' or 'device' for this call: an explicit loop='device' that cannot be had raises ValueError with the reason; the
+    attribute model1.ArenaLoop = 'device' is a preference and falls back to the host loop.  Makes no engine."""
+    explicit = loop is not None
+    if loop is None:
+        loop = getattr(model1, 'ArenaLoop', 'host')
+    if loop not in ('host', 'device'):
+        raise ValueError("the arena loop must be 'host' or 'device', not {!r}".format(loop))
+    if loop == 'device':
+        why = _device_loop_obstacle(model1, model2, playLimit, uniforms)
+        if why is not None:
+            if explicit:
+                raise ValueError("loop='device' is not possible here: " + why)
+            return 'host'
+    return loop
+
+
+def _device_arena(sides, game_id, temp, numTests, first, starts):
+    """The match loop on the device: create, begin, step + status until nobody is alive, fetch."""
+    arena = _lib.Arena(sides[0].engine, sides[1].engine, log_plies=0)
+    try:
+        arena.begin(first, temp, starts)
+        while True:
+            arena.step(_STEP_PLIES)
+            if arena.status() == 0:
+                break
+        return arena.fetch()['result'].astype(np.int32)
+    finally:
+        arena.close()
+
+
+def TestModelsBatched(model1, model2, temp, numTests, playLimit=None, first=None, uniforms=None, loop=None, startStates=None):
     """Play `numTests` games of model1 against model2 concurrently; returns an int array of +1 / 0 / -1 (model1's
     wins / draws / losses), one entry per game, in game order.
 
@@ -63,9 +118,24 @@ def TestModelsBatched(model1, model2, temp, numTests, playLimit=None, first=None
                TimeLimit searches all its games together until that many seconds have passed, every move)
     first      optional bool array: model1 moves first in game i (default: `random.choice([True, False])` per game,
                drawn in game order like the reference does at the top of each game)
-    uniforms   optional callable n -> float64[n] supplying np.random.choice's uniforms (default np.random.random_sample)"""
+    uniforms   optional callable n -> float64[n] supplying np.random.choice's uniforms (default np.random.random_sample);
+               host loop only
+    loop       'host' or 'device' (module docstring); None takes model1.ArenaLoop as a preference.  `last_loop` says which
+               loop played.  An explicit 'device' that is not possible raises ValueError naming the reason
+    startStates  device loop only: a list of numTests GameStates the games start from instead of `Game()`"""
+    global last_loop
     if numTests <= 0:
         raise ValueError('Use a positive integer for number of tests.')
+    which = _choose_loop(model1, model2, playLimit, uniforms, loop)
+    last_loop = which
+    starts = None
+    if startStates is not None and len(startStates) > 0:
+        if which != 'device':
+            raise ValueError("startStates= needs the device loop (loop='device')")
+        if len(startStates) != numTests:
+            raise ValueError('startStates must hold one state per game: %d for %d games' % (len(startStates), numTests))
+        from .Blackbird import _packed_starts
+        starts = _packed_starts(model1, startStates)
     game = model1.Game
     game_id = game.GAME_ID
     info = _lib.game_info(game_id)
@@ -82,6 +152,8 @@ def TestModelsBatched(model1, model2, temp, numTests, playLimit=None, first=None
             raise ValueError('Not enough information to decide a stop time.')
         sides.append(_Searcher(m, game_id, numTests, sims, seconds))
     try:
+        if which == 'device':
+            return _device_arena(sides, game_id, temp, numTests, first, starts)
         states = np.repeat(_lib.game_initial(game_id), numTests, axis=0)   # packed boards, host side
         alive = np.ones(numTests, dtype=bool)
         result = np.zeros(numTests, dtype=np.int32)

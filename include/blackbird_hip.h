@@ -363,6 +363,48 @@ int bb_examples_fetch_games(bb_engine *e, int n, const int32_t *game_ids, void *
 int bb_examples_device(bb_engine *e, void **records_out, uint64_t *bytes_out, uint64_t *record_bytes_out,
                        int32_t **game_hdr_out);
 
+/* ---- the arena on the device: Blackbird.TestModels (Blackbird.py:177-216) without the host in the loop ------------ */
+/* An arena plays n_games head-to-head games between two engines, `a` (model1) and `b` (model2), one game per slot index, and keeps
+ * per game the packed state, whose turn it is, the result and a move log on the device.  A ply of a live game is the reference's
+ * loop body: the mover -- a and b alternate every ply whatever state.Player says (Blackbird.py:196-201), DragonChess's W, W, B
+ * order included -- primes its slot on its first turn (DropRoot + FindMove's `Root is None` branch, MCTS.py:141-144, 184-186, game
+ * id = the slot index), runs its engine's sims_per_move simulations on that slot alone through the structure
+ * bb_run_sims_structure reports (_runMCTS, MCTS.py:284-303), picks the move as bb_sample_moves(e, temp, u = NULL) does
+ * (_selectAction, MCTS.py:335-338; the Philox draw of (engine seed, game id, ply) when temp != 0), the move is applied, every
+ * primed side follows with MoveRoot (Blackbird.py:198-200) and Winner() is asked with no previous action (Blackbird.py:202).  The
+ * other side's slot, and every slot of a finished game, is not touched.  Trees, counters and results are those of the same
+ * sequence made through bb_set_roots / bb_run_sims_masked / bb_sample_moves / bb_move_roots, bit for bit.
+ * Both sides' searches of one ply are enqueued on their engines' own streams and joined with events before the move, so they may
+ * overlap; nothing is allocated and nothing waits on the host between plies.
+ * The engines are BORROWED: they must outlive the arena, and between bb_arena_begin and the last bb_arena_fetch of a run calling
+ * the search or self-play entry points on them (bb_set_roots, bb_run_sims*, bb_sample_moves, bb_move_roots, bb_selfplay_*) is not
+ * supported.  bb_get_counters, bb_node_view / bb_node_edges and bb_get_root_states after a bb_arena_status are fine. */
+typedef struct bb_arena bb_arena;
+/* log_plies: moves logged per game (later moves are played, not logged).  BB_ERR_ARG, before any device call: a null pointer,
+ * a == b, engines of different games, n_slots or devices, log_plies < 0. */
+int bb_arena_create(bb_engine *a, bb_engine *b, int log_plies, bb_arena **out);
+/* Start n_games games (1 <= n_games <= n_slots; the slots beyond stay idle).  a_first[n_games] (host memory, required): a moves
+ * first in game i, the coin of Blackbird.py:187-193.  start_states: host memory, n_games packed states, or NULL for `Game()`
+ * (Blackbird.py:191); checked as bb_selfplay_set_starts checks its table -- BB_ERR_ARG naming the first index whose game is
+ * already over, has no legal move or (DragonChess) more than S legal moves.  temp >= 0 (TestModels' temp, handed to FindMove).
+ * Both engines' slots count as unprimed again: DropRoot at the top of every game (Blackbird.py:189-190).  Waits for both engines.
+ * BB_ERR_WEIGHTS: a network engine without weights.  BB_ERR_ARG: an engine with fewer than 2 simulations per move and
+ * temp != 0 (MCTS.py:336-338, the rule of bb_selfplay_begin), or any argument outside the above. */
+int bb_arena_begin(bb_arena *ar, int n_games, const uint8_t *a_first, const void *start_states, double temp);
+/* Enqueue `plies` plies of every live game (Blackbird.py:195-203).  Asynchronous: no host synchronisation inside or between the
+ * plies; a finished game costs masked-out lanes only. */
+int bb_arena_step(bb_arena *ar, int plies);
+/* Wait for both engines; *alive_out = games still running.  BB_ERR_CAPACITY if either engine's overflow counter is non-zero (a
+ * search tree outgrew its node pool), BB_ERR_NAN if a game stopped on a negative action ('probabilities contain NaN',
+ * MCTS.py:336-338) or an illegal move, else BB_OK. */
+int bb_arena_status(bb_arena *ar, int *alive_out);
+/* result_out[n_games]: +1 / 0 / -1 for a's win / draw / loss (Blackbird.py:204-212; 0 while the game runs); plies_out[n_games]:
+ * moves made; moves_out[n_games][log_plies]: the actions, -1 padded; states_out: n_games packed current states.  Any output may
+ * be NULL.  Waits for both engines, so it also works in the middle of a run. */
+int bb_arena_fetch(bb_arena *ar, int8_t *result_out, int32_t *plies_out, int32_t *moves_out, void *states_out);
+/* Waits for both engines and frees the arena's own memory; the engines stay.  NULL: BB_OK. */
+int bb_arena_destroy(bb_arena *ar);
+
 /* ---- training batches from example records, on the device ------------------------------------ */
 /* What TrainWithExamples stacks per batch (Blackbird.py:300-308: AsInputArray planes, the MCTS policy, z), after the float32
  * conversion of the loss's inputs -- formed where the records are, with nothing staged through the host.  Stateless; ALL

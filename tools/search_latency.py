@@ -24,9 +24,18 @@ or, with `--kind dynamic`, a plain DynamicMCTS, on the same two figures at the s
 this build, against the other checkout's lock-step with `--tree`, and for a dense game against `wave_plain`: the wave kernel whose
 lane 0 alone plays the leaf out (BB_SW_ROLLOUT_PLAIN=1) instead of the lane-parallel draws.
 
+`--arena-loop host|device` measures the WHOLE ARENA of `--games` games between two networks through the two loops of
+blackbird_amd/arena.py: `host` (moves read back every ply) and `device` (the match loop enqueued on the GPU, bb_arena_*), with the
+engines searching through `--launch lockstep|wave`.  `device` alternates the device loop with the host loop of this build, `host`
+runs the host loop alone; `--tree` adds the other checkout's host loop (the parent commit's: untouched code must not have moved).
+The games are played at `--temp 0` by default: no move is drawn, so every loop plays the very same games and the times compare
+like for like (the loops draw their moves from different streams otherwise, and an arena is as long as its longest game).
+DragonChess plays `--plies` plies (default 40) of every game, as in `--cache`.
+
 usage: python tools/search_latency.py [--game c4|dc] [--rounds 5] [--sims 800|400] [--games 64] [--reps 20] [--tree other/checkout]
        python tools/search_latency.py --cache [--game c4|dc] [--rounds 5] [--sims ..] [--games 64] [--plies 40] [--tree other/checkout]
        python tools/search_latency.py --evaluator rollout [--game c4|dc] [--kind fixed|dynamic] [--depth 10] [--rounds 5] [--reps 20] [--tree ..]
+       python tools/search_latency.py --arena-loop host|device [--launch lockstep|wave] [--game c4|dc] [--rounds 5] [--sims ..] [--games 64] [--temp 0] [--tree ..]
 """
 import argparse
 import json
@@ -195,7 +204,80 @@ def child_cache(a):
                       "game_evals": game_evals, "arena_ms": arena_ms, "arena_hit_share": arena_share, "arena_evals": arena_evals}))
 
 
-def capped_arena(np, _lib, players, games, sims, plies):
+def child_arena(a):
+    """One run of the --arena-loop leg: a whole arena through the loop a.child names ('host' or 'device')."""
+    sys.path.insert(0, os.path.abspath(a.tree) if a.tree else ROOT)
+    os.chdir(tempfile.mkdtemp())
+    import numpy as np
+    from blackbird_amd import Blackbird, Connect4, DragonChess, _lib, arena
+    from blackbird_amd.MCTS import MCTS
+    MCTS.SearchLaunch = a.launch
+    cfg = {"blocks": 4, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
+           "policy": {"dirichlet": {"alpha": 0.2, "epsilon": 0.3}}, "training": {"optimizer": "adam"}}
+    cls = DragonChess.BoardState if a.game == "dc" else Connect4.BoardState
+    np.random.seed(0)
+    p1 = Blackbird.Model(cls, "p1", {"explorationRate": 0.85, "playLimit": a.sims}, cfg)
+    p2 = Blackbird.Model(cls, "p2", {"explorationRate": 0.85, "playLimit": a.sims}, cfg)
+    warm = Blackbird.Model(cls, "w", {"explorationRate": 0.85, "playLimit": 16}, cfg)   # heat-up: code objects, clocks; its own engine
+    for _ in range(3):
+        warm.DropRoot()
+        warm.FindMove(cls(), 1.0)
+    first = np.arange(a.games) % 2 == 0
+    np.random.seed(2)   # (the engines' seeds come from numpy's state: the same in every run)
+    t = time.perf_counter()
+    if a.game == "dc":   # (a DragonChess game outlasts the arena's node pools: a.plies plies of every game)
+        if a.child == "device":
+            plies = device_capped_arena(np, _lib, (p1, p2), a.games, a.sims, a.plies, a.temp)
+        else:
+            capped_arena(np, _lib, (p1, p2), a.games, a.sims, a.plies, a.temp)
+            plies = a.plies
+        results = None
+    else:
+        kw = {"loop": a.child} if a.child == "device" else {}   # (another checkout has the host loop only, and no such argument)
+        res = arena.TestModelsBatched(p1, p2, a.temp, a.games, playLimit=a.sims, first=first, **kw)
+        plies, results = None, [int((res == v).sum()) for v in (1, 0, -1)]
+    arena_ms = (time.perf_counter() - t) * 1e3
+    print(json.dumps({"run": a.child, "game": a.game, "launch": a.launch, "tree": a.tree or "-", "arena_ms": arena_ms, "plies": plies,
+                      "wins_draws_losses": results}))
+
+
+def device_capped_arena(np, _lib, players, games, sims, plies, temp):
+    """capped_arena through the arena on the device: the first side moves first in every game."""
+    game_id = players[0].Game.GAME_ID
+    engines = []
+    for m in players:
+        eng = m._make_engine(game_id, games, sims, node_capacity=sims * (plies // 2 + 2) + 64)
+        m._after_engine_created(eng)
+        engines.append(eng)
+    ar = _lib.Arena(engines[0], engines[1])
+    ar.begin(np.ones(games, dtype=bool), temp)
+    ar.step(plies)
+    ar.status()
+    done = int(ar.fetch()["plies"].max())
+    ar.close()
+    for e in engines:
+        e.close()
+    return done
+
+
+def main_arena(a):
+    run(a, "host")   # heat-up, not counted
+    runs = {"device": [], "host": [], "other_host": []}
+    order = ([("device", "device", None)] if a.arena_loop == "device" else []) + [("host", "host", None)]
+    order += [("other_host", "host", a.tree)] if a.tree else []
+    for k in range(a.rounds):   # (the order rotates: no loop always runs right after the same other one)
+        for name, which, tree in order[k % len(order):] + order[:k % len(order)]:
+            runs[name].append(run(a, which, tree))
+    res = {"game": a.game, "sims": a.sims, "games": a.games, "rounds": a.rounds, "launch": a.launch, "temp": a.temp,
+           "plies_cap": a.plies if a.game == "dc" else None}
+    for name, rs in runs.items():
+        v = [r["arena_ms"] for r in rs]
+        if v:
+            res[f"{name}_arena_ms"] = {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+    print(json.dumps(res))
+
+
+def capped_arena(np, _lib, players, games, sims, plies, temp=1.0):
     """What arena.TestModelsBatched does with its two engines, for at most `plies` plies: the side to move searches all its
     games (run_sims under a mask), samples its moves, and both sides follow with move_roots."""
     game_id = players[0].Game.GAME_ID
@@ -209,7 +291,7 @@ def capped_arena(np, _lib, players, games, sims, plies):
     for ply in range(plies):
         eng = engines[ply % 2]
         eng.run_sims(sims, mask=np.ones(games, dtype=np.uint8))
-        act = eng.sample_moves(1.0, rng.random_sample(games))["action"]
+        act = eng.sample_moves(temp, rng.random_sample(games))["action"]
         act = np.where(act >= 0, act, -1).astype(np.int32)
         if (act < 0).all():
             break
@@ -240,6 +322,7 @@ def run(a, which, tree=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", which, "--game", a.game, "--sims", str(a.sims), "--games", str(a.games),
            "--reps", str(a.reps), "--plies", str(a.plies), "--evaluator", a.evaluator, "--kind", a.kind, "--depth", str(a.depth)]
     cmd += (["--tree", tree] if tree else []) + (["--cache"] if a.cache else [])
+    cmd += ["--arena-loop", a.arena_loop, "--launch", a.launch, "--temp", str(a.temp)] if a.arena_loop else []
     env = dict(os.environ, BB_SW_ROLLOUT_PLAIN="1" if which == "wave_plain" else "0")
     out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout, check=True, env=env).stdout.decode()
     r = json.loads(out.strip().splitlines()[-1])
@@ -261,12 +344,17 @@ def main():
     p.add_argument("--evaluator", choices=["net", "rollout"], default="net", help="rollout: FixedMCTS / DynamicMCTS instead of a Model")
     p.add_argument("--kind", choices=["fixed", "dynamic"], default="fixed", help="--evaluator rollout: the searcher")
     p.add_argument("--depth", type=int, default=10, help="--evaluator rollout --kind fixed: maxDepth")
+    p.add_argument("--arena-loop", choices=["host", "device"], default=None, help="the whole arena through the host / the device loop")
+    p.add_argument("--launch", choices=["lockstep", "wave"], default="lockstep", help="--arena-loop: MCTS.SearchLaunch of the engines")
+    p.add_argument("--temp", type=float, default=0.0, help="--arena-loop: TestModels' temp (0: every loop plays the same games)")
     p.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
     if a.sims is None:
         a.sims = 400 if a.game == "dc" else 800
     if a.plies is None:
         a.plies = 40 if a.game == "dc" else 43
+    if a.arena_loop and not a.cache:
+        return child_arena(a) if a.child else main_arena(a)
     if a.child:
         return child_cache(a) if a.cache else child_rollout(a) if a.evaluator == "rollout" else child(a)
     if a.cache:
