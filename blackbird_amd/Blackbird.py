@@ -168,6 +168,19 @@ def _side_to_move(game, packed):
     return int((int(np.asarray(packed).view(np.uint64).reshape(-1)[0]) >> 56) & 3)
 
 
+def _parked_without_probabilities(eng, temp):
+    """Whether a slot of a stopped self-play run sits on a root whose visit counts give no probabilities at `temp`: N ** (1 / temp)
+    overflowed (inf / inf), which parks the slot (bb_selfplay_begin) where the reference's np.random.choice raises ValueError."""
+    if temp == 0:
+        return False
+    for slot in range(eng.n_slots):
+        plays = eng.node_edges(slot)['plays'].astype(np.float64)
+        with np.errstate(over='ignore'):
+            if plays.sum() > 0 and not np.isfinite(np.sum(plays ** (1.0 / temp))):
+                return True
+    return False
+
+
 def GenerateTrainingSamples(model, nGames, temp, startStates=None):
     """Blackbird.py:219-268.  Raises ValueError if nGames <= 0.  With model.KeepDeviceExamples the run's records also stay on
     the GPU for TrainWithDeviceExamples (not under a time limit: _timed_selfplay leaves no engine records).
@@ -247,6 +260,8 @@ def GenerateTrainingSamples(model, nGames, temp, startStates=None):
                 pending = None
             hdr = eng.selfplay_headers(0, nGames)   # (waits for the launch)
             if eng.counters()['overflow']:  # pool exhausted, a parked slot or an aborted launch: the games would never finish
+                if _parked_without_probabilities(eng, temp):
+                    raise ValueError('probabilities contain NaN')   # np.random.choice in the reference's FindMove
                 raise _lib.BlackbirdHipError('self-play stopped: a search tree outgrew its node pool or a launch was aborted')
             new = np.nonzero((hdr[:, 3] != 0) & ~seen)[0]
             if len(new):

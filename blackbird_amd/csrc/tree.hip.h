@@ -658,7 +658,7 @@ __device__ __forceinline__ int choose_move(const TreeDev &d, int g, int lane, do
     double allp = 0.0;
 #pragma unroll
     for (int k = 0; k < A; k++) allp += ws[k];
-    if (!(allp > 0.0)) return -4;
+    if (!(allp > 0.0 && allp < INFINITY)) return -4; // 0 / 0, or N^(1/temp) overflowed: inf / inf = NaN in the reference
     double last = 0.0;
 #pragma unroll
     for (int k = 0; k < A; k++) last += __ddiv_rn(ws[k], allp);
@@ -944,7 +944,7 @@ __device__ __forceinline__ void selfplay_move_body(const TreeDev &d, int g, int 
     int total, Ni;
     float Wi;
     int act = choose_move<G>(d, g, lane, d.temp, u, total, Ni, Wi);
-    if (act < 0) { // cannot happen with sims_per_move >= 2; park the slot
+    if (act < 0) { // no probabilities (choose_move: N^(1/temp) overflowed; 0 / 0 needs sims_per_move < 2, which bb_selfplay_begin refuses): park the slot
         if (lane == 0) {
             d.game_lid[g] = -1;
             d.ctr[(size_t)g * 8 + 6] += 1;

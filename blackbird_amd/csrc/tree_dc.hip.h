@@ -890,7 +890,7 @@ __device__ int dc_choose_move(const TreeDev &d, const DCEdges &E, int g, int lan
                 double c = (double)E.e[base + k].N;
                 allp += (it == 1.0) ? c : pow(c, it);
             }
-            if (!(allp > 0.0)) {
+            if (!(allp > 0.0 && allp < INFINITY)) { // 0 / 0, or N^(1/temp) overflowed: inf / inf = NaN in the reference
                 act = -4;
             } else {
                 double last = 0.0;

@@ -281,7 +281,8 @@ int bb_search_rollouts(bb_engine *e, int on);
  * u[n_slots] uniforms in [0,1) for np.random.choice's law, or NULL to draw Philox(seed, game_id, ply).
  * Outputs per slot (S = bb_game_info.S): action (or BB_ERR_NAN), root_winrate = Root.WinRate(),
  * root_plays, child_action[S] (-1 pad), child_plays[S], child_value[S] (Node.Value of the child, f32).
- * Any output pointer may be NULL. */
+ * Any output pointer may be NULL.  action is BB_ERR_NAN where sum(N ^ (1 / temp)) is not a positive finite number: 0 / 0, or inf / inf
+ * when a power overflows (np.random.choice raises ValueError there). */
 int bb_sample_moves(bb_engine *e, double temp, const double *u, int32_t *action_out,
                     float *root_winrate_out, int32_t *root_plays_out, int32_t *child_action_out,
                     int32_t *child_plays_out, float *child_value_out);
@@ -314,7 +315,8 @@ int bb_node_edges(bb_engine *e, int slot, int node, int32_t *child_action_out, i
 int bb_set_rng_stream(bb_engine *e, uint64_t seed, uint32_t first_game_id);
 
 /* ---- batched self-play: Blackbird.GenerateTrainingSamples (Blackbird.py:219-268) ------------- */
-/* Start `n_games` games (local ids 0..n_games-1; slot g plays ids g, g+n_slots, ...). */
+/* Start `n_games` games (local ids 0..n_games-1; slot g plays ids g, g+n_slots, ...).  A slot whose move has no probabilities
+ * (bb_sample_moves' BB_ERR_NAN rule, e.g. N ^ (1 / temp) overflows) stops without a record and counts in bb_counters.overflow. */
 int bb_selfplay_begin(bb_engine *e, int n_games, double temp);
 /* Start positions for self-play -- an extension: the reference starts every game from `model.Game()` (Blackbird.py:238-251).
  * states: HOST memory, n packed states of the engine's game (the layout and state_bytes of bb_set_roots).  The engine copies the

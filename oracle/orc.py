@@ -282,6 +282,11 @@ class Search:
                     winrates=wrs, root_plays=rp.value)
 
 
+def u53(seed, game_id, ply):
+    """The move draw of (seed, game id, ply): what find_move uses for u < 0, and the engine's bb_u53."""
+    return float(lib().orc_u53(int(seed), int(game_id), int(ply)))
+
+
 def sample_action(plays, temp, u):
     plays = np.ascontiguousarray(plays, dtype=np.float64)
     return lib().orc_sample_action(plays.ctypes.data, len(plays), temp, u)

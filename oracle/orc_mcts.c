@@ -341,7 +341,9 @@ int orc_sample_action(const double *child_plays, int A, double temp, double u) {
     double it = 1.0 / temp;
     double allPlays = 0.0;
     for (int a = 0; a < A; a++) allPlays += (it == 1.0) ? child_plays[a] : pow(child_plays[a], it);
-    if (!(allPlays > 0.0)) return -3; /* ValueError: probabilities contain NaN */
+    /* ValueError: probabilities contain NaN -- 0 / 0, or a term or the sum overflowed (inf / inf; with finite terms and an
+     * infinite sum every p is 0 and np.random.choice refuses "probabilities do not sum to 1": the same refusal here) */
+    if (!(allPlays > 0.0 && allPlays < INFINITY)) return -3;
     double cdf_last = 0.0;
     for (int a = 0; a < A; a++) {
         double p = ((it == 1.0) ? child_plays[a] : pow(child_plays[a], it)) / allPlays;

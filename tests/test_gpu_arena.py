@@ -68,6 +68,7 @@ def test_batched_arena_against_random_player_and_coin(tmp_path, monkeypatch):
 from blackbird_amd import _lib  # noqa: E402
 from blackbird_amd.DynamicMCTS import DynamicMCTS  # noqa: E402
 from blackbird_amd.FixedMCTS import FixedMCTS  # noqa: E402
+from tests import arena_cases as AC  # noqa: E402
 
 
 class _HashPlayer(DynamicMCTS):
@@ -96,57 +97,27 @@ class _RolloutFixed(FixedMCTS):
                            seed=77, **kw)
 
 
-def _oracle_arena(orc, og, cfgs, sims, first, temp, draw):
-    """Blackbird.TestModels (Blackbird.py:177-216) for every game with two oracle searchers: the mover calls FindMove,
-    BOTH call MoveRoot after every move; +1 / 0 / -1 from side 0's point of view.  Plies advance in step across games
-    so that the uniforms are consumed in the batched arena's order (side 0's movers in game order, then side 1's)."""
-    n = len(first)
-    search = [[orc.Search(cfgs[k], g) for g in range(n)] for k in range(2)]
-    state = [orc.new_state(og) for _ in range(n)]
-    to0 = [bool(f) for f in first]
-    alive = [True] * n
-    result = [0] * n
-    while any(alive):
-        for k in range(2):
-            movers = [g for g in range(n) if alive[g] and to0[g] == (k == 0)]
-            us = draw(len(movers)) if (temp != 0 and movers) else [None] * len(movers)
-            for g, u in zip(movers, us):
-                r = search[k][g].find_move(state[g], temp, sims[k], u=-1.0 if u is None else float(u))
-                state[g] = r["next"]
-        for g in range(n):
-            if not alive[g]:
-                continue
-            search[0][g].move_root(state[g])
-            search[1][g].move_root(state[g])
-            to0[g] = not to0[g]
-            w = orc.winner(og, state[g])
-            if w is not None:
-                alive[g] = False
-                mine = 1 if first[g] else 2
-                result[g] = 0 if w == 0 else (1 if w == mine else -1)
-    return np.array(result)
-
-
-@pytest.mark.parametrize("key,temp", [("c4", 0), ("ttt", 0), ("c4", 1.0), ("ttt_rollout", 0), ("c4_rollout", 0)])
+@pytest.mark.parametrize("key,temp", [("c4", 0), ("ttt", 0), ("c4", 1.0), ("ttt_rollout", 0), ("c4_rollout", 0), ("c4", 0.1),
+                                      ("ttt", 0.1)])
 def test_batched_arena_equals_two_searcher_oracle(orc, key, temp):
     """TestModelsBatched against the oracle's own two-searcher game loop, game by game: hash-evaluator DynamicMCTS with
-    different salts / exploration rates on the two sides (exact), at temp 0 (PUCT argmax move) and temp 1 (sampled
-    moves, same uniforms); and DynamicMCTS against the rollout FixedMCTS that TestGood uses, on TicTacToe and on Connect4."""
+    different salts / exploration rates on the two sides (exact), at temp 0 (PUCT argmax move), temp 1 (sampled moves, same
+    uniforms) and the exploitation temperature 0.1 of every evaluation game (N ** 10 through pow; tests/test_sample_temp_cpu.py
+    holds every draw of these two cases 2^-40 away from the boundaries of its cdf, so the comparison stays exact); and
+    DynamicMCTS against the rollout FixedMCTS that TestGood uses, on TicTacToe and on Connect4."""
     game = TicTacToe.BoardState if key.startswith("ttt") else Connect4.BoardState
     og = 1 if key.startswith("ttt") else 0
-    first = np.array([True, False, False, True, True, False, True, False, False, True, True])
-    sims = (30, 20)
+    first, sims = AC.FIRST, AC.SIMS
     p1 = _HashPlayer(game, 11, explorationRate=0.85, playLimit=sims[0])
-    cfg1 = orc.make_cfg(og, evaluator=orc.EVAL_HASH, salt=11, c_puct=0.85, seed=77)
+    cfg1, cfg2 = AC.hash_cfgs(orc, og)
     if key.endswith("_rollout"):
         p2 = _RolloutFixed(game, maxDepth=10, explorationRate=0.85, playLimit=sims[1])
         cfg2 = orc.make_cfg(og, kind=orc.FIXED, max_depth=10, evaluator=orc.EVAL_ROLLOUT, c_puct=0.85, seed=77)
     else:
         p2 = _HashPlayer(game, 22, explorationRate=1.3, playLimit=sims[1])
-        cfg2 = orc.make_cfg(og, evaluator=orc.EVAL_HASH, salt=22, c_puct=1.3, seed=77)
-    rng_a, rng_b = np.random.RandomState(5), np.random.RandomState(5)
+    rng_a, rng_b = np.random.RandomState(AC.UNIFORM_SEED), np.random.RandomState(AC.UNIFORM_SEED)
     got = TestModelsBatched(p1, p2, temp, len(first), first=first, uniforms=rng_a.random_sample)
-    want = _oracle_arena(orc, og, (cfg1, cfg2), sims, first, temp, rng_b.random_sample)
+    want = AC.oracle_arena(orc, og, (cfg1, cfg2), sims, first, temp, rng_b.random_sample)
     assert np.array_equal(got, want), (got, want)
 
 

@@ -158,11 +158,12 @@ SHAPES = {"mixed8": (MIXED, 8), "afirst8": ([True] * 8, 8), "one": ([False], 1),
 
 
 @pytest.mark.parametrize("shape", sorted(SHAPES))
-@pytest.mark.parametrize("temp", [0, 0.7])
+@pytest.mark.parametrize("temp", [0, 0.7, 0.1])
 @pytest.mark.parametrize("game", [Connect4.BoardState, TicTacToe.BoardState], ids=["c4", "ttt"])
 def test_hash_players_equal_the_stepwise_statement(game, temp, shape):
     """Two hash-evaluator searchers (two salts, two exploration rates), 24 simulations, lock-step: mixed first movers, side b's
-    mask empty at ply 0, a single game, and fewer games than slots."""
+    mask empty at ply 0, a single game, and fewer games than slots.  temp 0.1 is the exploitation temperature every evaluation
+    game is played at (the law itself is held against the oracle in tests/test_gpu_arena.py and tests/test_gpu_sample_temp.py)."""
     first, n_slots = SHAPES[shape]
     players = (_HashPlayer(game, 11), _HashPlayer(game, 22, c_puct=1.3))
     want, _ = _check(players, first, temp, n_slots=n_slots, structure=(_lib.LAUNCH_LOCKSTEP,) * 2)

@@ -54,12 +54,12 @@ def starts_of(game):
     return _starts[game]
 
 
-def _play(eng, n_games, starts="keep", step=3):
-    """Play n_games to the end; starts: a packed table to set first, None to clear, "keep" to leave the engine as it is."""
+def _play(eng, n_games, starts="keep", step=3, temp=1.0):
+    """Play n_games to the end at `temp`; starts: a packed table to set first, None to clear, "keep" to leave the engine as it is."""
     if not isinstance(starts, str):
         eng.selfplay_set_starts(starts)
     eng.reset_counters()
-    eng.selfplay_begin(n_games, 1.0)
+    eng.selfplay_begin(n_games, temp)
     guard = 0
     while not eng.selfplay_done()[0]:
         eng.selfplay_step(step)
@@ -96,6 +96,17 @@ def assert_first_records_are(game, out, starts, first_id=0):
         assert r["state"].tobytes() == starts[k % len(starts)].tobytes(), k
 
 
+def assert_game_is_the_oracles(game, out, k, o, first_id):
+    """Game k's records, header and winner against one oracle game."""
+    r = out["rec"][out["offs"][k]:out["offs"][k + 1]]
+    assert len(r) == o["n"] and out["win"][k] == o["winner"], (k, len(r), o["n"], out["win"][k], o["winner"])
+    assert out["hdr"][k].tolist() == [o["n"], o["winner"], o["n"] - 1, 1], k
+    assert (r["game_id"] == first_id + k).all() and np.array_equal(r["ply"], np.arange(len(r))), k
+    assert np.array_equal(_lib.game_encode(game, _states(game, r)), o["boards"]), k
+    assert np.array_equal(_pi(game, r), o["pi"]), k
+    assert np.array_equal(r["player"], o["player"]) and np.array_equal(r["z"].astype(np.float32), o["z"]), k
+
+
 def assert_games_are_the_oracles(orc, game, out, starts, cfg_of, first_id, sims, max_plies):
     """Every game's records against oracle_selfplay_from(starts[k % n]); returns the oracle's simulation total."""
     og = OG[game]
@@ -103,13 +114,7 @@ def assert_games_are_the_oracles(orc, game, out, starts, cfg_of, first_id, sims,
     for k in range(len(out["win"])):
         start = SC.orc_state_from_packed(orc, og, game, starts[k % len(starts)])
         o = SC.oracle_selfplay_from(orc, cfg_of(k), first_id + k, start, 1.0, sims, max_plies)
-        r = out["rec"][out["offs"][k]:out["offs"][k + 1]]
-        assert len(r) == o["n"] and out["win"][k] == o["winner"], (k, len(r), o["n"], out["win"][k], o["winner"])
-        assert out["hdr"][k].tolist() == [o["n"], o["winner"], o["n"] - 1, 1], k
-        assert (r["game_id"] == first_id + k).all() and np.array_equal(r["ply"], np.arange(len(r))), k
-        assert np.array_equal(_lib.game_encode(game, _states(game, r)), o["boards"]), k
-        assert np.array_equal(_pi(game, r), o["pi"]), k
-        assert np.array_equal(r["player"], o["player"]) and np.array_equal(r["z"].astype(np.float32), o["z"]), k
+        assert_game_is_the_oracles(game, out, k, o, first_id)
         sims_total += o["stats"].sims
     return sims_total
 

@@ -26,13 +26,14 @@ CSRC = os.path.join(ROOT, "blackbird_amd", "csrc")
 
 # ---- the yardstick ---------------------------------------------------------------------------------------------------------------
 def oracle_selfplay_from(orc, cfg, game_id, start, temp, play_limit, max_plies):
-    """One self-play game of the oracle from `start` (an orc.State; not changed): the dict orc.selfplay_game returns."""
+    """One self-play game of the oracle from `start` (an orc.State; not changed): the dict orc.selfplay_game returns, and per
+    move the root's child visit counts (`plays`) and the keyed draw of (seed, game id, ply) (`u`; not consumed at temp 0)."""
     game = cfg.game
     A = orc.dims(game)[3]
     search = orc.Search(cfg, game_id)
     search.drop_root()
     st = start.copy()
-    boards, pi, player, actions = [], [], [], []
+    boards, pi, player, actions, plays, us = [], [], [], [], [], []
     winner, n = None, 0
     while winner is None and n < max_plies:
         o = search.find_move(st, temp, play_limit, u=-1.0, ply=n)
@@ -40,6 +41,8 @@ def oracle_selfplay_from(orc, cfg, game_id, start, temp, play_limit, max_plies):
         pi.append(o["prob"])
         player.append(st.player)
         actions.append(o["action"])
+        plays.append(o["plays"])
+        us.append(orc.u53(cfg.seed, game_id, n))
         st = o["next"]
         search.move_root(st)
         winner = orc.winner(game, st)            # lastAction is always None (Blackbird.py:242,253)
@@ -51,7 +54,8 @@ def oracle_selfplay_from(orc, cfg, game_id, start, temp, play_limit, max_plies):
     w = -1 if winner is None else int(winner)
     z = np.zeros(n + 1, dtype=np.float32) if w <= 0 else np.where(player == w, 1.0, -1.0).astype(np.float32)  # :260-264
     return dict(n=n + 1, boards=np.stack(boards), pi=np.stack(pi), player=player, z=z,
-                actions=np.array(actions, dtype=np.int32), winner=w, stats=search.stats())
+                actions=np.array(actions, dtype=np.int32), winner=w, stats=search.stats(), plays=np.array(plays).reshape(n, A),
+                u=np.array(us))
 
 
 def orc_state_from_packed(orc, og, game, packed):
