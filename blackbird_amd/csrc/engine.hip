@@ -93,6 +93,8 @@ struct DevBuf {
 };
 
 static inline int nblk(size_t n, int per = 256) { return (int)((n + per - 1) / per); }
+// grid and block of every one-wave-per-slot kernel (search_wave*.hip.h, selfplay_wave.hip.h): <<<SW_GRID(d), 0, stream>>>
+#define SW_GRID(d) nblk((d).n_slots, SW_WAVES), 64 * SW_WAVES
 
 // ---- launch tables ---------------------------------------------------------------------------------------------
 // THE place that knows which kernel a game family launches for a step of the lock-step engine, and on what grid: the primary template
@@ -117,20 +119,19 @@ struct Launch {
     // owns a table): the network's instantiation that probes and fills d.eval_cache, for a game with a one-word key.
     // false: this family has no such kernel.
     static bool search_wave(const TreeDev &d, const DCEdges &, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int noise, bool cache) {
-        const int blocks = (d.n_slots + SW_WAVES - 1) / SW_WAVES;
         if (d.evaluator == BB_EVAL_ROLLOUT) { // (bb_search_rollouts)
-            if (rollout_plain()) k_search_wave_rollout<G, false><<<blocks, 64 * SW_WAVES, 0, st>>>(d, sims);
-            else k_search_wave_rollout<G, true><<<blocks, 64 * SW_WAVES, 0, st>>>(d, sims);
+            if (rollout_plain()) k_search_wave_rollout<G, false><<<SW_GRID(d), 0, st>>>(d, sims);
+            else k_search_wave_rollout<G, true><<<SW_GRID(d), 0, st>>>(d, sims);
             return true;
         }
         if constexpr (G::CACHE_KEY) {
             if (x3.w0 && cache && d.eval_cache) {
-                k_search_wave<G, true, true><<<blocks, 64 * SW_WAVES, 0, st>>>(d, nd, x3, sims, noise);
+                k_search_wave<G, true, true><<<SW_GRID(d), 0, st>>>(d, nd, x3, sims, noise);
                 return true;
             }
         }
-        if (x3.w0) k_search_wave<G, true><<<blocks, 64 * SW_WAVES, 0, st>>>(d, nd, x3, sims, noise);
-        else k_search_wave<G, false><<<blocks, 64 * SW_WAVES, 0, st>>>(d, nd, x3, sims, 0);
+        if (x3.w0) k_search_wave<G, true><<<SW_GRID(d), 0, st>>>(d, nd, x3, sims, noise);
+        else k_search_wave<G, false><<<SW_GRID(d), 0, st>>>(d, nd, x3, sims, 0);
         return true;
     }
     static void hash(hipStream_t st, int n, const State *s, const uint32_t *game_id, uint64_t salt, int salt_per_game, uint32_t first_game_id, float *value, float *policy, int pstride) {
@@ -156,7 +157,7 @@ struct Launch {
     // PLAY_WAVE_ROLLOUT: `plies` times (`sims` steps of tree_step + rollout, then selfplay_move) as one launch with a wave per slot
     // (selfplay_wave.hip.h); move = 0: `sims` steps of one ply and no move
     static void selfplay_wave_rollout(const TreeDev &d, const DCEdges &, hipStream_t st, int plies, int sims, int move) {
-        k_selfplay_wave_rollout<G><<<(d.n_slots + SW_WAVES - 1) / SW_WAVES, 64 * SW_WAVES, 0, st>>>(d, plies, sims, move);
+        k_selfplay_wave_rollout<G><<<SW_GRID(d), 0, st>>>(d, plies, sims, move);
     }
     static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, float *boards, float *policy, float *value, int32_t *bad) {
         k_examples_to_batch<G><<<nblk((size_t)n * (G::H * G::W * G::C + G::A + 1)), 256, 0, st>>>(n_records, rec, n, index, boards, policy, value, bad);
@@ -173,13 +174,12 @@ struct Launch<DragonChess> {
     // its prior noise is mixed in at expansion: E.noise_on)
     static bool search_wave(const TreeDev &d, const DCEdges &E, hipStream_t st, int sims, const NetDev &nd, const NetX3 &x3, int, bool cache) {
         if (d.evaluator == BB_EVAL_ROLLOUT) { // (bb_search_rollouts)
-            k_dc_search_wave_rollout<<<(d.n_slots + SW_WAVES - 1) / SW_WAVES, 64 * SW_WAVES, 0, st>>>(d, E, sims);
+            k_dc_search_wave_rollout<<<SW_GRID(d), 0, st>>>(d, E, sims);
             return true;
         }
         if (!x3.w0 || nd.R > DC_RMAX || nd.head_floats > DC_HEAD_FLOATS) return false;
-        const int blocks = (d.n_slots + SW_WAVES - 1) / SW_WAVES;
-        if (cache && d.eval_cache) k_dc_search_wave_cached<<<blocks, 64 * SW_WAVES, 0, st>>>(d, E, nd, x3, sims);
-        else k_dc_search_wave<<<blocks, 64 * SW_WAVES, 0, st>>>(d, E, nd, x3, sims);
+        if (cache && d.eval_cache) k_dc_search_wave_cached<<<SW_GRID(d), 0, st>>>(d, E, nd, x3, sims);
+        else k_dc_search_wave<<<SW_GRID(d), 0, st>>>(d, E, nd, x3, sims);
         return true;
     }
     static void hash(hipStream_t st, int n, const State *s, const uint32_t *game_id, uint64_t salt, int salt_per_game, uint32_t first_game_id, float *value, float *policy, int pstride) {
@@ -203,7 +203,7 @@ struct Launch<DragonChess> {
     static void selfplay_begin(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_selfplay_begin<<<nblk(d.n_slots), 256, 0, st>>>(d, E); }
     static void selfplay_move(const TreeDev &d, const DCEdges &E, hipStream_t st) { k_dc_selfplay_move<<<nblk((size_t)d.n_slots * 64), 256, 0, st>>>(d, E); }
     static void selfplay_wave_rollout(const TreeDev &d, const DCEdges &E, hipStream_t st, int plies, int sims, int move) {
-        k_dc_selfplay_wave_rollout<<<(d.n_slots + SW_WAVES - 1) / SW_WAVES, 64 * SW_WAVES, 0, st>>>(d, E, plies, sims, move);
+        k_dc_selfplay_wave_rollout<<<SW_GRID(d), 0, st>>>(d, E, plies, sims, move);
     }
     static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, float *boards, float *policy, float *value, int32_t *bad) {
         k_dc_examples_to_batch<<<n, 256, 0, st>>>(n_records, rec, index, boards, policy, value, bad);
@@ -1537,7 +1537,7 @@ static int selfplay_dc_fused(bb_engine *e, int plies) {
 template <class G>
 static int selfplay_wave_rollout(bb_engine *e, int plies) {
     const int sims = e->sims_now;
-    // (a full device holds 2 waves per SIMD of either kernel -- 189 / 228 VGPRs -- that is 2048 slots on 256 CUs; more slots run one
+    // (a full device holds 2 waves per SIMD of either kernel -- 186 / 214 VGPRs -- that is 2048 slots on 256 CUs; more slots run one
     // after another inside the launch, so the figure is divided by the number of such rounds)
     const int rounds = (e->dev.n_slots + 2047) / 2048;
     const int dflt = (G::GID == BB_GAME_DRAGONCHESS ? 512 : 65536) / rounds;

@@ -119,18 +119,15 @@ __device__ __forceinline__ float rollout_value_wave(typename G::State s, uint64_
     return w == 0 ? 0.5f : (player == w ? 1.0f : 0.0f);
 }
 
-// k_search_wave with the rollout evaluator: phase_apply -> phase_select -> the playout of the leaf in the slot's mailbox -> ..., and
-// the last simulation's apply.  A kernel of its own, so the hash and network instantiations above are compiled as they were; no LDS.
+// Up to `sims` simulations of slot g with the rollout evaluator: phase_apply -> phase_select -> the playout of the leaf in the slot's
+// mailbox -> ...; the last leaf stays pending, as between two lock-step launches.  THE simulation loop of both rollout wave kernels
+// of the dense games (k_search_wave_rollout below, k_selfplay_wave_rollout in selfplay_wave.hip.h), inlined into each.
 // The draws are keyed (game id, sim_serial - 1, 'ROLL', step) with sim_serial read after phase_select has advanced it -- what
 // k_rollout reads in the lock-step loop -- so the trees are the lock-step ones bit for bit (tests/test_gpu_search_wave_rollout.py).
 // LANES: rollout_value_wave; else lane 0 runs rollout_value, literally k_rollout's thread (the form the other was measured against).
 template <class G, bool LANES>
-__global__ void __launch_bounds__(64 * SW_WAVES) k_search_wave_rollout(TreeDev d, int sims) {
-    constexpr int S = G::S;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int g = blockIdx.x * SW_WAVES + wave;
-    if (g >= d.n_slots) return; // (whole waves leave: nothing here synchronises the workgroup)
-    const bool tree_lane = lane < S;
+__device__ __forceinline__ void sw_rollout_sims(const TreeDev &d, int g, int lane, int sims) {
+    const bool tree_lane = lane < G::S;
     for (int s = 0; s < sims; s++) {
         if (tree_lane) {
             phase_apply<G>(d, g, lane);
@@ -150,5 +147,15 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_search_wave_rollout(TreeDev d
         }
         __threadfence_block(); // the value is in the mailbox before phase_apply reads it
     }
-    if (tree_lane) phase_apply<G>(d, g, lane); // the last simulation's evaluation (no-op without a pending leaf)
+}
+
+// k_search_wave with the rollout evaluator: the simulations above and the last simulation's apply.  A kernel of its own, so the hash
+// and network instantiations above are compiled as they were; no LDS.
+template <class G, bool LANES>
+__global__ void __launch_bounds__(64 * SW_WAVES) k_search_wave_rollout(TreeDev d, int sims) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * SW_WAVES + wave;
+    if (g >= d.n_slots) return; // (whole waves leave: nothing here synchronises the workgroup)
+    sw_rollout_sims<G, LANES>(d, g, lane, sims);
+    if (lane < G::S) phase_apply<G>(d, g, lane); // the last simulation's evaluation (no-op without a pending leaf)
 }

@@ -159,22 +159,26 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave_cached(TreeDev
 // (d.priors_ones), the value travels through d.eval_value[g] as in the lock-step loop (no DCHeadLocal), and the draws are keyed (game
 // id, sim_serial - 1, 'ROLL', step) with sim_serial read after dc_phase_select has advanced it: what k_dc_rollout reads, so the same
 // trees bit for bit (tests/test_gpu_search_wave_rollout.py).  None of the network's LDS: the tree's per-wave scratch and the
-// descriptor copies only.  The phases are out of line and instances of this kernel alone (COPY = 1).
+// descriptor copies only.
+// The helpers below -- tree step, playout, last apply -- and the workgroup prologue serve BOTH rollout wave kernels: this one and
+// k_dc_selfplay_wave_rollout (selfplay_wave.hip.h), whose ply is this kernel's simulation loop and then a move.  The phases are
+// out of line and one set of instances for the two (DC_COPY_ROLLOUT_WAVE, tree_dc.hip.h), apart from those of the kernels above.
+// Self-play refuses track_ancestors engines, so there the tree step's ancestor walk (ANC, as k_dc_tree_step) finds no chain.
 // Returns the posted leaf (wave-uniform; < 0: none).
 __device__ __attribute__((noinline)) int dc_swr_tree(const TreeDev &d_, const DCEdges &E_, int g, int lane, float *tl) {
     const TreeDev &d = *as_lds(&d_);
     const DCEdges &E = *as_lds(&E_);
     tl = as_lds(tl);
-    dc_phase_apply<false, true, 1>(d, E, g, lane, tl);
+    dc_phase_apply<false, true, DC_COPY_ROLLOUT_WAVE>(d, E, g, lane, tl);
     __threadfence_block();
-    dc_phase_select<false, 1>(d, E, g, lane, tl);
+    dc_phase_select<false, DC_COPY_ROLLOUT_WAVE>(d, E, g, lane, tl);
     __threadfence_block(); // lane 0's mailbox stores before the other lanes' loads
     return __builtin_amdgcn_readfirstlane(as_global(d.pend_leaf)[g]);
 }
 __device__ __attribute__((noinline)) void dc_swr_apply(const TreeDev &d_, const DCEdges &E_, int g, int lane, float *tl) {
     const TreeDev &d = *as_lds(&d_);
     const DCEdges &E = *as_lds(&E_);
-    dc_phase_apply<false, true, 1>(d, E, g, lane, as_lds(tl));
+    dc_phase_apply<false, true, DC_COPY_ROLLOUT_WAVE>(d, E, g, lane, as_lds(tl));
     __threadfence_block();
 }
 __device__ __attribute__((noinline)) void dc_swr_rollout(const TreeDev &d_, int g, int lane) {
@@ -185,24 +189,39 @@ __device__ __attribute__((noinline)) void dc_swr_rollout(const TreeDev &d_, int 
     if (lane == 0) as_global(d.eval_value)[g] = v;
     __threadfence_block(); // the value is in the mailbox before dc_phase_apply reads it
 }
-__global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave_rollout(TreeDev d_arg, DCEdges E_arg, int sims) {
+// The workgroup prologue of a rollout wave kernel: the descriptors copied to LDS behind the one barrier of the kernel, then the
+// wave's lane, slot and tree scratch.  g < 0: a wave beyond n_slots, which leaves (nothing after the prologue synchronises the
+// workgroup).
+struct DCRolloutWave {
+    const TreeDev *d; // the LDS copies, as the out-of-line helpers take them
+    const DCEdges *E;
+    float *tl;
+    int g, lane;
+};
+__device__ __forceinline__ DCRolloutWave dc_swr_prologue(const TreeDev &d_arg, const DCEdges &E_arg) {
     __shared__ __attribute__((aligned(16))) float lds_all[SW_WAVES][DC_LDS_FLOATS];
     __shared__ TreeDev s_d;
     __shared__ DCEdges s_E;
-    if (threadIdx.x == 0) { // workgroup prologue: the one barrier of the kernel
+    if (threadIdx.x == 0) {
         s_d = d_arg;
         s_E = E_arg;
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int g = blockIdx.x * SW_WAVES + wv;
-    if (g >= d_arg.n_slots) return; // (whole waves leave: nothing below synchronises the workgroup)
-    float *tl = lds_all[wv];
-    bool pending = false; // (no leaf is pending on entry: see dc_search_wave_body)
+    const int wv = threadIdx.x >> 6, g = blockIdx.x * SW_WAVES + wv;
+    return {&s_d, &s_E, lds_all[wv], g < d_arg.n_slots ? g : -1, (int)(threadIdx.x & 63)};
+}
+// Up to `sims` simulations of the wave's slot; the last leaf stays pending.  Returns whether one is (wave-uniform).
+__device__ __forceinline__ bool dc_swr_sims(const DCRolloutWave &w, int sims) {
+    bool pending = false; // (no leaf is pending on entry, or the first tree step applies it: see dc_search_wave_body)
     for (int s = 0; s < sims; s++) {
-        pending = dc_swr_tree(s_d, s_E, g, lane, tl) >= 0;
+        pending = dc_swr_tree(*w.d, *w.E, w.g, w.lane, w.tl) >= 0;
         if (!pending) break; // (uniform) no game or no simulations left: every further step is a no-op (see the head of this file)
-        dc_swr_rollout(s_d, g, lane);
+        dc_swr_rollout(*w.d, w.g, w.lane);
     }
-    if (pending) dc_swr_apply(s_d, s_E, g, lane, tl); // the last simulation's evaluation
+    return pending;
+}
+__global__ void __launch_bounds__(64 * SW_WAVES) k_dc_search_wave_rollout(TreeDev d_arg, DCEdges E_arg, int sims) {
+    const DCRolloutWave w = dc_swr_prologue(d_arg, E_arg);
+    if (w.g < 0) return;
+    if (dc_swr_sims(w, sims)) dc_swr_apply(*w.d, *w.E, w.g, w.lane, w.tl); // the last simulation's evaluation
 }

@@ -23,34 +23,19 @@
 #include "search_wave.hip.h"
 #include "search_wave_dc.hip.h"
 
-// Connect4 and TicTacToe.  The fences are those of k_search_wave_rollout and k_selfplay_move; no LDS.  TreeDev stays a kernel
-// argument (SGPRs) and every helper is inlined (see search_wave.hip.h).
+// Connect4 and TicTacToe.  A ply's simulations are sw_rollout_sims (search_wave.hip.h), the loop k_search_wave_rollout runs; the
+// move's fences are those of k_selfplay_move; no LDS.  TreeDev stays a kernel argument (SGPRs) and every helper is inlined (see
+// search_wave.hip.h).
 template <class G>
 __global__ void __launch_bounds__(64 * SW_WAVES) k_selfplay_wave_rollout(TreeDev d, int plies, int sims, int move) {
-    constexpr int S = G::S;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int g = blockIdx.x * SW_WAVES + wave;
     if (g >= d.n_slots) return; // (whole waves leave: nothing here synchronises the workgroup)
-    const bool tree_lane = lane < S;
     for (int p = 0; p < plies; p++) {
         if (__builtin_amdgcn_readfirstlane(d.game_lid[g]) < 0) break; // (uniform) the slot has played its last game
-        for (int s = 0; s < sims; s++) {
-            if (tree_lane) {
-                phase_apply<G>(d, g, lane);
-                __threadfence_block();
-                phase_select<G>(d, g, lane);
-            }
-            __threadfence_block(); // lane 0's mailbox stores before the other lanes' loads
-            if (__builtin_amdgcn_readfirstlane(d.pend_leaf[g]) < 0) break; // (uniform) nothing posted: every further step is a no-op
-            const typename G::State st = ((const typename G::State *)d.leaf_state)[g];
-            const uint32_t gid = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.leaf_game_id[g]);
-            const uint32_t serial = (uint32_t)(__builtin_amdgcn_readfirstlane(d.sim_serial[g]) - 1);
-            const float v = rollout_value_wave<G>(st, d.seed, gid, serial, lane);
-            if (lane == 0) d.eval_value[g] = v;
-            __threadfence_block(); // the value is in the mailbox before phase_apply reads it
-        }
+        sw_rollout_sims<G, true>(d, g, lane, sims);
         if (!move) break; // (uniform) part of a ply: the leaf stays pending for the next launch
-        if (tree_lane) { // k_selfplay_move
+        if (lane < G::S) { // k_selfplay_move
             phase_apply<G>(d, g, lane);
             __threadfence_block();
             selfplay_move_body<G>(d, g, lane);
@@ -59,57 +44,24 @@ __global__ void __launch_bounds__(64 * SW_WAVES) k_selfplay_wave_rollout(TreeDev
     }
 }
 
-// DragonChess: the same loop with dc_phase_apply / dc_phase_select / dc_rollout_wave / dc_selfplay_move_body, on the per-wave tree
-// scratch and the LDS copies of the descriptors as in k_dc_search_wave_rollout.  The phases are out of line (inlined into one loop
-// body they spill: mega_dc.hip.h) and instances of this kernel alone (COPY = 2), so the existing kernels are compiled as they were.
-// Self-play refuses track_ancestors engines, so the tree step's ancestor walk (ANC, as k_dc_tree_step) finds no chain.
-// Returns the posted leaf (wave-uniform; < 0: none).
-__device__ __attribute__((noinline)) int dc_spw_tree(const TreeDev &d_, const DCEdges &E_, int g, int lane, float *tl) {
-    const TreeDev &d = *as_lds(&d_);
-    const DCEdges &E = *as_lds(&E_);
-    tl = as_lds(tl);
-    dc_phase_apply<false, true, 2>(d, E, g, lane, tl);
-    __threadfence_block();
-    dc_phase_select<false, 2>(d, E, g, lane, tl);
-    __threadfence_block(); // lane 0's mailbox stores before the other lanes' loads
-    return __builtin_amdgcn_readfirstlane(as_global(d.pend_leaf)[g]);
-}
-__device__ __attribute__((noinline)) void dc_spw_rollout(const TreeDev &d_, int g, int lane) {
-    const TreeDev &d = *as_lds(&d_);
-    const uint32_t gid = (uint32_t)__builtin_amdgcn_readfirstlane((int)as_global(d.leaf_game_id)[g]);
-    const uint32_t serial = (uint32_t)(__builtin_amdgcn_readfirstlane(as_global(d.sim_serial)[g]) - 1);
-    const float v = dc_rollout_wave(as_global((const DCState *)d.leaf_state) + g, gid, serial, d.seed, lane);
-    if (lane == 0) as_global(d.eval_value)[g] = v;
-    __threadfence_block(); // the value is in the mailbox before dc_phase_apply reads it
-}
+// DragonChess: a ply is the simulations of k_dc_search_wave_rollout -- its prologue, its out-of-line tree step and playout, the one
+// set of instances the two kernels share (search_wave_dc.hip.h) -- and then dc_spw_move, out of line for the same reason (inlined
+// into one loop body the phases spill: mega_dc.hip.h).
 // k_dc_selfplay_move for the wave's slot (the body applies the last leaf first).  Returns the slot's game (wave-uniform; < 0: none).
 __device__ __attribute__((noinline)) int dc_spw_move(const TreeDev &d_, const DCEdges &E_, int g, int lane, float *tl) {
     const TreeDev &d = *as_lds(&d_);
     const DCEdges &E = *as_lds(&E_);
-    dc_selfplay_move_body<2>(d, E, g, lane, as_lds(tl));
+    dc_selfplay_move_body<DC_COPY_ROLLOUT_WAVE>(d, E, g, lane, as_lds(tl));
     __threadfence_block(); // lane 0's slot state (ply, sims_left, a new game's root) before the next ply's loads
     return __builtin_amdgcn_readfirstlane(as_global(d.game_lid)[g]);
 }
 __global__ void __launch_bounds__(64 * SW_WAVES) k_dc_selfplay_wave_rollout(TreeDev d_arg, DCEdges E_arg, int plies, int sims, int move) {
-    __shared__ __attribute__((aligned(16))) float lds_all[SW_WAVES][DC_LDS_FLOATS];
-    __shared__ TreeDev s_d;
-    __shared__ DCEdges s_E;
-    if (threadIdx.x == 0) { // workgroup prologue: the one barrier of the kernel
-        s_d = d_arg;
-        s_E = E_arg;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int g = blockIdx.x * SW_WAVES + wv;
-    if (g >= d_arg.n_slots) return; // (whole waves leave: nothing below synchronises the workgroup)
-    float *tl = lds_all[wv];
-    if (__builtin_amdgcn_readfirstlane(d_arg.game_lid[g]) < 0) return; // (uniform) the slot has played its last game
+    const DCRolloutWave w = dc_swr_prologue(d_arg, E_arg);
+    if (w.g < 0) return;
+    if (__builtin_amdgcn_readfirstlane(d_arg.game_lid[w.g]) < 0) return; // (uniform) the slot has played its last game
     for (int p = 0; p < plies; p++) {
-        for (int s = 0; s < sims; s++) {
-            if (dc_spw_tree(s_d, s_E, g, lane, tl) < 0) break; // (uniform) no simulations left: every further step is a no-op
-            dc_spw_rollout(s_d, g, lane);
-        }
+        dc_swr_sims(w, sims);
         if (!move) break; // (uniform) part of a ply: the leaf stays pending for the next launch
-        if (dc_spw_move(s_d, s_E, g, lane, tl) < 0) break; // (uniform) that was the slot's last game
+        if (dc_spw_move(*w.d, *w.E, w.g, w.lane, w.tl) < 0) break; // (uniform) that was the slot's last game
     }
 }

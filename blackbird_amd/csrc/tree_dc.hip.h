@@ -405,8 +405,10 @@ __device__ __forceinline__ uint32_t *dc_anc_edge(const TreeDev &d, int g) {
 
 // ANC: also back up through the ancestor chain when the engine keeps one.  Only the launch-per-simulation kernels
 // (k_dc_tree_step / k_dc_tree_apply, which bb_run_sims drives) are built with it; self-play refuses track_ancestors engines.
-// COPY: a caller that names another value gets instances of its own, so adding it leaves the code of the existing callers as it was
-// (k_dc_search_wave_rollout, search_wave_dc.hip.h).
+// COPY: a caller that names another value gets instances of its own, so adding it leaves the code of the existing callers as it was.
+// Two values: 0 (the lock-step kernels, k_dc_selfplay_fused, k_dc_search_wave(_cached)) and DC_COPY_ROLLOUT_WAVE, the one set of
+// instances that both rollout wave kernels share (k_dc_search_wave_rollout, k_dc_selfplay_wave_rollout).
+constexpr int DC_COPY_ROLLOUT_WAVE = 1;
 template <bool SH = false, bool ANC = false, int COPY = 0>
 __device__ void dc_phase_apply(const TreeDev &d, const DCEdges &E, int g, int lane, float *lds, const DCHeadLocal *hl = nullptr) {
     static_assert(!(SH && ANC), "the ancestor chain is walked by the launch-per-simulation kernels only");
@@ -1194,8 +1196,8 @@ __device__ void dc_write_example(const TreeDev &d, const DCEdges &E, int lid, in
 
 // GenerateTrainingSamples' loop body for one game (one wave): last result applied, move sampled, example written,
 // root advanced, game finished / slot handed to the next game (Blackbird.py:240-268)
-// COPY: instances of the body and of everything out of line under it for one caller alone (k_dc_selfplay_wave_rollout,
-// selfplay_wave.hip.h), so the kernels that share COPY = 0 are compiled as they were
+// COPY: DC_COPY_ROLLOUT_WAVE gives k_dc_selfplay_wave_rollout (selfplay_wave.hip.h) instances of the body and of everything out
+// of line under it, so the kernels that share COPY = 0 are compiled as they were
 template <int COPY = 0>
 __device__ void dc_selfplay_move_body(const TreeDev &d, const DCEdges &E, int g, int lane, float *lds, const DCHeadLocal *hl = nullptr) {
     dc_phase_apply<false, false, COPY>(d, E, g, lane, lds, hl);
