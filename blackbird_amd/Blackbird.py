@@ -296,14 +296,22 @@ def TrainWithExamples(model, batchSize, learningRate, epochs=1, teacher=None, mo
     model.Conn.PutModel(model.Game.GameType, model.Name, model.Version)
 
 
-def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=None):
+def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=None, augment=False):
     """TrainWithExamples (Blackbird.py:271-312) on examples that never left the GPU: `examples` (a training.DeviceExamples),
     or else what GenerateTrainingSamples kept for the model's current Version (model.KeepDeviceExamples).  The same steps
     in the same order -- the epoch's order drawn from numpy's generator as there (the same seed visits the same examples in
     the same batches), one optimiser step per batch --, but a batch is formed on the device (bb_examples_to_batch) and the
     trained weights are exported and handed to the engines once, after the last batch, not after every one.  `epochs` is
-    accepted and ignored, as in the reference.  Raises ValueError when there is nothing to train from."""
+    accepted and ignored, as in the reference.  Raises ValueError when there is nothing to train from.
+
+    augment (an extension: the reference does not augment): every visited example is presented under a symmetry of the game
+    drawn for it -- Connect4 mirrored or not, TicTacToe in one of its eight orientations --, planes and policy alike
+    (bb_examples_to_batch_sym).  The draw is one np.random.randint(symmetries, size=len(order)) right after the epoch's
+    order; with augment=False numpy's generator is consumed as before.  DragonChess has no symmetry: ValueError."""
     from .training import epoch_order
+    if augment and _lib.game_symmetries(model.Game.GAME_ID if examples is None else examples.game) < 2:
+        raise ValueError('augment=True: this game has no board symmetry but the identity (DragonChess: the start position is '
+                         'not mirror-symmetric and pawns have a direction), there is nothing to augment with')
     model.SampleValue.cache_clear()
     model.GetPriors.cache_clear()
     if examples is None:
@@ -312,11 +320,13 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
         raise ValueError('no device examples for %s version %d: pass `examples`, or set KeepDeviceExamples before '
                          'GenerateTrainingSamples' % (model.Name, model.Version))
     order = examples.index_tensor(epoch_order(len(examples), batchSize))
+    syms = examples.sym_tensor(np.random.randint(examples.symmetries, size=len(order))) if augment else None
     nBatches = len(order) // batchSize
     if nBatches:
         trainer = model._trainer_for(examples.info.C)
         for i in range(nBatches):
-            boards, value, policy = examples._batch(order[i * batchSize:(i + 1) * batchSize])
+            rows = slice(i * batchSize, (i + 1) * batchSize)
+            boards, value, policy = examples._batch(order[rows], None if syms is None else syms[rows])
             trainer.step_tensors(boards, value, policy, learningRate)
         bad = examples.bad()  # (one look per epoch: it waits for the GPU)
         if bad:

@@ -27,7 +27,7 @@ EXPORTS = (
     "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked", "bb_run_sims_structure", "bb_search_rollouts", "bb_selfplay_rollouts",
     "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_set_starts", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
-    "bb_examples_to_batch",
+    "bb_examples_to_batch", "bb_examples_to_batch_sym", "bb_game_symmetries",
     "bb_arena_create", "bb_arena_begin", "bb_arena_step", "bb_arena_status", "bb_arena_fetch", "bb_arena_destroy",
     "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_param_count", "bb_trainer_read",
 )
@@ -131,6 +131,8 @@ def lib():
     L.bb_examples_fetch_games.argtypes = [vp, ip, vp, vp, ip, vp, vp]
     L.bb_examples_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp)]
     L.bb_examples_to_batch.argtypes = [ip, ip, vp, ip, vp, vp, vp, vp, vp, vp]
+    L.bb_examples_to_batch_sym.argtypes = [ip, ip, vp, ip, vp, vp, vp, vp, vp, vp, vp]
+    L.bb_game_symmetries.argtypes = [ip]
     L.bb_arena_create.argtypes = [vp, vp, ip, C.POINTER(vp)]
     L.bb_arena_begin.argtypes = [vp, ip, vp, vp, C.c_double]
     L.bb_arena_step.argtypes = [vp, ip]
@@ -180,6 +182,12 @@ def game_info(game):
         check(lib().bb_game_info_get(game, C.byref(gi)))
         _info_cache[game] = gi
     return _info_cache[game]
+
+
+def game_symmetries(game):
+    """bb_game_symmetries: how many board symmetries the game has for examples_to_batch_sym (Connect4 2, TicTacToe 8,
+    DragonChess 1; symmetry 0 is the identity).  ValueError for an unknown game."""
+    return check(lib().bb_game_symmetries(int(game)))
 
 
 # ---- packed states (layout: include/blackbird_hip.h) -------------------------------------------------
@@ -302,6 +310,16 @@ def examples_to_batch(game, n_records, records, n, index=None, boards=None, poli
     check(lib().bb_examples_to_batch(int(game), int(n_records), C.c_void_p(records or None), int(n), C.c_void_p(index or None),
                                      C.c_void_p(boards or None), C.c_void_p(policy or None), C.c_void_p(value or None),
                                      C.c_void_p(bad or None), C.c_void_p(stream or None)))
+
+
+def examples_to_batch_sym(game, n_records, records, n, index=None, sym=None, boards=None, policy=None, value=None, bad=None,
+                          stream=0):
+    """bb_examples_to_batch_sym: examples_to_batch with row k transformed by the game's symmetry sym[k] (uint8 [n] on the
+    device, each < game_symmetries(game); None: the identity everywhere, i.e. examples_to_batch).  A row whose symmetry is
+    out of range is written as zeros and counted in `bad`.  The same argument rules as examples_to_batch."""
+    check(lib().bb_examples_to_batch_sym(int(game), int(n_records), C.c_void_p(records or None), int(n), C.c_void_p(index or None),
+                                         C.c_void_p(sym or None), C.c_void_p(boards or None), C.c_void_p(policy or None),
+                                         C.c_void_p(value or None), C.c_void_p(bad or None), C.c_void_p(stream or None)))
 
 
 def net_weights(H, W, flat):

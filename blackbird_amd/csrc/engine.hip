@@ -80,6 +80,11 @@ extern "C" int bb_game_info_get(int game, bb_game_info *out) {
     }
 }
 
+extern "C" int bb_game_symmetries(int game) {
+    const int n = game_symmetries(game); // (symmetry.h)
+    return n > 0 ? n : fail(BB_ERR_ARG, "unknown or unsupported game %d", game);
+}
+
 // ---- device scratch with automatic release ---------------------------------------------------
 struct DevBuf {
     void *p = nullptr;
@@ -159,8 +164,8 @@ struct Launch {
     static void selfplay_wave_rollout(const TreeDev &d, const DCEdges &, hipStream_t st, int plies, int sims, int move) {
         k_selfplay_wave_rollout<G><<<SW_GRID(d), 0, st>>>(d, plies, sims, move);
     }
-    static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, float *boards, float *policy, float *value, int32_t *bad) {
-        k_examples_to_batch<G><<<nblk((size_t)n * (G::H * G::W * G::C + G::A + 1)), 256, 0, st>>>(n_records, rec, n, index, boards, policy, value, bad);
+    static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, const uint8_t *sym, float *boards, float *policy, float *value, int32_t *bad) {
+        k_examples_to_batch<G><<<nblk((size_t)n * (G::H * G::W * G::C + G::A + 1)), 256, 0, st>>>(n_records, rec, n, index, sym, boards, policy, value, bad);
     }
 };
 template <>
@@ -205,8 +210,8 @@ struct Launch<DragonChess> {
     static void selfplay_wave_rollout(const TreeDev &d, const DCEdges &E, hipStream_t st, int plies, int sims, int move) {
         k_dc_selfplay_wave_rollout<<<SW_GRID(d), 0, st>>>(d, E, plies, sims, move);
     }
-    static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, float *boards, float *policy, float *value, int32_t *bad) {
-        k_dc_examples_to_batch<<<n, 256, 0, st>>>(n_records, rec, index, boards, policy, value, bad);
+    static void examples_to_batch(hipStream_t st, int n_records, const uint8_t *rec, int n, const int64_t *index, const uint8_t *sym, float *boards, float *policy, float *value, int32_t *bad) {
+        k_dc_examples_to_batch<<<n, 256, 0, st>>>(n_records, rec, index, sym, boards, policy, value, bad);
     }
 };
 
@@ -1794,17 +1799,22 @@ extern "C" int bb_examples_device(bb_engine *e, void **ptr_out, uint64_t *bytes_
     return BB_OK;
 }
 
-extern "C" int bb_examples_to_batch(int game, int n_records, const void *records, int n, const int64_t *index, float *boards_out,
-                                    float *policy_out, float *value_out, int32_t *bad_out, void *stream) {
+extern "C" int bb_examples_to_batch_sym(int game, int n_records, const void *records, int n, const int64_t *index, const uint8_t *sym,
+                                        float *boards_out, float *policy_out, float *value_out, int32_t *bad_out, void *stream) {
     if (n == 0) return BB_OK; // an empty batch is a no-op
     if (n < 0 || n_records < 0 || !records || (!boards_out && !policy_out && !value_out)) return fail(BB_ERR_ARG, "bad arguments");
     if (((uintptr_t)records | (uintptr_t)boards_out | (uintptr_t)policy_out) % 16)
         return fail(BB_ERR_ARG, "records, boards_out and policy_out are accessed in 16-byte units");
     hipStream_t st = (hipStream_t)stream;
     const uint8_t *rec = (const uint8_t *)records;
-    GAME_SWITCH(game, Launch<G>::examples_to_batch(st, n_records, rec, n, index, boards_out, policy_out, value_out, bad_out); break);
+    GAME_SWITCH(game, Launch<G>::examples_to_batch(st, n_records, rec, n, index, sym, boards_out, policy_out, value_out, bad_out); break);
     HIPCHK(hipGetLastError());
     return BB_OK;
+}
+
+extern "C" int bb_examples_to_batch(int game, int n_records, const void *records, int n, const int64_t *index, float *boards_out,
+                                    float *policy_out, float *value_out, int32_t *bad_out, void *stream) {
+    return bb_examples_to_batch_sym(game, n_records, records, n, index, nullptr, boards_out, policy_out, value_out, bad_out, stream);
 }
 
 // ---- the arena on the device (arena.hip.h): Blackbird.TestModels' match loop without the host in it -----------------------

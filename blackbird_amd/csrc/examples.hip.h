@@ -7,7 +7,11 @@
 // Row k comes from record index[k] (index == nullptr: record k).  A row whose index is outside [0, n_records), whose
 // n_children exceeds S or (compact games) one of whose actions is >= A is written as zeros and counted in *bad: nothing of
 // what a record says is used as an address before it has been checked.
+// sym (bb_examples_to_batch_sym; nullptr: the identity everywhere): row k is the row of the position transformed by the game's
+// symmetry sym[k] (symmetry.h) -- the same values, a cell's planes at the cell's image and an action's share at the action's image.
+// A row whose sym[k] is not a symmetry of the game is a malformed row like the others: zeros and one count, and no map sees it.
 #pragma once
+#include "symmetry.h"
 #include "tree.hip.h"
 
 // records are read in 16-byte units (headers and states whole); they are multiples of 16 bytes (bb_examples_fetch_games)
@@ -16,9 +20,14 @@ static_assert(sizeof(ExampleHdr) == 16, "example header is one 16-byte load");
 // Dense games (slot i == action i): one thread per output element, rows back to back -- a 256-thread block covers a few
 // records (Connect4: 134 floats per row, TicTacToe: 37), a wave's stores are contiguous within each of the three outputs.
 // The header and the state are one 16-byte load each; the lanes of a row read the same addresses (one fetch, broadcast).
+// A thread finds the cell or the action its element comes FROM through the symmetry's inverse maps: the stores stay as they are.
+// One kernel with and without sym: the only branch is the uniform one around the load of sym[k], the maps run with 0 otherwise.
 template <class G>
 __global__ void __launch_bounds__(256) k_examples_to_batch(int n_records, const uint8_t *records, int n, const int64_t *index,
-                                                           float *boards, float *policy, float *value, int32_t *bad) {
+                                                           const uint8_t *sym, float *boards, float *policy, float *value,
+                                                           int32_t *bad) {
+    using Sym = Symmetries<G::GID>;
+    static_assert(Sym::H == G::H && Sym::W == G::W && Sym::A == G::A, "symmetry.h describes this game");
     static_assert(sizeof(typename G::State) == 16, "grid state is one 16-byte load");
     constexpr int PL = G::H * G::W * G::C, E = PL + G::A + 1;
     constexpr size_t OFF_VIS = sizeof(ExampleHdr) + sizeof(typename G::State), EB = OFF_VIS + 4 * G::S;
@@ -29,7 +38,9 @@ __global__ void __launch_bounds__(256) k_examples_to_batch(int n_records, const 
     const size_t k = t / E;
     const int e = (int)(t % E);
     const int64_t r = index ? index[k] : (int64_t)k;
-    bool ok = r >= 0 && r < (int64_t)n_records;
+    const uint32_t sk = sym ? sym[k] : 0u;
+    bool ok = r >= 0 && r < (int64_t)n_records && sk < (uint32_t)Sym::NSYM;
+    const int s = ok ? (int)sk : 0; // (only a symmetry of the game reaches the maps)
     ExampleHdr h = {};
     typename G::State st = {};
     const uint8_t *rec = records + (size_t)(ok ? r : 0) * EB;
@@ -41,15 +52,15 @@ __global__ void __launch_bounds__(256) k_examples_to_batch(int n_records, const 
     }
     if (e < PL) {
         if (!boards) return;
-        const int cell = e / G::C;
+        const int cell = Sym::cell_inv(s, e / G::C); // the cell whose planes land on cell e / C
         int8_t v[G::C] = {};
         if (ok) G::encode_cell(st, cell / G::W, cell % G::W, v);
         boards[k * PL + e] = (float)v[e % G::C];
     } else if (e < PL + G::A) {
         if (!policy) return;
-        const int a = e - PL; // (a < A <= S: inside the record's visits)
+        const int a = e - PL, from = Sym::action_inv(s, a); // (both < A <= S: inside the record's visits)
         float p = 0.f;
-        if (ok && h.total) p = (float)((double)((const uint32_t *)(rec + OFF_VIS))[a] / (double)h.total);
+        if (ok && h.total) p = (float)((double)((const uint32_t *)(rec + OFF_VIS))[from] / (double)h.total);
         policy[k * G::A + a] = p;
     } else { // the row's last element: z, and the row's word in the count of rejected rows
         if (value) value[k] = ok ? (float)h.z : 0.f;
@@ -61,9 +72,11 @@ __global__ void __launch_bounds__(256) k_examples_to_batch(int n_records, const 
 // (960 bytes) comes in as 60 16-byte loads; the 4032-wide policy row is built in LDS -- zeroed, then up to S entries
 // scattered -- and streamed out with 16-byte stores, so global memory sees every float once and in order.  The planes
 // (64 cells x 17) take the same way through LDS: a cell's 17 values are written by its own lane, rows of 17 floats, an odd
-// stride, so that the 64 lanes fall on different banks.
+// stride, so that the 64 lanes fall on different banks.  DragonChess has no symmetry but the identity: a row with any other
+// sym[k] is treated as a row whose index is out of range.
 __global__ void __launch_bounds__(256) k_dc_examples_to_batch(int n_records, const uint8_t *records, const int64_t *index,
-                                                              float *boards, float *policy, float *value, int32_t *bad) {
+                                                              const uint8_t *sym, float *boards, float *policy, float *value,
+                                                              int32_t *bad) {
     using G = DragonChess;
     constexpr int S = G::S, A = G::A, PL = G::H * G::W * G::C;
     constexpr int EB = (int)(sizeof(ExampleHdr) + sizeof(DCState)) + 4 * S + 2 * S;
@@ -75,7 +88,7 @@ __global__ void __launch_bounds__(256) k_dc_examples_to_batch(int n_records, con
     const int tid = threadIdx.x;
     const size_t k = blockIdx.x;
     const int64_t r = index ? index[k] : (int64_t)k;
-    const bool in_range = r >= 0 && r < (int64_t)n_records; // (the same for the whole block)
+    const bool in_range = r >= 0 && r < (int64_t)n_records && (sym ? sym[k] : 0) < Symmetries<G::GID>::NSYM; // (the same for the whole block)
     if (in_range && tid < EB / 16) s_rec[tid] = ((const uint4 *)(records + (size_t)r * EB))[tid];
     for (int i = tid; i < A / 4; i += 256) s_pol[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = tid; i < PL / 4; i += 256) s_brd[i] = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -307,15 +307,39 @@ class DeviceExamples:
             raise IndexError('example index out of range [0, %d)' % len(self))
         return idx.contiguous()
 
-    def batch(self, index=None):
-        """(boards [n,H,W,C], value [n], policy [n,A]) of the records `index` names (None: all, in order), fresh float32
-        tensors on the records' device: what TrainWithExamples stacks per batch, in Network.train's argument order."""
-        return self._batch(None if index is None else self.index_tensor(index))
+    @property
+    def symmetries(self):
+        """How many board symmetries the game has (bb_game_symmetries): the values `sym` may take are 0 .. symmetries - 1."""
+        return _lib.game_symmetries(self.game)
 
-    def _batch(self, idx):
-        """`batch` for an index tensor that index_tensor returned (or a slice of one)."""
+    def sym_tensor(self, sym):
+        """`sym` (uint8 tensor on the records' device, or anything numpy takes) as a uint8 tensor on the records' device.  What
+        arrives from the host is range-checked here against `symmetries` (ValueError); a tensor that is on the device already
+        is left to the kernel, which writes a row of zeros for a symmetry the game does not have and counts it in bad()."""
+        if torch.is_tensor(sym) and sym.device == self.records.device and sym.device.type != 'cpu':
+            if sym.dtype != torch.uint8:
+                raise ValueError('sym: a uint8 tensor is expected on the device, got %s' % sym.dtype)
+            return sym.reshape(-1).contiguous()
+        host = np.asarray(sym.cpu() if torch.is_tensor(sym) else sym).reshape(-1)
+        if host.size and (host.dtype.kind not in 'iub' or int(host.min()) < 0 or int(host.max()) >= self.symmetries):
+            raise ValueError('sym: integers in [0, %d) are expected (the symmetries of game %d)' % (self.symmetries, self.game))
+        return torch.from_numpy(host.astype(np.uint8)).to(self.records.device)
+
+    def batch(self, index=None, sym=None):
+        """(boards [n,H,W,C], value [n], policy [n,A]) of the records `index` names (None: all, in order), fresh float32
+        tensors on the records' device: what TrainWithExamples stacks per batch, in Network.train's argument order.
+        sym (None: as played): one symmetry of the game per output row, < `symmetries` -- the row is that of the position
+        mirrored or turned so, planes and policy alike (bb_examples_to_batch_sym; an extension, the reference does not
+        augment)."""
+        return self._batch(None if index is None else self.index_tensor(index), None if sym is None else self.sym_tensor(sym))
+
+    def _batch(self, idx, sym=None):
+        """`batch` for an index tensor that index_tensor returned (or a slice of one), and a symmetry tensor that sym_tensor
+        returned (or a slice of one)."""
         gi, dev = self.info, self.records.device
         n = len(self) if idx is None else int(idx.numel())
+        if sym is not None and int(sym.numel()) != n:
+            raise ValueError('sym: one entry per output row is expected (%d rows, %d entries)' % (n, int(sym.numel())))
         boards = torch.empty((n, gi.H, gi.W, gi.C), dtype=torch.float32, device=dev)
         value = torch.empty((n,), dtype=torch.float32, device=dev)
         policy = torch.empty((n, gi.A), dtype=torch.float32, device=dev)
@@ -324,9 +348,10 @@ class DeviceExamples:
         if dev.type != 'cuda':
             raise _lib.BlackbirdHipError('DeviceExamples.batch runs on the GPU only (records on %s)' % dev)
         with torch.cuda.device(dev):
-            _lib.examples_to_batch(self.game, len(self), self.records.data_ptr(), n,
-                                   None if idx is None else idx.data_ptr(), boards.data_ptr(), policy.data_ptr(),
-                                   value.data_ptr(), self._bad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            _lib.examples_to_batch_sym(self.game, len(self), self.records.data_ptr(), n,
+                                       None if idx is None else idx.data_ptr(), None if sym is None else sym.data_ptr(),
+                                       boards.data_ptr(), policy.data_ptr(), value.data_ptr(), self._bad.data_ptr(),
+                                       torch.cuda.current_stream(dev).cuda_stream)
         return boards, value, policy
 
     def bad(self):

@@ -66,6 +66,9 @@ typedef struct {
 } bb_game_info;
 
 int bb_game_info_get(int game, bb_game_info *out);
+/* The number of board symmetries bb_examples_to_batch_sym knows for the game (index 0 is the identity; the others are listed
+ * in csrc/symmetry.h): Connect4 2 (the column mirror), TicTacToe 8 (the square's), DragonChess 1.  BB_ERR_ARG: unknown game. */
+int bb_game_symmetries(int game);
 const char *bb_last_error(void);
 int bb_device_count(void);
 
@@ -427,6 +430,29 @@ int bb_arena_destroy(bb_arena *ar);
  * n == 0: BB_OK, nothing touched (GPU or not).  n < 0, records NULL, every output NULL, a misaligned pointer: BB_ERR_ARG. */
 int bb_examples_to_batch(int game, int n_records, const void *records, int n, const int64_t *index, float *boards_out,
                          float *policy_out, float *value_out, int32_t *bad_out, void *stream);
+/* The same batch with every row in an orientation of its own -- an extension (the reference does not augment its examples), opt-in
+ * and exact.  bb_examples_to_batch is this call with sym == NULL.  Stateless; ALL pointers are device memory of the calling
+ * thread's current device, and the launch is asynchronous on `stream` (a hipStream_t; 0 = the default stream).
+ *   records  [n_records][example_bytes], the bb_examples_fetch layout: the engine's own store (bb_examples_device), a compacted
+ *            copy or an all-gathered tensor.  16-byte aligned.
+ *   index    [n] record of every batch row, in output order; NULL = records 0..n-1.
+ *   sym      [n] uint8, the symmetry of every batch row, each < bb_game_symmetries(game) (0 = the identity; the order of the
+ *            others, their cell maps and the action maps the rules imply: csrc/symmetry.h); NULL = the identity everywhere.
+ * Row k, from record r = records[index[k]] and sigma = sym[k] (any single output may be NULL, not all three):
+ *   boards_out[k][H][W][C] float32: the AsInputArray planes of the position r's state becomes under sigma: cell sigma(row, col)
+ *                          holds what bb_game_encode gives for cell (row, col) of r's state (the side-to-move plane is constant);
+ *   policy_out[k][A]       float32: entry sigma(a) is (float)((double)visits_a / (double)total) -- divided in double, rounded
+ *                          once --, all zeros when total == 0 (the terminal example).  Dense games: from visits[a], a < A (the
+ *                          spare slots A..S-1 are ignored); DragonChess (sigma is the identity): zeros except entry action[j]
+ *                          from visits[j], j < n_children;
+ *   value_out[k]           float32: r.z.
+ *   boards_out and policy_out 16-byte aligned.
+ * A row is written as all zeros, and *bad_out (when non-NULL) incremented by one per such row, if index[k] is outside
+ * [0, n_records), if sym[k] >= bb_game_symmetries(game) (DragonChess: anything but 0), if n_children > S, or if a compact
+ * action[j] >= A: malformed input never becomes an out-of-bounds access, and a sym[k] out of range never becomes an index.
+ * n == 0: BB_OK, nothing touched (GPU or not).  n < 0, records NULL, every output NULL, a misaligned pointer: BB_ERR_ARG. */
+int bb_examples_to_batch_sym(int game, int n_records, const void *records, int n, const int64_t *index, const uint8_t *sym,
+                             float *boards_out, float *policy_out, float *value_out, int32_t *bad_out, void *stream);
 
 /* ---- the training step as HIP kernels (opt-in; the default trainer is PyTorch's autograd) --------- */
 /* One step of Network.train (Network.py:66-84; loss and optimiser NetworkFactory.py:185-245) for the dense games (Connect4,

@@ -1,5 +1,5 @@
 """From finished self-play games to a trained network, both ways, timed: python tools/train_path.py [--games N]
-[--play-limit P] [--batch B] [--lr LR]
+[--play-limit P] [--batch B] [--lr LR] [--augment]
 
 N Connect4 games at PlayLimit P are played once (Model.KeepDeviceExamples on, so that sqlite and the GPU hold the same
 examples); then one epoch over them is trained twice with the same batch size:
@@ -12,8 +12,9 @@ examples); then one epoch over them is trained twice with the same batch size:
                training step as HIP kernels, bb_trainer_step), on a second model built from the same saved weights
 
 and the bare DeviceExamples.batch calls of that epoch alone.  Every timed region ends in a device synchronise; one training
-step is run before any of them, per trainer (the first step pays for the library's kernel selection).  Prints one JSON
-line."""
+step is run before any of them, per trainer (the first step pays for the library's kernel selection).  --augment: the
+device and hip paths and the bare batches present every example mirrored or not (TrainWithDeviceExamples' augment=True,
+bb_examples_to_batch_sym); the host path has no such thing and stays as it is.  Prints one JSON line."""
 import argparse
 import copy
 import json
@@ -41,6 +42,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--augment", action="store_true")
     a = ap.parse_args()
     os.chdir(tempfile.mkdtemp())  # the sqlite file and the saved networks of this run
     np.random.seed(a.seed)
@@ -64,10 +66,11 @@ def main():
 
     # bare batches of one epoch
     order = kept.index_tensor(epoch_order(n, B))
+    syms = kept.sym_tensor(np.random.randint(kept.symmetries, size=len(order))) if a.augment else None
     torch.cuda.synchronize()
     t = time.time()
     for i in range(len(order) // B):
-        kept._batch(order[i * B:(i + 1) * B])
+        kept._batch(order[i * B:(i + 1) * B], None if syms is None else syms[i * B:(i + 1) * B])
     torch.cuda.synchronize()
     batch_s = time.time() - t
 
@@ -88,18 +91,18 @@ def main():
 
     # device path
     t = time.time()
-    Blackbird.TrainWithDeviceExamples(model, B, a.lr, examples=kept)
+    Blackbird.TrainWithDeviceExamples(model, B, a.lr, examples=kept, augment=a.augment)
     torch.cuda.synchronize()
     device_s = time.time() - t
 
     # hip path: the same epoch (the same examples, an order drawn the same way) with the step as HIP kernels
     t = time.time()
-    Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept)
+    Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment)
     torch.cuda.synchronize()
     hip_s = time.time() - t
 
     print(json.dumps({"tool": "train_path", "game": "connect4", "games": a.games, "warmup_games": 64, "play_limit": a.play_limit,
-                      "examples": n, "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
+                      "examples": n, "augment": bool(a.augment), "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
                       "host_path_s": round(host_s, 3), "host_decode_s": round(decode_s, 3),
                       "device_path_s": round(device_s, 3), "device_batches_only_s": round(batch_s, 4),
                       "host_over_device": round(host_s / device_s, 2), "hip_path_s": round(hip_s, 3),
