@@ -2,6 +2,9 @@
 two-searcher game loop over the oracle, the two hash-evaluator sides, first movers, play limits and the seed of the uniforms."""
 import numpy as np
 
+from blackbird_amd import _lib, arena
+from blackbird_amd.DynamicMCTS import DynamicMCTS
+
 FIRST = np.array([True, False, False, True, True, False, True, False, False, True, True])
 SIMS = (30, 20)
 UNIFORM_SEED = 5
@@ -45,3 +48,29 @@ def oracle_arena(orc, og, cfgs, sims, first, temp, draw, trace=None):
                 mine = 1 if first[g] else 2
                 result[g] = 0 if w == 0 else (1 if w == mine else -1)
     return np.array(result)
+
+
+# ---- players and engines of the device tests ------------------------------------------------------------------------------
+class HashPlayer(DynamicMCTS):
+    """DynamicMCTS on the deterministic validation evaluator; honours SearchLaunch like the stock searchers."""
+    _EVALUATOR = _lib.EVAL_HASH
+
+    def __init__(self, game, salt, c_puct=0.85, playLimit=24, node_capacity=None):
+        DynamicMCTS.__init__(self, explorationRate=c_puct, playLimit=playLimit)
+        self.Game, self.salt, self.node_capacity = game, salt, node_capacity
+
+    def _make_engine(self, game_id, n_slots, sims, **kw):
+        kw.setdefault('launch', self._search_launch())
+        if self.node_capacity is not None:
+            kw['node_capacity'] = self.node_capacity
+        return _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
+                           evaluator=_lib.EVAL_HASH, hash_salt=self.salt, c_puct=float(self.ExplorationRate), seed=77, **kw)
+
+
+def searcher_engines(players, n_slots):
+    """One engine per side, made as the arena makes them (arena._Searcher); numpy's seed fixes the engines' random streams."""
+    out = []
+    for k, p in enumerate(players):
+        np.random.seed(100 + k)
+        out.append(arena._Searcher(p, p.Game.GAME_ID, n_slots, p.PlayLimit, None).engine)
+    return out

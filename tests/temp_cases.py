@@ -10,7 +10,7 @@ cdf over at most 144 terms then moves by less than 2^-44 relative.  A draw that 
 boundary of its cdf lands in the same interval whichever pow computed it, so the GPU tests may demand exact agreement."""
 import numpy as np
 
-from tests import test_selfplay_starts_cpu as SC
+from tests import selfplay_cases as SC
 
 # 1 / 0.1 is exactly 10.0 and 1 / 0.5, 1 / 2.0, 1 / 50.0 are exact too; 0.3 and 0.7 give NON-INTEGER exponents (3.33.., 1.42..):
 # pow has no integer shortcut there.  That is why they are in the list.

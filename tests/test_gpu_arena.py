@@ -9,14 +9,13 @@ from blackbird_amd import Blackbird, Connect4, TicTacToe
 from blackbird_amd.RandomMCTS import RandomMCTS
 from blackbird_amd.arena import TestModelsBatched
 
+from tests import model_cases as M
+
 pytestmark = pytest.mark.gpu
 
 
 def _model(game, name, tmp_seed, play_limit, eps=0.0):
-    cfg = {"blocks": 2, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
-           "policy": {"dirichlet": {"alpha": 0.2, "epsilon": eps}}, "training": {"optimizer": "adam"}}
-    np.random.seed(tmp_seed)  # weight initialisation draws from numpy's stream
-    return Blackbird.Model(game, name, {"explorationRate": 0.85, "playLimit": play_limit}, cfg)
+    return M.model(game, name, seed=tmp_seed, play_limit=play_limit, eps=eps, blocks=2)
 
 
 def _serial(model1, model2, temp, first):

@@ -11,44 +11,18 @@ import numpy as np
 import pytest
 
 from blackbird_amd import Blackbird, Connect4, DragonChess, TicTacToe, _lib, arena
-from blackbird_amd.DynamicMCTS import DynamicMCTS
 from blackbird_amd.FixedMCTS import FixedMCTS
+
+from tests import model_cases as M
+from tests.arena_cases import HashPlayer as _HashPlayer, searcher_engines as _engines
 
 pytestmark = pytest.mark.gpu
 
 LOG = 64  # move log long enough for every dense game played here (Connect4: 42 plies at most)
 
 
-class _HashPlayer(DynamicMCTS):
-    """DynamicMCTS on the deterministic validation evaluator; honours SearchLaunch like the stock searchers."""
-    _EVALUATOR = _lib.EVAL_HASH
-
-    def __init__(self, game, salt, c_puct=0.85, playLimit=24, node_capacity=None):
-        DynamicMCTS.__init__(self, explorationRate=c_puct, playLimit=playLimit)
-        self.Game, self.salt, self.node_capacity = game, salt, node_capacity
-
-    def _make_engine(self, game_id, n_slots, sims, **kw):
-        kw.setdefault('launch', self._search_launch())
-        if self.node_capacity is not None:
-            kw['node_capacity'] = self.node_capacity
-        return _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
-                           evaluator=_lib.EVAL_HASH, hash_salt=self.salt, c_puct=float(self.ExplorationRate), seed=77, **kw)
-
-
 def _model(game, name, seed, play_limit, eps=0.0):
-    cfg = {"blocks": 2, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
-           "policy": {"dirichlet": {"alpha": 0.2, "epsilon": eps}}, "training": {"optimizer": "adam"}}
-    np.random.seed(seed)  # weight initialisation draws from numpy's stream
-    return Blackbird.Model(game, name, {"explorationRate": 0.85, "playLimit": play_limit}, cfg)
-
-
-def _engines(players, n_slots):
-    """One engine per side, made as the arena makes them (arena._Searcher); numpy's seed fixes the engines' random streams."""
-    out = []
-    for k, p in enumerate(players):
-        np.random.seed(100 + k)
-        out.append(arena._Searcher(p, p.Game.GAME_ID, n_slots, p.PlayLimit, None).engine)
-    return out
+    return M.model(game, name, seed=seed, play_limit=play_limit, eps=eps, blocks=2)
 
 
 def statement(ea, eb, first, temp, starts=None, max_plies=None):

@@ -7,22 +7,11 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib, Connect4, DragonChess
-from blackbird_amd.DynamicMCTS import DynamicMCTS
+from tests.search_cases import DirectHashSearch as HashSearch
 
 pytestmark = pytest.mark.gpu
 DC = _lib.GAME_DRAGONCHESS
 A = 4032
-
-
-class HashSearch(DynamicMCTS):
-    """DynamicMCTS on the validation evaluator (what the golden fixtures were generated with)."""
-    _EVALUATOR = _lib.EVAL_HASH
-    salt = 0
-
-    def _make_engine(self, game_id, n_slots, sims, **kw):
-        return _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
-                           max_depth=self._max_depth(), evaluator=_lib.EVAL_HASH, hash_salt=self.salt,
-                           c_puct=float(self.ExplorationRate), **kw)
 
 
 def dense(idx, vals):

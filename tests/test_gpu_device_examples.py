@@ -11,6 +11,7 @@ import pytest
 
 from blackbird_amd import Blackbird, Connect4, _lib
 from blackbird_amd.training import DeviceExamples, Trainer, epoch_order
+from tests import selfplay_cases as SP
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -55,14 +56,7 @@ def played(game):
         cfg = SELFPLAY[game]
         eng = _lib.Engine(game, n_slots=cfg["n_games"], sims_per_move=cfg["sims"], evaluator=_lib.EVAL_HASH, hash_salt=5, seed=3,
                           max_games=cfg["n_games"], max_plies=cfg.get("max_plies"))
-        eng.selfplay_begin(cfg["n_games"], 1.0)
-        guard = 0
-        while not eng.selfplay_done()[0]:
-            eng.selfplay_step(4)
-            guard += 1
-            assert guard < 64
-        rec, _offs, _win = eng.fetch_examples()
-        rec = rec.copy()
+        rec = SP.play_to_end(eng, cfg["n_games"], 4, 1.0, steps_below=64)["rec"].copy()
         ex = DeviceExamples.from_engine(eng, DEV)
         eng.set_rng_stream(99, 1000)
         eng.selfplay_begin(cfg["n_games"], 1.0)

@@ -11,7 +11,9 @@ import torch
 
 from blackbird_amd import Blackbird, Connect4, TicTacToe, _lib
 from blackbird_amd.training import DeviceExamples, epoch_order
-from tests.test_symmetry_cpu import maps  # noqa: F401  (a fixture: the header's maps from the stand-alone program)
+from tests import model_cases as M
+from tests import selfplay_cases as SP
+from tests.host_cases import maps  # noqa: F401  (a fixture: the header's maps from the stand-alone program)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -29,14 +31,8 @@ def played(game):
         cfg = SELFPLAY[game]
         eng = _lib.Engine(game, n_slots=cfg["n_games"], sims_per_move=cfg["sims"], evaluator=_lib.EVAL_HASH, hash_salt=9, seed=4,
                           max_games=cfg["n_games"], max_plies=cfg.get("max_plies"))
-        eng.selfplay_begin(cfg["n_games"], 1.0)
-        guard = 0
-        while not eng.selfplay_done()[0]:
-            eng.selfplay_step(4)
-            guard += 1
-            assert guard < 64
-        rec, offs, _win = eng.fetch_examples()
-        rec, offs = rec.copy(), offs.copy()
+        out = SP.play_to_end(eng, cfg["n_games"], 4, 1.0, steps_below=64)
+        rec, offs = out["rec"].copy(), out["offs"].copy()
         eng.close()
         ex = DeviceExamples.from_records(game, rec, DEV)
         assert (rec["total"] == 0).sum() == cfg["n_games"] and (rec["total"] > 0).any()  # the terminal examples are there
@@ -264,13 +260,8 @@ def test_dragonchess_all_zero_is_the_old_entry_point_and_one_is_bad():
 
 
 # ---- the front end: TrainWithDeviceExamples(augment=...) ----------------------------------------------------------------
-def _cfg():
-    return {"blocks": 1, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
-            "policy": {"dirichlet": {"alpha": 0.2, "epsilon": 0}}, "training": {"optimizer": "adam"}}
-
-
 def _model(game, name):
-    return Blackbird.Model(BOARD_CLS[game], name, {"explorationRate": 0.85, "playLimit": 8}, _cfg())
+    return M.model(BOARD_CLS[game], name, seed=None, play_limit=8, eps=0, blocks=1)
 
 
 def _same_weights(a, b):

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib, weights as W
+from tests import selfplay_cases as SP
 
 pytestmark = pytest.mark.gpu
 SIMS = 800
@@ -232,13 +233,8 @@ def test_c5_network_full_size_in_search():
                           epsilon=0.3, max_games=n, max_plies=cap)
         eng.load_weights(flat)
         assert eng.net_form() == 3 and eng.selfplay_mode() == 1
-        eng.selfplay_begin(n, 1.0)
-        guard = 0
-        while not eng.selfplay_done()[0]:
-            eng.selfplay_step(1)
-            guard += 1
-            assert guard < 64
-        rec, offs, win = eng.fetch_examples()
+        out = SP.play_to_end(eng, n, 1, 1.0, steps_below=64)
+        rec, offs, win = out["rec"], out["offs"], out["win"]
         cnt = eng.counters()
         eng.close()
         return rec, offs, win, cnt

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib, weights as W
-from .test_gpu_net import boards_for
+from tests.net_cases import boards_for
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -98,7 +98,7 @@ def test_dragonchess_general_filters(orc):
 def test_selfplay_with_general_network_matches_oracle_tree(orc):
     """Asynchronous self-play driven by a 32-filter network == the oracle's sequential search fed with the same
     network values (taken from the GPU so that only the search is compared)."""
-    from .test_gpu_net import _selfplay_vs_oracle_tree
+    from tests.net_cases import selfplay_vs_oracle_tree as _selfplay_vs_oracle_tree
     _selfplay_vs_oracle_tree(orc, filters=32, blocks=2)
 
 
@@ -128,5 +128,5 @@ def test_large_batch_kernels_equal_small_batch_kernels(orc, F, R, n):
 def test_wide_network_rounds_on_two_streams(orc):
     """A wide network runs self-play as asynchronous rounds; with >= 512 slots two slot-range views are pipelined on two
     streams, both run the general path at once and must not share activation scratch: self-play still equals the oracle's search."""
-    from .test_gpu_net import _selfplay_vs_oracle_tree
+    from tests.net_cases import selfplay_vs_oracle_tree as _selfplay_vs_oracle_tree
     _selfplay_vs_oracle_tree(orc, filters=32, blocks=1, n_slots=512, n_games=24, sims=16)

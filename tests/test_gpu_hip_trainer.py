@@ -1,5 +1,5 @@
 """-m gpu: the training step as HIP kernels (training.HipTrainer over bb_trainer_*, csrc/train.hip.h) against the float64
-statement of the reference's graph in tests/test_hip_trainer_cpu.py: the loss terms and the gradient of every variable, two
+statement of the reference's graph in tests/trainer_cases.py (tests/test_hip_trainer_cpu.py checks it): the loss terms and the gradient of every variable, two
 optimiser steps per optimiser, the shapes where the kernels can go wrong, bit-repeatability, the device-drawn noise, the same
 training as the PyTorch trainer over real self-play records, and the front end.
 
@@ -12,7 +12,7 @@ import torch
 from blackbird_amd import Blackbird, Connect4, _lib
 from blackbird_amd import weights as W
 from blackbird_amd.training import DeviceExamples, HipTrainer, Trainer
-from tests.test_hip_trainer_cpu import ALPHA, EPS, GAMES, RefOptimizer, close, make_batch, statement
+from tests.trainer_cases import ALPHA, EPS, GAMES, RefOptimizer, close, make_batch, statement
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

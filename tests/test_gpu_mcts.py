@@ -8,27 +8,13 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib
+from tests import selfplay_cases as SP
+from tests.search_cases import replay_find_move_golden
 
 pytestmark = pytest.mark.gpu
 GAMES = {"c4": (_lib.GAME_CONNECT4, 0), "ttt": (_lib.GAME_TICTACTOE, 1), "dc": (_lib.GAME_DRAGONCHESS, 2)}
 
 
-def pack_states(game, g):
-    if game == _lib.GAME_DRAGONCHESS:
-        return _lib.pack_dc(g["board"].reshape(-1, 8, 8), g["player"], g["prev"], g["castle"])
-    H, W, _s = _lib.GRID[game]
-    return _lib.pack_grid(game, g["board"].reshape(-1, H, W, 2), g["player"], g["prev"])
-
-
-def same_position(game, a, b):
-    """GameState.__eq__: PreviousPlayer is ignored."""
-    if game == _lib.GAME_DRAGONCHESS:
-        a, b = a.copy(), b.copy()
-        a[:, 65] = 0
-        b[:, 65] = 0
-        return np.array_equal(a[:, :70], b[:, :70])
-    m = np.uint64((1 << 58) - 1)
-    return np.array_equal(a & m, b & m)
 FILES = sorted(os.path.basename(p) for p in glob.glob(
     os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mcts_*.npz"))
     if os.path.basename(p).split("_")[1] in GAMES)
@@ -36,65 +22,7 @@ FILES = sorted(os.path.basename(p) for p in glob.glob(
 
 @pytest.mark.parametrize("fname", FILES)
 def test_find_move_golden(golden_dir, fname):
-    g = np.load(os.path.join(golden_dir, fname), allow_pickle=False)
-    key = fname.split("_")[1]
-    game, _ = GAMES[key]
-    A = _lib.game_info(game).A
-    dc = game == _lib.GAME_DRAGONCHESS
-    cells = 64 if dc else _lib.GRID[game][0] * _lib.GRID[game][1]
-    sims, seed, salt, max_depth, fixed, reuse = [int(x) for x in g["meta"]]
-    c, temp = [float(x) for x in g["cfg"]]
-    gs = g["game_start"]
-    ng = len(gs) - 1
-    lens = np.diff(gs)
-    st_all = pack_states(game, g)
-    eng = _lib.Engine(game, n_slots=ng, sims_per_move=sims, mcts_kind=_lib.MCTS_FIXED if fixed else _lib.MCTS_DYNAMIC,
-                      max_depth=max_depth, evaluator=_lib.EVAL_HASH, c_puct=c, hash_salt=salt, salt_per_game=True,
-                      node_capacity=sims * (cells + 1) * (max_depth if fixed else 1) + 8)
-    eng.set_roots(st_all[gs[:-1]], game_ids=np.arange(ng))
-    for ply in range(int(lens.max())):
-        live = lens > ply
-        idx = gs[:-1] + np.minimum(ply, lens - 1)
-        # FindMove asserts Root.State == state: the engine's root must be the fixture's position
-        roots = eng.root_states()
-        assert same_position(game, roots[live], st_all[idx][live])
-        eng.run_sims(sims)
-        out = eng.sample_moves(temp, u=g["u"][idx])
-        for s in np.where(live)[0]:
-            i = idx[s]
-            if dc:  # compact child lists: (action, plays) pairs in ascending action order
-                k = int((g["plays"][i][:, 0] >= 0).sum())
-                assert np.array_equal(out["child_action"][s, :k], g["plays"][i][:k, 0].astype(np.int32)), (fname, s, ply)
-                assert (out["child_action"][s, k:] == -1).all()
-                plays = out["child_plays"][s, :k].astype(np.float64)
-                assert np.array_equal(plays, g["plays"][i][:k, 1]), (fname, s, ply)
-                n32 = out["child_plays"][s, :k].astype(np.float32)
-                wr = np.where(n32 > 0, out["child_value"][s, :k] / np.maximum(n32, 1), 0).astype(np.float64)
-                assert np.array_equal(wr, g["winrates"][i][:k])
-                assert out["root_plays"][s] == g["root_plays"][i] and float(out["root_winrate"][s]) == g["v"][i]
-                assert out["action"][s] == g["action"][i], (fname, s, ply)
-                assert np.array_equal(plays / plays.sum(), g["prob"][i][:k])
-                continue
-            plays = out["child_plays"][s, :A].astype(np.float64)
-            assert np.array_equal(plays, g["plays"][i]), (fname, s, ply, plays, g["plays"][i])
-            n32 = out["child_plays"][s, :A].astype(np.float32)
-            wr = np.where(n32 > 0, out["child_value"][s, :A] / np.maximum(n32, 1), 0).astype(np.float64)
-            assert np.array_equal(wr, g["winrates"][i]), (fname, s, ply)
-            assert out["root_plays"][s] == g["root_plays"][i]
-            assert float(out["root_winrate"][s]) == g["v"][i]
-            assert out["action"][s] == g["action"][i], (fname, s, ply)
-            tot = plays.sum()
-            assert np.array_equal(plays / tot if tot > 0 else plays, g["prob"][i])
-        acts = np.where(live, g["action"][idx], -1).astype(np.int32)
-        if reuse:
-            eng.move_roots(acts)
-        else:  # the fixture called DropRoot() after every move
-            nxt_live = lens > ply + 1
-            if nxt_live.any():
-                sl = np.where(nxt_live)[0]
-                eng.set_roots(st_all[gs[:-1][sl] + ply + 1], slots=sl, game_ids=sl)
-    assert eng.counters()["overflow"] == 0
-    eng.close()
+    replay_find_move_golden(golden_dir, fname, GAMES[fname.split("_")[1]][0])
 
 
 @pytest.mark.parametrize("key,sims,n_games,n_slots", [("c4", 48, 96, 64), ("ttt", 30, 200, 64), ("c4", 200, 12, 16)])
@@ -104,13 +32,8 @@ def test_selfplay_vs_oracle(orc, key, sims, n_games, n_slots):
     A = _lib.game_info(game).A
     eng = _lib.Engine(game, n_slots=n_slots, sims_per_move=sims, evaluator=_lib.EVAL_HASH, hash_salt=4242, seed=99,
                       max_games=n_games, first_game_id=1000)
-    eng.selfplay_begin(n_games, 1.0)
-    guard = 0
-    while not eng.selfplay_done()[0]:
-        eng.selfplay_step(3)
-        guard += 1
-        assert guard < 200
-    rec, offs, win = eng.fetch_examples()
+    out = SP.play_to_end(eng, n_games, 3, 1.0, steps_below=200)
+    rec, offs, win = out["rec"], out["offs"], out["win"]
     cnt = eng.counters()
     assert cnt["overflow"] == 0 and cnt["games_finished"] == n_games
     cfg = orc.make_cfg(og, evaluator=orc.EVAL_HASH, salt=4242, seed=99)
@@ -140,10 +63,8 @@ def test_rollout_fixed_vs_oracle(orc):
     n_games = 40
     eng = _lib.Engine(game, n_slots=16, sims_per_move=50, mcts_kind=_lib.MCTS_FIXED, max_depth=10,
                       evaluator=_lib.EVAL_ROLLOUT, seed=31, max_games=n_games)
-    eng.selfplay_begin(n_games, 1.0)
-    while not eng.selfplay_done()[0]:
-        eng.selfplay_step(3)
-    rec, offs, win = eng.fetch_examples()
+    out = SP.play_to_end(eng, n_games, 3, 1.0)
+    rec, offs, win = out["rec"], out["offs"], out["win"]
     assert eng.counters()["overflow"] == 0
     cfg = orc.make_cfg(og, kind=orc.FIXED, max_depth=10, evaluator=orc.EVAL_ROLLOUT, seed=31)
     for gidx in range(n_games):
@@ -187,13 +108,8 @@ def test_dc_selfplay_vs_oracle(orc):
     n_games, sims, cap = 12, 20, 40
     eng = _lib.Engine(game, n_slots=8, sims_per_move=sims, evaluator=_lib.EVAL_HASH, hash_salt=555, seed=7,
                       max_games=n_games, max_plies=cap)
-    eng.selfplay_begin(n_games, 1.0)
-    guard = 0
-    while not eng.selfplay_done()[0]:
-        eng.selfplay_step(4)
-        guard += 1
-        assert guard < 100
-    rec, offs, win = eng.fetch_examples()
+    out = SP.play_to_end(eng, n_games, 4, 1.0, steps_below=100)
+    rec, offs, win = out["rec"], out["offs"], out["win"]
     assert eng.counters()["overflow"] == 0
     cfg = orc.make_cfg(orc.DC, evaluator=orc.EVAL_HASH, salt=555, seed=7)
     for gidx in range(n_games):
@@ -227,13 +143,8 @@ def test_dc_selfplay_one_wave_per_game(orc):
                           max_plies=cap, noise_on=noise, launch=launch)
         eng.load_weights(flat)
         mode = eng.selfplay_mode()
-        eng.selfplay_begin(n_games, 1.0)
-        guard = 0
-        while not eng.selfplay_done()[0]:
-            eng.selfplay_step(3)
-            guard += 1
-            assert guard < 100
-        rec, offs, win = eng.fetch_examples()
+        out = SP.play_to_end(eng, n_games, 3, 1.0, steps_below=100)
+        rec, offs, win = out["rec"], out["offs"], out["win"]
         assert eng.counters()["overflow"] == 0
         eng.close()
         return rec, offs, win, mode
@@ -286,13 +197,8 @@ def test_exact_ties_follow_the_float64_first_maximum(orc, game, og, n_slots, n_g
                       max_plies=cap, noise_on=False)
     eng.load_weights(flat)
     assert eng.selfplay_mode() in (3, 5)
-    eng.selfplay_begin(n_games, 1.0)
-    guard = 0
-    while not eng.selfplay_done()[0]:
-        eng.selfplay_step(3)
-        guard += 1
-        assert guard < 200 and eng.counters()["overflow"] == 0
-    rec, offs, win = eng.fetch_examples()
+    out = SP.play_to_end(eng, n_games, 3, 1.0, steps_below=200, overflow_each_step=True)
+    rec, offs, win = out["rec"], out["offs"], out["win"]
     eng.close()
     ev = _lib.Engine(game, n_slots=4, sims_per_move=2, evaluator=_lib.EVAL_NET)
     ev.load_weights(flat)

@@ -9,9 +9,9 @@ import pytest
 from blackbird_amd import _lib, Connect4, TicTacToe
 from blackbird_amd import weights as W
 from blackbird_amd.Blackbird import ExampleState
-from blackbird_amd.DynamicMCTS import DynamicMCTS
 from blackbird_amd.FixedMCTS import FixedMCTS
 from blackbird_amd.GameState import GameState
+from tests.search_cases import DirectHashSearch as HashSearch
 
 pytestmark = pytest.mark.gpu
 GAMES = {"c4": Connect4.BoardState, "ttt": TicTacToe.BoardState}
@@ -61,17 +61,6 @@ def test_gamestate_interface(golden_dir, key):
     with pytest.raises(ValueError, match="illegal move"):
         s.ApplyAction(0)
     assert type(cls().Winner()) is type(None)
-
-
-class HashSearch(DynamicMCTS):
-    """DynamicMCTS on the validation evaluator (what the golden fixtures were generated with)."""
-    _EVALUATOR = _lib.EVAL_HASH
-    salt = 0
-
-    def _make_engine(self, game_id, n_slots, sims, **kw):
-        return _lib.Engine(game_id, n_slots=n_slots, sims_per_move=max(int(sims), 1), mcts_kind=self._KIND,
-                           max_depth=self._max_depth(), evaluator=_lib.EVAL_HASH, hash_salt=self.salt,
-                           c_puct=float(self.ExplorationRate), **kw)
 
 
 class HashFixed(FixedMCTS):

@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib, weights as W
-from .test_gpu_net import boards_for
+from tests.net_cases import boards_for
+from tests import selfplay_cases as SP
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -161,35 +162,19 @@ def _engine(game, n_slots, n_games, sims, seed, first_id, launch=_lib.LAUNCH_AUT
 
 
 def _play(eng, n_games):
-    eng.reset_counters()
-    eng.selfplay_begin(n_games, 1.0)
-    guard = 0
-    while not eng.selfplay_done()[0]:
-        eng.selfplay_step(2)
-        guard += 1
-        assert guard < 400 and eng.counters()["overflow"] == 0
-    rec, offs, win = eng.fetch_examples()
-    cnt = eng.counters()
-    assert cnt["overflow"] == 0
-    return rec, offs, win, cnt
+    return SP.play_loaded(eng, None, n_games, 2, mode=None, steps_below=400, overflow_each_step=True)
 
 
 def _selfplay(game, n_slots, n_games, sims, R, D, seed, first_id, launch=_lib.LAUNCH_AUTO):
-    """tests/test_gpu_noise_parity.py::_selfplay with the dense width as a parameter: (flat, records, offsets, winners, counters, mode)"""
+    """A run (tests/selfplay_cases.py) with the dense width as a parameter, and its weights (flat) and bb_selfplay_mode (mode)."""
     flat = W.flatten(_weights(game, R, D))
     eng = _engine(game, n_slots, n_games, sims, seed, first_id, launch)
     try:
         eng.load_weights(flat)
         mode = eng.selfplay_mode()
-        rec, offs, win, cnt = _play(eng, n_games)
+        return dict(_play(eng, n_games), flat=flat, mode=mode)
     finally:
         eng.close()
-    return flat, rec, offs, win, cnt, mode
-
-
-def _same(a, b):
-    assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
-    assert a[0].tobytes() == b[0].tobytes()
 
 
 SIZES = {C4: (19, 24, 16), TTT: (21, 30, 16), DC: (6, 8, 16)}  # slots (ragged: not whole workgroups), games (> slots), simulations a move
@@ -204,12 +189,10 @@ def test_structure_by_shape_plays_the_lockstep_games(game, R, D, mode):
     leaves DragonChess 8 of 12288: an LDS copy that overran would change a neighbour's operands and with them the games."""
     n_slots, n_games, sims = SIZES[game]
     a = _selfplay(game, n_slots, n_games, sims, R, D, 5, 300)
-    assert a[5] == mode
+    assert a["mode"] == mode
     b = _selfplay(game, n_slots, n_games, sims, R, D, 5, 300, launch=_lib.LAUNCH_LOCKSTEP)
-    assert b[5] == 0
-    _same(a[1:4], b[1:4])
-    assert a[4]["overflow"] == 0 and b[4]["overflow"] == 0
-    assert a[4]["sims"] == b[4]["sims"]
+    assert b["mode"] == 0
+    SP.assert_same_records(a, b, (game, R, D), counters=("sims",), no_overflow=True)
 
 
 @pytest.mark.parametrize("game,R,D,mode", [(C4, 4, 32, 3), (TTT, 4, 32, 3), (C4, 5, 16, 1)], ids=["c4-exact-fit", "ttt-exact-fit", "c4-fallback"])
@@ -220,7 +203,8 @@ def test_structure_by_shape_matches_oracle_search(orc, game, R, D, mode):
     n_slots, n_games, sims = SIZES[game]
     max_plies = {C4: 43, TTT: 10}[game]
     seed, first_id = 17, 500
-    flat, rec, offs, win, cnt, got = _selfplay(game, n_slots, n_games, sims, R, D, seed, first_id)
+    run = _selfplay(game, n_slots, n_games, sims, R, D, seed, first_id)
+    flat, rec, offs, win, cnt, got = (run[k] for k in ("flat", "rec", "offs", "win", "cnt", "mode"))
     assert got == mode
     ev = _lib.Engine(game, n_slots=4, sims_per_move=2, evaluator=_lib.EVAL_NET, seed=seed, alpha=ALPHA, epsilon=EPS)
     ev.load_weights(flat)
@@ -264,14 +248,9 @@ def test_fallback_rounds_and_the_evaluation_cache(monkeypatch, R, D):
         else:
             monkeypatch.setenv("BB_EVAL_CACHE", "0")
         res[cache] = _selfplay(C4, n_slots, n_games, sims, R, D, 5, 300)
-        assert res[cache][5] == 1
-    _same(res[True][1:4], res[False][1:4])
-    on, off = res[True][4], res[False][4]
-    print("on:", on, "off:", off)
-    assert off["eval_cache_hits"] == 0 and off["eval_cache_probes"] == 0
-    assert on["eval_cache_hits"] == 0 and on["eval_cache_probes"] == 0
-    assert on["evals"] + on["eval_cache_hits"] == off["evals"]
-    assert on["sims"] == off["sims"]
+        assert res[cache]["mode"] == 1
+    SP.assert_same_records(res[True], res[False], (R, D))
+    SP.assert_cache_counters(res[True]["cnt"], res[False]["cnt"], probed=False)
 
 
 # ---- weights of another shape on a live engine -----------------------------------------------------------------------------------
@@ -300,9 +279,8 @@ def test_reload_another_shape_on_a_live_engine(game, first, other, modes):
         eng.set_rng_stream(seed, first_id)
         run_b = _play(eng, n_games)
         ref_b = _play(fresh, n_games)
-        _same(run_b, ref_b)
-        assert run_b[3]["sims"] == ref_b[3]["sims"]
-        assert run_b[0].tobytes() != run_a[0].tobytes()  # (another network: other games)
+        SP.assert_same_records(run_b, ref_b, "other shape", counters=("sims",))
+        assert run_b["rec"].tobytes() != run_a["rec"].tobytes()  # (another network: other games)
 
         eng.load_weights(fa)
         assert eng.selfplay_mode() == modes[0]
@@ -310,8 +288,7 @@ def test_reload_another_shape_on_a_live_engine(game, first, other, modes):
             assert np.array_equal(x, y)
         eng.set_rng_stream(seed, first_id)
         again = _play(eng, n_games)
-        _same(again, run_a)
-        assert again[3]["sims"] == run_a[3]["sims"]
+        SP.assert_same_records(again, run_a, "first shape again", counters=("sims",))
     finally:
         eng.close()
         fresh.close()

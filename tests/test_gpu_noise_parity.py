@@ -15,28 +15,18 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib, weights as W
+from tests import selfplay_cases as SP
 
 pytestmark = pytest.mark.gpu
 ALPHA, EPS = 0.2, 0.3
 
 
 def _selfplay(game, n_slots, n_games, sims, blocks, seed, first_id, noise=True, launch=_lib.LAUNCH_AUTO):
-    gi = _lib.game_info(game)
-    flat = W.flatten(W.init_weights(gi.C, 16, blocks, 16, gi.A, seed=21, perturb=True))
-    eng = _lib.Engine(game, n_slots=n_slots, sims_per_move=sims, evaluator=_lib.EVAL_NET, seed=seed, max_games=n_games,
-                      first_game_id=first_id, noise_on=noise, alpha=ALPHA, epsilon=EPS, launch=launch)
-    eng.load_weights(flat)
+    eng, flat = SP.net_engine(game, n_slots, n_games, sims, blocks, launch=launch, noise=noise, seed=seed, first_id=first_id)
     mode = eng.selfplay_mode()
-    eng.selfplay_begin(n_games, 1.0)
-    guard = 0
-    while not eng.selfplay_done()[0]:
-        eng.selfplay_step(2)
-        guard += 1
-        assert guard < 400 and eng.counters()["overflow"] == 0
-    rec, offs, win = eng.fetch_examples()
-    cnt = eng.counters()
+    out = SP.play_to_end(eng, n_games, 2, 1.0, steps_below=400, overflow_each_step=True)
     eng.close()
-    return flat, rec, offs, win, cnt, mode
+    return flat, out["rec"], out["offs"], out["win"], out["cnt"], mode
 
 
 @pytest.mark.parametrize("game,og,n_slots,n_games,sims,max_plies,blocks", [

@@ -3,16 +3,15 @@ only rollouts take, against the oracle's restatement of MCTS.SampleValue (MCTS.p
 Both sides draw move k of a rollout from Philox(seed, game id, simulation serial, 'ROLL', k) and pick x0 * n >> 32, so
 every comparison is exact.  Every compared search also asserts, on the oracle's side, that no rollout reached the engine's
 2048-ply cap or a position without a legal move (tests/rollout_cases.py), except where that is what is tested."""
-import os
-
 import numpy as np
 import pytest
 
 from blackbird_amd import _lib
 from tests import rollout_cases as RC
+from tests import selfplay_cases as SP
 
 pytestmark = pytest.mark.gpu
-GAMES = {"c4": _lib.GAME_CONNECT4, "ttt": _lib.GAME_TICTACTOE, "dc": _lib.GAME_DRAGONCHESS}
+GAMES = RC.GAMES
 
 
 def _selfplay(name, n_slots=None):
@@ -21,56 +20,19 @@ def _selfplay(name, n_slots=None):
                       mcts_kind=_lib.MCTS_FIXED if fixed else _lib.MCTS_DYNAMIC, max_depth=max_depth,
                       evaluator=_lib.EVAL_ROLLOUT, c_puct=RC.C_PUCT, seed=RC.SEED, max_games=n_games, max_plies=max_plies,
                       first_game_id=RC.FIRST_GAME_ID)
-    eng.selfplay_begin(n_games, 1.0)
-    guard = 0
-    while not eng.selfplay_done()[0]:
-        eng.selfplay_step(8)
-        guard += 1
-        assert guard < 200  # (one slot playing 24 Connect4 games one after another: at most 24 * 42 / 8 = 126 steps)
-    rec, offs, win = eng.fetch_examples()
-    cnt = eng.counters()
+    out = SP.play_to_end(eng, n_games, 8, 1.0, steps_below=200)    # (SP.step_bound: 24 Connect4 games on one slot, 168)
+    rec, offs, win, cnt = out["rec"], out["offs"], out["win"], out["cnt"]
     eng.close()
     assert cnt["overflow"] == 0 and cnt["games_finished"] == n_games and cnt["examples"] == len(rec)
     return rec, offs, win, cnt
-
-
-def _pi(game, r):
-    """visits / total of the example records r as [len(r), A]; DragonChess: the compact child list spread over 4032 actions."""
-    gi = _lib.game_info(game)
-    if gi.dense:
-        return r["visits"][:, :gi.A] / np.maximum(r["total"].astype(np.float64), 1.0)[:, None]
-    pi = np.zeros((len(r), gi.A))
-    for k in range(len(r)):
-        nch = int(r["n_children"][k])
-        if r["total"][k] > 0:
-            pi[k, r["action"][k][:nch]] = r["visits"][k][:nch] / float(r["total"][k])
-    return pi
 
 
 @pytest.mark.parametrize("name", sorted(RC.SELFPLAY))
 def test_rollout_selfplay_vs_oracle(orc, name):
     """Batched self-play with rollouts == the oracle's serial games, example by example.  Fewer slots than games (slots are
     reused), slot counts that do not fill the workgroups' four waves, game ids from 1000."""
-    key = RC.SELFPLAY[name][0]
-    game = GAMES[key]
     rec, offs, win, cnt = _selfplay(name)
-    tot = dict(sims=0, sum_depth=0, nodes=0, terminal_leaves=0)
-    for gidx, o in enumerate(RC.oracle_selfplay(orc, name)):
-        RC.assert_rollouts_decided(o["stats"])
-        r = rec[offs[gidx]:offs[gidx + 1]]
-        assert len(r) == o["n"] and win[gidx] == o["winner"], (gidx, len(r), o["n"], win[gidx], o["winner"])
-        assert (r["game_id"] == RC.FIRST_GAME_ID + gidx).all() and np.array_equal(r["ply"], np.arange(len(r)))
-        assert np.array_equal(_pi(game, r), o["pi"]), gidx
-        assert np.array_equal(r["player"], o["player"]) and np.array_equal(r["z"].astype(np.float32), o["z"]), gidx
-        st = np.ascontiguousarray(r["state"])
-        if key != "dc":
-            st = st.view(np.uint64).reshape(-1, 2)
-        assert np.array_equal(_lib.game_encode(game, st), o["boards"]), gidx
-        tot["sims"] += o["stats"].sims
-        tot["sum_depth"] += o["stats"].sum_depth
-        tot["nodes"] += o["stats"].nodes_reached  # (the engine builds a child when a descent first selects it)
-        tot["terminal_leaves"] += o["stats"].terminal_leaves
-    assert {k: cnt[k] for k in tot} == tot
+    RC.assert_selfplay_is_the_oracles(orc, name, rec, offs, win, cnt)
 
 
 @pytest.mark.parametrize("name", ["c4_fixed10", "dc_dynamic"])
@@ -83,26 +45,6 @@ def test_rollout_selfplay_does_not_depend_on_the_schedule(name):
 
 
 # ---- FindMove in its steps, from mid-game positions, with tree reuse -------------------------------------------------------
-def _positions(golden_dir, key, every):
-    g = np.load(os.path.join(golden_dir, f"playouts_{key}.npz"), allow_pickle=False)
-    idx = np.flatnonzero(g["win_none"] < 0)[::every]
-    return g, idx
-
-
-def _dense(out, s, gi):
-    """Slot s of bb_sample_moves as (plays [A], child values [A])."""
-    plays, value = np.zeros(gi.A), np.zeros(gi.A)
-    if gi.dense:
-        plays[:] = out["child_plays"][s, :gi.A]
-        value[:] = out["child_value"][s, :gi.A]
-    else:
-        k = int((out["child_action"][s] >= 0).sum())
-        assert (out["child_action"][s, k:] == -1).all() and (np.diff(out["child_action"][s, :k]) > 0).all()
-        plays[out["child_action"][s, :k]] = out["child_plays"][s, :k]
-        value[out["child_action"][s, :k]] = out["child_value"][s, :k]
-    return plays, value
-
-
 @pytest.mark.parametrize("masked", [False, True], ids=["all", "masked"])
 @pytest.mark.parametrize("key,fixed,max_depth,every", [("c4", True, 10, 67), ("c4", False, 10, 67),
                                                        ("dc", True, 3, 26), ("dc", False, 10, 26)])
@@ -114,65 +56,7 @@ def test_rollout_find_move_steps_vs_oracle(orc, golden_dir, key, fixed, max_dept
     masked: the second round searches through bb_run_sims_masked with every third slot left out; those slots keep their
     statistics and their later rollouts use the serials of an oracle search that skipped the round.
     root_winrate is the float32 the ABI returns: the oracle's float64 WinRate rounded once."""
-    game, og = GAMES[key], RC.ORC_GAME[key]
-    gi = _lib.game_info(game)
-    g, idx = _positions(golden_dir, key, every)
-    n = len(idx)
-    assert (60 <= n <= 70) if key == "c4" else (44 <= n <= 52)
-    turns = set(zip(g["player"][idx].tolist(), g["prev"][idx].tolist()))
-    assert {p for p, _ in turns} == {1, 2} and (key != "dc" or {(1, 1), (1, 2), (2, 1)} <= turns)
-    if key == "dc":
-        packed = _lib.pack_dc(g["board"][idx].reshape(-1, 8, 8), g["player"][idx], g["prev"][idx], g["castle"][idx])
-    else:
-        H, W, _s = _lib.GRID[game]
-        packed = _lib.pack_grid(game, g["board"][idx].reshape(-1, H, W, 2), g["player"][idx], g["prev"][idx])
-    lids = 7 + 3 * np.arange(n)  # distinct, not the slot numbers
-    eng = _lib.Engine(game, n_slots=n, sims_per_move=9, mcts_kind=_lib.MCTS_FIXED if fixed else _lib.MCTS_DYNAMIC,
-                      max_depth=max_depth, evaluator=_lib.EVAL_ROLLOUT, c_puct=RC.C_PUCT, seed=RC.SEED,
-                      first_game_id=RC.FIRST_GAME_ID, max_plies=42 if key == "c4" else 64)
-    eng.set_roots(packed, game_ids=lids)
-    cfg = RC.oracle_cfg(orc, key, fixed, max_depth)
-    search = [orc.Search(cfg, RC.FIRST_GAME_ID + int(lids[s])) for s in range(n)]
-    state = [orc.state_from_arrays(og, g["board"][i], g["player"][i], g["prev"][i] or None, g["castle"][i]) for i in idx]
-    alive = np.ones(n, dtype=bool)  # (a game that ends drops out)
-    for rnd, sims in enumerate((2, 5, 9)):
-        run = alive & ((np.arange(n) % 3 != 2) if (masked and rnd == 1) else True)
-        if masked and rnd == 1:
-            before = eng.sample_moves(0)
-            eng.run_sims(sims, mask=run.astype(np.uint8))
-        else:
-            eng.run_sims(sims, mask=None if alive.all() else run.astype(np.uint8))
-        out = eng.sample_moves(0)
-        acts = np.full(n, -1, dtype=np.int32)
-        for s in range(n):
-            if not run[s]:
-                if alive[s]:  # left out of this round: nothing of the slot has changed
-                    for f in ("root_plays", "root_winrate", "child_action", "child_plays", "child_value", "action"):
-                        assert np.array_equal(out[f][s], before[f][s]), (f, s)
-                continue
-            o = search[s].find_move(state[s], 0, sims)
-            where = (key, fixed, rnd, s)
-            plays, value = _dense(out, s, gi)
-            assert out["root_plays"][s] == o["root_plays"], where
-            assert out["root_winrate"][s] == np.float32(o["winrate"]), where
-            assert np.array_equal(plays, o["plays"]), where
-            assert out["action"][s] == o["action"], where
-            assert np.array_equal(np.where(plays > 0, value / np.maximum(plays, 1), 0.0), o["winrates"]), where
-            acts[s] = o["action"]
-            state[s] = o["next"]
-            search[s].move_root(state[s])
-            if orc.winner(og, state[s]) is not None:
-                alive[s] = False
-        eng.move_roots(acts)
-    cnt = eng.counters()
-    eng.close()
-    stats = [sr.stats() for sr in search]
-    for st in stats:
-        RC.assert_rollouts_decided(st)
-    assert cnt["overflow"] == 0
-    assert cnt["sims"] == sum(st.sims for st in stats) and cnt["sum_depth"] == sum(st.sum_depth for st in stats)
-    assert cnt["nodes"] == sum(st.nodes_reached for st in stats)
-    assert cnt["terminal_leaves"] == sum(st.terminal_leaves for st in stats)
+    RC.find_move_steps_vs_oracle(orc, golden_dir, key, fixed, max_depth, every, masked)
 
 
 # ---- DragonChess: a position without a legal move --------------------------------------------------------------------------

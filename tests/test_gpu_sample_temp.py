@@ -17,8 +17,10 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib
+from tests import arena_cases as AC
 from tests import temp_cases as T
-from tests import test_gpu_selfplay_starts as SS
+from tests import model_cases as M
+from tests import selfplay_cases as SS
 
 pytestmark = pytest.mark.gpu
 C4, TTT, DC = _lib.GAME_CONNECT4, _lib.GAME_TICTACTOE, _lib.GAME_DRAGONCHESS
@@ -97,7 +99,7 @@ def test_lockstep_hash_selfplay_vs_oracle(orc, game, temp):
     orc.selfplay_game at temps 0.1, 0.5 and 0, game by game."""
     L = T.LOCKSTEP
     eng = _lockstep_engine(game)
-    out = SS._play(eng, L["n_games"], temp=temp)
+    out = SS.play_from_starts(eng, L["n_games"], temp=temp)
     eng.close()
     games = T.lockstep_games(orc, OG[game], temp)
     for k, o in enumerate(games):
@@ -105,7 +107,7 @@ def test_lockstep_hash_selfplay_vs_oracle(orc, game, temp):
     assert out["cnt"]["sims"] == sum(o["stats"].sims for o in games) and out["cnt"]["examples"] == len(out["rec"])
     if temp == 0:
         other = _lockstep_engine(game, seed=L["seed"] + 1)
-        SS._same(out, SS._play(other, L["n_games"], temp=0.0), "another seed")
+        SS.assert_same_runs(out, SS.play_from_starts(other, L["n_games"], temp=0.0), "another seed")
         other.close()
 
 
@@ -115,13 +117,13 @@ def test_dense_launch_structures_are_byte_identical(game, n_slots, n_games, sims
     """1-block network, prior noise on: queue kernel (mode 3), rounds (mode 1), lock-step (mode 0)."""
     runs, modes = {}, {}
     for name, launch in (("queue", _lib.LAUNCH_AUTO), ("rounds", _lib.LAUNCH_ROUNDS), ("lockstep", _lib.LAUNCH_LOCKSTEP)):
-        eng, _flat = SS._net_engine(game, n_slots, n_games, sims, 1, launch=launch, seed=5, first_id=0)
+        eng, _flat = SS.net_engine(game, n_slots, n_games, sims, 1, launch=launch, seed=5, first_id=0)
         modes[name] = eng.selfplay_mode()
-        runs[name] = SS._play(eng, n_games, step=2, temp=temp)
+        runs[name] = SS.play_from_starts(eng, n_games, step=2, temp=temp)
         eng.close()
     assert modes == {"queue": 3, "rounds": 1, "lockstep": 0}
     for other in ("rounds", "lockstep"):
-        SS._same(runs["queue"], runs[other], (other, temp))
+        SS.assert_same_runs(runs["queue"], runs[other], (other, temp))
 
 
 @pytest.mark.parametrize("temp", T.SELFPLAY_TEMPS)
@@ -129,12 +131,12 @@ def test_dc_one_wave_kernel_is_lockstep(temp):
     n_slots, n_games, sims = 5, 9, 12
     runs, modes = {}, {}
     for name, launch in (("wave", _lib.LAUNCH_AUTO), ("lockstep", _lib.LAUNCH_LOCKSTEP)):
-        eng, _flat = SS._net_engine(DC, n_slots, n_games, sims, 1, launch=launch, seed=7, first_id=0, max_plies=5)
+        eng, _flat = SS.net_engine(DC, n_slots, n_games, sims, 1, launch=launch, seed=7, first_id=0, max_plies=5)
         modes[name] = eng.selfplay_mode()
-        runs[name] = SS._play(eng, n_games, temp=temp)
+        runs[name] = SS.play_from_starts(eng, n_games, temp=temp)
         eng.close()
     assert modes == {"wave": 5, "lockstep": 0}
-    SS._same(runs["wave"], runs["lockstep"], ("dc", temp))
+    SS.assert_same_runs(runs["wave"], runs["lockstep"], ("dc", temp))
 
 
 @pytest.mark.parametrize("temp", T.SELFPLAY_TEMPS)
@@ -150,9 +152,9 @@ def test_rollout_wave_selfplay_is_lockstep(game, fixed, temp):
                           max_plies=5 if game == DC else None)
         eng.selfplay_rollouts(wave)
         assert eng.selfplay_mode() == (6 if wave else 0)
-        runs[wave] = SS._play(eng, n_games, temp=temp)
+        runs[wave] = SS.play_from_starts(eng, n_games, temp=temp)
         eng.close()
-    SS._same(runs[True], runs[False], (game, fixed, temp))
+    SS.assert_same_runs(runs[True], runs[False], (game, fixed, temp))
     assert {k: runs[True]["cnt"][k] for k in SS.COUNTERS} == {k: runs[False]["cnt"][k] for k in SS.COUNTERS}
 
 
@@ -163,7 +165,6 @@ def test_sample_moves_refuses_an_overflowing_temperature_connect4(orc):
     and FindMove raises ValueError.  (Engine.sample_moves itself does not raise: bb_sample_moves reports per slot, which
     tests/test_gpu_mcts.py::test_error_mapping holds; the ValueError is the front end's, MCTS.FindMove.)"""
     from blackbird_amd import Connect4
-    from tests import test_gpu_arena_device as AD
     n = T.SAMPLE["n_slots"]
     eng, rows = _sample_engine(orc, C4, _lib.LAUNCH_LOCKSTEP)
     for u in (np.full(n, 0.5), np.zeros(n), None):
@@ -174,7 +175,7 @@ def test_sample_moves_refuses_an_overflowing_temperature_connect4(orc):
             assert orc.sample_action(o["plays"], T.OVERFLOW_TEMP, 0.5) == -3
     assert (eng.sample_moves(50.0, np.full(n, 0.5))["action"] >= 0).all()     # the tree is untouched, a sane temp still samples
     eng.close()
-    player = AD._HashPlayer(Connect4.BoardState, 11, playLimit=48)
+    player = AC.HashPlayer(Connect4.BoardState, 11, playLimit=48)
     with pytest.raises(ValueError, match="NaN"):
         player.FindMove(Connect4.BoardState(), T.OVERFLOW_TEMP)
     nxt, _wr, _p = player.FindMove(Connect4.BoardState(), 50.0)                # (the same root, 48 more simulations)
@@ -183,7 +184,6 @@ def test_sample_moves_refuses_an_overflowing_temperature_connect4(orc):
 
 def test_sample_moves_refuses_an_overflowing_temperature_dragonchess(orc):
     from blackbird_amd import DragonChess
-    from tests import test_gpu_arena_device as AD
     n, S = T.SAMPLE["n_slots"], T.SAMPLE
     eng = _lib.Engine(DC, n_slots=n, sims_per_move=S["sims"], evaluator=_lib.EVAL_HASH, hash_salt=S["salt"], salt_per_game=True,
                       seed=S["seed"])
@@ -200,7 +200,7 @@ def test_sample_moves_refuses_an_overflowing_temperature_dragonchess(orc):
     ok = eng.sample_moves(50.0, np.full(n, 0.5))
     assert (ok["action"] >= 0).all() and ok["action"][0] == orc.sample_action(o["plays"], 50.0, 0.5)
     eng.close()
-    player = AD._HashPlayer(DragonChess.BoardState, 11, playLimit=48)
+    player = AC.HashPlayer(DragonChess.BoardState, 11, playLimit=48)
     with pytest.raises(ValueError, match="NaN"):
         player.FindMove(DragonChess.BoardState(), T.OVERFLOW_TEMP)
 
@@ -233,7 +233,7 @@ def test_generate_training_samples_raises_at_an_overflowing_temperature(tmp_path
     from blackbird_amd import Blackbird, Connect4
     monkeypatch.chdir(tmp_path)
     np.random.seed(11)
-    m = Blackbird.Model(Connect4.BoardState, "hot", {"explorationRate": 0.85, "playLimit": 48}, SS._net_cfg())
+    m = Blackbird.Model(Connect4.BoardState, "hot", {"explorationRate": 0.85, "playLimit": 48}, M.net_config(blocks=1, eps=0.3))
     np.random.seed(21)
     with pytest.raises(ValueError, match="NaN"):
         Blackbird.GenerateTrainingSamples(m, 3, T.OVERFLOW_TEMP)
@@ -246,9 +246,8 @@ def test_generate_training_samples_raises_at_an_overflowing_temperature(tmp_path
 
 def test_arena_reports_nan_for_every_game_at_an_overflowing_temperature():
     from blackbird_amd import Connect4
-    from tests import test_gpu_arena_device as AD
-    players = (AD._HashPlayer(Connect4.BoardState, 11, playLimit=48), AD._HashPlayer(Connect4.BoardState, 22, c_puct=1.3, playLimit=48))
-    ea, eb = AD._engines(players, 5)
+    players = (AC.HashPlayer(Connect4.BoardState, 11, playLimit=48), AC.HashPlayer(Connect4.BoardState, 22, c_puct=1.3, playLimit=48))
+    ea, eb = AC.searcher_engines(players, 5)
     ar = _lib.Arena(ea, eb, log_plies=4)
     try:
         ar.begin([True, False, True, True, False], T.OVERFLOW_TEMP)

@@ -10,88 +10,45 @@ import numpy as np
 import pytest
 
 from blackbird_amd import Connect4, _lib, arena
-from blackbird_amd import weights as W
 from blackbird_amd.MCTS import MCTS
-from tests.test_gpu_search_wave import _endgame_roots, _engine, _model, _openings, _snap
+from tests import model_cases as M
+from tests import search_cases as S
 
 pytestmark = pytest.mark.gpu
 C4, TTT = _lib.GAME_CONNECT4, _lib.GAME_TICTACTOE
 AUTO, LOCK, WAVE = _lib.LAUNCH_AUTO, _lib.LAUNCH_LOCKSTEP, _lib.LAUNCH_WAVE
 NET = ("net", 16, 2)
-CACHE_COUNTERS = ("evals", "eval_cache_hits", "eval_cache_probes")
 
 
-def _trio(game, n_slots, ev=NET, **kw):
+def _engine(game, n_slots, launch, ev, **kw):
+    return S.dense_engine(game, n_slots, launch, ev, node_capacity=512, **kw)
+
+
+def _trio(game, n_slots):
     """Lock-step, wave, wave with search_cache: the same engine otherwise."""
-    lock, wave = _engine(game, n_slots, LOCK, ev, **kw), _engine(game, n_slots, WAVE, ev, **kw)
-    cached = _engine(game, n_slots, WAVE, ev, search_cache=True, **kw)
-    assert lock.run_sims_structure() == LOCK and wave.run_sims_structure() == WAVE and cached.run_sims_structure() == WAVE
-    return lock, wave, cached
+    return S.lock_and_wave(lambda launch, **kw: _engine(game, n_slots, launch, NET, **kw), WAVE, cached=True)
 
 
-def _set(engines, states):
-    for e in engines:
-        e.set_roots(states, game_ids=7 * np.arange(len(states)) + 3)
+def _model(game, name, seed):
+    return M.model(game, name, seed=seed, play_limit=32, eps=0.3, blocks=2)
 
 
-def _close(*engines):
-    for e in engines:
-        e.close()
-
-
-def _same_trees(a, b, what=""):
-    """Snapshots (tests/test_gpu_search_wave.py::_snap) equal in everything but the three counters the cache may change."""
-    (oa, ra, ca), (ob, rb, cb) = a, b
-    for k in oa:
-        assert np.array_equal(oa[k], ob[k]), (what, k, oa[k], ob[k])
-    assert len(ra) == len(rb), what
-    for i, (x, y) in enumerate(zip(ra, rb)):
-        for k in x:
-            assert np.array_equal(x[k], y[k]), (what, "node row", i, k, x[k], y[k])
-    rest = lambda c: {k: v for k, v in c.items() if k not in CACHE_COUNTERS}
-    assert rest(ca) == rest(cb), (what, ca, cb)
-
-
-def _check(snaps, what=""):
-    """(lock-step, wave, cached wave) snapshots of one moment: same trees, and the counter identities."""
-    a, b, c = snaps
-    _same_trees(a, b, what)
-    _same_trees(a, c, what)
-    ca, cb, cc = a[2], b[2], c[2]
-    assert ca == cb, (what, ca, cb)
-    assert ca["eval_cache_hits"] == 0 and ca["eval_cache_probes"] == 0, (what, ca)
-    assert cc["eval_cache_probes"] == cc["evals"] + cc["eval_cache_hits"] == ca["evals"], (what, ca, cc)
-
-
-def _step(engines, sims, rng, mask=None, what=""):
-    u = rng.random_sample(engines[0].n_slots)
-    for e in engines:
-        e.run_sims(sims, mask=mask)
-    snaps = [_snap(e, 1.0, u) for e in engines]
-    _check(snaps, what)
-    return snaps
-
-
-def _moves(snapshot):
-    return np.where(snapshot[0]["action"] >= 0, snapshot[0]["action"], -1).astype(np.int32)
+def _equal_trees(a, b, what):
+    S.assert_same(a, b, what, ignore_counters=tuple(a[2]))
 
 
 @pytest.mark.parametrize("sims", [2, 50])
 @pytest.mark.parametrize("n_slots", [1, 3, 5])   # never a multiple of the four waves of a workgroup
 def test_same_bits_over_three_moves(n_slots, sims):
     engines = _trio(C4, n_slots)
-    _set(engines, _openings(C4, n_slots))
+    S.set_roots_on(engines, S.openings(C4, n_slots))
     rng = np.random.RandomState(5)
     for move in range(3):
-        snaps = _step(engines, sims, rng, what=(n_slots, sims, move))
+        snaps = S.step_and_compare(engines, sims, rng, S.view_rows, what=(n_slots, sims, move), check=S.same_trio)
         assert snaps[0][2]["overflow"] == 0 and snaps[0][2]["sims"] == (move + 1) * sims * n_slots
         for e in engines:
-            e.move_roots(_moves(snaps[0]))
-    _close(*engines)
-
-
-def _delta(after, before):
-    return {k: after[k] - before[k] for k in CACHE_COUNTERS}
+            e.move_roots(S.sampled_moves(snaps[0]))
+    S.close_all(*engines)
 
 
 def test_second_pass_is_all_hits_and_a_reload_empties_the_table():
@@ -100,69 +57,64 @@ def test_second_pass_is_all_hits_and_a_reload_empties_the_table():
     Then other weights: no entry of the first network may answer, so every position's first evaluation is a tower run and the
     trees are those of a fresh lock-step engine with the second weights."""
     cached = _engine(C4, 3, WAVE, NET, search_cache=True)
-    st, ids = _openings(C4, 3), 7 * np.arange(3) + 3
+    st, ids = S.openings(C4, 3), S.game_ids(3)
     u = np.random.RandomState(12).random_sample(3)
     zero = cached.counters()
     cached.set_roots(st, game_ids=ids)
     cached.run_sims(50)
-    first = _snap(cached, 1.0, u)
-    d1 = _delta(first[2], zero)
+    first = S.snapshot(cached, 1.0, u, S.view_rows)
+    d1 = S.counter_delta(first[2], zero)
     assert d1["eval_cache_probes"] == d1["evals"] + d1["eval_cache_hits"] > 0
     cached.set_roots(st, game_ids=ids)
     cached.run_sims(50)
-    second = _snap(cached, 1.0, u)
-    d2 = _delta(second[2], first[2])
+    second = S.snapshot(cached, 1.0, u, S.view_rows)
+    d2 = S.counter_delta(second[2], first[2])
     assert d2["evals"] == 0 and d2["eval_cache_hits"] == d2["eval_cache_probes"] == d1["eval_cache_probes"], (d1, d2)
-    (oa, ra, _), (ob, rb, _) = first, second
-    assert all(np.array_equal(oa[k], ob[k]) for k in oa) and len(ra) == len(rb)
-    assert all(np.array_equal(x[k], y[k]) for x, y in zip(ra, rb) for k in x)
+    _equal_trees(first, second, "second pass")
 
-    gi = _lib.game_info(C4)
-    other = W.flatten(W.init_weights(gi.C, 16, 2, 16, gi.A, seed=22, perturb=True))
+    other = S.dense_weights(C4, 16, 2, seed=22)
     cached.load_weights(other)
     cached.set_roots(st, game_ids=ids)
     cached.run_sims(1)    # each slot's first simulation evaluates its root: three positions the table held before the reload
-    d3 = _delta(cached.counters(), second[2])
+    d3 = S.counter_delta(cached.counters(), second[2])
     assert d3 == {"evals": 3, "eval_cache_hits": 0, "eval_cache_probes": 3}, d3
     cached.run_sims(49)
-    third = _snap(cached, 1.0, u)
-    fresh = _lib.Engine(C4, evaluator=_lib.EVAL_NET, noise_on=True, alpha=0.2, epsilon=0.3, n_slots=3, sims_per_move=8, seed=17,
-                        first_game_id=1000, launch=LOCK, node_capacity=512)
+    third = S.snapshot(cached, 1.0, u, S.view_rows)
+    fresh = _lib.Engine(C4, n_slots=3, launch=LOCK, node_capacity=512, **S.SEARCH_KW, **S.NET_KW)   # has seen no other weights
     fresh.load_weights(other)
     fresh.set_roots(st, game_ids=ids)
     fresh.run_sims(50)
-    want = _snap(fresh, 1.0, u)
-    (oa, ra, ca), (ob, rb, _) = want, third
-    assert all(np.array_equal(oa[k], ob[k]) for k in oa) and len(ra) == len(rb)
-    assert all(np.array_equal(x[k], y[k]) for x, y in zip(ra, rb) for k in x)
+    want = S.snapshot(fresh, 1.0, u, S.view_rows)
+    _equal_trees(want, third, "other weights")
+    ca = want[2]
     assert not np.array_equal(want[0]["child_value"], first[0]["child_value"])   # (the second network is another one)
-    d4 = _delta(third[2], second[2])
+    d4 = S.counter_delta(third[2], second[2])
     assert d4["eval_cache_probes"] == d4["evals"] + d4["eval_cache_hits"] == ca["evals"], (d4, ca)
-    _close(cached, fresh)
+    S.close_all(cached, fresh)
 
 
 def test_masked_slots():
     engines = _trio(C4, 3)
-    _set(engines, _openings(C4, 3))
+    S.set_roots_on(engines, S.openings(C4, 3))
     rng = np.random.RandomState(7)
     for k, mask in enumerate((np.array([1, 0, 1], dtype=np.uint8), np.array([1, 1, 0], dtype=np.uint8))):
         before = engines[2].node_view(int(np.nonzero(mask == 0)[0][0]), -1)
-        _step(engines, 20, rng, mask=mask, what=k)
+        S.step_and_compare(engines, 20, rng, S.view_rows, mask=mask, what=k, check=S.same_trio)
         now = engines[2].node_view(int(np.nonzero(mask == 0)[0][0]), -1)
         assert all(np.array_equal(now[f], before[f]) for f in now), k
-    _close(*engines)
+    S.close_all(*engines)
 
 
 def test_endgame_roots(golden_dir):
     engines = _trio(C4, 5)
-    _set(engines, _endgame_roots(golden_dir, "c4"))
+    S.set_roots_on(engines, S.endgame_roots(golden_dir, "c4"))
     rng = np.random.RandomState(6)
     for move in range(2):
-        snaps = _step(engines, 50, rng, what=move)
+        snaps = S.step_and_compare(engines, 50, rng, S.view_rows, what=move, check=S.same_trio)
         assert snaps[0][2]["terminal_leaves"] > 0 and snaps[0][2]["overflow"] == 0
         for e in engines:
-            e.move_roots(_moves(snaps[0]))
-    _close(*engines)
+            e.move_roots(S.sampled_moves(snaps[0]))
+    S.close_all(*engines)
 
 
 NO_PROBE = {
@@ -180,14 +132,14 @@ def test_engines_without_table_or_wave_take_the_flag_and_probe_nothing(monkeypat
         monkeypatch.setenv("BB_EVAL_CACHE", env)
     off, on = _engine(game, 3, launch, ev, **kw), _engine(game, 3, launch, ev, search_cache=True, **kw)
     assert off.run_sims_structure() == on.run_sims_structure() == (LOCK if launch == AUTO else WAVE)
-    _set((off, on), _openings(game, 3))
+    S.set_roots_on((off, on), S.openings(game, 3))
     u = np.random.RandomState(11).random_sample(3)
     for e in (off, on):
         e.run_sims(50)
-    a, b = _snap(off, 1.0, u), _snap(on, 1.0, u)
-    _same_trees(a, b, case)
+    a, b = S.snapshot(off, 1.0, u, S.view_rows), S.snapshot(on, 1.0, u, S.view_rows)
+    S.assert_same(a, b, case, ignore_counters=S.CACHE_COUNTERS)
     assert a[2] == b[2] and b[2]["eval_cache_probes"] == 0 and b[2]["evals"] > 0, (case, a[2], b[2])
-    _close(off, on)
+    S.close_all(off, on)
 
 
 def test_any_other_value_is_refused():

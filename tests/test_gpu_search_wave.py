@@ -2,101 +2,29 @@
 lock-step loop it replaces.  Per slot the sequence of operations is the same, from the same device functions, so everything
 a caller can see -- sampled moves, root statistics, the node rows of the root and of its children, the counters -- must be
 the lock-step engine's bit for bit; engines the kernel does not cover must say so and search lock-step."""
-import functools
 import os
 
 import numpy as np
 import pytest
 
-from blackbird_amd import Blackbird, Connect4, TicTacToe, _lib, arena
-from blackbird_amd import weights as W
-from blackbird_amd.DynamicMCTS import DynamicMCTS
+from blackbird_amd import Connect4, TicTacToe, _lib, arena
 from blackbird_amd.MCTS import MCTS
-from tests.test_gpu_mcts import pack_states, same_position
+from tests import model_cases as M
+from tests import search_cases as S
+from tests.search_cases import GAME_OF, HashSearch, launches  # noqa: F401  (launches: a fixture)
 
 pytestmark = pytest.mark.gpu
 C4, TTT, DC = _lib.GAME_CONNECT4, _lib.GAME_TICTACTOE, _lib.GAME_DRAGONCHESS
 LOCK, WAVE = _lib.LAUNCH_LOCKSTEP, _lib.LAUNCH_WAVE
-GAME_OF = {"c4": C4, "ttt": TTT}
 CLS_OF = {"c4": Connect4.BoardState, "ttt": TicTacToe.BoardState}
 
 
-@functools.lru_cache(maxsize=None)
-def _weights(game, filters, blocks):
-    gi = _lib.game_info(game)
-    return W.flatten(W.init_weights(gi.C, filters, blocks, 16, gi.A, seed=21, perturb=True))
-
-
-def _engine(game, n_slots, launch, ev="hash", **kw):
-    """ev: 'hash', 'rollout', or ('net', filters, blocks) with the prior noise on (epsilon 0.3)."""
-    kw.setdefault("node_capacity", 512)
-    common = dict(n_slots=n_slots, sims_per_move=8, seed=17, first_game_id=1000, launch=launch, **kw)
-    if ev == "hash":
-        return _lib.Engine(game, evaluator=_lib.EVAL_HASH, hash_salt=4242, salt_per_game=True, **common)
-    if ev == "rollout":
-        return _lib.Engine(game, evaluator=_lib.EVAL_ROLLOUT, **common)
-    eng = _lib.Engine(game, evaluator=_lib.EVAL_NET, noise_on=True, alpha=0.2, epsilon=0.3, **common)
-    eng.load_weights(_weights(game, ev[1], ev[2]))
-    return eng
+def _engine(game, n_slots, launch, ev="hash", node_capacity=512, **kw):
+    return S.dense_engine(game, n_slots, launch, ev, node_capacity=node_capacity, **kw)
 
 
 def _pair(game, n_slots, ev="hash", want=WAVE, **kw):
-    lock, wave = _engine(game, n_slots, LOCK, ev, **kw), _engine(game, n_slots, WAVE, ev, **kw)
-    assert lock.run_sims_structure() == LOCK and wave.run_sims_structure() == want
-    return lock, wave
-
-
-def _openings(game, n):
-    """n different positions two plies into the game."""
-    A = _lib.game_info(game).A
-    st = np.repeat(_lib.game_initial(game), n, axis=0)
-    i = np.arange(n)
-    for moves in (i % A, (i + 4) % A):
-        st, status = _lib.game_apply(game, st, moves.astype(np.int32))
-        assert (status == 0).all()
-    return st
-
-
-def _set(engines, states):
-    for e in engines:
-        e.set_roots(states, game_ids=7 * np.arange(len(states)) + 3)
-
-
-def _snap(eng, temp=1.0, u=None):
-    """Everything of the trees a caller can read: bb_sample_moves' outputs, the node rows of every root and of its children
-    (bb_node_view), the counters."""
-    out = eng.sample_moves(temp, u)
-    rows = []
-    for s in range(eng.n_slots):
-        root = eng.node_view(s, -1)
-        rows.append(root)
-        rows += [eng.node_view(s, int(c) & 0x3FFFFFFF) for c in root["child"] if c >= 0]
-    return out, rows, eng.counters()
-
-
-def _same(a, b, what=""):
-    (oa, ra, ca), (ob, rb, cb) = a, b
-    for k in oa:
-        assert np.array_equal(oa[k], ob[k]), (what, k, oa[k], ob[k])
-    assert len(ra) == len(rb), what
-    for i, (x, y) in enumerate(zip(ra, rb)):
-        for k in x:
-            assert np.array_equal(x[k], y[k]), (what, "node row", i, k, x[k], y[k])
-    assert ca == cb, (what, ca, cb)
-
-
-def _step(lock, wave, sims, rng, mask=None, what=""):
-    """One run_sims on both engines, compared; returns the lock-step snapshot."""
-    u = rng.random_sample(lock.n_slots)
-    for e in (lock, wave):
-        e.run_sims(sims, mask=mask)
-    a, b = _snap(lock, 1.0, u), _snap(wave, 1.0, u)
-    _same(a, b, what)
-    return a
-
-
-def _moves(snapshot):
-    return np.where(snapshot[0]["action"] >= 0, snapshot[0]["action"], -1).astype(np.int32)
+    return S.lock_and_wave(lambda launch: _engine(game, n_slots, launch, ev, **kw), want)
 
 
 EVALUATORS = {"hash": "hash", "net_r0": ("net", 16, 0), "net_r2": ("net", 16, 2)}
@@ -110,29 +38,14 @@ def test_same_bits_as_lockstep_over_three_moves(key, ev, n_slots, sims):
     """Three consecutive moves with tree reuse (move_roots); after every search the two engines agree on everything."""
     game = GAME_OF[key]
     lock, wave = _pair(game, n_slots, EVALUATORS[ev])
-    _set((lock, wave), _openings(game, n_slots))
+    S.set_roots_on((lock, wave), S.openings(game, n_slots))
     rng = np.random.RandomState(5)
     for move in range(3):
-        a = _step(lock, wave, sims, rng, what=(key, ev, n_slots, sims, move))
+        a = S.step_and_compare((lock, wave), sims, rng, S.view_rows, what=(key, ev, n_slots, sims, move))[0]
         assert a[2]["overflow"] == 0 and a[2]["sims"] == (move + 1) * sims * n_slots
         for e in (lock, wave):
-            e.move_roots(_moves(a))
-    for e in (lock, wave):
-        e.close()
-
-
-def _endgame_roots(golden_dir, key):
-    """Five roots close to the end of recorded games: two and three plies before a full board (a drawn game: few legal moves,
-    terminal leaves everywhere) and one or two plies before a win."""
-    g = np.load(os.path.join(golden_dir, f"playouts_{key}.npz"), allow_pickle=False)
-    st = pack_states(GAME_OF[key], g)
-    gs = g["game_start"]
-    last = gs[1:] - 1                      # a game's final position (no action follows)
-    drawn = [i for i in range(len(last)) if g["win_none"][last[i]] == 0]
-    won = [i for i in range(len(last)) if g["win_none"][last[i]] > 0 and last[i] - gs[i] >= 4]
-    assert drawn and len(won) >= 2
-    idx = [last[drawn[0]] - 2, last[drawn[0]] - 3, last[won[0]] - 1, last[won[1]] - 1, last[won[1]] - 2]
-    return st[np.array(idx)]
+            e.move_roots(S.sampled_moves(a))
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("ev", ["hash", "net_r2"])
@@ -140,34 +53,32 @@ def _endgame_roots(golden_dir, key):
 def test_roots_next_to_a_win_and_to_a_full_board(golden_dir, key, ev):
     game = GAME_OF[key]
     lock, wave = _pair(game, 5, EVALUATORS[ev])
-    _set((lock, wave), _endgame_roots(golden_dir, key))
+    S.set_roots_on((lock, wave), S.endgame_roots(golden_dir, key))
     rng = np.random.RandomState(6)
     for move in range(2):
-        a = _step(lock, wave, 50, rng, what=(key, ev, move))
+        a = S.step_and_compare((lock, wave), 50, rng, S.view_rows, what=(key, ev, move))[0]
         assert a[2]["terminal_leaves"] > 0 and a[2]["overflow"] == 0
         for e in (lock, wave):
-            e.move_roots(_moves(a))
-    for e in (lock, wave):
-        e.close()
+            e.move_roots(S.sampled_moves(a))
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("ev", ["hash", "net_r2"])
 def test_masked_search_leaves_the_other_slots_alone(ev):
     lock, wave = _pair(C4, 5, EVALUATORS[ev])
-    _set((lock, wave), _openings(C4, 5))
+    S.set_roots_on((lock, wave), S.openings(C4, 5))
     rng = np.random.RandomState(7)
     even = np.array([1, 0, 1, 0, 1], dtype=np.uint8)
     before = None
     for k, mask in enumerate((even, 1 - even, even, 1 - even)):
-        a = _step(lock, wave, 20, rng, mask=mask, what=(ev, k))
+        a = S.step_and_compare((lock, wave), 20, rng, S.view_rows, mask=mask, what=(ev, k))[0]
         for s in np.nonzero(mask == 0)[0]:   # a slot outside the mask: its tree is what it was
             now = wave.node_view(int(s), -1)
             if before is not None:
                 assert all(np.array_equal(now[f], before[int(s)][f]) for f in now), (ev, k, s)
         before = {s: wave.node_view(s, -1) for s in range(5)}
         assert a[2]["sims"] == 20 * sum(int(m.sum()) for m in (even, 1 - even, even, 1 - even)[:k + 1])
-    for e in (lock, wave):
-        e.close()
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("ev", ["hash", "net_r0"])
@@ -175,17 +86,16 @@ def test_three_short_calls_equal_one_long_call(ev):
     """run_sims(16) three times == run_sims(48) once: nothing of a call outlives its launch but the tree."""
     lock, once = _pair(C4, 3, EVALUATORS[ev])
     thrice = _engine(C4, 3, WAVE, EVALUATORS[ev])
-    _set((lock, once, thrice), _openings(C4, 3))
+    S.set_roots_on((lock, once, thrice), S.openings(C4, 3))
     u = np.random.RandomState(8).random_sample(3)
     lock.run_sims(48)
     once.run_sims(48)
     for _ in range(3):
         thrice.run_sims(16)
-    a = _snap(lock, 1.0, u)
-    _same(a, _snap(once, 1.0, u), "48 at once")
-    _same(a, _snap(thrice, 1.0, u), "3 x 16")
-    for e in (lock, once, thrice):
-        e.close()
+    a = S.snapshot(lock, 1.0, u, S.view_rows)
+    S.assert_same(a, S.snapshot(once, 1.0, u, S.view_rows), "48 at once")
+    S.assert_same(a, S.snapshot(thrice, 1.0, u, S.view_rows), "3 x 16")
+    S.close_all(lock, once, thrice)
 
 
 @pytest.mark.parametrize("ev", ["hash", "net_r2"])
@@ -193,112 +103,38 @@ def test_ancestors_and_reset_roots(ev):
     """track_ancestors: every backup also walks the chain above the root (backup_path, not the store-only variants), so
     after two moves bb_reset_roots finds the same statistics at the top."""
     lock, wave = _pair(TTT, 3, EVALUATORS[ev], track_ancestors=True)
-    _set((lock, wave), _openings(TTT, 3))
+    S.set_roots_on((lock, wave), S.openings(TTT, 3))
     rng = np.random.RandomState(9)
     for move in range(2):
-        a = _step(lock, wave, 30, rng, what=(ev, move))
+        a = S.step_and_compare((lock, wave), 30, rng, S.view_rows, what=(ev, move))[0]
         for e in (lock, wave):
-            e.move_roots(_moves(a))
-    a = _step(lock, wave, 30, rng, what=(ev, "below"))
+            e.move_roots(S.sampled_moves(a))
+    a = S.step_and_compare((lock, wave), 30, rng, S.view_rows, what=(ev, "below"))[0]
     for e in (lock, wave):
         e.reset_roots()
-    top = _snap(lock, 0.0)
-    _same(top, _snap(wave, 0.0), (ev, "after reset"))
+    top = S.snapshot(lock, 0.0, None, S.view_rows)
+    S.assert_same(top, S.snapshot(wave, 0.0, None, S.view_rows), (ev, "after reset"))
     assert (top[0]["root_plays"] == 90).all()
-    _step(lock, wave, 10, rng, what=(ev, "on the reset tree"))
-    for e in (lock, wave):
-        e.close()
+    S.step_and_compare((lock, wave), 10, rng, S.view_rows, what=(ev, "on the reset tree"))
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("ev", ["hash", "net_r0"])
 def test_full_node_pool_counts_the_same_overflow(ev):
     lock, wave = _pair(C4, 3, EVALUATORS[ev], node_capacity=24)
-    _set((lock, wave), _openings(C4, 3))
-    a = _step(lock, wave, 50, np.random.RandomState(10), what=ev)
+    S.set_roots_on((lock, wave), S.openings(C4, 3))
+    a = S.step_and_compare((lock, wave), 50, np.random.RandomState(10), S.view_rows, what=ev)[0]
     assert a[2]["overflow"] > 0 and a[2]["nodes"] <= 3 * 23   # (the root takes one of a pool's 24 rows)
-    for e in (lock, wave):
-        e.close()
+    S.close_all(lock, wave)
 
 
 # ---- golden vectors of the reference, replayed under the wave launch (as tests/test_gpu_mcts.py::test_find_move_golden) ----
 @pytest.mark.parametrize("fname", ["mcts_c4_s50.npz", "mcts_ttt_s50.npz", "mcts_c4_s64_t0.npz"])
 def test_find_move_golden_under_wave(golden_dir, fname):
-    g = np.load(os.path.join(golden_dir, fname), allow_pickle=False)
-    game = GAME_OF[fname.split("_")[1]]
-    A = _lib.game_info(game).A
-    cells = _lib.GRID[game][0] * _lib.GRID[game][1]
-    sims, seed, salt, max_depth, fixed, reuse = [int(x) for x in g["meta"]]
-    assert not fixed
-    c, temp = [float(x) for x in g["cfg"]]
-    gs = g["game_start"]
-    ng = len(gs) - 1
-    lens = np.diff(gs)
-    st_all = pack_states(game, g)
-    eng = _lib.Engine(game, n_slots=ng, sims_per_move=sims, mcts_kind=_lib.MCTS_DYNAMIC, max_depth=max_depth,
-                      evaluator=_lib.EVAL_HASH, c_puct=c, hash_salt=salt, salt_per_game=True,
-                      node_capacity=sims * (cells + 1) + 8, launch=WAVE)
-    assert eng.run_sims_structure() == WAVE
-    eng.set_roots(st_all[gs[:-1]], game_ids=np.arange(ng))
-    for ply in range(int(lens.max())):
-        live = lens > ply
-        idx = gs[:-1] + np.minimum(ply, lens - 1)
-        roots = eng.root_states()
-        assert same_position(game, roots[live], st_all[idx][live])
-        eng.run_sims(sims)
-        out = eng.sample_moves(temp, u=g["u"][idx])
-        for s in np.where(live)[0]:
-            i = idx[s]
-            plays = out["child_plays"][s, :A].astype(np.float64)
-            assert np.array_equal(plays, g["plays"][i]), (fname, s, ply, plays, g["plays"][i])
-            n32 = out["child_plays"][s, :A].astype(np.float32)
-            wr = np.where(n32 > 0, out["child_value"][s, :A] / np.maximum(n32, 1), 0).astype(np.float64)
-            assert np.array_equal(wr, g["winrates"][i]), (fname, s, ply)
-            assert out["root_plays"][s] == g["root_plays"][i]
-            assert float(out["root_winrate"][s]) == g["v"][i]
-            assert out["action"][s] == g["action"][i], (fname, s, ply)
-            tot = plays.sum()
-            assert np.array_equal(plays / tot if tot > 0 else plays, g["prob"][i])
-        acts = np.where(live, g["action"][idx], -1).astype(np.int32)
-        if reuse:
-            eng.move_roots(acts)
-        else:
-            nxt_live = lens > ply + 1
-            if nxt_live.any():
-                sl = np.where(nxt_live)[0]
-                eng.set_roots(st_all[gs[:-1][sl] + ply + 1], slots=sl, game_ids=sl)
-    assert eng.counters()["overflow"] == 0
-    eng.close()
+    S.replay_find_move_golden(golden_dir, fname, GAME_OF[fname.split("_")[1]], launch=WAVE)
 
 
 # ---- the front end: MCTS.SearchLaunch --------------------------------------------------------------------------------
-class HashSearch(DynamicMCTS):
-    """DynamicMCTS on the validation evaluator, through the base class's _make_engine (which reads SearchLaunch)."""
-    _EVALUATOR = _lib.EVAL_HASH
-    salt = 0
-
-    def __init__(self, game=None, salt=0, **kw):
-        DynamicMCTS.__init__(self, **kw)
-        self.Game, self.salt = game, salt
-
-    def _make_engine(self, game_id, n_slots, sims, **kw):
-        return DynamicMCTS._make_engine(self, game_id, n_slots, sims, hash_salt=self.salt, **kw)
-
-
-@pytest.fixture
-def launches(monkeypatch):
-    """bb_config.launch and run_sims_structure() of every engine the front end creates and searches with."""
-    seen = []
-    real = _lib.Engine
-
-    class Spy(real):
-        def run_sims(self, sims, mask=None):
-            seen.append((self.cfg.launch, self.run_sims_structure()))
-            real.run_sims(self, sims, mask=mask)
-
-    monkeypatch.setattr(_lib, "Engine", Spy)
-    return seen
-
-
 def test_resetroot_and_children_golden_under_wave(golden_dir, monkeypatch, launches):
     """tests/test_gpu_mirror.py::test_resetroot_and_children_golden with MCTS.SearchLaunch = 'wave'."""
     monkeypatch.setattr(MCTS, "SearchLaunch", "wave")
@@ -337,10 +173,7 @@ def test_resetroot_and_children_golden_under_wave(golden_dir, monkeypatch, launc
 
 
 def _model(game, name, seed):
-    cfg = {"blocks": 2, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
-           "policy": {"dirichlet": {"alpha": 0.2, "epsilon": 0.3}}, "training": {"optimizer": "adam"}}
-    np.random.seed(seed)  # weight initialisation draws from numpy's stream
-    return Blackbird.Model(game, name, {"explorationRate": 0.85, "playLimit": 32}, cfg)
+    return M.model(game, name, seed=seed, play_limit=32, eps=0.3, blocks=2)
 
 
 @pytest.mark.parametrize("players", ["hash", "model"])
@@ -381,8 +214,8 @@ FALLBACKS = {
 def test_uncovered_engines_search_lockstep_and_say_so(case):
     game, ev, kw = FALLBACKS[case]
     lock, wave = _pair(game, 3, ev, want=LOCK, **kw)
-    states = np.repeat(_lib.game_initial(game), 3, axis=0) if game == DC else _openings(game, 3)
-    _set((lock, wave), states)
+    states = np.repeat(_lib.game_initial(game), 3, axis=0) if game == DC else S.openings(game, 3)
+    S.set_roots_on((lock, wave), states)
     u = np.random.RandomState(11).random_sample(3)
     for e in (lock, wave):
         e.run_sims(20)
@@ -393,8 +226,7 @@ def test_uncovered_engines_search_lockstep_and_say_so(case):
         ra, rb = lock.node_edges(s, -1), wave.node_edges(s, -1)
         assert all(np.array_equal(ra[k], rb[k]) for k in ra), (case, s)
     assert lock.counters() == wave.counters()
-    for e in (lock, wave):
-        e.close()
+    S.close_all(lock, wave)
 
 
 def test_structure_entry_point_arguments():
@@ -404,9 +236,8 @@ def test_structure_entry_point_arguments():
     net = _lib.Engine(C4, n_slots=1, sims_per_move=8, evaluator=_lib.EVAL_NET, launch=WAVE)
     out = C.c_int32(-1)
     assert _lib.lib().bb_run_sims_structure(net.h, C.byref(out)) == _lib.ERR_WEIGHTS   # read it after bb_load_weights
-    net.load_weights(_weights(C4, 16, 2))
+    net.load_weights(S.dense_weights(C4, 16, 2))
     assert net.run_sims_structure() == WAVE and net.selfplay_mode() == 0   # self-play treats the value as lock-step
     with pytest.raises(ValueError):
         _lib.Engine(C4, n_slots=1, sims_per_move=8, evaluator=_lib.EVAL_HASH, launch=4)
-    for e in (eng, net):
-        e.close()
+    S.close_all(eng, net)

@@ -3,106 +3,27 @@ slot, the policy head kept as five numbers in LDS) against the lock-step loop it
 a 4032-float policy row through memory).  Per slot the sequence of operations is the same, so everything a caller can see --
 sampled moves, root statistics, the edges of every root and of its children, the counters -- must be the lock-step engine's bit
 for bit; engines the kernel does not cover must say so and search lock-step."""
-import functools
-
 import numpy as np
 import pytest
 
-from blackbird_amd import Blackbird, DragonChess, _lib
-from blackbird_amd import weights as W
+from blackbird_amd import DragonChess, _lib
 from blackbird_amd.MCTS import MCTS
+from tests import model_cases as M
+from tests import search_cases as S
+from tests.search_cases import launches  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 DC = _lib.GAME_DRAGONCHESS
 LOCK, WAVE = _lib.LAUNCH_LOCKSTEP, _lib.LAUNCH_WAVE
 
 
-@functools.lru_cache(maxsize=None)
-def _weights(blocks):
-    return W.flatten(W.init_weights(17, 16, blocks, 16, 4032, seed=21, perturb=True))
-
-
-def _engine(n_slots, launch, blocks=2, **kw):
-    """As tests/test_gpu_search_wave.py's helper: the network evaluator with the prior noise on (epsilon 0.3)."""
-    kw.setdefault("node_capacity", 256)
-    kw.setdefault("max_plies", 24)
-    eng = _lib.Engine(DC, n_slots=n_slots, sims_per_move=8, seed=17, first_game_id=1000, launch=launch, evaluator=_lib.EVAL_NET,
-                      noise_on=True, alpha=0.2, epsilon=0.3, **kw)
-    eng.load_weights(_weights(blocks))
-    return eng
+def _engine(n_slots, launch, blocks=2, node_capacity=256, max_plies=24, **kw):
+    return S.dc_engine(n_slots, launch, blocks, node_capacity=node_capacity, max_plies=max_plies, **kw)
 
 
 def _pair(n_slots, blocks=2, want=WAVE, **kw):
-    lock, wave = _engine(n_slots, LOCK, blocks, **kw), _engine(n_slots, WAVE, blocks, **kw)
-    assert lock.run_sims_structure() == LOCK
-    assert wave.run_sims_structure() == want     # (want = WAVE: what an engine without k_dc_search_wave cannot say)
-    return lock, wave
-
-
-PLIES = (2, 1, 2, 4, 3)   # White moves twice, then Black (W, W, B): after 1 and after 4 plies the pair of White moves is half played
-
-
-def _openings(n):
-    """n different positions a few plies into the game: slot i plays PLIES[i % 5] moves, each the (3 i + 2 ply)-th legal one."""
-    out = []
-    for i in range(n):
-        st = _lib.game_initial(DC)
-        for ply in range(PLIES[i % len(PLIES)]):
-            legal = np.nonzero(_lib.game_legal(DC, st)[0])[0]
-            st, status = _lib.game_apply(DC, st, np.array([legal[(3 * i + 2 * ply) % len(legal)]], dtype=np.int32))
-            assert (status == 0).all()
-        out.append(st)
-    st = np.concatenate(out, axis=0)
-    movers = [(int(s[64]), int(s[65])) for s in st]          # (player, previous player)
-    assert n < 2 or (1, 1) in movers                          # a position between White's two moves is among them
-    return st
-
-
-def _set(engines, states):
-    for e in engines:
-        e.set_roots(states, game_ids=7 * np.arange(len(states)) + 3)
-
-
-def _snap(eng, temp=1.0, u=None):
-    """Everything of the trees a caller can read: bb_sample_moves' outputs, the edges of every root and of each of its children
-    (bb_node_edges), the counters."""
-    out = eng.sample_moves(temp, u)
-    rows = []
-    for s in range(eng.n_slots):
-        root = eng.node_edges(s, -1)
-        rows.append(root)
-        rows += [eng.node_edges(s, int(c) & 0x3FFFFFFF) for c in root["child"][:root["n_children"]] if c >= 0]
-    return out, rows, eng.counters()
-
-
-def _same(a, b, what=""):
-    (oa, ra, ca), (ob, rb, cb) = a, b
-    for k in oa:
-        assert oa[k].tobytes() == ob[k].tobytes(), (what, k, oa[k], ob[k])
-    assert len(ra) == len(rb), what
-    for i, (x, y) in enumerate(zip(ra, rb)):
-        for k in x:
-            assert np.asarray(x[k]).tobytes() == np.asarray(y[k]).tobytes(), (what, "node", i, k, x[k], y[k])
-    assert ca == cb, (what, ca, cb)
-
-
-def _step(lock, wave, sims, rng, mask=None, what=""):
-    """One run_sims on both engines, compared; returns the lock-step snapshot."""
-    u = rng.random_sample(lock.n_slots)
-    for e in (lock, wave):
-        e.run_sims(sims, mask=mask)
-    a, b = _snap(lock, 1.0, u), _snap(wave, 1.0, u)
-    _same(a, b, what)
-    return a
-
-
-def _moves(snapshot):
-    return np.where(snapshot[0]["action"] >= 0, snapshot[0]["action"], -1).astype(np.int32)
-
-
-def _close(*engines):
-    for e in engines:
-        e.close()
+    """want = WAVE: what an engine without k_dc_search_wave cannot say"""
+    return S.lock_and_wave(lambda launch: _engine(n_slots, launch, blocks, **kw), want)
 
 
 @pytest.mark.parametrize("sims", [1, 2, 24])
@@ -111,14 +32,14 @@ def _close(*engines):
 def test_same_bits_as_lockstep_over_three_moves(blocks, n_slots, sims):
     """Three consecutive moves with tree reuse (move_roots); after every search the two engines agree on everything."""
     lock, wave = _pair(n_slots, blocks)
-    _set((lock, wave), _openings(n_slots))
+    S.set_roots_on((lock, wave), S.dc_openings(n_slots))
     rng = np.random.RandomState(5)
     for move in range(3):
-        a = _step(lock, wave, sims, rng, what=(blocks, n_slots, sims, move))
+        a = S.step_and_compare((lock, wave), sims, rng, S.edge_rows, what=(blocks, n_slots, sims, move))[0]
         assert a[2]["overflow"] == 0 and a[2]["sims"] == (move + 1) * sims * n_slots   # every slot searched, every time
         for e in (lock, wave):
-            e.move_roots(_moves(a))
-    _close(lock, wave)
+            e.move_roots(S.sampled_moves(a))
+    S.close_all(lock, wave)
 
 
 def _king_captured():
@@ -134,39 +55,39 @@ def test_masks_carry_over_and_a_finished_game():
     """A slot outside the mask keeps its tree and its simulations for a later call; a root whose game is over searches the
     same way under both launches."""
     lock, wave = _pair(5)
-    states = _openings(5)
+    states = S.dc_openings(5)
     states[3] = _king_captured()[0]
-    _set((lock, wave), states)
+    S.set_roots_on((lock, wave), states)
     rng = np.random.RandomState(7)
     but2 = np.array([1, 1, 0, 1, 1], dtype=np.uint8)
     calls = (but2, 1 - but2, but2, np.ones(5, dtype=np.uint8), 1 - but2)
     before = None
     for k, mask in enumerate(calls):
-        a = _step(lock, wave, 12, rng, mask=mask, what=k)
+        a = S.step_and_compare((lock, wave), 12, rng, S.edge_rows, mask=mask, what=k)[0]
         for s in np.nonzero(mask == 0)[0]:   # a slot outside the mask: its tree is what it was
             now = wave.node_edges(int(s), -1)
             if before is not None:
                 assert all(np.asarray(now[f]).tobytes() == np.asarray(before[int(s)][f]).tobytes() for f in now), (k, s)
         before = {s: wave.node_edges(s, -1) for s in range(5)}
         assert a[2]["sims"] == 12 * sum(int(m.sum()) for m in calls[:k + 1])
-    _close(lock, wave)
+    S.close_all(lock, wave)
 
 
 def test_three_short_calls_equal_one_long_call():
     """run_sims(8) three times == run_sims(24) once: nothing of a call outlives its launch but the tree."""
     lock, once = _pair(3)
     thrice = _engine(3, WAVE)
-    _set((lock, once, thrice), _openings(3))
+    S.set_roots_on((lock, once, thrice), S.dc_openings(3))
     u = np.random.RandomState(8).random_sample(3)
     lock.run_sims(24)
     once.run_sims(24)
     for _ in range(3):
         thrice.run_sims(8)
-    a = _snap(lock, 1.0, u)
+    a = S.snapshot(lock, 1.0, u, S.edge_rows)
     assert a[2]["sims"] == 3 * 24
-    _same(a, _snap(once, 1.0, u), "24 at once")
-    _same(a, _snap(thrice, 1.0, u), "3 x 8")
-    _close(lock, once, thrice)
+    S.assert_same(a, S.snapshot(once, 1.0, u, S.edge_rows), "24 at once")
+    S.assert_same(a, S.snapshot(thrice, 1.0, u, S.edge_rows), "3 x 8")
+    S.close_all(lock, once, thrice)
 
 
 def _walk_down(eng, slot, actions):
@@ -184,20 +105,20 @@ def test_ancestors_and_reset_roots():
     """track_ancestors: every backup also walks the chain above the root (dc_phase_apply's ANC half), so after two moves
     bb_reset_roots finds the same statistics at the top and all the way down to the old root."""
     lock, wave = _pair(3, track_ancestors=True)
-    _set((lock, wave), _openings(3))
+    S.set_roots_on((lock, wave), S.dc_openings(3))
     rng = np.random.RandomState(9)
     played = []
     for move in range(2):
-        a = _step(lock, wave, 24, rng, what=move)
-        played.append(_moves(a))
+        a = S.step_and_compare((lock, wave), 24, rng, S.edge_rows, what=move)[0]
+        played.append(S.sampled_moves(a))
         for e in (lock, wave):
             e.move_roots(played[-1])
-    a = _step(lock, wave, 24, rng, what="below")
+    a = S.step_and_compare((lock, wave), 24, rng, S.edge_rows, what="below")[0]
     assert a[2]["sims"] == 3 * 3 * 24
     for e in (lock, wave):
         e.reset_roots()
-    top = _snap(lock, 0.0)
-    _same(top, _snap(wave, 0.0), "after reset")
+    top = S.snapshot(lock, 0.0, None, S.edge_rows)
+    S.assert_same(top, S.snapshot(wave, 0.0, None, S.edge_rows), "after reset")
     assert (top[0]["root_plays"] == 72).all()
     for s in range(3):
         line = [int(p[s]) for p in played]
@@ -205,36 +126,36 @@ def test_ancestors_and_reset_roots():
         assert len(ra) == len(rb) == 3, s
         for x, y in zip(ra, rb):
             assert all(np.asarray(x[k]).tobytes() == np.asarray(y[k]).tobytes() for k in x), s
-    _step(lock, wave, 8, rng, what="on the reset tree")
-    _close(lock, wave)
+    S.step_and_compare((lock, wave), 8, rng, S.edge_rows, what="on the reset tree")
+    S.close_all(lock, wave)
 
 
 def test_broken_ancestor_chain_is_refused_by_both():
     """More moves than max_plies + 2 ancestors: the searches below the broken chain agree, and both engines refuse ResetRoot."""
     lock, wave = _pair(1, track_ancestors=True, max_plies=2)
-    _set((lock, wave), _openings(1))
+    S.set_roots_on((lock, wave), S.dc_openings(1))
     rng = np.random.RandomState(12)
     for move in range(5):
-        a = _step(lock, wave, 8, rng, what=move)
+        a = S.step_and_compare((lock, wave), 8, rng, S.edge_rows, what=move)[0]
         for e in (lock, wave):
-            e.move_roots(_moves(a))
-    a = _step(lock, wave, 8, rng, what="below the broken chain")
+            e.move_roots(S.sampled_moves(a))
+    a = S.step_and_compare((lock, wave), 8, rng, S.edge_rows, what="below the broken chain")[0]
     assert a[2]["sims"] == 6 * 8
     for e in (lock, wave):
         here = e.root_states().tobytes()
         with pytest.raises(_lib.BlackbirdHipError, match="max_plies"):
             e.reset_roots()
         assert e.root_states().tobytes() == here
-    _close(lock, wave)
+    S.close_all(lock, wave)
 
 
 def test_full_pools_count_the_same_overflow():
     """12 node rows (and 12 x 24 edges) per slot: 24 simulations outgrow them."""
     lock, wave = _pair(3, node_capacity=12)
-    _set((lock, wave), _openings(3))
-    a = _step(lock, wave, 24, np.random.RandomState(10))
+    S.set_roots_on((lock, wave), S.dc_openings(3))
+    a = S.step_and_compare((lock, wave), 24, np.random.RandomState(10), S.edge_rows)[0]
     assert a[2]["overflow"] > 0 and a[2]["nodes"] <= 3 * 11 and a[2]["sims"] == 3 * 24   # (the root takes one of a pool's 12 rows)
-    _close(lock, wave)
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("case", ["nine_blocks", "net_form_f32"])
@@ -242,33 +163,15 @@ def test_uncovered_networks_search_lockstep_and_say_so(case):
     """A tower whose constants do not fit the kernel's LDS copy (R > 8) and the float32-MFMA form: lock-step, visibly."""
     kw = dict(blocks=9) if case == "nine_blocks" else dict(net_form=_lib.NET_FORM_F32)
     lock, wave = _pair(3, want=LOCK, **kw)
-    _set((lock, wave), _openings(3))
-    a = _step(lock, wave, 8, np.random.RandomState(11), what=case)
+    S.set_roots_on((lock, wave), S.dc_openings(3))
+    a = S.step_and_compare((lock, wave), 8, np.random.RandomState(11), S.edge_rows, what=case)[0]
     assert a[2]["sims"] == 3 * 8
-    _close(lock, wave)
+    S.close_all(lock, wave)
 
 
 # ---- the front end: MCTS.SearchLaunch --------------------------------------------------------------------------------
-@pytest.fixture
-def launches(monkeypatch):
-    """bb_config.launch and run_sims_structure() of every engine the front end creates and searches with."""
-    seen = []
-    real = _lib.Engine
-
-    class Spy(real):
-        def run_sims(self, sims, mask=None):
-            seen.append((self.cfg.launch, self.run_sims_structure()))
-            real.run_sims(self, sims, mask=mask)
-
-    monkeypatch.setattr(_lib, "Engine", Spy)
-    return seen
-
-
 def _model(name, seed):
-    cfg = {"blocks": 2, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
-           "policy": {"dirichlet": {"alpha": 0.2, "epsilon": 0.3}}, "training": {"optimizer": "adam"}}
-    np.random.seed(seed)  # weight initialisation draws from numpy's stream
-    return Blackbird.Model(DragonChess.BoardState, name, {"explorationRate": 0.85, "playLimit": 16}, cfg)
+    return M.model(DragonChess.BoardState, name, seed=seed, play_limit=16, eps=0.3, blocks=2)
 
 
 def _node_facts(node):

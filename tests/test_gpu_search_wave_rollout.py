@@ -10,10 +10,8 @@ from blackbird_amd import Connect4, _lib, arena
 from blackbird_amd.FixedMCTS import FixedMCTS
 from blackbird_amd.MCTS import MCTS
 from tests import rollout_cases as RC
-from tests import test_gpu_rollout as GR
-from tests import test_gpu_search_wave as SW
-from tests import test_gpu_search_wave_dc as DCW
-from tests.test_gpu_search_wave import HashSearch, launches  # noqa: F401  (launches: a fixture)
+from tests import search_cases as S
+from tests.search_cases import HashSearch, launches  # noqa: F401  (launches: a fixture)
 
 pytestmark = pytest.mark.gpu
 C4, TTT, DC = _lib.GAME_CONNECT4, _lib.GAME_TICTACTOE, _lib.GAME_DRAGONCHESS
@@ -24,20 +22,19 @@ KINDS = {"dynamic": dict(mcts_kind=_lib.MCTS_DYNAMIC),
 DC_KW = dict(max_plies=24, node_capacity=128)
 
 
-def _rollout_engine(game, n_slots, launch, kind="dynamic", **kw):
-    return SW._engine(game, n_slots, launch, "rollout", **dict(KINDS[kind], **kw))
+def _rollout_engine(game, n_slots, launch, kind="dynamic", node_capacity=512, **kw):
+    return S.dense_engine(game, n_slots, launch, "rollout", node_capacity=node_capacity, **dict(KINDS[kind], **kw))
+
+
+def _searching(game, n_slots, launch, kind, **kw):
+    eng = _rollout_engine(game, n_slots, launch, kind, **kw)
+    if launch == WAVE:
+        eng.search_rollouts(True)
+    return eng
 
 
 def _pair(game, n_slots, kind="dynamic", **kw):
-    lock, wave = _rollout_engine(game, n_slots, LOCK, kind, **kw), _rollout_engine(game, n_slots, WAVE, kind, **kw)
-    wave.search_rollouts(True)
-    assert lock.run_sims_structure() == LOCK and wave.run_sims_structure() == WAVE
-    return lock, wave
-
-
-def _close(*engines):
-    for e in engines:
-        e.close()
+    return S.lock_and_wave(lambda launch: _searching(game, n_slots, launch, kind, **kw), WAVE)
 
 
 # ---- structure ---------------------------------------------------------------------------------------------------------------
@@ -58,17 +55,17 @@ def test_structure_follows_the_setter(game, kind):
     for bad in (2, -1):
         assert _lib.lib().bb_search_rollouts(wave.h, bad) == _lib.ERR_ARG
     assert wave.run_sims_structure() == WAVE
-    _close(wave, lock)
+    S.close_all(wave, lock)
 
 
 def test_setter_changes_nothing_for_another_evaluator():
-    hashed = SW._engine(DC, 1, WAVE, "hash", **DC_KW)      # no one-launch kernel for DragonChess's hash evaluator
+    hashed = S.dense_engine(DC, 1, WAVE, "hash", **DC_KW)      # no one-launch kernel for DragonChess's hash evaluator
     hashed.search_rollouts(True)
     assert hashed.run_sims_structure() == LOCK
-    dense = SW._engine(C4, 1, WAVE, "hash")
+    dense = S.dense_engine(C4, 1, WAVE, "hash", node_capacity=512)
     dense.search_rollouts(False)
     assert dense.run_sims_structure() == WAVE
-    _close(hashed, dense)
+    S.close_all(hashed, dense)
 
 
 # ---- dense games -------------------------------------------------------------------------------------------------------------
@@ -77,55 +74,55 @@ def test_setter_changes_nothing_for_another_evaluator():
 @pytest.mark.parametrize("kind", list(KINDS))
 @pytest.mark.parametrize("key", ["c4", "ttt"])
 def test_same_bits_as_lockstep_over_three_moves(key, kind, n_slots, sims):
-    game = SW.GAME_OF[key]
+    game = S.GAME_OF[key]
     lock, wave = _pair(game, n_slots, kind, node_capacity=2048)
-    SW._set((lock, wave), SW._openings(game, n_slots))
+    S.set_roots_on((lock, wave), S.openings(game, n_slots))
     rng = np.random.RandomState(5)
     for move in range(3):
-        a = SW._step(lock, wave, sims, rng, what=(key, kind, n_slots, sims, move))
+        a = S.step_and_compare((lock, wave), sims, rng, S.view_rows, what=(key, kind, n_slots, sims, move))[0]
         assert a[2]["overflow"] == 0 and a[2]["sims"] == (move + 1) * sims * n_slots
         for e in (lock, wave):
-            e.move_roots(SW._moves(a))
-    _close(lock, wave)
+            e.move_roots(S.sampled_moves(a))
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("kind", ["dynamic", "fixed10"])
 @pytest.mark.parametrize("key", ["c4", "ttt"])
 def test_roots_next_to_a_win_and_to_a_full_board(golden_dir, key, kind):
     """Terminal leaves (rollouts of zero steps) and playouts that fill the board (0.5)."""
-    game = SW.GAME_OF[key]
+    game = S.GAME_OF[key]
     lock, wave = _pair(game, 5, kind, node_capacity=2048)
-    SW._set((lock, wave), SW._endgame_roots(golden_dir, key))
+    S.set_roots_on((lock, wave), S.endgame_roots(golden_dir, key))
     rng = np.random.RandomState(6)
     halves = 0
     for move in range(2):
-        a = SW._step(lock, wave, 50, rng, what=(key, kind, move))
+        a = S.step_and_compare((lock, wave), 50, rng, S.view_rows, what=(key, kind, move))[0]
         assert a[2]["terminal_leaves"] > 0 and a[2]["overflow"] == 0
         # a child every one of whose backups was 0.5: a drawn playout (or a drawn terminal leaf)
         halves += int(((a[0]["child_plays"] > 0) & (a[0]["child_value"] == 0.5 * a[0]["child_plays"])).sum())
         for e in (lock, wave):
-            e.move_roots(SW._moves(a))
+            e.move_roots(S.sampled_moves(a))
     assert halves > 0
-    _close(lock, wave)
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("kind", ["dynamic", "fixed10"])
 def test_masked_search_leaves_the_other_slots_alone(kind):
     lock, wave = _pair(C4, 5, kind, node_capacity=2048)
-    SW._set((lock, wave), SW._openings(C4, 5))
+    S.set_roots_on((lock, wave), S.openings(C4, 5))
     rng = np.random.RandomState(7)
     even = np.array([1, 0, 1, 0, 1], dtype=np.uint8)
     before = None
     masks = (even, 1 - even, even, 1 - even)
     for k, mask in enumerate(masks):
-        a = SW._step(lock, wave, 20, rng, mask=mask, what=(kind, k))
+        a = S.step_and_compare((lock, wave), 20, rng, S.view_rows, mask=mask, what=(kind, k))[0]
         for s in np.nonzero(mask == 0)[0]:   # a slot outside the mask: its tree is what it was
             now = wave.node_view(int(s), -1)
             if before is not None:
                 assert all(np.array_equal(now[f], before[int(s)][f]) for f in now), (kind, k, s)
         before = {s: wave.node_view(s, -1) for s in range(5)}
         assert a[2]["sims"] == 20 * sum(int(m.sum()) for m in masks[:k + 1])
-    _close(lock, wave)
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("kind", ["dynamic", "fixed10"])
@@ -134,58 +131,58 @@ def test_three_short_calls_equal_one_long_call(kind):
     lock, once = _pair(C4, 3, kind, node_capacity=2048)
     thrice = _rollout_engine(C4, 3, WAVE, kind, node_capacity=2048)
     thrice.search_rollouts(True)
-    SW._set((lock, once, thrice), SW._openings(C4, 3))
+    S.set_roots_on((lock, once, thrice), S.openings(C4, 3))
     u = np.random.RandomState(8).random_sample(3)
     lock.run_sims(48)
     once.run_sims(48)
     for _ in range(3):
         thrice.run_sims(16)
-    a = SW._snap(lock, 1.0, u)
-    SW._same(a, SW._snap(once, 1.0, u), "48 at once")
-    SW._same(a, SW._snap(thrice, 1.0, u), "3 x 16")
-    _close(lock, once, thrice)
+    a = S.snapshot(lock, 1.0, u, S.view_rows)
+    S.assert_same(a, S.snapshot(once, 1.0, u, S.view_rows), "48 at once")
+    S.assert_same(a, S.snapshot(thrice, 1.0, u, S.view_rows), "3 x 16")
+    S.close_all(lock, once, thrice)
 
 
 @pytest.mark.parametrize("kind", ["dynamic", "fixed3"])
 def test_ancestors_and_reset_roots(kind):
     lock, wave = _pair(TTT, 3, kind, track_ancestors=True)
-    SW._set((lock, wave), SW._openings(TTT, 3))
+    S.set_roots_on((lock, wave), S.openings(TTT, 3))
     rng = np.random.RandomState(9)
     for move in range(2):
-        a = SW._step(lock, wave, 30, rng, what=(kind, move))
+        a = S.step_and_compare((lock, wave), 30, rng, S.view_rows, what=(kind, move))[0]
         for e in (lock, wave):
-            e.move_roots(SW._moves(a))
-    SW._step(lock, wave, 30, rng, what=(kind, "below"))
+            e.move_roots(S.sampled_moves(a))
+    S.step_and_compare((lock, wave), 30, rng, S.view_rows, what=(kind, "below"))
     for e in (lock, wave):
         e.reset_roots()
-    top = SW._snap(lock, 0.0)
-    SW._same(top, SW._snap(wave, 0.0), (kind, "after reset"))
+    top = S.snapshot(lock, 0.0, None, S.view_rows)
+    S.assert_same(top, S.snapshot(wave, 0.0, None, S.view_rows), (kind, "after reset"))
     assert (top[0]["root_plays"] == 90).all()
-    SW._step(lock, wave, 10, rng, what=(kind, "on the reset tree"))
-    _close(lock, wave)
+    S.step_and_compare((lock, wave), 10, rng, S.view_rows, what=(kind, "on the reset tree"))
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("kind", ["dynamic", "fixed10"])
 def test_full_node_pool_counts_the_same_overflow(kind):
     lock, wave = _pair(C4, 3, kind, node_capacity=24)
-    SW._set((lock, wave), SW._openings(C4, 3))
-    a = SW._step(lock, wave, 50, np.random.RandomState(10), what=kind)
+    S.set_roots_on((lock, wave), S.openings(C4, 3))
+    a = S.step_and_compare((lock, wave), 50, np.random.RandomState(10), S.view_rows, what=kind)[0]
     assert a[2]["overflow"] > 0 and a[2]["nodes"] <= 3 * 23   # (the root takes one of a pool's 24 rows)
-    _close(lock, wave)
+    S.close_all(lock, wave)
 
 
 # ---- DragonChess (<= 16 simulations, <= 5 slots: 2048-ply playouts at worst) -----------------------------------------------------
 @pytest.mark.parametrize("kind", ["dynamic", "fixed3"])
 def test_dragonchess_same_bits_as_lockstep_over_two_moves(kind):
     lock, wave = _pair(DC, 3, kind, **DC_KW)
-    DCW._set((lock, wave), DCW._openings(3))
+    S.set_roots_on((lock, wave), S.dc_openings(3))
     rng = np.random.RandomState(12)
     for move in range(2):
-        a = DCW._step(lock, wave, 12, rng, what=(kind, move))      # (bb_node_edges of every root and of its children)
+        a = S.step_and_compare((lock, wave), 12, rng, S.edge_rows, what=(kind, move))[0]      # (bb_node_edges of every root and of its children)
         assert a[2]["overflow"] == 0 and a[2]["sims"] == (move + 1) * 12 * 3
         for e in (lock, wave):
-            e.move_roots(DCW._moves(a))
-    _close(lock, wave)
+            e.move_roots(S.sampled_moves(a))
+    S.close_all(lock, wave)
 
 
 @pytest.mark.parametrize("kind", ["dynamic", "fixed3"])
@@ -195,18 +192,18 @@ def test_dragonchess_rollout_without_a_legal_move(kind):
     pos = [RC.FORCED, RC.STUCK_ROOK]
     packed = _lib.pack_dc(np.stack([p["board"] for p in pos]), [p["player"] for p in pos], [p["prev"] for p in pos])
     lock, wave = _pair(DC, 2, kind, **DC_KW)
-    DCW._set((lock, wave), packed)
+    S.set_roots_on((lock, wave), packed)
     rng = np.random.RandomState(13)
-    a = DCW._step(lock, wave, 12, rng, what=(kind, "first"))
+    a = S.step_and_compare((lock, wave), 12, rng, S.edge_rows, what=(kind, "first"))[0]
     out = a[0]
     assert out["action"].tolist() == [RC.FORCED_ACTION, _lib.ERR_NAN] and out["root_plays"].tolist() == [12, 12]
     assert out["child_plays"][0, 0] > 0 and out["child_value"][0, 0] == 0.5 * out["child_plays"][0, 0]   # every backup was 0.5
     for e in (lock, wave):
-        e.move_roots(DCW._moves(a))
-    b = DCW._step(lock, wave, 12, rng, what=(kind, "after the forced move"))
+        e.move_roots(S.sampled_moves(a))
+    b = S.step_and_compare((lock, wave), 12, rng, S.edge_rows, what=(kind, "after the forced move"))[0]
     assert b[0]["action"].tolist() == [_lib.ERR_NAN, _lib.ERR_NAN] and b[2]["overflow"] == 0 and b[2]["terminal_leaves"] == 0
     assert b[0]["root_winrate"][0] == 0.5   # (the root that was moved to has a previous player; a root that was set counts no value)
-    _close(lock, wave)
+    S.close_all(lock, wave)
 
 
 # ---- against the oracle directly -------------------------------------------------------------------------------------------------
@@ -222,7 +219,7 @@ def test_connect4_fixed10_under_wave_vs_oracle(orc, golden_dir, monkeypatch):
             made.append(self.run_sims_structure())
 
     monkeypatch.setattr(_lib, "Engine", WaveEngine)
-    GR.test_rollout_find_move_steps_vs_oracle(orc, golden_dir, "c4", True, 10, 67, True)
+    RC.find_move_steps_vs_oracle(orc, golden_dir, "c4", True, 10, 67, True)
     assert made == [WAVE]
 
 

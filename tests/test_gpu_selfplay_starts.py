@@ -2,7 +2,7 @@
 
 Game k of a run starts from starts[k % n] in EVERY launch structure: lock-step, asynchronous rounds, the persistent Connect4 /
 TicTacToe queue kernel (mode 3), the DragonChess one-wave kernel (mode 5) and the one-launch rollout self-play (mode 6).  The
-yardstick is tests/test_selfplay_starts_cpu.py::oracle_selfplay_from, which that file pins to the committed oracle.
+yardstick is tests/selfplay_cases.py::oracle_selfplay_from, which tests/test_selfplay_starts_cpu.py pins to the committed oracle.
 
 Start sets are fixed action lists applied to the initial position (no random boards).  Every run uses a table whose length
 neither divides the number of games nor equals the number of slots, and more games than slots: the modulo wraps, and both the
@@ -10,123 +10,14 @@ begin sites and the refill site of every structure run.  All comparisons are exa
 import numpy as np
 import pytest
 
-from blackbird_amd import _lib, weights as W
+from blackbird_amd import _lib
 from tests import dc_wide_cases as WC
-from tests import test_selfplay_starts_cpu as SC
+from tests import model_cases as M
+from tests import selfplay_cases as SP
+from tests.selfplay_cases import ALPHA, COUNTERS, EPS, OG, assert_first_records_are, assert_games_are_the_oracles, starts_of
 
 pytestmark = pytest.mark.gpu
 C4, TTT, DC = _lib.GAME_CONNECT4, _lib.GAME_TICTACTOE, _lib.GAME_DRAGONCHESS
-OG = {C4: 0, TTT: 1, DC: 2}
-ACTIONS = {C4: ([], [3], [3, 3, 2, 4], [0, 1, 0, 1, 0, 1]),   # the last: one move from a win for either side -> short games
-           TTT: ([], [4], [4, 0, 8], [0, 4, 1])}
-DC_FIRST_LEGAL_TIMES = (1, 2, 3, 5)                            # crosses White's double move
-ALPHA, EPS = 0.2, 0.3
-COUNTERS = ("sims", "sum_depth", "nodes", "terminal_leaves", "games_finished", "plies", "examples")
-
-
-def _apply(game, st, a):
-    nxt, status = _lib.game_apply(game, st, [int(a)])
-    assert status[0] == 0
-    return nxt
-
-
-_starts = {}
-
-
-def starts_of(game):
-    """The game's start set as packed states [4, ...]; built once, the caller must not change it."""
-    if game not in _starts:
-        out = []
-        if game == DC:
-            for times in DC_FIRST_LEGAL_TIMES:
-                st = _lib.game_initial(game)
-                for _ in range(times):
-                    st = _apply(game, st, int(np.flatnonzero(_lib.game_legal(game, st)[0])[0]))
-                out.append(st)
-        else:
-            for acts in ACTIONS[game]:
-                st = _lib.game_initial(game)
-                for a in acts:
-                    st = _apply(game, st, a)
-                out.append(st)
-        _starts[game] = np.ascontiguousarray(np.concatenate(out, axis=0))
-        assert (_lib.game_winner(game, _starts[game]) < 0).all()
-    return _starts[game]
-
-
-def _play(eng, n_games, starts="keep", step=3, temp=1.0):
-    """Play n_games to the end at `temp`; starts: a packed table to set first, None to clear, "keep" to leave the engine as it is."""
-    if not isinstance(starts, str):
-        eng.selfplay_set_starts(starts)
-    eng.reset_counters()
-    eng.selfplay_begin(n_games, temp)
-    guard = 0
-    while not eng.selfplay_done()[0]:
-        eng.selfplay_step(step)
-        guard += 1
-        assert guard < 400
-    rec, offs, win = eng.fetch_examples()
-    out = dict(rec=rec, offs=offs, win=win, hdr=eng.selfplay_headers(), cnt=eng.counters())
-    assert out["cnt"]["overflow"] == 0 and out["cnt"]["games_finished"] == n_games
-    return out
-
-
-def _states(game, r):
-    return np.ascontiguousarray(r["state"]).view(_lib.STATE_DTYPE[game]).reshape(len(r), -1)
-
-
-def _pi(game, r):
-    gi = _lib.game_info(game)
-    tot = np.maximum(r["total"].astype(np.float64), 1.0)[:, None]
-    if gi.dense:
-        return r["visits"][:, :gi.A] / tot
-    pi = np.zeros((len(r), gi.A))
-    for k in range(len(r)):
-        nch = int(r["n_children"][k])
-        if r["total"][k] > 0:
-            pi[k, r["action"][k][:nch]] = r["visits"][k][:nch] / float(r["total"][k])
-    return pi
-
-
-def assert_first_records_are(game, out, starts, first_id=0):
-    """The first record of game k holds starts[k % n] at ply 0."""
-    for k in range(len(out["win"])):
-        r = out["rec"][out["offs"][k]]
-        assert r["ply"] == 0 and r["game_id"] == first_id + k
-        assert r["state"].tobytes() == starts[k % len(starts)].tobytes(), k
-
-
-def assert_game_is_the_oracles(game, out, k, o, first_id):
-    """Game k's records, header and winner against one oracle game."""
-    r = out["rec"][out["offs"][k]:out["offs"][k + 1]]
-    assert len(r) == o["n"] and out["win"][k] == o["winner"], (k, len(r), o["n"], out["win"][k], o["winner"])
-    assert out["hdr"][k].tolist() == [o["n"], o["winner"], o["n"] - 1, 1], k
-    assert (r["game_id"] == first_id + k).all() and np.array_equal(r["ply"], np.arange(len(r))), k
-    assert np.array_equal(_lib.game_encode(game, _states(game, r)), o["boards"]), k
-    assert np.array_equal(_pi(game, r), o["pi"]), k
-    assert np.array_equal(r["player"], o["player"]) and np.array_equal(r["z"].astype(np.float32), o["z"]), k
-
-
-def assert_games_are_the_oracles(orc, game, out, starts, cfg_of, first_id, sims, max_plies):
-    """Every game's records against oracle_selfplay_from(starts[k % n]); returns the oracle's simulation total."""
-    og = OG[game]
-    sims_total = 0
-    for k in range(len(out["win"])):
-        start = SC.orc_state_from_packed(orc, og, game, starts[k % len(starts)])
-        o = SC.oracle_selfplay_from(orc, cfg_of(k), first_id + k, start, 1.0, sims, max_plies)
-        assert_game_is_the_oracles(game, out, k, o, first_id)
-        sims_total += o["stats"].sims
-    return sims_total
-
-
-def _same(a, b, what):
-    assert np.array_equal(a["offs"], b["offs"]) and a["win"].tobytes() == b["win"].tobytes(), what
-    assert a["rec"].tobytes() == b["rec"].tobytes(), what
-    assert a["hdr"].tobytes() == b["hdr"].tobytes(), what
-    assert a["cnt"]["overflow"] == 0 and b["cnt"]["overflow"] == 0, what
-    assert a["cnt"]["sims"] == b["cnt"]["sims"] and a["cnt"]["sum_depth"] == b["cnt"]["sum_depth"], what
-
-
 # ---- 1. against the oracle: lock-step, hash evaluator ----------------------------------------------------------------------------
 @pytest.mark.parametrize("game", [C4, TTT, DC])
 def test_lockstep_hash_selfplay_from_starts_vs_oracle(orc, game):
@@ -137,7 +28,7 @@ def test_lockstep_hash_selfplay_from_starts_vs_oracle(orc, game):
                       seed=seed, max_games=n_games, first_game_id=first_id, launch=_lib.LAUNCH_LOCKSTEP,
                       max_plies=6 if game == DC else None)
     assert eng.selfplay_mode() == 0
-    out = _play(eng, n_games, starts)
+    out = SP.play_from_starts(eng, n_games, starts)
     assert_first_records_are(game, out, starts, first_id)
     total = assert_games_are_the_oracles(
         orc, game, out, starts, lambda k: orc.make_cfg(OG[game], evaluator=orc.EVAL_HASH, salt=salt + k, seed=seed), first_id, sims,
@@ -147,24 +38,15 @@ def test_lockstep_hash_selfplay_from_starts_vs_oracle(orc, game):
 
 
 # ---- 2. against the oracle: the queue kernel, network and prior noise ------------------------------------------------------------
-def _net_engine(game, n_slots, n_games, sims, blocks, launch=_lib.LAUNCH_AUTO, noise=True, seed=17, first_id=500, **kw):
-    gi = _lib.game_info(game)
-    flat = W.flatten(W.init_weights(gi.C, 16, blocks, 16, gi.A, seed=21, perturb=True))
-    eng = _lib.Engine(game, n_slots=n_slots, sims_per_move=sims, evaluator=_lib.EVAL_NET, seed=seed, max_games=n_games,
-                      first_game_id=first_id, noise_on=noise, alpha=ALPHA, epsilon=EPS, launch=launch, **kw)
-    eng.load_weights(flat)
-    return eng, flat
-
-
 def test_queue_kernel_with_prior_noise_from_starts_vs_oracle(orc):
     """TicTacToe, 21 slots (one 16-game workgroup + 5: ragged), 30 games over 4 starts; the oracle's keyed callback gets the
     priors the engine's network waves drew for (game id, node serial): tests/test_gpu_noise_parity.py."""
     game, n_slots, n_games, sims, seed, first_id = TTT, 21, 30, 16, 17, 500
     gi = _lib.game_info(game)
     starts = starts_of(game)
-    eng, flat = _net_engine(game, n_slots, n_games, sims, 1, seed=seed, first_id=first_id)
+    eng, flat = SP.net_engine(game, n_slots, n_games, sims, 1, seed=seed, first_id=first_id)
     assert eng.selfplay_mode() == 3
-    out = _play(eng, n_games, starts, step=2)
+    out = SP.play_from_starts(eng, n_games, starts, step=2)
     max_plies = eng.max_plies
     eng.close()
     assert_first_records_are(game, out, starts, first_id)
@@ -192,14 +74,14 @@ def test_dense_launch_structures_from_starts_are_byte_identical(game, n_slots, n
     starts = starts_of(game)
     runs, modes = {}, {}
     for name, launch in (("queue", _lib.LAUNCH_AUTO), ("rounds", _lib.LAUNCH_ROUNDS), ("lockstep", _lib.LAUNCH_LOCKSTEP)):
-        eng, _flat = _net_engine(game, n_slots, n_games, sims, 1, launch=launch, seed=5, first_id=0)
+        eng, _flat = SP.net_engine(game, n_slots, n_games, sims, 1, launch=launch, seed=5, first_id=0)
         modes[name] = eng.selfplay_mode()
-        runs[name] = _play(eng, n_games, starts, step=2)
+        runs[name] = SP.play_from_starts(eng, n_games, starts, step=2)
         eng.close()
     assert modes == {"queue": 3, "rounds": 1, "lockstep": 0}
     assert_first_records_are(game, runs["queue"], starts)
     for other in ("rounds", "lockstep"):
-        _same(runs["queue"], runs[other], other)
+        SP.assert_same_runs(runs["queue"], runs[other], other)
 
 
 def test_dc_one_wave_kernel_from_starts_is_lockstep():
@@ -207,13 +89,13 @@ def test_dc_one_wave_kernel_from_starts_is_lockstep():
     starts = starts_of(game)
     runs, modes = {}, {}
     for name, launch in (("wave", _lib.LAUNCH_AUTO), ("lockstep", _lib.LAUNCH_LOCKSTEP)):
-        eng, _flat = _net_engine(game, n_slots, n_games, sims, 1, launch=launch, seed=7, first_id=0, max_plies=5)
+        eng, _flat = SP.net_engine(game, n_slots, n_games, sims, 1, launch=launch, seed=7, first_id=0, max_plies=5)
         modes[name] = eng.selfplay_mode()
-        runs[name] = _play(eng, n_games, starts)
+        runs[name] = SP.play_from_starts(eng, n_games, starts)
         eng.close()
     assert modes == {"wave": 5, "lockstep": 0}
     assert_first_records_are(game, runs["wave"], starts)
-    _same(runs["wave"], runs["lockstep"], "dc")
+    SP.assert_same_runs(runs["wave"], runs["lockstep"], "dc")
 
 
 @pytest.mark.parametrize("game", [C4, TTT, DC])
@@ -229,10 +111,10 @@ def test_rollout_wave_selfplay_from_starts_is_lockstep(game, fixed):
                           max_plies=5 if game == DC else None)
         eng.selfplay_rollouts(wave)
         assert eng.selfplay_mode() == (6 if wave else 0)
-        runs[wave] = _play(eng, n_games, starts)
+        runs[wave] = SP.play_from_starts(eng, n_games, starts)
         eng.close()
     assert_first_records_are(game, runs[True], starts, 1000)
-    _same(runs[True], runs[False], (game, fixed))
+    SP.assert_same_runs(runs[True], runs[False], (game, fixed))
     assert {k: runs[True]["cnt"][k] for k in COUNTERS} == {k: runs[False]["cnt"][k] for k in COUNTERS}
 
 
@@ -250,11 +132,11 @@ def test_no_table_cleared_table_and_initial_table_are_the_same_run(game):
         if table == "cleared":
             eng.selfplay_set_starts(starts_of(game))
             eng.selfplay_set_starts(None)
-        runs.append(_play(eng, n_games, _lib.game_initial(game) if table == "initial" else "keep"))
+        runs.append(SP.play_from_starts(eng, n_games, _lib.game_initial(game) if table == "initial" else "keep"))
         eng.close()
     assert_first_records_are(game, runs[0], _lib.game_initial(game))
     for other in runs[1:]:
-        _same(runs[0], other, game)
+        SP.assert_same_runs(runs[0], other, game)
         assert {k: runs[0]["cnt"][k] for k in COUNTERS} == {k: other["cnt"][k] for k in COUNTERS}
 
 
@@ -270,25 +152,25 @@ def test_states_no_game_can_start_from_are_refused():
     # Connect4: four in a row for player 1 at the bottom (after 0 0 1 1 2 2 3); refused for reason 1, at index 2 of the table
     st = _lib.game_initial(C4)
     for a in (0, 0, 1, 1, 2, 2, 3):
-        st = _apply(C4, st, a)
+        st = SP._apply(C4, st, a)
     assert _lib.game_winner(C4, st)[0] == 1
     good = starts_of(C4)
     eng = _lib.Engine(C4, n_slots=3, sims_per_move=16, evaluator=_lib.EVAL_HASH, hash_salt=1, seed=2, max_games=7,
                       launch=_lib.LAUNCH_LOCKSTEP)
     eng.selfplay_set_starts(good)
     _refused(eng, np.concatenate([good[:2], st, good[2:]]), 2, "already over")
-    out = _play(eng, 7)                      # after the refusal the previous table is still in force
+    out = SP.play_from_starts(eng, 7)                      # after the refusal the previous table is still in force
     assert_first_records_are(C4, out, good)
     eng.close()
     # TicTacToe: a full board without a line (X O X / X O O / O X X) is a draw: Winner() == 0, so reason 1 (the game is over)
     # fires, before reason 2 (no legal move, which also holds) is looked at
     st = _lib.game_initial(TTT)
     for a in (0, 1, 2, 4, 3, 5, 7, 6, 8):
-        st = _apply(TTT, st, a)
+        st = SP._apply(TTT, st, a)
     assert _lib.game_winner(TTT, st)[0] == 0 and _lib.game_legal(TTT, st).sum() == 0
     eng = _lib.Engine(TTT, n_slots=3, sims_per_move=16, evaluator=_lib.EVAL_HASH, max_games=7)
     _refused(eng, st, 0, "already over")
-    out = _play(eng, 7)                      # there was no table before: initial positions
+    out = SP.play_from_starts(eng, 7)                      # there was no table before: initial positions
     assert_first_records_are(TTT, out, _lib.game_initial(TTT))
     eng.close()
     # DragonChess: the hand-built position with 148 legal moves (more than S = 144): reason 3
@@ -304,17 +186,12 @@ def test_states_no_game_can_start_from_are_refused():
     dead = good[:1].copy()
     dead[0, :64][dead[0, :64] == 1] = 0
     _refused(eng, np.concatenate([good[:1], dead]), 1, "already over")
-    out = _play(eng, 7)
+    out = SP.play_from_starts(eng, 7)
     assert_first_records_are(DC, out, good)
     eng.close()
 
 
 # ---- 6. the front end ------------------------------------------------------------------------------------------------------------
-def _net_cfg():
-    return {"blocks": 1, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
-            "policy": {"dirichlet": {"alpha": 0.2, "epsilon": 0.3}}, "training": {"optimizer": "adam"}}
-
-
 def test_generate_training_samples_from_start_states(tmp_path, monkeypatch):
     from blackbird_amd import Blackbird, TicTacToe
     monkeypatch.chdir(tmp_path)
@@ -328,7 +205,7 @@ def test_generate_training_samples_from_start_states(tmp_path, monkeypatch):
 
     def model(name):
         np.random.seed(11)  # weight initialisation draws from numpy's stream
-        m = Blackbird.Model(cls, name, {"explorationRate": 0.85, "playLimit": 16}, _net_cfg())
+        m = Blackbird.Model(cls, name, {"explorationRate": 0.85, "playLimit": 16}, M.net_config(blocks=1, eps=0.3))
         games = []
         inner = m.Conn.PutGames
         monkeypatch.setattr(m.Conn, "PutGames", lambda *a: (games.append(list(a[3])), inner(*a))[1])
@@ -345,7 +222,7 @@ def test_generate_training_samples_from_start_states(tmp_path, monkeypatch):
         r = rec[offs[k]:offs[k + 1]]
         want0 = start_states[k % 2]
         assert r["state"][0].tobytes() == want0._packed().tobytes() and r["ply"][0] == 0
-        planes = _lib.game_encode(TTT, _states(TTT, r))
+        planes = _lib.game_encode(TTT, SP.states_of(TTT, r))
         # the game's PutGames call: the blobs whose boards are the game's records, in ply order
         hit = [j for j, blobs in enumerate(games) if j not in used and len(blobs) == len(r) and all(
             np.array_equal(Blackbird.ExampleState.FromSerialized(b).Board, planes[i:i + 1]) for i, b in enumerate(blobs))]
@@ -395,7 +272,7 @@ def test_timed_selfplay_honours_start_states(tmp_path, monkeypatch):
     for a in (0, 4, 1):
         s1.ApplyAction(a)
     np.random.seed(11)
-    m = Blackbird.Model(cls, "timed", {"explorationRate": 0.85, "playLimit": 16, "timeLimit": 0.001}, _net_cfg())
+    m = Blackbird.Model(cls, "timed", {"explorationRate": 0.85, "playLimit": 16, "timeLimit": 0.001}, M.net_config(blocks=1, eps=0.3))
     m._MAX_NODES = 4096      # (the lock-step engine's pool per slot: 9 plies of 16 simulations need far less)
     games = []
     inner = m.Conn.PutGames

@@ -5,12 +5,11 @@ id, simulation serial, 'ROLL', step), never by who computes them: so every case 
 wave, and compares everything a caller can read -- records, game offsets, winners, headers, counters -- byte for byte.
 Lock-step itself is held to the CPU oracle by tests/test_gpu_rollout.py; two cases are compared with the oracle directly here.
 Only the cases of tests/rollout_cases.py are played; a lock-step run is made once per case and shared (never changed)."""
-import numpy as np
 import pytest
 
 from blackbird_amd import _lib
 from tests import rollout_cases as RC
-from tests import test_gpu_rollout as GR
+from tests import selfplay_cases as SP
 
 pytestmark = pytest.mark.gpu
 WAVE_MODE = 6
@@ -24,7 +23,7 @@ def _engine(name, wave, n_slots=None, **kw):
                max_depth=max_depth, evaluator=_lib.EVAL_ROLLOUT, c_puct=RC.C_PUCT, seed=RC.SEED, max_games=n_games,
                max_plies=max_plies, first_game_id=RC.FIRST_GAME_ID)
     cfg.update(kw)
-    eng = _lib.Engine(GR.GAMES[key], **cfg)
+    eng = _lib.Engine(RC.GAMES[key], **cfg)
     assert eng.selfplay_mode() == 0                      # without the call: as before
     if wave:
         eng.selfplay_rollouts(True)
@@ -32,23 +31,16 @@ def _engine(name, wave, n_slots=None, **kw):
     return eng
 
 
-def _finish(eng, step=8, between=None):
-    """Play the begun games to the end in steps of `step` plies; between(k): called after step k.  Everything a caller can read."""
-    guard = 0
-    while not eng.selfplay_done()[0]:
-        eng.selfplay_step(step)
-        if between:
-            between(guard)
-        guard += 1
-        assert guard < 1100  # (one slot playing 24 Connect4 games one after another, a ply per step: at most 24 * 42 steps)
-    rec, offs, win = eng.fetch_examples()
-    return dict(rec=rec, offs=offs, win=win, hdr=eng.selfplay_headers(), cnt=eng.counters())
+def _finish(eng, n_games, step=8, between=None):
+    """Play the begun games to the end in steps of `step` plies; between(k): called after step k.  Everything a caller can read.
+    (One slot playing 24 Connect4 games one after another, a ply per step: at most 24 * 42 steps.)"""
+    return SP.play_to_end(eng, n_games, step, 1.0, begin=False, steps_below=1100, between=between, headers=True)
 
 
 def _play(name, wave, n_slots=None, step=8, **kw):
     eng = _engine(name, wave, n_slots, **kw)
     eng.selfplay_begin(RC.SELFPLAY[name][4], 1.0)
-    out = _finish(eng, step)
+    out = _finish(eng, RC.SELFPLAY[name][4], step)
     eng.close()
     return out
 
@@ -65,13 +57,8 @@ def _lockstep(name):
     return _lock[name]
 
 
-def _same(a, b, what, counters=True):
-    assert np.array_equal(a["offs"], b["offs"]) and a["win"].tobytes() == b["win"].tobytes(), what
-    assert a["rec"].tobytes() == b["rec"].tobytes(), what
-    assert a["hdr"].tobytes() == b["hdr"].tobytes(), what
-    assert a["cnt"]["overflow"] == 0 and b["cnt"]["overflow"] == 0, what
-    if counters:
-        assert {k: a["cnt"][k] for k in COUNTERS} == {k: b["cnt"][k] for k in COUNTERS}, what
+def _same(a, b, what):
+    SP.assert_same_records(a, b, what, counters=COUNTERS, no_overflow=True)
 
 
 # ---- 1. equality with lock-step and with the oracle ------------------------------------------------------------------------------
@@ -86,27 +73,9 @@ def test_wave_selfplay_vs_oracle(orc, name):
     """The wave engine's games against the oracle's serial games, example by example, as
     tests/test_gpu_rollout.py::test_rollout_selfplay_vs_oracle compares the lock-step engine's; no compared value comes from a
     rollout that ran into the ply cap or found no legal move (RC.assert_rollouts_decided)."""
-    key = RC.SELFPLAY[name][0]
-    game = GR.GAMES[key]
     out = _play(name, True)
-    rec, offs, win, cnt = out["rec"], out["offs"], out["win"], out["cnt"]
-    tot = dict(sims=0, sum_depth=0, nodes=0, terminal_leaves=0)
-    for gidx, o in enumerate(RC.oracle_selfplay(orc, name)):
-        RC.assert_rollouts_decided(o["stats"])
-        r = rec[offs[gidx]:offs[gidx + 1]]
-        assert len(r) == o["n"] and win[gidx] == o["winner"], (gidx, len(r), o["n"], win[gidx], o["winner"])
-        assert (r["game_id"] == RC.FIRST_GAME_ID + gidx).all() and np.array_equal(r["ply"], np.arange(len(r)))
-        assert np.array_equal(GR._pi(game, r), o["pi"]), gidx
-        assert np.array_equal(r["player"], o["player"]) and np.array_equal(r["z"].astype(np.float32), o["z"]), gidx
-        st = np.ascontiguousarray(r["state"])
-        if key != "dc":
-            st = st.view(np.uint64).reshape(-1, 2)
-        assert np.array_equal(_lib.game_encode(game, st), o["boards"]), gidx
-        tot["sims"] += o["stats"].sims
-        tot["sum_depth"] += o["stats"].sum_depth
-        tot["nodes"] += o["stats"].nodes_reached  # (the engine builds a child when a descent first selects it)
-        tot["terminal_leaves"] += o["stats"].terminal_leaves
-    assert cnt["overflow"] == 0 and {k: cnt[k] for k in tot} == tot
+    assert out["cnt"]["overflow"] == 0
+    RC.assert_selfplay_is_the_oracles(orc, name, out["rec"], out["offs"], out["win"], out["cnt"])
 
 
 # ---- 2. schedule independence ----------------------------------------------------------------------------------------------------
@@ -137,7 +106,7 @@ def test_every_slot_makes_exactly_plies_moves_per_step(name):
             c = eng.counters()
             seen[id(eng)].append((eng.selfplay_headers().tobytes(), c["plies"], c["sims"], c["games_finished"]))
 
-        _finish(eng, 3, note)
+        _finish(eng, n_games, 3, note)
         eng.close()
     a, b = seen[id(lock)], seen[id(wave)]
     assert len(a) == len(b) and len(a) > 3
@@ -155,7 +124,7 @@ def test_set_sims_per_move_between_steps():
         eng.set_sims_per_move(20)
         eng.selfplay_step(5)
         eng.set_sims_per_move(45)
-        out = _finish(eng, 4)
+        out = _finish(eng, 12, 4)
         eng.close()
         return out
 
@@ -188,7 +157,7 @@ def test_split_launches_give_the_same_bytes(monkeypatch, name, cap, launches):
     eng.selfplay_step(8)
     assert eng.timing_read()[2] == launches, (name, cap)   # (every launch of this structure is bracketed)
     eng.timing_enable(0)
-    out = _finish(eng, 8)
+    out = _finish(eng, RC.SELFPLAY[name][4], 8)
     eng.close()
     _same(_lockstep(name), out, (name, cap))
 
@@ -200,7 +169,7 @@ def test_switching_back_and_in_mid_run(name):
     eng.selfplay_rollouts(False)
     assert eng.selfplay_mode() == 0
     eng.selfplay_begin(RC.SELFPLAY[name][4], 1.0)
-    _same(_lockstep(name), _finish(eng, 8), (name, "on, then off"))
+    _same(_lockstep(name), _finish(eng, RC.SELFPLAY[name][4], 8), (name, "on, then off"))
     eng.close()
     eng = _engine(name, False)                         # lock-step and wave steps in turn: both leave what the other expects
     eng.selfplay_begin(RC.SELFPLAY[name][4], 1.0)
@@ -211,7 +180,7 @@ def test_switching_back_and_in_mid_run(name):
         eng.selfplay_rollouts(flip[0])
         assert eng.selfplay_mode() == (WAVE_MODE if flip[0] else 0)
 
-    _same(_lockstep(name), _finish(eng, 3, turn), (name, "alternating"))
+    _same(_lockstep(name), _finish(eng, RC.SELFPLAY[name][4], 3, turn), (name, "alternating"))
     eng.close()
 
 

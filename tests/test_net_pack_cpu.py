@@ -6,11 +6,12 @@ was recorded from the packing loops as they stood inside engine.hip before they 
 import hashlib
 import json
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from tests.host_cases import host_compiler
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "blackbird_amd", "csrc")
@@ -149,13 +150,6 @@ F32, U16, U32 = np.float32, np.uint16, np.uint32
 SLICE_TAPS = np.array([[0, 1], [3, 4], [6, 7], [2, 5]])  # the four K = 32 slices of a tower layer; tap 8 goes alone
 
 
-def _compiler():
-    for c in (os.environ.get("CXX"), "g++", "clang++", "c++", "/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++"):
-        if c and (shutil.which(c) or os.path.exists(c)):
-            return c
-    pytest.fail("no host C++ compiler found (set CXX)")
-
-
 @pytest.fixture(scope="module")
 def images(tmp_path_factory):
     """{shape: {image or in_<tensor>: bytes}} -- compiled, packed and read once for the module"""
@@ -163,7 +157,7 @@ def images(tmp_path_factory):
     src = d / "pack.cpp"
     src.write_text(PROGRAM)
     exe = d / "pack"
-    subprocess.check_call([_compiler(), "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-I", CSRC,
+    subprocess.check_call([host_compiler(), "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-I", CSRC,
                            str(src), "-o", str(exe)])
     out = d / "out"
     out.mkdir()

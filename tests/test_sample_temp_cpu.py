@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from tests import temp_cases as T
-from tests import test_selfplay_starts_cpu as SC
+from tests import selfplay_cases as SC
 
 
 @pytest.mark.parametrize("A", [7, 9])

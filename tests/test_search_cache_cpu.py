@@ -9,6 +9,7 @@ import pytest
 from blackbird_amd import Blackbird, Connect4, DragonChess, _lib
 from blackbird_amd.DynamicMCTS import DynamicMCTS
 from blackbird_amd.MCTS import MCTS
+from tests.model_cases import Recorded, engine_args  # noqa: F401  (engine_args: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "blackbird_hip.h")
@@ -35,23 +36,6 @@ def test_attribute_defaults_to_off():
     assert MCTS.SearchEvalCache is False and MCTS.SearchLaunch == "lockstep"
 
 
-class _Recorded(Exception):
-    pass
-
-
-@pytest.fixture
-def engine_args(monkeypatch):
-    """The arguments of the next _lib.Engine(...) call (nothing is created: no GPU here)."""
-    seen = {}
-
-    def fake(game, **kw):
-        seen.update(kw, game=game)
-        raise _Recorded()
-
-    monkeypatch.setattr(_lib, "Engine", fake)
-    return seen
-
-
 @pytest.mark.parametrize("on", [False, True])
 @pytest.mark.parametrize("key", list(GAMES))
 def test_searcher_passes_the_option_on(monkeypatch, engine_args, key, on):
@@ -59,7 +43,7 @@ def test_searcher_passes_the_option_on(monkeypatch, engine_args, key, on):
     monkeypatch.setattr(MCTS, "SearchLaunch", "wave")
     monkeypatch.setattr(MCTS, "SearchEvalCache", on)
     m = DynamicMCTS(explorationRate=0.85, playLimit=16)
-    with pytest.raises(_Recorded):
+    with pytest.raises(Recorded):
         m._ensure_engine(cls())                              # what FindMove / MoveRoot / ResetRoot search with
     assert engine_args["game"] == gid and engine_args["launch"] == _lib.LAUNCH_WAVE
     assert (engine_args.get("search_cache") is True) == on
@@ -76,17 +60,17 @@ def test_model_passes_the_option_on(tmp_path, monkeypatch, engine_args, key, on)
     cfg = {"blocks": 2, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
            "policy": {"dirichlet": {"alpha": 0.2, "epsilon": 0.3}}, "training": {"optimizer": "adam"}}
     m = Blackbird.Model(cls, "m", {"explorationRate": 0.85, "playLimit": 16}, cfg)
-    with pytest.raises(_Recorded):
+    with pytest.raises(Recorded):
         m._ensure_engine(cls())
     assert engine_args["evaluator"] == _lib.EVAL_NET and (engine_args.get("search_cache") is True) == on
     engine_args.clear()
-    with pytest.raises(_Recorded):                           # the arena's engines: one slot per game (arena._Searcher)
+    with pytest.raises(Recorded):                           # the arena's engines: one slot per game (arena._Searcher)
         m._make_engine(gid, 4, 16, node_capacity=1088)
     assert engine_args["n_slots"] == 4 and engine_args["launch"] == _lib.LAUNCH_WAVE
     assert (engine_args.get("search_cache") is True) == on
     engine_args.clear()
     monkeypatch.setattr(_lib, "fit_slots", lambda *a, **k: (4, 0))
-    with pytest.raises(_Recorded):                           # self-play engines are not concerned
+    with pytest.raises(Recorded):                           # self-play engines are not concerned
         m._selfplay_engine(4)
     assert engine_args["launch"] == _lib.LAUNCH_AUTO and not engine_args.get("search_cache")
 

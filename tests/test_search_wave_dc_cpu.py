@@ -8,6 +8,7 @@ import pytest
 from blackbird_amd import Blackbird, DragonChess, _lib
 from blackbird_amd.DynamicMCTS import DynamicMCTS
 from blackbird_amd.MCTS import MCTS
+from tests.model_cases import Recorded, engine_args  # noqa: F401  (engine_args: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "blackbird_hip.h")
@@ -30,28 +31,11 @@ def test_no_new_entry_point():
     assert all(hasattr(L, name) for name in declared)
 
 
-class _Recorded(Exception):
-    pass
-
-
-@pytest.fixture
-def engine_args(monkeypatch):
-    """The arguments of the next _lib.Engine(...) call (nothing is created: no GPU here)."""
-    seen = {}
-
-    def fake(game, **kw):
-        seen.update(kw, game=game)
-        raise _Recorded()
-
-    monkeypatch.setattr(_lib, "Engine", fake)
-    return seen
-
-
 @pytest.mark.parametrize("launch, want", [("wave", _lib.LAUNCH_WAVE), ("lockstep", _lib.LAUNCH_AUTO)])
 def test_dragonchess_searcher_passes_the_launch_on(monkeypatch, engine_args, launch, want):
     monkeypatch.setattr(MCTS, "SearchLaunch", launch)
     m = DynamicMCTS(explorationRate=0.85, playLimit=16)
-    with pytest.raises(_Recorded):
+    with pytest.raises(Recorded):
         m._ensure_engine(DragonChess.BoardState())          # what FindMove / MoveRoot / ResetRoot search with
     assert engine_args["game"] == _lib.GAME_DRAGONCHESS and engine_args["launch"] == want
     assert engine_args["track_ancestors"] is True and engine_args["n_slots"] == 1
@@ -64,11 +48,11 @@ def test_dragonchess_model_passes_the_launch_on(tmp_path, monkeypatch, engine_ar
     cfg = {"blocks": 2, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
            "policy": {"dirichlet": {"alpha": 0.2, "epsilon": 0.3}}, "training": {"optimizer": "adam"}}
     m = Blackbird.Model(DragonChess.BoardState, "dc", {"explorationRate": 0.85, "playLimit": 16}, cfg)
-    with pytest.raises(_Recorded):
+    with pytest.raises(Recorded):
         m._ensure_engine(DragonChess.BoardState())
     assert engine_args["game"] == _lib.GAME_DRAGONCHESS and engine_args["launch"] == want
     assert engine_args["evaluator"] == _lib.EVAL_NET and engine_args["noise_on"] is True
     engine_args.clear()
-    with pytest.raises(_Recorded):                           # the arena's engines: one slot per game (arena._Searcher)
+    with pytest.raises(Recorded):                           # the arena's engines: one slot per game (arena._Searcher)
         m._make_engine(_lib.GAME_DRAGONCHESS, 4, 16, node_capacity=1088)
     assert engine_args["launch"] == want and engine_args["n_slots"] == 4

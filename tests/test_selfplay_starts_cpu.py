@@ -19,52 +19,10 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib
+from tests.selfplay_cases import oracle_selfplay_from
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "blackbird_amd", "csrc")
-
-
-# ---- the yardstick ---------------------------------------------------------------------------------------------------------------
-def oracle_selfplay_from(orc, cfg, game_id, start, temp, play_limit, max_plies):
-    """One self-play game of the oracle from `start` (an orc.State; not changed): the dict orc.selfplay_game returns, and per
-    move the root's child visit counts (`plays`) and the keyed draw of (seed, game id, ply) (`u`; not consumed at temp 0)."""
-    game = cfg.game
-    A = orc.dims(game)[3]
-    search = orc.Search(cfg, game_id)
-    search.drop_root()
-    st = start.copy()
-    boards, pi, player, actions, plays, us = [], [], [], [], [], []
-    winner, n = None, 0
-    while winner is None and n < max_plies:
-        o = search.find_move(st, temp, play_limit, u=-1.0, ply=n)
-        boards.append(orc.encode(game, st)[0])   # ExampleState(..., state.AsInputArray(), player) of the state before the move
-        pi.append(o["prob"])
-        player.append(st.player)
-        actions.append(o["action"])
-        plays.append(o["plays"])
-        us.append(orc.u53(cfg.seed, game_id, n))
-        st = o["next"]
-        search.move_root(st)
-        winner = orc.winner(game, st)            # lastAction is always None (Blackbird.py:242,253)
-        n += 1
-    boards.append(orc.encode(game, st)[0])       # terminal example with pi = zeros (Blackbird.py:256-258)
-    pi.append(np.zeros(A))
-    player.append(st.player)
-    player = np.array(player, dtype=np.int8)
-    w = -1 if winner is None else int(winner)
-    z = np.zeros(n + 1, dtype=np.float32) if w <= 0 else np.where(player == w, 1.0, -1.0).astype(np.float32)  # :260-264
-    return dict(n=n + 1, boards=np.stack(boards), pi=np.stack(pi), player=player, z=z,
-                actions=np.array(actions, dtype=np.int32), winner=w, stats=search.stats(), plays=np.array(plays).reshape(n, A),
-                u=np.array(us))
-
-
-def orc_state_from_packed(orc, og, game, packed):
-    """One packed engine state (include/blackbird_hip.h) as the oracle's state."""
-    if game == _lib.GAME_DRAGONCHESS:
-        b, p, pv, c = _lib.unpack_dc(np.asarray(packed).view(np.uint8).reshape(1, 80))
-        return orc.state_from_arrays(og, b[0], p[0], int(pv[0]) or None, c[0])
-    b, p, pv = _lib.unpack_grid(game, np.asarray(packed).view(np.uint64).reshape(1, 2))
-    return orc.state_from_arrays(og, b[0], p[0], int(pv[0]) or None)
 
 
 @pytest.mark.parametrize("og,sims,max_plies,games", [(0, 24, 42, 4), (1, 16, 9, 6), (2, 12, 8, 3)])

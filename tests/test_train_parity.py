@@ -17,119 +17,7 @@ import torch
 
 from blackbird_amd import weights as W
 from blackbird_amd.training import Trainer
-
-TOL = 1e-5
-H, Wd, C, F, R, D, A, B = 6, 7, 3, 16, 2, 16, 7, 6
-ALPHA, EPS = 0.2, 0.3
-
-
-def _batch(seed):
-    rng = np.random.RandomState(seed)
-    cells = rng.randint(0, 3, size=(B, H, Wd))
-    boards = np.zeros((B, H, Wd, C), dtype=np.int8)
-    boards[..., 0] = cells == 1
-    boards[..., 1] = cells == 2
-    boards[..., 2] = rng.choice([-1, 1], size=(B, 1, 1))
-    ev = rng.choice([-1.0, 0.0, 1.0], size=B).astype(np.float32)
-    pl = rng.dirichlet(np.ones(A), size=B)
-    pl[-1] = 0.0  # a terminal example: pi = zeros (Blackbird.py:256-258)
-    noise = rng.beta(ALPHA, 1 - ALPHA, size=A)
-    return boards, ev, pl, noise
-
-
-# ---- the independent statement (float64, NHWC, no conv2d) ---------------------------------------------------------
-def _ref_loss(w, boards, ev, pl, noise):
-    x = torch.tensor(boards.astype(np.float64))
-    ev = torch.tensor(ev.astype(np.float64))
-    pl = torch.tensor(pl.astype(np.float64))
-    nz = torch.tensor(noise.astype(np.float64))
-
-    def conv(t, scope):  # tf.layers.conv2d, SAME, stride 1, bias
-        k, b = w[scope + "/kernel"], w[scope + "/bias"]
-        kh = k.shape[0]
-        p = kh // 2
-        tp = torch.nn.functional.pad(t, (0, 0, p, p, p, p))
-        out = 0
-        for dy in range(kh):
-            for dx in range(kh):
-                out = out + torch.einsum("bhwc,cf->bhwf", tp[:, dy:dy + H, dx:dx + Wd, :], k[dy, dx])
-        return out + b
-
-    def bn(t, scope):  # batch_normalization, training=False, epsilon 1e-3
-        g, be, mu, var = (w[f"{scope}/{f}"] for f in W.BN_FIELDS)
-        return g * (t - mu) / torch.sqrt(var + 1e-3) + be
-
-    t = torch.relu(bn(conv(x, "resTower/conv_block/conv"), "resTower/conv_block/batch_norm"))
-    for i in range(R):
-        h = torch.relu(bn(conv(t, f"resTower/block_{i}/conv_1"), f"resTower/block_{i}/batch_norm_1"))
-        h = bn(conv(h, f"resTower/block_{i}/conv_2"), f"resTower/block_{i}/batch_norm_2")
-        t = torch.relu(h + t)
-    v = torch.relu(bn(conv(t, "value/convolution"), "value/batch_norm"))                       # [B,H,W,1]
-    v = torch.einsum("bhwo,od->bhwd", v, w["value/dense_1/kernel"]) + w["value/dense_1/bias"]  # dense on the last axis
-    v = torch.relu(v.sum(dim=(1, 2)))                                                           # reduce_sum over H, W
-    value = torch.tanh((torch.einsum("bd,do->bo", v, w["value/dense_2/kernel"]) + w["value/dense_2/bias"]).sum(dim=1))
-    p = torch.relu(bn(conv(t, "policy/convolution"), "policy/batch_norm"))                     # [B,H,W,2]
-    logits = (torch.einsum("bhwo,oa->bhwa", p, w["policy/policy/kernel"]) + w["policy/policy/bias"]).sum(dim=(1, 2))
-    z = logits - logits.max(dim=1, keepdim=True).values
-    base = torch.exp(z) / torch.exp(z).sum(dim=1, keepdim=True)
-    policy = (1 - EPS) * base + EPS * nz[None, :]
-    policy = policy / policy.sum()                        # over ALL elements, batch axis included (:182)
-    l_eval = ((value - ev) ** 2).mean()
-    l_pol = -(torch.log(policy) @ pl.t()).mean()          # the full B x B cross matrix (:190-194)
-    l2 = [0.5 * (t_ ** 2).sum() for k_, t_ in w.items() if t_.requires_grad and "bias" not in k_]
-    l_par = torch.stack(l2).mean()
-    return l_eval + l_pol + l_par, (l_eval, l_pol, l_par)
-
-
-def _ref_weights(w0):
-    w = {}
-    for k, v in w0.items():
-        t = torch.tensor(np.asarray(v, dtype=np.float64))
-        if not (k.endswith("moving_mean") or k.endswith("moving_variance")):
-            t.requires_grad_(True)
-        w[k] = t
-    return w
-
-
-def _ref_grads(w0, batch):
-    w = _ref_weights(w0)
-    total, parts = _ref_loss(w, *batch)
-    names = [k for k, t in w.items() if t.requires_grad]
-    gs = torch.autograd.grad(total, [w[k] for k in names])
-    return float(total.detach()), [float(p.detach()) for p in parts], {k: g.numpy() for k, g in zip(names, gs)}
-
-
-class _RefOptimizer:
-    """tf.compat.v1.train.{Adam,Momentum,GradientDescent}Optimizer update rules in numpy float64."""
-
-    def __init__(self, kind, momentum=0.9):
-        self.kind, self.mom, self.t, self.m, self.v = kind, momentum, 0, {}, {}
-
-    def apply(self, w, grads, lr):
-        out = dict(w)
-        self.t += 1
-        for k, g in grads.items():
-            x = np.asarray(w[k], dtype=np.float64)
-            if self.kind == "adam":
-                m = 0.9 * self.m.get(k, 0.0) + 0.1 * g
-                v = 0.999 * self.v.get(k, 0.0) + 0.001 * g * g
-                self.m[k], self.v[k] = m, v
-                lr_t = lr * np.sqrt(1 - 0.999 ** self.t) / (1 - 0.9 ** self.t)
-                out[k] = x - lr_t * m / (np.sqrt(v) + 1e-8)
-            elif self.kind == "momentum":
-                acc = self.mom * self.m.get(k, 0.0) + g
-                self.m[k] = acc
-                out[k] = x - lr * acc
-            else:
-                out[k] = x - lr * g
-        return out
-
-
-def _close(got, want, what):
-    scale = max(1.0, float(np.max(np.abs(want))))
-    err = float(np.max(np.abs(np.asarray(got, dtype=np.float64) - want)))
-    assert err <= TOL * scale, (what, err, scale)
-
+from tests.trainer_cases import ALPHA, EPS, A, C, D, F, H, R, TOL, Wd, _batch, _close, _ref_grads, _RefOptimizer
 
 def _check_step(device, kind):
     w0 = W.init_weights(C, F, R, D, A, seed=3, perturb=True)
