@@ -296,7 +296,7 @@ def TrainWithExamples(model, batchSize, learningRate, epochs=1, teacher=None, mo
     model.Conn.PutModel(model.Game.GameType, model.Name, model.Version)
 
 
-def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=None, augment=False):
+def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=None, augment=False, merge=False):
     """TrainWithExamples (Blackbird.py:271-312) on examples that never left the GPU: `examples` (a training.DeviceExamples),
     or else what GenerateTrainingSamples kept for the model's current Version (model.KeepDeviceExamples).  The same steps
     in the same order -- the epoch's order drawn from numpy's generator as there (the same seed visits the same examples in
@@ -307,8 +307,16 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
     augment (an extension: the reference does not augment): every visited example is presented under a symmetry of the game
     drawn for it -- Connect4 mirrored or not, TicTacToe in one of its eight orientations --, planes and policy alike
     (bb_examples_to_batch_sym).  The draw is one np.random.randint(symmetries, size=len(order)) right after the epoch's
-    order; with augment=False numpy's generator is consumed as before.  DragonChess has no symmetry: ValueError."""
+    order; with augment=False numpy's generator is consumed as before.  DragonChess has no symmetry: ValueError.
+
+    merge (an extension: the reference trains on every stored row): the copies of a position among the examples -- the start
+    position once per game, the openings, transpositions -- become one row with the pooled search policy (summed visits / summed
+    totals) and the mean outcome (examples.merged(): bb_examples_merge, Connect4 and TicTacToe); the epoch's order is drawn as
+    before, over the merged rows, and augment composes with it.  With merge=False nothing changes.  DragonChess: ValueError."""
     from .training import epoch_order
+    if merge and (model.Game.GAME_ID if examples is None else examples.game) not in _lib.GRID:
+        raise ValueError('merge=True covers Connect4 and TicTacToe: a DragonChess position is keyed by its 64-byte board, castle '
+                         'flags and double-move bit, its records hold compact child lists, and it transposes rarely')
     if augment and _lib.game_symmetries(model.Game.GAME_ID if examples is None else examples.game) < 2:
         raise ValueError('augment=True: this game has no board symmetry but the identity (DragonChess: the start position is '
                          'not mirror-symmetric and pawns have a direction), there is nothing to augment with')
@@ -319,6 +327,8 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
     if examples is None or len(examples) == 0:
         raise ValueError('no device examples for %s version %d: pass `examples`, or set KeepDeviceExamples before '
                          'GenerateTrainingSamples' % (model.Name, model.Version))
+    if merge:
+        examples = examples.merged()
     order = examples.index_tensor(epoch_order(len(examples), batchSize))
     syms = examples.sym_tensor(np.random.randint(examples.symmetries, size=len(order))) if augment else None
     nBatches = len(order) // batchSize

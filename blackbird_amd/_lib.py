@@ -28,6 +28,7 @@ EXPORTS = (
     "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_set_starts", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
     "bb_examples_to_batch", "bb_examples_to_batch_sym", "bb_game_symmetries",
+    "bb_examples_merge_workspace", "bb_examples_merge", "bb_examples_merged_to_batch",
     "bb_arena_create", "bb_arena_begin", "bb_arena_step", "bb_arena_status", "bb_arena_fetch", "bb_arena_destroy",
     "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_param_count", "bb_trainer_read",
 )
@@ -133,6 +134,9 @@ def lib():
     L.bb_examples_to_batch.argtypes = [ip, ip, vp, ip, vp, vp, vp, vp, vp, vp]
     L.bb_examples_to_batch_sym.argtypes = [ip, ip, vp, ip, vp, vp, vp, vp, vp, vp, vp]
     L.bb_game_symmetries.argtypes = [ip]
+    L.bb_examples_merge_workspace.argtypes = [ip, ip, C.POINTER(C.c_uint64)]
+    L.bb_examples_merge.argtypes = [ip, ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]
+    L.bb_examples_merged_to_batch.argtypes = [ip, ip, vp, ip, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]
     L.bb_arena_create.argtypes = [vp, vp, ip, C.POINTER(vp)]
     L.bb_arena_begin.argtypes = [vp, ip, vp, vp, C.c_double]
     L.bb_arena_step.argtypes = [vp, ip]
@@ -320,6 +324,34 @@ def examples_to_batch_sym(game, n_records, records, n, index=None, sym=None, boa
     check(lib().bb_examples_to_batch_sym(int(game), int(n_records), C.c_void_p(records or None), int(n), C.c_void_p(index or None),
                                          C.c_void_p(sym or None), C.c_void_p(boards or None), C.c_void_p(policy or None),
                                          C.c_void_p(value or None), C.c_void_p(bad or None), C.c_void_p(stream or None)))
+
+
+def examples_merge_workspace(game, n_records):
+    """bb_examples_merge_workspace: the bytes of scratch memory examples_merge needs for n_records records.  Host only.
+    ValueError for DragonChess (not covered), an unknown game or a negative count."""
+    out = C.c_uint64(0)
+    check(lib().bb_examples_merge_workspace(int(game), int(n_records), C.byref(out)))
+    return int(out.value)
+
+
+def examples_merge(game, n_records, records, group=None, rep=None, count=None, zsum=None, total=None, visits=None, n_groups=None,
+                   bad=None, workspace=None, workspace_bytes=0, stream=0):
+    """bb_examples_merge: the device records grouped by position (cells and side to move) and their targets summed per group
+    -- group [n_records] int32, rep / count / zsum [n_records] int32, total [n_records] and visits [n_records, A] 64-bit, n_groups
+    [1] and bad [1] int32 --, every argument after `n_records` a DEVICE address as in examples_to_batch, `workspace` of at least
+    examples_merge_workspace bytes.  Asynchronous: n_groups (negative: an error code for check()) is valid once the stream has run."""
+    p = lambda a: C.c_void_p(a or None)  # noqa: E731
+    check(lib().bb_examples_merge(int(game), int(n_records), p(records), p(group), p(rep), p(count), p(zsum), p(total), p(visits),
+                                  p(n_groups), p(bad), p(workspace), int(workspace_bytes), p(stream)))
+
+
+def examples_merged_to_batch(game, n_records, records, n_groups, rep, count, zsum, total, visits, n, index=None, sym=None,
+                             boards=None, policy=None, value=None, bad=None, stream=0):
+    """bb_examples_merged_to_batch: examples_to_batch_sym over the groups examples_merge made of these records -- row k is group
+    index[k] (None: group k) under symmetry sym[k] (None: as played).  The same argument rules as examples_to_batch."""
+    p = lambda a: C.c_void_p(a or None)  # noqa: E731
+    check(lib().bb_examples_merged_to_batch(int(game), int(n_records), p(records), int(n_groups), p(rep), p(count), p(zsum), p(total),
+                                            p(visits), int(n), p(index), p(sym), p(boards), p(policy), p(value), p(bad), p(stream)))
 
 
 def net_weights(H, W, flat):

@@ -17,6 +17,7 @@
 #include "search_wave_dc.hip.h"
 #include "selfplay_wave.hip.h"
 #include "examples.hip.h"
+#include "examples_merge.hip.h"
 #include "arena.hip.h"
 #include "train.hip.h"
 #include "net_pack.h"
@@ -1815,6 +1816,86 @@ extern "C" int bb_examples_to_batch_sym(int game, int n_records, const void *rec
 extern "C" int bb_examples_to_batch(int game, int n_records, const void *records, int n, const int64_t *index, float *boards_out,
                                     float *policy_out, float *value_out, int32_t *bad_out, void *stream) {
     return bb_examples_to_batch_sym(game, n_records, records, n, index, nullptr, boards_out, policy_out, value_out, bad_out, stream);
+}
+
+// ---- duplicate positions merged (examples_merge.hip.h): the dense games only -------------------------------------------------
+static int merge_game_check(int game) {
+    if (game == BB_GAME_DRAGONCHESS)
+        return fail(BB_ERR_ARG, "merging example records covers Connect4 and TicTacToe; DragonChess (a 64-byte key, compact child "
+                                "lists, few transpositions) is not covered");
+    if (game != BB_GAME_CONNECT4 && game != BB_GAME_TICTACTOE) return fail(BB_ERR_ARG, "unknown game %d", game);
+    return BB_OK;
+}
+
+extern "C" int bb_examples_merge_workspace(int game, int n_records, uint64_t *bytes_out) {
+    if (int rc = merge_game_check(game)) return rc;
+    if (n_records < 0 || n_records > MERGE_MAX_RECORDS || !bytes_out)
+        return fail(BB_ERR_ARG, "n_records in [0, %d] and a place for the size are expected", MERGE_MAX_RECORDS);
+    *bytes_out = n_records ? (uint64_t)merge_workspace(n_records).bytes : 0;
+    return BB_OK;
+}
+
+template <class G>
+static void merge_launch(hipStream_t st, int n, const uint8_t *rec, const MergeWorkspace &w, uint8_t *ws, int32_t *group, int32_t *rep,
+                         int32_t *count, int32_t *zsum, uint64_t *total, uint64_t *visits, int32_t *n_groups, int32_t *bad) {
+    int32_t *owner = (int32_t *)(ws + w.owner), *first = (int32_t *)(ws + w.first), *slot_of = (int32_t *)(ws + w.slot_of);
+    int32_t *sums = (int32_t *)(ws + w.sums), *err = (int32_t *)(ws + w.err);
+    k_merge_insert<G><<<w.blocks, 256, 0, st>>>(n, rec, w.cap, owner, first, slot_of, bad, err);
+    k_merge_count<<<w.blocks, 256, 0, st>>>(n, slot_of, first, sums);
+    k_merge_offsets<<<1, 256, 0, st>>>(w.blocks, sums, err, n_groups);
+    k_merge_number<G><<<w.blocks, 256, 0, st>>>(n, rec, slot_of, first, sums, owner, rep, count, zsum, total, visits);
+    k_merge_sum<G><<<nblk((size_t)n * (G::A + 1)), 256, 0, st>>>(n, rec, slot_of, first, owner, group, count, zsum, total, visits);
+}
+
+extern "C" int bb_examples_merge(int game, int n_records, const void *records, int32_t *group_out, int32_t *rep_out, int32_t *count_out,
+                                 int32_t *zsum_out, uint64_t *total_out, uint64_t *visits_out, int32_t *n_groups_out, int32_t *bad_out,
+                                 void *workspace, uint64_t workspace_bytes, void *stream) {
+    if (int rc = merge_game_check(game)) return rc;
+    if (n_records < 0 || n_records > MERGE_MAX_RECORDS) return fail(BB_ERR_ARG, "n_records must be in [0, %d]", MERGE_MAX_RECORDS);
+    if (n_records == 0) return BB_OK; // nothing to merge: a no-op
+    if (!records || !group_out || !rep_out || !count_out || !zsum_out || !total_out || !visits_out || !n_groups_out || !bad_out || !workspace)
+        return fail(BB_ERR_ARG, "bb_examples_merge: every pointer is required");
+    if (((uintptr_t)records | (uintptr_t)workspace) % 16 || ((uintptr_t)total_out | (uintptr_t)visits_out) % 8 ||
+        ((uintptr_t)group_out | (uintptr_t)rep_out | (uintptr_t)count_out | (uintptr_t)zsum_out | (uintptr_t)n_groups_out | (uintptr_t)bad_out) % 4)
+        return fail(BB_ERR_ARG, "bb_examples_merge: records and workspace are accessed in 16-byte units, the outputs in their own");
+    const MergeWorkspace w = merge_workspace(n_records);
+    if (workspace_bytes < w.bytes)
+        return fail(BB_ERR_ARG, "workspace of %llu bytes, %zu are needed (bb_examples_merge_workspace)", (unsigned long long)workspace_bytes, w.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t *ws = (uint8_t *)workspace;
+    HIPCHK(hipMemsetAsync(ws + w.owner, 0xFF, (size_t)w.cap * 4, st)); // MERGE_EMPTY
+    HIPCHK(hipMemsetAsync(ws + w.first, 0x7F, (size_t)w.cap * 4, st)); // MERGE_NO_FIRST
+    HIPCHK(hipMemsetAsync(ws + w.err, 0, 16, st));
+    const uint8_t *rec = (const uint8_t *)records;
+    if (game == BB_GAME_CONNECT4)
+        merge_launch<Connect4>(st, n_records, rec, w, ws, group_out, rep_out, count_out, zsum_out, total_out, visits_out, n_groups_out, bad_out);
+    else
+        merge_launch<TicTacToe>(st, n_records, rec, w, ws, group_out, rep_out, count_out, zsum_out, total_out, visits_out, n_groups_out, bad_out);
+    HIPCHK(hipGetLastError());
+    return BB_OK;
+}
+
+extern "C" int bb_examples_merged_to_batch(int game, int n_records, const void *records, int n_groups, const int32_t *rep, const int32_t *count,
+                                           const int32_t *zsum, const uint64_t *total, const uint64_t *visits, int n, const int64_t *index,
+                                           const uint8_t *sym, float *boards_out, float *policy_out, float *value_out, int32_t *bad_out,
+                                           void *stream) {
+    if (int rc = merge_game_check(game)) return rc;
+    if (n == 0) return BB_OK; // an empty batch is a no-op
+    if (n < 0 || n_records < 0 || n_groups < 0 || !records || !rep || !count || !zsum || !total || !visits ||
+        (!boards_out && !policy_out && !value_out))
+        return fail(BB_ERR_ARG, "bad arguments");
+    if (((uintptr_t)records | (uintptr_t)boards_out | (uintptr_t)policy_out) % 16 || ((uintptr_t)total | (uintptr_t)visits) % 8)
+        return fail(BB_ERR_ARG, "records, boards_out and policy_out are accessed in 16-byte units, total and visits in 8-byte units");
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t *rec = (const uint8_t *)records;
+    if (game == BB_GAME_CONNECT4)
+        k_merged_to_batch<Connect4><<<nblk((size_t)n * (Connect4::H * Connect4::W * Connect4::C + Connect4::A + 1)), 256, 0, st>>>(
+            n_records, rec, n_groups, rep, count, zsum, total, visits, n, index, sym, boards_out, policy_out, value_out, bad_out);
+    else
+        k_merged_to_batch<TicTacToe><<<nblk((size_t)n * (TicTacToe::H * TicTacToe::W * TicTacToe::C + TicTacToe::A + 1)), 256, 0, st>>>(
+            n_records, rec, n_groups, rep, count, zsum, total, visits, n, index, sym, boards_out, policy_out, value_out, bad_out);
+    HIPCHK(hipGetLastError());
+    return BB_OK;
 }
 
 // ---- the arena on the device (arena.hip.h): Blackbird.TestModels' match loop without the host in it -----------------------

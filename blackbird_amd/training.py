@@ -358,3 +358,139 @@ class DeviceExamples:
         """Rows that bb_examples_to_batch rejected (and wrote as zeros) since this object was made: malformed records.
         Waits for the GPU -- look at it once per epoch, not once per batch."""
         return int(self._bad.item())
+
+    def merged(self):
+        """These records with the copies of a position merged into one row each (MergedExamples; an extension, Connect4 and
+        TicTacToe): bb_examples_merge on torch's current stream and one look at the group count."""
+        return MergedExamples(self)
+
+
+def _merge_scope(game):
+    if game not in _lib.GRID:
+        raise ValueError('merging duplicate positions covers Connect4 and TicTacToe: DragonChess (game %d) has a 64-byte board key '
+                         'plus castle flags, compact child lists and few transpositions, and is not covered' % game)
+
+
+def merge_records_host(game, records):
+    """The definition of merging, in numpy, on a host structured array (_lib.example_dtype) -- the statement the tests hold
+    bb_examples_merge against; the product uses it for records that are on the CPU and never for device records.
+
+    The key of a record is what the network sees of its state: the cells of both players and the side to move (not the previous
+    player, not the header).  A record with n_children > S is malformed: group -1.  Groups are numbered by the index of their
+    first member.  Returns (group [n] int32, rep [G] int32, count [G] int32, zsum [G] int32, total [G] uint64, visits [G, A]
+    uint64): per group the first member, the member count and the integer sums of z, total and visits[:A]."""
+    _merge_scope(game)
+    gi = _lib.game_info(game)
+    records = np.asarray(records)
+    n = len(records)
+    group = np.full(n, -1, dtype=np.int32)
+    good = np.flatnonzero(records['n_children'] <= gi.S) if n else np.zeros(0, dtype=np.int64)
+    if good.size == 0:
+        return (group, np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint64),
+                np.zeros((0, gi.A), np.uint64))
+    st = np.ascontiguousarray(records['state']).view('<u8').reshape(n, 2)[good]
+    cells = np.uint64(0x00FFFFFFFFFFFFFF)
+    key = np.stack([st[:, 0] & cells, st[:, 1] & cells, (st[:, 0] >> np.uint64(56)) & np.uint64(3)], axis=1)
+    _uniq, first, inverse = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    by_first = np.argsort(first, kind='stable')          # unique keys in the order of their first member
+    number = np.empty(len(first), dtype=np.int64)
+    number[by_first] = np.arange(len(first))
+    g = number[inverse.reshape(-1)]
+    group[good] = g
+    G = len(first)
+    rep = good[first[by_first]].astype(np.int32)
+    count = np.bincount(g, minlength=G).astype(np.int32)
+    zsum = np.zeros(G, dtype=np.int64)
+    np.add.at(zsum, g, records['z'][good].astype(np.int64))
+    total = np.zeros(G, dtype=np.uint64)
+    np.add.at(total, g, records['total'][good].astype(np.uint64))
+    visits = np.zeros((G, gi.A), dtype=np.uint64)
+    np.add.at(visits, g, records['visits'][good][:, :gi.A].astype(np.uint64))
+    return group, rep, count, zsum.astype(np.int32), total, visits
+
+
+class MergedExamples:
+    """A DeviceExamples with the copies of every position merged into one training row (DeviceExamples.merged): the source
+    records plus, per group, its first member `rep`, its size `count` and the integer sums `zsum`, `total`, `visits` -- tensors
+    on the records' device, trimmed to the number of groups --, and `group` [records], the group of every record (-1: malformed).
+    A row's planes are those of its first member, its policy visits / total over the whole group (a copy searched longer weighs
+    more), its value the mean outcome; a group of one is exactly DeviceExamples.batch's row.  `batch` is DeviceExamples.batch
+    over groups (bb_examples_merged_to_batch).  Made with one look at the device (the group count); sums are integers, so the
+    same records give the same bits every time.  Records on the CPU are merged by merge_records_host (batch needs the GPU)."""
+
+    def __init__(self, examples):
+        _merge_scope(examples.game)
+        self.game, self.info, self.records = examples.game, examples.info, examples.records
+        dev, n, A = self.records.device, len(examples), examples.info.A
+        self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        if dev.type != 'cuda':
+            raw = self.records.numpy().reshape(-1).view(_lib.example_dtype(self.game))
+            group, rep, count, zsum, total, visits = merge_records_host(self.game, raw)
+            self._merge_bad = int((group < 0).sum())
+            parts = [torch.from_numpy(group), torch.from_numpy(rep), torch.from_numpy(count), torch.from_numpy(zsum),
+                     torch.from_numpy(total.astype(np.int64)), torch.from_numpy(visits.astype(np.int64))]
+        else:
+            i32 = dict(dtype=torch.int32, device=dev)
+            parts = [torch.empty(n, **i32), torch.empty(n, **i32), torch.empty(n, **i32), torch.empty(n, **i32),
+                     torch.empty(n, dtype=torch.int64, device=dev), torch.empty((n, A), dtype=torch.int64, device=dev)]
+            look = torch.zeros(2, **i32)      # [n_groups, malformed records]
+            if n:
+                nbytes = _lib.examples_merge_workspace(self.game, n)
+                work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                with torch.cuda.device(dev):
+                    _lib.examples_merge(self.game, n, self.records.data_ptr(), *[t.data_ptr() for t in parts],
+                                        n_groups=look.data_ptr(), bad=look.data_ptr() + 4, workspace=work.data_ptr(),
+                                        workspace_bytes=nbytes, stream=torch.cuda.current_stream(dev).cuda_stream)
+            n_groups, self._merge_bad = (int(x) for x in look.cpu())   # the one host look (waits for the launches above)
+            _lib_check_merge(n_groups)
+            parts = [parts[0]] + [t[:n_groups] for t in parts[1:]]
+        self.group, self.rep, self.count, self.zsum, self.total, self.visits = parts
+
+    def __len__(self):
+        return int(self.rep.shape[0])
+
+    def counts(self):
+        """The number of records in every group (int32 tensor on the records' device)."""
+        return self.count
+
+    index_tensor = DeviceExamples.index_tensor     # (range-checked against len(self): the number of groups)
+    sym_tensor = DeviceExamples.sym_tensor
+    symmetries = DeviceExamples.symmetries
+
+    def batch(self, index=None, sym=None):
+        """DeviceExamples.batch over merged rows: (boards [n,H,W,C], value [n], policy [n,A]) of the groups `index` names (None:
+        all, in order), each under the symmetry `sym` gives it (None: as played)."""
+        return self._batch(None if index is None else self.index_tensor(index), None if sym is None else self.sym_tensor(sym))
+
+    def _batch(self, idx, sym=None):
+        """`batch` for tensors that index_tensor and sym_tensor returned (or slices of them)."""
+        gi, dev = self.info, self.records.device
+        n = len(self) if idx is None else int(idx.numel())
+        if sym is not None and int(sym.numel()) != n:
+            raise ValueError('sym: one entry per output row is expected (%d rows, %d entries)' % (n, int(sym.numel())))
+        boards = torch.empty((n, gi.H, gi.W, gi.C), dtype=torch.float32, device=dev)
+        value = torch.empty((n,), dtype=torch.float32, device=dev)
+        policy = torch.empty((n, gi.A), dtype=torch.float32, device=dev)
+        if n == 0:
+            return boards, value, policy
+        if dev.type != 'cuda':
+            raise _lib.BlackbirdHipError('MergedExamples.batch runs on the GPU only (records on %s)' % dev)
+        with torch.cuda.device(dev):
+            _lib.examples_merged_to_batch(self.game, int(self.records.shape[0]), self.records.data_ptr(), len(self),
+                                          self.rep.data_ptr(), self.count.data_ptr(), self.zsum.data_ptr(), self.total.data_ptr(),
+                                          self.visits.data_ptr(), n, None if idx is None else idx.data_ptr(),
+                                          None if sym is None else sym.data_ptr(), boards.data_ptr(), policy.data_ptr(),
+                                          value.data_ptr(), self._bad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return boards, value, policy
+
+    def bad(self):
+        """Malformed records that the merge left out, plus rows that `batch` rejected (and wrote as zeros) since.  Waits for
+        the GPU -- look at it once per epoch, not once per batch."""
+        return self._merge_bad + int(self._bad.item())
+
+
+def _lib_check_merge(n_groups):
+    """bb_examples_merge reports a probe that ran out through its group count: an error code where a count belongs."""
+    if n_groups < 0:
+        raise _lib.BlackbirdHipError('libblackbird_hip error %d: bb_examples_merge found no place for a record in its position '
+                                     'table' % n_groups)

@@ -454,6 +454,46 @@ int bb_examples_to_batch(int game, int n_records, const void *records, int n, co
 int bb_examples_to_batch_sym(int game, int n_records, const void *records, int n, const int64_t *index, const uint8_t *sym,
                              float *boards_out, float *policy_out, float *value_out, int32_t *bad_out, void *stream);
 
+/* ---- duplicate positions merged into one training row (Connect4, TicTacToe) -------------------- */
+/* An extension (the reference trains on every stored row), opt-in.  Concurrent self-play from one start position stores the same
+ * position many times, each copy with its own visit counts and outcome; bb_examples_merge groups the records by position and sums
+ * their targets, bb_examples_merged_to_batch forms training rows from the sums.  Definition:
+ *   key      what the network sees of a record's state: the cells of both players and the side to move.  The previous player,
+ *            game_id, ply and player of the header are not part of it.  Equal keys: the same position.
+ *   groups   numbered 0 .. n_groups-1 by the index of their first member in record order: rep[] is ascending.  A record with
+ *            n_children > S belongs to no group: group -1, one count in *bad_out, and nothing it says is used as an address.
+ *   sums     count[g] (int32), zsum[g] (int32, of z), total[g] (uint64, of total), visits[g][a], a < A (uint64, of visits[a]).
+ *   row      planes of record rep[g]; policy[a] = (float)((double)visits[g][a] / (double)total[g]), zeros when total[g] == 0;
+ *            value = (float)((double)zsum[g] / (double)count[g]).  The policy pools visits: a copy searched longer weighs more.
+ *            A group of one member is, bit for bit, that record's row of bb_examples_to_batch.
+ * All sums are integers and no float atomic is used: the same input gives the same bits on every run.
+ * DragonChess, an unknown game, n_records < 0 or a null or misaligned pointer: BB_ERR_ARG before any device call.  Stateless; ALL
+ * pointers but bytes_out are device memory of the calling thread's current device; the launches are asynchronous on `stream`,
+ * nothing is allocated and nothing is waited for. */
+/* The scratch memory bb_examples_merge needs for n_records records, in bytes (0 for none).  Host only: no device call. */
+int bb_examples_merge_workspace(int game, int n_records, uint64_t *bytes_out);
+/*   records     [n_records][example_bytes], the bb_examples_fetch layout, 16-byte aligned; read only
+ *   group_out   [n_records] the group of every record, -1 for a malformed one
+ *   rep_out, count_out, zsum_out, total_out [n_records], visits_out [n_records][A]: entries 0 .. n_groups-1 are written
+ *   n_groups_out  [1] the number of groups -- or BB_ERR_CAPACITY if a probe of the position table ran its whole (bounded) length
+ *                 without finding a place, which a table of twice the records cannot do unless memory was damaged: the caller's
+ *                 one look at this word after the stream has run is where that is reported, and no other output is valid then
+ *   bad_out     [1] incremented by one per malformed record (the caller zeroes it)
+ *   workspace   workspace_bytes >= bb_examples_merge_workspace bytes, 16-byte aligned; contents need not be kept
+ * n_records == 0: BB_OK, nothing touched (GPU or not). */
+int bb_examples_merge(int game, int n_records, const void *records, int32_t *group_out, int32_t *rep_out, int32_t *count_out,
+                      int32_t *zsum_out, uint64_t *total_out, uint64_t *visits_out, int32_t *n_groups_out, int32_t *bad_out,
+                      void *workspace, uint64_t workspace_bytes, void *stream);
+/* bb_examples_to_batch_sym over merged rows: row k is group index[k] (NULL: group k; n rows) in the orientation sym[k] (NULL: as
+ * played), from rep / count / zsum / total / visits as bb_examples_merge filled them for these records (n_groups the host's copy of
+ * its count).  Outputs, alignment and the n == 0 rule as there.  A row is zeros, and *bad_out incremented, if index[k] is outside
+ * [0, n_groups), if sym[k] >= bb_game_symmetries(game), if rep is outside [0, n_records) or names a malformed record, or if count is
+ * not positive: no value becomes an index before it has been checked. */
+int bb_examples_merged_to_batch(int game, int n_records, const void *records, int n_groups, const int32_t *rep, const int32_t *count,
+                                const int32_t *zsum, const uint64_t *total, const uint64_t *visits, int n, const int64_t *index,
+                                const uint8_t *sym, float *boards_out, float *policy_out, float *value_out, int32_t *bad_out,
+                                void *stream);
+
 /* ---- the training step as HIP kernels (opt-in; the default trainer is PyTorch's autograd) --------- */
 /* One step of Network.train (Network.py:66-84; loss and optimiser NetworkFactory.py:185-245) for the dense games (Connect4,
  * TicTacToe) with 16 filters, 0..9 blocks and a dense width of 1..64: three launches (csrc/train.hip.h) -- the step's noise,

@@ -1,5 +1,5 @@
 """From finished self-play games to a trained network, both ways, timed: python tools/train_path.py [--games N]
-[--play-limit P] [--batch B] [--lr LR] [--augment]
+[--play-limit P] [--batch B] [--lr LR] [--augment] [--merge] [--skip-host] [--skip-hip]
 
 N Connect4 games at PlayLimit P are played once (Model.KeepDeviceExamples on, so that sqlite and the GPU hold the same
 examples); then one epoch over them is trained twice with the same batch size:
@@ -14,7 +14,12 @@ examples); then one epoch over them is trained twice with the same batch size:
 and the bare DeviceExamples.batch calls of that epoch alone.  Every timed region ends in a device synchronise; one training
 step is run before any of them, per trainer (the first step pays for the library's kernel selection).  --augment: the
 device and hip paths and the bare batches present every example mirrored or not (TrainWithDeviceExamples' augment=True,
-bb_examples_to_batch_sym); the host path has no such thing and stays as it is.  Prints one JSON line."""
+bb_examples_to_batch_sym); the host path has no such thing and stays as it is.  --merge: the copies of a position among the
+kept records are merged first (DeviceExamples.merged, bb_examples_merge): the records, the groups, the five largest groups and
+the time of merged() (its kernels and its one host look, after one untimed call on 256 records that loads the kernels) are
+printed, and one more epoch is timed on the first model through TrainWithDeviceExamples(merge=True), next to the bare merged
+batches of that epoch; every other figure is measured as without it.  --skip-host / --skip-hip leave the host path / the hip
+path out (their figures are null).  Prints one JSON line."""
 import argparse
 import copy
 import json
@@ -43,6 +48,9 @@ def main():
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--augment", action="store_true")
+    ap.add_argument("--merge", action="store_true")
+    ap.add_argument("--skip-host", action="store_true")
+    ap.add_argument("--skip-hip", action="store_true")
     a = ap.parse_args()
     os.chdir(tempfile.mkdtemp())  # the sqlite file and the saved networks of this run
     np.random.seed(a.seed)
@@ -61,7 +69,8 @@ def main():
     hip_model = Blackbird.Model(Connect4.BoardState, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, hip_cfg)
     assert all(np.array_equal(hip_model._weights[k], model._weights[k]) for k in model._weights)
     model.train(boards, value, policy, a.lr)  # warm-up step
-    hip_model.train(boards, value, policy, a.lr)
+    if not a.skip_hip:
+        hip_model.train(boards, value, policy, a.lr)
     torch.cuda.synchronize()
 
     # bare batches of one epoch
@@ -75,19 +84,21 @@ def main():
     batch_s = time.time() - t
 
     # host path: TrainWithExamples, statement by statement, with a clock after the decode
-    t = time.time()
-    states = model.Conn.GetGames(model.Name, model.Version)
-    examples = [Blackbird.ExampleState.FromSerialized(s) for s in states]
-    decode_s = time.time() - t
-    assert len(examples) == n, (len(examples), n)
-    horder = np.random.choice(len(examples), len(examples) - (len(examples) % B), replace=False)
-    examples = [examples[i] for i in horder]
-    for i in range(len(examples) // B):
-        b = examples[i * B:(i + 1) * B]
-        model.train(np.vstack([e.Board for e in b]), np.hstack([e.MctsEval for e in b]),
-                    np.vstack([e.MctsPolicy for e in b]), a.lr)
-    torch.cuda.synchronize()
-    host_s = time.time() - t
+    host_s = decode_s = None
+    if not a.skip_host:
+        t = time.time()
+        states = model.Conn.GetGames(model.Name, model.Version)
+        examples = [Blackbird.ExampleState.FromSerialized(s) for s in states]
+        decode_s = time.time() - t
+        assert len(examples) == n, (len(examples), n)
+        horder = np.random.choice(len(examples), len(examples) - (len(examples) % B), replace=False)
+        examples = [examples[i] for i in horder]
+        for i in range(len(examples) // B):
+            b = examples[i * B:(i + 1) * B]
+            model.train(np.vstack([e.Board for e in b]), np.hstack([e.MctsEval for e in b]),
+                        np.vstack([e.MctsPolicy for e in b]), a.lr)
+        torch.cuda.synchronize()
+        host_s = time.time() - t
 
     # device path
     t = time.time()
@@ -96,17 +107,45 @@ def main():
     device_s = time.time() - t
 
     # hip path: the same epoch (the same examples, an order drawn the same way) with the step as HIP kernels
-    t = time.time()
-    Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment)
-    torch.cuda.synchronize()
-    hip_s = time.time() - t
+    hip_s = None
+    if not a.skip_hip:
+        t = time.time()
+        Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment)
+        torch.cuda.synchronize()
+        hip_s = time.time() - t
 
+    # merged: the merge itself, the bare merged batches of an epoch, and the epoch through TrainWithDeviceExamples(merge=True)
+    merge = {}
+    if a.merge:
+        type(kept)(kept.game, kept.records[:256]).merged()  # (untimed: the first call loads the kernels)
+        torch.cuda.synchronize()
+        t = time.time()
+        merged = kept.merged()
+        merge_s = time.time() - t   # (merged() ends in its host look: nothing is in flight)
+        sizes = merged.counts().cpu().numpy()
+        morder = merged.index_tensor(epoch_order(len(merged), B))
+        msyms = merged.sym_tensor(np.random.randint(merged.symmetries, size=len(morder))) if a.augment else None
+        torch.cuda.synchronize()
+        t = time.time()
+        for i in range(len(morder) // B):
+            merged._batch(morder[i * B:(i + 1) * B], None if msyms is None else msyms[i * B:(i + 1) * B])
+        torch.cuda.synchronize()
+        mbatch_s = time.time() - t
+        t = time.time()
+        Blackbird.TrainWithDeviceExamples(model, B, a.lr, examples=kept, augment=a.augment, merge=True)
+        torch.cuda.synchronize()
+        merge = {"merge_records": n, "merge_groups": len(merged), "merge_bad": merged.bad(),
+                 "merge_largest_groups": np.sort(sizes)[::-1][:5].tolist(), "merge_singletons": int((sizes == 1).sum()),
+                 "merge_s": round(merge_s, 5), "merged_batches": len(merged) // B, "merged_batches_only_s": round(mbatch_s, 4),
+                 "device_path_merge_s": round(time.time() - t, 3)}
+
+    r3 = lambda x: None if x is None else round(x, 3)  # noqa: E731
     print(json.dumps({"tool": "train_path", "game": "connect4", "games": a.games, "warmup_games": 64, "play_limit": a.play_limit,
                       "examples": n, "augment": bool(a.augment), "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
-                      "host_path_s": round(host_s, 3), "host_decode_s": round(decode_s, 3),
+                      "host_path_s": r3(host_s), "host_decode_s": r3(decode_s),
                       "device_path_s": round(device_s, 3), "device_batches_only_s": round(batch_s, 4),
-                      "host_over_device": round(host_s / device_s, 2), "hip_path_s": round(hip_s, 3),
-                      "device_over_hip": round(device_s / hip_s, 2)}))
+                      "host_over_device": None if host_s is None else round(host_s / device_s, 2), "hip_path_s": r3(hip_s),
+                      "device_over_hip": None if hip_s is None else round(device_s / hip_s, 2), **merge}))
 
 
 if __name__ == "__main__":
