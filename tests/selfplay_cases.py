@@ -46,7 +46,9 @@ def step_bound(n_games, max_plies, step):
 def play_to_end(eng, n_games, step, temp, *, begin=True, steps_below=None, between=None, headers=False,
                 overflow_each_step=False):
     """bb_selfplay_begin(n_games, temp) unless begin=False (the caller has begun them), then steps of `step` plies until every
-    game is over; between(k): called after step k.  The number of steps stays below step_bound() -- and below steps_below,
+    game is over; between(k): called after step k -- the place to harvest finished games in mid-run: feed a
+    tests/harvest_cases.py Ledger there (harvest(eng, ledger)) and hand it this function's result at the end (headers=True).
+    The number of steps stays below step_bound() -- and below steps_below,
     a caller's own tighter count -- or the run fails; overflow_each_step: no node pool has overflowed after any step.
     Everything a caller can read (headers=True: hdr too)."""
     if begin:
