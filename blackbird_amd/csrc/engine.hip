@@ -419,7 +419,7 @@ static int engine_alloc(bb_engine *e) {
     BB_SLOT_ARRAYS(X)
 #undef X
     if (bad || dalloc(e, e->d_u, n) || dalloc(e, e->d_actions, n) || dalloc(e, e->d_child_action, n * S) ||
-        dalloc(e, d.stamps, 16 * 64) || dalloc(e, d.visit_pool, 16) || dalloc(e, d.post_count, 8))
+        dalloc(e, d.stamps, STAMP_BUFFER_WORDS) || dalloc(e, d.visit_pool, 16) || dalloc(e, d.post_count, 8))
         return BB_ERR_HIP;
     typename G::State *ls;
     if (dalloc(e, ls, n)) return BB_ERR_HIP;
@@ -940,7 +940,7 @@ extern "C" int bb_load_weights(bb_engine *e, const bb_net_weights *w) {
     nd.eps = e->cfg.epsilon;
     nd.inv_alpha = 1.0f / nd.alpha;
     nd.inv_beta = 1.0f / (1.0f - nd.alpha);
-    nd.dbg = 0; // (ablation switches exist in diagnostic builds only: bb_timing_net, -DBB_DIAG)
+    nd.dbg = 0; // (ablation switches exist in diagnostic builds only: bb_timing_net, stamps.hip.h)
     e->has_weights = true;
     e->net_F = F;
     e->net_C = C;
@@ -2377,12 +2377,12 @@ extern "C" int bb_timing_net(bb_engine *e, int iters, int noise, int ablate, dou
 }
 
 
-#ifdef BB_STAMPS
+#ifdef BB_STAMPS // (host API of the diagnostic builds; the switches and the stamp-word map: stamps.hip.h)
 // diagnostic builds only: point the stamp buffer at host-coherent memory so that it can be read while a kernel runs
 extern "C" int bb_debug_host_stamps(bb_engine *e, unsigned long long **host_out) {
     unsigned long long *p = nullptr;
-    HIPCHK(hipHostMalloc((void **)&p, 16 * 64 * 8, hipHostMallocCoherent | hipHostMallocMapped));
-    memset(p, 0, 16 * 64 * 8);
+    HIPCHK(hipHostMalloc((void **)&p, STAMP_BUFFER_BYTES, hipHostMallocCoherent | hipHostMallocMapped));
+    memset(p, 0, STAMP_BUFFER_BYTES);
     e->dev.stamps = p;
     for (int v = 0; v < 2; v++) e->view[v].stamps = p;
     *host_out = p;
@@ -2390,20 +2390,20 @@ extern "C" int bb_debug_host_stamps(bb_engine *e, unsigned long long **host_out)
 }
 extern "C" int bb_debug_net_stamps(bb_engine *e, unsigned long long *out8) {
     HIPCHK(sync_all(e));
-    HIPCHK(hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_net_stamps), 64));
-    unsigned long long z[8] = {0};
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_net_stamps), z, 64));
+    HIPCHK(hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_net_stamps), NET_STAMP_WORDS * 8));
+    unsigned long long z[NET_STAMP_WORDS] = {0};
+    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_net_stamps), z, sizeof(z)));
     return BB_OK;
 }
 extern "C" int bb_stream_done(bb_engine *e) { return hipStreamQuery(e->stream) == hipSuccess ? 1 : 0; }
 // diagnostic builds only (tools/): in-kernel cycle stamps accumulated by the tree / persistent kernels
 extern "C" int bb_debug_stamps(bb_engine *e, unsigned long long *out8) {
     HIPCHK(sync_all(e));
-    unsigned long long all[16 * 64]; // 64 copies (the DragonChess kernels spread their flushes), summed here
+    unsigned long long all[STAMP_BUFFER_WORDS]; // STAMP_COPIES copies (the DragonChess kernels spread their flushes), summed here
     HIPCHK(hipMemcpy(all, e->dev.stamps, sizeof(all), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 16; i++) {
+    for (int i = 0; i < STAMP_WORDS; i++) {
         out8[i] = 0;
-        for (int c = 0; c < 64; c++) out8[i] += all[c * 16 + i];
+        for (int c = 0; c < STAMP_COPIES; c++) out8[i] += all[c * STAMP_WORDS + i];
     }
     HIPCHK(hipMemset(e->dev.stamps, 0, sizeof(all)));
     return BB_OK;

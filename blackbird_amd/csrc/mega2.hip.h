@@ -186,9 +186,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
     // waited for its slowest workgroup (~35 ms of a 16-step launch); a game's results do not depend on when its visits happen.
     __shared__ int wg_pool, wg_dry, wg_refill;
     constexpr int CHUNK = GW * 32;
-#ifdef BB_STAMPS
-    __shared__ long long ts_post[GW], ts_done[GW];
-#endif
+    IF_STAMPS(__shared__ long long ts_post[GW], ts_done[GW];) // wall clock: leaf posted, result published
     const int wave = threadIdx.x >> 6, l64 = threadIdx.x & 63;
     const int g0 = blockIdx.x * GW;
     const int n_mine = dg.n_slots - g0 < GW ? dg.n_slots - g0 : GW;
@@ -204,9 +202,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
         wg_refill = 0;
     }
     if (threadIdx.x < TREEW * 8) gstate[threadIdx.x] = 0;
-#ifdef BB_STAMPS_NET
-    if (threadIdx.x < 8) s_net_stamps[threadIdx.x] = 0;
-#endif
+    net_stamps_zero();
     if (threadIdx.x < MEGA2_QCAP) qc.q[threadIdx.x] = -1;
     for (int i = threadIdx.x; i < NETW * WAVE_F; i += MEGA2_THREADS) lds[i] = 0.f;
     NetDev ndl = nd;
@@ -243,9 +239,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
         const bool mine = l64 < GPT * S && li < GW && g0 + li < d.n_slots;
         const int g = li; // local game number: index of the LDS copies
         bool alive = mine && d.game_lid[mine ? g : 0] >= 0; // false once the slot has run out of games (or never had one)
-#ifdef BB_STAMPS
-        long long t_work = 0, t_all0 = clock64(), n_calls = 0, n_lanes = 0, t_pick = 0, n_pick = 0;
-#endif
+        IF_STAMPS(long long t_work = 0, t_all0 = clock64(), n_calls = 0, n_lanes = 0, t_pick = 0, n_pick = 0;)
         // A leaf goes to the network waves the moment its mailbox is written (async_game's on_post hook), not when the call
         // returns: a call of this wave lasts as long as the slowest of its games' descents.  The network wave that evaluates the
         // leaf also draws its prior noise (head_one).
@@ -253,9 +247,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
             if (NET_APPLIES) release_global_then_lds(); // mailbox (+ tree writes) before the queue entry
             else __threadfence_block();
             if (ln == 0) {
-#ifdef BB_STAMPS
-                ts_post[li] = wall_clock64();
-#endif
+                IF_STAMPS(ts_post[li] = wall_clock64();)
                 *(volatile uint8_t *)&gstate[GSI(li)] = 1;
                 const int idx = atomicAdd(&qc.tail, 1); // the entry becomes valid when its slot turns non-negative
                 *(volatile int *)&qc.q[idx & (MEGA2_QCAP - 1)] = li;
@@ -289,47 +281,21 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
             if (__any(ready)) {
                 __threadfence_block(); // acquire: the network wave's results for state 2
                 bool posted = false;
-#ifdef BB_STAMPS
-                long long ts = clock64();
-                n_calls++;
-                n_lanes += __popcll(__ballot(ready)) / S;
-                if (ready && lane == 0 && stt == 2) {
-                    t_pick += wall_clock64() - ts_done[li];
-                    n_pick++;
-                }
-#endif
-#ifdef BB_STAMPS_LIGHT
-                int ll = 0, lv = 0, lld = 0, lpu = 0;
+                IF_STAMPS(long long ts = clock64(); n_calls++; n_lanes += __popcll(__ballot(ready)) / S;)
+                IF_STAMPS(if (ready && lane == 0 && stt == 2) { t_pick += wall_clock64() - ts_done[li]; n_pick++; })
+                LevelStamps light;
                 if (ready) {
-                    posted = async_game<G, X3>(d, g, lane, ll, lv, lld, lpu, early_post);
-                    if (d.game_lid[g] < 0) alive = false;
-                }
-                { // the game with the most levels ran the whole length of the call: its loop time per level is undiluted
-                    int m = lv;
-                    for (int o = 32; o; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
-                    unsigned long long who = __ballot(ready && lane == 0 && lv == m);
-                    if (who && l64 == (int)__builtin_ctzll(who) && d.stamps) {
-                        atomicAdd(&d.stamps[6], (unsigned long long)ll);
-                        atomicAdd(&d.stamps[7], (unsigned long long)lv);
-                        atomicAdd(&d.stamps[11], (unsigned long long)lld);   // (LIGHT: 11 / 12 carry the split, not the call totals)
-                        atomicAdd(&d.stamps[12], (unsigned long long)lpu);
-                    }
-                }
-#else
-                if (ready) {
-                    posted = async_game<G, X3>(d, g, lane, early_post);
+                    posted = async_game<G, X3>(d, g, lane, early_post, &light);
                     if (d.game_lid[g] < 0) alive = false; // slot ran out of games
                 }
-#endif
+                level_stamps_flush(d.stamps, light, ready && lane == 0, l64);
                 {
                     int used = __popcll(__ballot(ready && lane == 0));
                     if (l64 == 0) atomicSub(&wg_pool, used);
                 }
                 // (posted leaves went to the network waves inside the call: early_post; the others go back to their tree wave)
                 queue_push<NET_APPLIES>(&qc, &gstate[GSI(li < GW ? li : 0)], ready && lane == 0 && !posted, false, li);
-#ifdef BB_STAMPS
-                t_work += clock64() - ts;
-#endif
+                IF_STAMPS(t_work += clock64() - ts;)
             } else {
                 __builtin_amdgcn_s_sleep(BB_TREE_IDLE_SLEEP);
                 int late = wall_clock64() - t_start > t_limit || lds_load(&qc.abort_flag);
@@ -340,19 +306,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
             }
         }
         if (l64 == 0) atomicAdd(&qc.tree_done, 1);
-#ifdef BB_STAMPS
-        if (l64 == 0 && d.stamps) {
-            atomicAdd(&d.stamps[2], (unsigned long long)t_work);
-            atomicAdd(&d.stamps[3], (unsigned long long)(clock64() - t_all0));
-            atomicAdd(&d.stamps[5], 1ull);
-            atomicAdd(&d.stamps[13], (unsigned long long)n_calls);
-            atomicAdd(&d.stamps[14], (unsigned long long)n_lanes);
-        }
-        if (lane == 0 && d.stamps && n_pick) {
-            atomicAdd(&d.stamps[8], (unsigned long long)t_pick);
-            atomicAdd(&d.stamps[9], (unsigned long long)n_pick);
-        }
-#endif
+        IF_STAMPS(if (l64 == 0) stamp_add_all(d.stamps, QS_TREE_WORK, t_work, QS_TREE_ALIVE, clock64() - t_all0, QS_TREE_WAVES, 1, QS_TREE_CALLS, n_calls, QS_TREE_GAMES, n_lanes);)
+        IF_STAMPS(if (lane == 0 && n_pick) stamp_add_all(d.stamps, QS_PICK_WAIT, t_pick, QS_PICKS, n_pick);)
     } else { // ---------------- network waves ----------------
         float *wl = lds + wave * WAVE_F;
         // The evaluation cache (net.hip.h; off when dg.eval_cache is null): a hit costs the prior-noise tail instead of the tower.
@@ -360,9 +315,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
         constexpr bool CACHE = X3 && G::CACHE_KEY;
         const EvalCache ecache = {(u32x4 *)dg.eval_cache, dg.eval_cache_log2};
         unsigned long long n_probes = 0, n_hits = 0;
-#ifdef BB_STAMPS
-        long long t_work = 0, t_all0 = clock64(), n_evals = 0, t_qwait = 0;
-#endif
+        IF_STAMPS(long long t_work = 0, t_all0 = clock64(), n_evals = 0, t_qwait = 0;)
         for (;;) {
             const int li = __builtin_amdgcn_readfirstlane(queue_pop(&qc, t_start, t_limit, TREEW)); // scalar: uniform branches below
             if (li == -2) break;
@@ -371,11 +324,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
                 continue;
             }
             __threadfence_block(); // acquire: the tree wave's mailbox writes
-#ifdef BB_STAMPS
-            long long ts = clock64();
-            n_evals++;
-            t_qwait += wall_clock64() - ts_post[li];
-#endif
+            IF_STAMPS(long long ts = clock64(); n_evals++; t_qwait += wall_clock64() - ts_post[li];)
             if (l64 == 0) myslot[wave] = li;
             if constexpr (X3) {
                 int probe = -1;
@@ -398,44 +347,26 @@ __global__ void __launch_bounds__(WAVES * 64) k_selfplay_queue(TreeDev dg, NetDe
             // busier side of the queue: 91 % against 67 %; a result used to wait ~10 us to be picked up).  Same function,
             // same lane layout (lane i <-> child slot i on lanes 0..S-1), so the same bits.
             __threadfence_block(); // the mailbox writes of net_body (other lanes) before phase_apply reads them
-#ifdef BB_STAMPS_NET
-            long long _na = clock64();
-#endif
+            IF_STAMPS_NET(NetStamps na;)
             if (l64 < S) {
                 phase_apply<G>(d, li, l64);
                 if (l64 == 0) d.sims_left[li] -= 1;
             }
-#ifdef BB_STAMPS_NET
-            if (l64 == 0) atomicAdd(&s_net_stamps[5], (unsigned long long)(clock64() - _na));
-#endif
+            IF_STAMPS_NET(na.stop(NS_APPLY, l64);)
             }
             release_global_then_lds(); // value / policy (and the tree rows) before the state word
-#ifdef BB_STAMPS
-            if (l64 == 0) ts_done[li] = wall_clock64();
-#endif
+            IF_STAMPS(if (l64 == 0) ts_done[li] = wall_clock64();)
             if (l64 == 0) *(volatile uint8_t *)&gstate[GSI(li)] = 2;
-#ifdef BB_STAMPS
-            t_work += clock64() - ts;
-#endif
+            IF_STAMPS(t_work += clock64() - ts;)
         }
-#ifdef BB_STAMPS
-        if (l64 == 0 && d.stamps) {
-            atomicAdd(&d.stamps[0], (unsigned long long)t_work);
-            atomicAdd(&d.stamps[1], (unsigned long long)(clock64() - t_all0));
-            atomicAdd(&d.stamps[4], 1ull);
-            atomicAdd(&d.stamps[15], (unsigned long long)n_evals);
-            atomicAdd(&d.stamps[10], (unsigned long long)t_qwait);
-        }
-#endif
+        IF_STAMPS(if (l64 == 0) stamp_add_all(d.stamps, QS_NET_WORK, t_work, QS_NET_ALIVE, clock64() - t_all0, QS_NET_WAVES, 1, QS_EVALS, n_evals, QS_QUEUE_WAIT, t_qwait);)
         if (CACHE && l64 == 0 && n_probes && dg.eval_cache_ctr) {
             atomicAdd(&dg.eval_cache_ctr[0], n_hits);
             atomicAdd(&dg.eval_cache_ctr[1], n_probes);
         }
     }
     __syncthreads();
-#ifdef BB_STAMPS_NET
-    if (threadIdx.x < 8) atomicAdd(&g_net_stamps[threadIdx.x], s_net_stamps[threadIdx.x]);
-#endif
+    net_stamps_flush();
     if (qc.abort_flag) { // a wait ran into the wall-clock limit: surfaces as bb_counters.overflow
         if (threadIdx.x == 0) d.ctr[6] += 1;
         // a leaf that was queued but never evaluated must not be applied by the next launch (its mailbox holds the

@@ -207,9 +207,7 @@ __global__ void __launch_bounds__(256) k_dc_selfplay_fused(TreeDev d_arg, DCEdge
         s_hl[threadIdx.x].pdb = (LP)s_head + nd_arg.off_pdb;
         s_hl[threadIdx.x].h = WideHead{0.f, 0.f, 0.f, 0.f, 0.f};
     }
-#ifdef BB_STAMPS_NET
-    if (threadIdx.x < 8) s_net_stamps[threadIdx.x] = 0;
-#endif
+    net_stamps_zero();
     __syncthreads();
     (void)noise_on; // E.noise_on carries it to the expansion
     const TreeDev &d = s_d;
@@ -222,11 +220,8 @@ __global__ void __launch_bounds__(256) k_dc_selfplay_fused(TreeDev d_arg, DCEdge
     float *nl = (float *)lds_all[wv];
     DCHeadLocal *hl = &s_hl[wv];
     if (lane == 0) myslot[wv] = g;
-#ifdef BB_STAMPS
-    float *lds = tl; // DST's accumulator sits past the policy image and the network's activations
     static_assert(DC_STAMP_OFF >= NG::WAVE_FLOATS && DC_STAMP_OFF * 4 >= X3Geom<DragonChess>::WAVE_BYTES_PP, "stamp words must survive the network's zeroing of its scratch");
-    if (lane < 16) ((unsigned long long *)(lds + DC_STAMP_OFF))[lane] = 0;
-#endif
+    dst_zero(tl, lane); // (diagnostic: the stamp words sit past the policy image and the network's activations)
     __threadfence_block();
     // A wave starts with its own share of the launch's simulations (`own_sims`: 7/8 of plies x simulations per move -- so that
     // every game advances even when more workgroups are launched than the chip holds at once); the last eighth is one pool
@@ -254,35 +249,22 @@ __global__ void __launch_bounds__(256) k_dc_selfplay_fused(TreeDev d_arg, DCEdge
             }
         }
         chunk--;
-#ifdef BB_STAMPS
-        long long c0 = clock64();
-#endif
+        IF_STAMPS(long long c0 = clock64();)
         dc_fused_tree(d, E, g, lane, tl, hl);
-#ifdef BB_STAMPS
-        long long c1 = clock64();
-#endif
+        IF_STAMPS(long long c1 = clock64();)
         if (d.pend_leaf[g] >= 0) { // (uniform) a leaf was posted: evaluate it right here, unless the evaluation cache has it
             const int probe = s_x3.w0 ? dc_fused_net_x3(nd, s_x3, d, &myslot[wv], nl, hl) : dc_fused_net(nd, d, &myslot[wv], nl, hl);
             n_probes += probe >= 0;
             n_hits += probe > 0;
         }
-#ifdef BB_STAMPS
-        DST(0, c1 - c0);          // tree phases (tools/dc_stamps.py)
-        DST(2, clock64() - c1);   // network
-        DST(4, 1);
-#endif
+        IF_STAMPS(dst_add(tl, lane, DST_APPLY, c1 - c0); dst_add(tl, lane, DST_SELECT, clock64() - c1); dst_add(tl, lane, DST_STEPS, 1);) // tree phases, network (tools/dc_stamps.py)
     }
     if (lane == 0 && n_probes && d.eval_cache_ctr) {
         atomicAdd(&d.eval_cache_ctr[0], (unsigned long long)n_hits);
         atomicAdd(&d.eval_cache_ctr[1], (unsigned long long)n_probes);
     }
-#ifdef BB_STAMPS
-    if (mine && lane == 0 && d.stamps)
-        for (int i = 0; i < 16; i++) atomicAdd(&d.stamps[(size_t)((g0 + g) & 63) * 16 + i], ((unsigned long long *)(lds + DC_STAMP_OFF))[i]);
-#endif
+    if (mine && lane == 0) dst_flush(d.stamps, tl, g0 + g);
     __syncthreads();
-#ifdef BB_STAMPS_NET
-    if (threadIdx.x < 8) atomicAdd(&g_net_stamps[threadIdx.x], s_net_stamps[threadIdx.x]);
-#endif
+    net_stamps_flush();
     shadow.store(d_arg, E_arg, g0, n_mine, blockDim.x); // hand the per-game state back to HBM
 }

@@ -23,6 +23,7 @@
 #include <type_traits>
 #include "games.hip.h"
 #include "rng.hip.h"
+#include "stamps.hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -46,22 +47,6 @@ struct NetDev {
     float inv_alpha, inv_beta; // 1 / alpha and 1 / (1 - alpha) (float32 quotients, formed once on the host)
     int dbg; // ablation switches for bb_timing_net, looked at in diagnostic builds only (ND_DBG): 1 no heads, 2 no tower, 8 no noise draws
 };
-#ifdef BB_DIAG
-#define ND_DBG(bit) (nd.dbg & (bit))
-#else
-#define ND_DBG(bit) false
-#endif
-
-#ifdef BB_STAMPS
-__device__ unsigned long long g_net_stamps[8];
-#endif
-#ifdef BB_STAMPS_NET
-#define NSTAMP_ON 1 // diagnostic build: cycles per section of net_body, summed over calls (per workgroup in LDS, flushed by the persistent kernel)
-__shared__ unsigned long long s_net_stamps[8];
-#define NSTAMP(i) do { long long _t = clock64(); if (lane == 0) atomicAdd(&s_net_stamps[i], (unsigned long long)(_t - _ns)); _ns = clock64(); } while (0)
-#else
-#define NSTAMP(i) do {} while (0)
-#endif
 
 template <class G, int PW_>
 struct NetGeom {
@@ -504,9 +489,7 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
     float *actB = actA + ACT;
     float *inp = actB + ACT;
     auto OI = [&](int pos) { return slot_list ? slot_list[pos] : pos; };
-#ifdef BB_STAMPS_NET
-    long long _ns = clock64();
-#endif
+    NetStamps ns; // (diagnostic: cycles per section, stamps.hip.h)
 
     // ---- issue every global load of the prologue first, then zero LDS while they are in flight ---------
     // (one packed board per lane, the first conv's weights and epilogue constants)
@@ -574,7 +557,7 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
         ioffb[t] = (pp * SLOTS + slot - TAP0) * CP;
     }
     wave_lds_handover(); // input planes (and the staged boards) written above are read by other lanes below
-    NSTAMP(0);
+    ns.section(NS_PROLOGUE, lane);
     f32x4 acc[NT];
     // ---- first conv: K = 9*CIN in natural (tap, c) order, 4 k per MFMA ---------------------------
     {
@@ -630,7 +613,7 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
         }
     }
     wave_lds_handover();
-    NSTAMP(1);
+    ns.section(NS_CONV0, lane);
     // ---- residual tower: 2R convs, K order (tap, r, j) with channel c = 4j + r ---------------------
     // One layer = 9 taps x 4 k-steps x NT tiles of MFMAs + the epilogue; written once (conv_layer) and instantiated for
     // the first conv of a block (actA -> actB) and the second (actB -> actA, + the block's input before the ReLU), so
@@ -781,7 +764,7 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
         if (value_out && lane == 0) value_out[OI(pos0)] = acc[0][0];
         return;
     }
-    NSTAMP(2);
+    ns.section(NS_TOWER, lane);
     // ---- heads (tower output is in actA; actB and inp are scratch now) --------------------------
     const float *hp = nd.head;
     const float *vk = hp + nd.off_vk, *v3 = hp + nd.off_v3, *pk = hp + nd.off_pk, *p6 = hp + nd.off_p6;
@@ -809,14 +792,14 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
         static_assert(HW <= 64, "one lane per pixel");
         float x = 0.f, x0 = 0.f, x1 = 0.f;
         if (lane < HW) head_convs(lane, x, x0, x1);
-        NSTAMP(3);
+        ns.section(NS_HEAD_CONVS, lane);
         const bool live = pos0 < n;
         const int opos = live ? OI(pos0) : 0;
         uint64_t ckey;
         u32x4 *centry = eval_cache_store_entry<G>(store, planes ? nullptr : states, opos, live, ckey);
         head_one<G>(nd, pooled_sum(x), pooled_sum(x0), pooled_sum(x1), opos, live, game_id, serial, noise, value_out,
                     logits_out, policy_out, pstride, compact, centry, ckey);
-        NSTAMP(4);
+        ns.section(NS_HEAD_TAIL, lane);
     } else {
         float *rv = actB;               // [PW*HW] value-conv output
         float *rp = actB + PW * HW;     // [PW*HW][2] policy-conv output
@@ -828,10 +811,10 @@ __device__ __forceinline__ void net_body(const NetDev &nd, int n, int pos0, cons
             rp[2 * q + 1] = x1;
         }
         wave_lds_handover();
-        NSTAMP(3);
+        ns.section(NS_HEAD_CONVS, lane);
         net_head_tail<G, PW>(nd, n, pos0, slot_list, rv, rp, game_id, serial, noise, value_out, logits_out, policy_out, pstride,
                              compact, store, planes ? nullptr : states);
-        NSTAMP(4);
+        ns.section(NS_HEAD_TAIL, lane);
         if (!zero_lds) { // persistent caller: the head scratch overlaid actB's halo slots -- restore the zeros
             wave_lds_handover();
             for (int i = lane; i < 3 * PW * HW; i += 64) actB[i] = 0.f;

@@ -173,11 +173,6 @@ __device__ __forceinline__ void x3_split4(const f32x4 y, u32x2 &p1, u32x2 &p2, u
 __device__ __forceinline__ bf16x8 x3_ldg(const unsigned char *p) {
     return *(const __attribute__((address_space(1))) bf16x8 *)(const void *)p;
 }
-#ifdef BB_STAMPS_NET_SUB
-#define NSUB(i) NSTAMP(i) // prologue split (diagnostic): 5 = loads issued + zero fill, 6 = state to LDS, 7 = planes; 0 = the rest
-#else
-#define NSUB(i) do {} while (0)
-#endif
 #define X3_DBG(bit) ND_DBG(bit) // ablation switches of the diagnostic build (bb_timing_net; results are wrong when set)
 // CACHE (persistent kernel, Connect4): the position's evaluation cache entry (net.hip.h) is requested before the prologue and
 // tested after it -- on a miss the probe's latency hides under the prologue.  A hit skips the tower and the heads and runs only
@@ -207,9 +202,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
     typename G::State *sst = (typename G::State *)(wl + (PP ? 2 : 1) * XG::X_B);
     auto OI = [&](int pos) { return slot_list ? slot_list[pos] : pos; };
     const bool live = pos0 < n;
-#ifdef BB_STAMPS_NET
-    long long _ns = clock64();
-#endif
+    NetStamps ns; // (diagnostic: cycles per section, stamps.hip.h)
 
     // ---- prologue: the board, the first conv's operands, zero fill -------------------------------------------------
     // (PP = the one-wave-per-game kernel: its leaf positions already live in LDS (DCShadow), read them where they are)
@@ -243,7 +236,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
     const float *epi = PP ? as_lds(nd.epi) : nd.epi; // (the one-wave-per-game kernel keeps the constants in its LDS)
     const f32x4 bias0 = *(const f32x4 *)(epi + 4 * g), scale0 = *(const f32x4 *)(epi + 16 + 4 * g),
                 shift0 = *(const f32x4 *)(epi + 32 + 4 * g);
-    NSUB(5);
+    ns.sub(NS_SUB_LOADS, lane);
     if (zero_lds) {
         u32x4 z = {0u, 0u, 0u, 0u};
         if constexpr (PP) {
@@ -264,7 +257,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         }
     }
     wave_lds_handover();
-    NSUB(6);
+    ns.sub(NS_SUB_STATE, lane);
     if constexpr (!PP && WIDE_IN) { // (a 16-byte board is decoded from registers below; an 80-byte one through LDS)
         if (!planes && lane == 0) *sst = my_state;
         wave_lds_handover();
@@ -319,7 +312,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         for (int c = 0; c < 4; c++) b[c] = __float_as_uint((float)v[c]) >> 16;
         *(u32x2 *)(X + ((y + 1) * RS + (x + 1)) * SB) = u32x2{b[0] | (b[1] << 16), b[2] | (b[3] << 16)};
     }
-    NSUB(7);
+    ns.sub(NS_SUB_PLANES, lane);
     if constexpr (CACHE) {
         float cv, cpr;
         int cway = 0;
@@ -363,7 +356,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
 #define aH3(t) (aH3 + (t) * TS)
 #define iA(t) (iA0 + (t) * TS)
     wave_lds_handover();
-    NSTAMP(0);
+    ns.section(NS_PROLOGUE, lane);
     f32x4 acc[NT], sk[NT];
     // ---- first conv: K = (tap, 4 planes); inputs in one bf16 plane, weights in three ---------------------------------
     {
@@ -413,7 +406,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         }
     }
     wave_lds_handover();
-    NSTAMP(1);
+    ns.section(NS_CONV0, lane);
     // ---- residual tower ------------------------------------------------------------------------------------------------
     const int R_eff = X3_DBG(2) ? 0 : nd.R;
     const int L = 2 * R_eff;
@@ -710,7 +703,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         else conv_layer(2 * blk + 1, std::true_type{}, std::true_type{});
     }
     (void)L;
-    NSTAMP(2);
+    ns.section(NS_TOWER, lane);
     // ---- heads: the value (1 filter) and policy (2 filters) 1x1 convolutions are one more K = 16 "tap" on the matrix pipe --
     // rows 0..2 of a 16-filter operand, the three plane-concatenated products of tap 8 at the pixel itself -- then BN + ReLU and
     // the spatial sums: lane (g = 0, nn) holds the three head activations of column nn of every tile.  (Round 2 formed them
@@ -758,7 +751,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
         R0 = lane_f32(xs, 16);
         R1 = lane_f32(xs, 32);
     }
-    NSTAMP(3);
+    ns.section(NS_HEAD_CONVS, lane);
     if constexpr (CACHE) { // a miss: its entry again from the board (nothing held in registers through the tower)
         if (centry) {
             ckey = G::cache_key(states[OI(pos0)]);
@@ -769,7 +762,7 @@ __device__ __forceinline__ void net_body_x3(const NetDev &nd, const NetX3 &x3, i
     }
     head_one<G>(nd, R, R0, R1, live ? OI(pos0) : 0, live, game_id, serial, noise, value_out,
                 logits_out, policy_out, pstride, compact, centry, ckey);
-    NSTAMP(4);
+    ns.section(NS_HEAD_TAIL, lane);
 }
 
 #undef aA

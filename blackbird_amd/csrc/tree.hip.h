@@ -19,6 +19,7 @@
 #include "games.hip.h"
 #include "rng.hip.h"
 #include "starts.h"
+#include "stamps.hip.h"
 
 #define NODE_EXPANDED 1
 #define NODE_TERMINAL 2
@@ -143,7 +144,7 @@ struct TreeDev {
     void *eval_cache;
     int eval_cache_log2;
     unsigned long long *eval_cache_ctr;
-    unsigned long long *stamps; // diagnostic build only (BB_STAMPS): [apply, fence, select, levels, waves]
+    unsigned long long *stamps; // diagnostic builds only: STAMP_COPIES x STAMP_WORDS words, what each means is in stamps.hip.h
     // self-play start positions (bb_selfplay_set_starts): n_starts packed states, game lid starts from starts[lid % n_starts];
     // null: G::initial().  Indexed by the engine-wide lid, so a slot-range view carries the pointer as it is.  (Last members:
     // see the note on member order above.)
@@ -495,14 +496,9 @@ __device__ void phase_select(const TreeDev &d, int g, int lane) {
     typename G::State st;
     int flags = 0;
     bool have = false; // st/flags of `cur` already in registers (node created this simulation)
-#ifdef BB_STAMPS
-    long long acc_load = 0, acc_iter = 0;
-#endif
+    IF_STAMPS(long long acc_load = 0, acc_iter = 0;)
     for (int it = 0;; it++) {
-#ifdef BB_STAMPS
-        long long ts0 = clock64();
-        acc_iter++;
-#endif
+        IF_STAMPS(long long ts0 = clock64(); acc_iter++;)
         Node *node = pool + cur;
         // ONE round trip per level: issue every load of the row together, then wait once.
         typename G::State st_l = node->st;
@@ -515,9 +511,7 @@ __device__ void phase_select(const TreeDev &d, int g, int lane) {
         double cPi = node->cP[lane];
         int ci = node->child[lane];
         asm volatile("" ::"v"(flags_l), "v"(mask), "v"(sq), "v"(Ni), "v"(Qi), "v"(cPi), "v"(ci)); // keep them ahead of the branches
-#ifdef BB_STAMPS
-        acc_load += clock64() - ts0;
-#endif
+        IF_STAMPS(acc_load += clock64() - ts0;)
         if (!have) {
             st = st_l;
             flags = flags_l;
@@ -555,14 +549,8 @@ __device__ void phase_select(const TreeDev &d, int g, int lane) {
         depth++;
         cur = child & ~CHILD_TERM_BIT;
     }
-#ifdef BB_STAMPS
-    if (d.stamps && lane == 0) {
-        atomicAdd(&d.stamps[5], (unsigned long long)acc_load);
-        atomicAdd(&d.stamps[6], (unsigned long long)acc_iter);
-        atomicAdd(&d.stamps[7], 1ull);
-    }
-#endif
     if (lane == 0) {
+        IF_STAMPS(stamp_add(d.stamps, TS_ROW_LOAD, acc_load); stamp_add(d.stamps, TS_ITERATIONS, acc_iter); stamp_add(d.stamps, TS_DESCENTS, 1);)
         ((typename G::State *)d.leaf_state)[g] = st;
         d.leaf_game_id[g] = d.first_game_id + (uint32_t)d.game_lid[g];
         d.leaf_serial[g] = cur;
@@ -589,27 +577,19 @@ __global__ void __launch_bounds__(256) k_tree_step(TreeDev d) {
     if (l64 >= d.gpw * S) return;
     int g = wv * d.gpw + l64 / S, lane = l64 % S;
     if (g >= d.n_slots) return;
-#ifdef BB_STAMPS
-    long long t0 = clock64();
-#endif
+    const long long t0 = stamp_clock();
     phase_apply<G>(d, g, lane);
-#ifdef BB_STAMPS
-    long long t1 = clock64();
-#endif
+    const long long t1 = stamp_clock();
     __threadfence_block();
-#ifdef BB_STAMPS
-    long long t2 = clock64();
-#endif
+    const long long t2 = stamp_clock();
     phase_select<G>(d, g, lane);
-#ifdef BB_STAMPS
-    long long t3 = clock64();
-    if ((threadIdx.x & 63) == 0 && d.stamps) {
-        atomicAdd(&d.stamps[0], (unsigned long long)(t1 - t0));
-        atomicAdd(&d.stamps[1], (unsigned long long)(t2 - t1));
-        atomicAdd(&d.stamps[2], (unsigned long long)(t3 - t2));
-        atomicAdd(&d.stamps[4], 1ull);
+    const long long t3 = stamp_clock();
+    if ((threadIdx.x & 63) == 0) {
+        stamp_add(d.stamps, TS_APPLY, t1 - t0);
+        stamp_add(d.stamps, TS_FENCE, t2 - t1);
+        stamp_add(d.stamps, TS_SELECT, t3 - t2);
+        stamp_add(d.stamps, TS_WAVES, 1);
     }
-#endif
 }
 
 template <class G>
@@ -1026,18 +1006,12 @@ struct NoPostHook {
     __device__ __forceinline__ void operator()(int, int) const {}
 };
 template <class G, bool REC = false, class OnPost = NoPostHook>
-__device__ bool async_game(const TreeDev &d, int g, int lane
-#ifdef BB_STAMPS_LIGHT
-                           , int &g_light_loop, int &g_light_levels, int &g_light_load, int &g_light_puct
-#endif
-                           , OnPost on_post = OnPost()) {
+__device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = OnPost(), LevelStamps *light_out = nullptr) {
     using Node = DenseNode<G>;
     constexpr int S = G::S, A = G::A;
     if (d.game_lid[g] < 0) return false;
     Node *pool = (Node *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
-#ifdef BB_STAMPS_LIGHT
-    int lt_in = (int)clock64(), lt_loop = 0, ln_levels = 0, lt_create = 0, lt_puct = 0;
-#endif
+    LevelStamps light; // (diagnostic: empty in the product build, stamps.hip.h)
     if (d.pend_leaf[g] >= 0) {
         if (REC && (d.leaf_flags[g] & LEAF_RECORDED)) phase_apply_rec<G>(d, g, lane);
         else phase_apply<G>(d, g, lane);
@@ -1064,16 +1038,11 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
         // every exit of the loop below pays a three-instruction merge for each of them on every iteration
         enum { F_PARKED = 2, F_LEAF = 4, F_TERM = 8, F_EXPAND = 16, F_OVERFLOW = 32 };
         int fl = 0;
-#ifdef BB_STAMPS_LIGHT
-        int lt_e = (int)clock64();
-#endif
+        IF_STAMPS_LIGHT(int lt_e = (int)clock64();)
         for (;;) {
             if (budget <= 0) { fl |= F_PARKED; break; }
             budget--;
-#ifdef BB_STAMPS_LIGHT
-            ln_levels++;
-            int lt_a = (int)clock64();
-#endif
+            IF_STAMPS_LIGHT(light.levels++; int lt_a = (int)clock64();)
             Node *node = pool + cur;
             typename G::State st_l = node->st;
             int flags_l = node->flags;
@@ -1091,10 +1060,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
                 all_l = node->all;
             }
             asm volatile("" ::"v"(flags_l), "v"(mask), "v"(sq), "v"(Ni), "v"(Qi), "v"(cPi), "v"(ci)); // one wait for the whole row
-#ifdef BB_STAMPS_LIGHT
-            int lt_b = (int)clock64(); // the row has arrived (the asm above made the loads' results live)
-            lt_create += lt_b - lt_a;
-#endif
+            IF_STAMPS_LIGHT(int lt_b = (int)clock64(); light.row_load += lt_b - lt_a;) // the row has arrived (the asm above made the loads' results live)
             st = st_l;
             flags = flags_l;
             if (!(flags & NODE_EXPANDED)) {
@@ -1125,10 +1091,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
             // (float32 evaluators only reach this kernel: a child's WinRate is its float32 Q, child_q)
             int child = ci;
             int a = grp_argmax_puct<S>(Qi, cPi, sq, Ni, lane < A && ((mask >> lane) & 1u), child);
-#ifdef BB_STAMPS_LIGHT
-            asm volatile("" ::"v"(a), "v"(child));
-            lt_puct += (int)clock64() - lt_b;
-#endif
+            IF_STAMPS_LIGHT(asm volatile("" ::"v"(a), "v"(child)); light.puct += (int)clock64() - lt_b;)
             if (lane == 0) path[depth] = ((uint32_t)cur << 6) | ((uint32_t)((flags >> 4) & 3) << 4) | (uint32_t)a;
             if (REC) { // what the backup of this edge will start from
                 if (lane == 0) d.path_all[(size_t)g * G::MAXPATH + depth] = all_l;
@@ -1153,9 +1116,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
             depth++;
             cur = child & ~CHILD_TERM_BIT;
         }
-#ifdef BB_STAMPS_LIGHT
-        lt_loop += (int)clock64() - lt_e;
-#endif
+        IF_STAMPS_LIGHT(light.loop += (int)clock64() - lt_e;)
         if (lane == 0) {
             d.resume_cur[g] = (fl & F_PARKED) ? cur : -1;
             d.resume_depth[g] = (fl & F_PARKED) ? depth : 0;
@@ -1184,13 +1145,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane
         posted = true;
         break;
     }
-#ifdef BB_STAMPS_LIGHT
-    g_light_loop = lt_loop;
-    g_light_load = lt_create;
-    g_light_puct = lt_puct;      // read back by the caller, which reduces over the wave (mega2.hip.h)
-    g_light_levels = ln_levels;
-    (void)lt_in;
-#endif
+    if (light_out) *light_out = light; // read back by the caller, which reduces over the wave (level_stamps_flush)
     if (lane == 0 && sims_done) {
         uint64_t *c = d.ctr + (size_t)g * 8;
         c[0] += (uint64_t)sims_done;
@@ -1207,23 +1162,9 @@ __global__ void __launch_bounds__(256) k_tree_async(TreeDev d, int round) {
     int wv = t >> 6, l64 = t & 63;
     int g = wv * d.gpw + l64 / S, lane = l64 % S;
     bool live = l64 < d.gpw * S && g < d.n_slots;
-#ifdef BB_STAMPS_LIGHT
-    int ll = 0, lv = 0, lld = 0, lpu = 0;
-    bool posted = live ? async_game<G>(d, g, lane, ll, lv, lld, lpu) : false;
-    {
-        int m = lv;
-        for (int o = 32; o; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
-        unsigned long long who = __ballot(live && lane == 0 && lv == m);
-        if (who && l64 == (int)__builtin_ctzll(who) && d.stamps) {
-            atomicAdd(&d.stamps[6], (unsigned long long)ll);
-            atomicAdd(&d.stamps[7], (unsigned long long)lv);
-            atomicAdd(&d.stamps[11], (unsigned long long)lld);
-            atomicAdd(&d.stamps[12], (unsigned long long)lpu);
-        }
-    }
-#else
-    bool posted = live ? async_game<G>(d, g, lane) : false;
-#endif
+    LevelStamps light;
+    bool posted = live ? async_game<G>(d, g, lane, NoPostHook(), &light) : false;
+    level_stamps_flush(d.stamps, light, live && lane == 0, l64);
     // wave-aggregated append to the round's compacted leaf list
     unsigned long long m = __ballot(posted && lane == 0);
     if (t == 0) d.post_count[(round + 2) & 3] = 0; // recycled two rounds from now

@@ -56,17 +56,9 @@ struct DCEdges { // per-slot edge pool, stride edge_cap
 
 // The wave's LDS scratch: the dense float32 image of the masked policy (4032 entries; the values ARE float32 -- the
 // float64 of the reference's `policy * LegalActions` is formed when they are summed) + the compact move list.
-#ifdef BB_STAMPS
-// diagnostic build: cycle stamps accumulate in the wave's LDS scratch (16 words past the policy image) and are flushed
-// once when the kernel ends, spread over 64 copies -- atomics inside the timed sections would sit in front of every
-// later s_waitcnt and a thousand waves on one address serialise in L2
-#define DC_STAMP_OFF 5136 // past the policy image and its 112 floats of sum scratch AND past the network's activations, which share the scratch in mega_dc.hip.h
-#define DC_LDS_FLOATS (DC_STAMP_OFF + 32)
-#define DST(i, v) do { if (lane == 0) ((unsigned long long *)(lds + DC_STAMP_OFF))[i] += (unsigned long long)(v); } while (0)
-#else
-#define DC_LDS_FLOATS (4032 + 112) // the policy image + dc_np_sum's scratch (8 + 48 doubles)
-#define DST(i, v) do {} while (0)
-#endif
+// The policy image + dc_np_sum's scratch (8 + 48 doubles); a diagnostic build keeps its stamp words behind them (stamps.hip.h:
+// dst_add) -- a thousand waves' atomics on one address would serialise in L2, so they are flushed once when the kernel ends.
+constexpr int DC_LDS_FLOATS = kStamps ? DC_STAMP_OFF + 2 * STAMP_WORDS : 4032 + 112;
 
 // What the one-wave-per-game kernel hands from its network phase to its tree phase instead of the evaluator mailbox in
 // global memory (mega_dc.hip.h): the evaluation reduced to five numbers (net.hip.h: WideHead) and the policy-head weights
@@ -275,9 +267,7 @@ __device__ bool dc_expand(const TreeDev &d, const DCEdges &E, int g, DCNode *nod
                           const int8_t *board_mem, const float *policy, const DCHeadLocal *hl, uint32_t gid, int lane,
                           float *lds, int node_idx, int node_flags, int &used) {
     const bool priors = policy != nullptr || hl != nullptr; // evaluator priors (dense row in memory, or the compact head)
-#ifdef BB_STAMPS
-    long long x0 = clock64();
-#endif
+    IF_STAMPS(long long x0 = clock64();)
     // move generation: lane = from-square; occupancy by two ballots, targets by bit operations (games.hip.h)
     const int piece = board_mem[lane];
     const uint64_t white = __ballot(piece > 0), black = __ballot(piece < 0);
@@ -290,10 +280,7 @@ __device__ bool dc_expand(const TreeDev &d, const DCEdges &E, int g, DCNode *nod
     // whole edge run.  A position with more legal moves is refused like a full edge pool -- the caller counts the
     // simulation in `overflow` and the node stays unexpanded.
     if (total > DragonChess::S || off + total > E.edge_cap) return false;
-#ifdef BB_STAMPS
-    long long e0 = clock64(), e1 = e0, e2 = e0;
-    if (priors) DST(9, e0 - x0);
-#endif
+    IF_STAMPS(long long e0 = clock64(), e1 = e0, e2 = e0; if (priors) dst_add(lds, lane, DST_EXP_MOVEGEN, e0 - x0);)
     // The moves are dealt evenly over the lanes (move j of the from-square-major enumeration -> lane j & 63): one
     // policy load, one Beta draw and one edge per lane instead of a serial loop over the busiest square's moves.
     constexpr int MPL = (DragonChess::S + 63) / 64; // moves per lane: total <= S
@@ -336,9 +323,7 @@ __device__ bool dc_expand(const TreeDev &d, const DCEdges &E, int g, DCNode *nod
                 lds[mya[i]] = p; // float32 * float64 legal mask (1.0): widened when summed
             }
         }
-#ifdef BB_STAMPS
-        e1 = clock64();
-#endif
+        IF_STAMPS(e1 = clock64();)
         __threadfence_block();
         {   // OR the lanes' leaf bits together (DPP inside the rows, row broadcasts across them, lane 63 has the wave's)
             unsigned lo = (unsigned)leaves, hi = (unsigned)(leaves >> 32);
@@ -349,9 +334,7 @@ __device__ bool dc_expand(const TreeDev &d, const DCEdges &E, int g, DCNode *nod
             leaves = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)hi, 63) << 32) | (unsigned)__builtin_amdgcn_readlane((int)lo, 63);
         }
         tot = dc_np_sum(lds, leaves, (double *)(lds + 4032), lane);
-#ifdef BB_STAMPS
-        e2 = clock64();
-#endif
+        IF_STAMPS(e2 = clock64();)
     }
     size_t base = (size_t)(g + d.pool_g0) * E.edge_cap + off;
 #pragma unroll
@@ -376,14 +359,7 @@ __device__ bool dc_expand(const TreeDev &d, const DCEdges &E, int g, DCNode *nod
         E.used[g] = off + total;
     }
     used = off + total;
-#ifdef BB_STAMPS
-    if (priors) {
-        DST(5, e1 - e0);
-        DST(6, e2 - e1);
-        DST(7, clock64() - e2);
-        DST(8, 1);
-    }
-#endif
+    IF_STAMPS(if (priors) { dst_add(lds, lane, DST_EXP_GATHER, e1 - e0); dst_add(lds, lane, DST_EXP_SUM, e2 - e1); dst_add(lds, lane, DST_EXP_EDGES, clock64() - e2); dst_add(lds, lane, DST_EXPANSIONS, 1); })
     return true;
 }
 
@@ -415,9 +391,7 @@ __device__ void dc_phase_apply(const TreeDev &d, const DCEdges &E, int g, int la
     // One wave per game and one wave per SIMD: this step is a chain of dependent HBM round trips (2-3 us each on
     // these sparsely touched pools), so every word that does not depend on another load is requested up front, and
     // the statistics the backup will update are fetched BEFORE the expansion, whose work then hides their latency.
-#ifdef BB_STAMPS
-    const long long a_in = clock64();
-#endif
+    IF_STAMPS(const long long a_in = clock64();)
     const int leaf = dc_ctl<SH>(d.pend_leaf)[g];
     const int pend_exp = dc_ctl<SH>(d.pend_expand)[g];
     const float v = hl ? hl->h.value : dc_ctl<SH>(d.eval_value)[g];
@@ -435,10 +409,7 @@ __device__ void dc_phase_apply(const TreeDev &d, const DCEdges &E, int g, int la
     }
     int used = dc_ctl<SH>(E.used)[g];
     if (leaf < 0) return;
-#ifdef BB_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const long long a_r1 = clock64();
-#endif
+    IF_STAMPS(stamp_wait_loads(); const long long a_r1 = clock64();)
     DCNode *pool = (DCNode *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
     DCNode *node = pool + leaf;
     const DCState *leaf_st = dc_ctl<SH>((const DCState *)d.leaf_state) + g;
@@ -455,14 +426,7 @@ __device__ void dc_phase_apply(const TreeDev &d, const DCEdges &E, int g, int la
         my_all = my_nd->all;
     }
     const int leaf_flags = node->flags;
-#ifdef BB_STAMPS
-    {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        long long a_r2 = clock64();
-        DST(3, a_r2 - a_r1);  // second round of loads
-        DST(10, a_r1 - a_in); // entry -> first round complete (tools/dc_stamps.py)
-    }
-#endif
+    IF_STAMPS(stamp_wait_loads(); dst_add(lds, lane, DST_APPLY_LOADS2, clock64() - a_r1); dst_add(lds, lane, DST_APPLY_LOADS1, a_r1 - a_in);) // second round of loads; entry -> first round complete (tools/dc_stamps.py)
     if (pend_exp) {
         uint32_t gid = d.first_game_id + (uint32_t)lid;
         const int used0 = used;
@@ -483,9 +447,6 @@ __device__ void dc_phase_apply(const TreeDev &d, const DCEdges &E, int g, int la
         if (player != prev) v01 = 1.0f - v01;
     }
     float vflip = 1.0f - v01;
-#ifdef BB_STAMPS
-    long long b0 = clock64();
-#endif
     if (on_path) {
         int pl = (int)(pe0 >> 30);
         int n = my_n + 1, all = my_all + 1;
@@ -534,9 +495,6 @@ __device__ void dc_phase_apply(const TreeDev &d, const DCEdges &E, int g, int la
         if (pp) dc_ctl<SH>(d.root_W)[g] = root_w + ((pp == prev) ? v01 : vflip);
         dc_ctl<SH>(d.pend_leaf)[g] = -1;
     }
-#ifdef BB_STAMPS
-    (void)b0;
-#endif
 }
 
 // create the child reached by edge e (absolute) of parent; lane 0 writes
@@ -619,13 +577,7 @@ __device__ void dc_phase_select(const TreeDev &d, const DCEdges &E, int g, int l
         t_c6 = ctr[6];
     }
     if (lid < 0 || sims_left <= 0) return;
-#ifdef BB_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    long long q0 = clock64(), q_pre = 0, q_hdr = 0, q_edge = 0, q_cmp = 0, q_rest = 0, q_lv = 0;
-#define QS(acc) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); long long _q = clock64(); acc += _q - q0; q0 = _q; } while (0)
-#else
-#define QS(acc) do {} while (0)
-#endif
+    IF_STAMPS(StampSections qs; long long q_pre = 0, q_hdr = 0, q_edge = 0, q_cmp = 0, q_rest = 0, q_lv = 0;) // starts once the first round of loads has arrived; every lap() drains the memory pipeline
     DCNode *pool = (DCNode *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
     uint32_t *pn = dc_ctl<SH>(d.path) + (size_t)g * DragonChess::MAXPATH;
     uint32_t *pe = dc_ctl<SH>(E.path_edge) + (size_t)g * DragonChess::MAXPATH;
@@ -652,12 +604,7 @@ __device__ void dc_phase_select(const TreeDev &d, const DCEdges &E, int g, int l
         int n_edges = hd.n_edges, edge_off = hd.edge_off;
         double sq = hd.sq;
         const bool pre_ok = hint_n > 0 && hint_n == n_edges && hint_off == (uint32_t)edge_off;
-#ifdef BB_STAMPS
-        asm volatile("" ::"v"(n_edges), "v"(edge_off), "v"(sq), "v"(flags));
-        if (it == 0) QS(q_pre); else QS(q_rest);
-        q_lv++;
-        QS(q_hdr);
-#endif
+        IF_STAMPS(asm volatile("" ::"v"(n_edges), "v"(edge_off), "v"(sq), "v"(flags)); (it == 0 ? q_pre : q_rest) += qs.lap(); q_lv++; q_hdr += qs.lap();)
         bool have_st = have;
         have = false;
         if (fixed && it >= d.max_depth) {
@@ -684,10 +631,7 @@ __device__ void dc_phase_select(const TreeDev &d, const DCEdges &E, int g, int l
         int bi = -1, bchild = CHILD_NONE, bact = 0;
         size_t base = ebase + edge_off;
         if (!pre_ok) pre = dc_edge_load(E.e + base + min(lane, max(n_edges, 1) - 1)); // (root, a node whose incoming edge carries no hint)
-#ifdef BB_STAMPS
-        asm volatile("" ::"v"(pre.N), "v"(pre.cP));
-        QS(q_edge);
-#endif
+        IF_STAMPS(asm volatile("" ::"v"(pre.N), "v"(pre.cP)); q_edge += qs.lap();)
         int bhint = 0; // the winner's c_edges, c_off
         uint32_t bhoff = 0u;
         bool picked = false;
@@ -742,7 +686,7 @@ __device__ void dc_phase_select(const TreeDev &d, const DCEdges &E, int g, int l
         }
         hint_n = bhint;
         hint_off = bhoff;
-        QS(q_cmp);
+        IF_STAMPS(q_cmp += qs.lap();)
         if (depth >= DragonChess::MAXPATH) { overflow = 1; if (!have_st) st = dc_lane_load(&node->st, lane); break; }
         int child = bchild;
         { // the path stays in registers (lane k <-> depth k) until the descent is over: a store per level would put
@@ -816,16 +760,8 @@ __device__ void dc_phase_select(const TreeDev &d, const DCEdges &E, int g, int l
         ctr[3] = t_c3 + (uint64_t)term_leaf;
         ctr[6] = t_c6 + (uint64_t)overflow;
     }
-#ifdef BB_STAMPS
-    QS(q_rest);
-    DST(11, q_pre);
-    DST(12, q_hdr);
-    DST(13, q_edge);
-    DST(14, q_cmp);
-    DST(15, q_rest);
-    DST(1, q_lv);
-#endif
-#undef QS
+    IF_STAMPS(q_rest += qs.lap(); dst_add(lds, lane, DST_SEL_FIRST, q_pre); dst_add(lds, lane, DST_SEL_NODE, q_hdr); dst_add(lds, lane, DST_SEL_EDGE, q_edge);)
+    IF_STAMPS(dst_add(lds, lane, DST_SEL_PUCT, q_cmp); dst_add(lds, lane, DST_SEL_REST, q_rest); dst_add(lds, lane, DST_LEVELS, q_lv);)
 }
 
 __global__ void __launch_bounds__(256) k_dc_tree_step(TreeDev d, DCEdges E) {
@@ -833,26 +769,16 @@ __global__ void __launch_bounds__(256) k_dc_tree_step(TreeDev d, DCEdges E) {
     int g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (g >= d.n_slots) return;
     float *lds = lds_all[wv];
-#ifdef BB_STAMPS
-    if (lane < 16) ((unsigned long long *)(lds + DC_STAMP_OFF))[lane] = 0;
-    __threadfence_block();
-    long long t0 = clock64();
-#endif
+    dst_zero(lds, lane);
+    const long long t0 = stamp_clock();
     dc_phase_apply<false, true>(d, E, g, lane, lds);
-#ifdef BB_STAMPS
-    long long t1 = clock64();
-#endif
+    const long long t1 = stamp_clock();
     __threadfence_block();
     dc_phase_select(d, E, g, lane, lds);
-#ifdef BB_STAMPS
-    long long t2 = clock64();
-    if (lane == 0 && d.stamps) {
-        DST(0, t1 - t0);
-        DST(2, t2 - t1);
-        DST(4, 1);
-        for (int i = 0; i < 16; i++) atomicAdd(&d.stamps[(size_t)(g & 63) * 16 + i], ((unsigned long long *)(lds + DC_STAMP_OFF))[i]);
-    }
-#endif
+    dst_add(lds, lane, DST_SELECT, stamp_clock() - t1);
+    dst_add(lds, lane, DST_APPLY, t1 - t0);
+    dst_add(lds, lane, DST_STEPS, 1);
+    if (lane == 0) dst_flush(d.stamps, lds, g);
 }
 
 __global__ void __launch_bounds__(256) k_dc_tree_apply(TreeDev d, DCEdges E) {
