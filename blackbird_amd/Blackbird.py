@@ -296,7 +296,8 @@ def TrainWithExamples(model, batchSize, learningRate, epochs=1, teacher=None, mo
     model.Conn.PutModel(model.Game.GameType, model.Name, model.Version)
 
 
-def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=None, augment=False, merge=False):
+def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=None, augment=False, merge=False,
+                            fused=False):
     """TrainWithExamples (Blackbird.py:271-312) on examples that never left the GPU: `examples` (a training.DeviceExamples),
     or else what GenerateTrainingSamples kept for the model's current Version (model.KeepDeviceExamples).  The same steps
     in the same order -- the epoch's order drawn from numpy's generator as there (the same seed visits the same examples in
@@ -312,7 +313,13 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
     merge (an extension: the reference trains on every stored row): the copies of a position among the examples -- the start
     position once per game, the openings, transpositions -- become one row with the pooled search policy (summed visits / summed
     totals) and the mean outcome (examples.merged(): bb_examples_merge, Connect4 and TicTacToe); the epoch's order is drawn as
-    before, over the merged rows, and augment composes with it.  With merge=False nothing changes.  DragonChess: ValueError."""
+    before, over the merged rows, and augment composes with it.  With merge=False nothing changes.  DragonChess: ValueError.
+
+    fused (on request only): with the hip training backend (NetworkConfig['training']['backend'] = 'hip') and merge=False the
+    whole epoch is one call, HipTrainer.epoch_records (bb_trainer_epoch): the step's kernels read the records themselves, no
+    batch tensor is formed and Python is not visited per batch -- the same steps bit for bit, numpy's generator consumed alike.
+    It is not the default because it measured no faster on the MI355X than the per-batch loop, whose launches already queue
+    ahead of the GPU (README, training row).  merge=True and the PyTorch trainer take the per-batch loop whatever it says."""
     from .training import epoch_order
     if merge and (model.Game.GAME_ID if examples is None else examples.game) not in _lib.GRID:
         raise ValueError('merge=True covers Connect4 and TicTacToe: a DragonChess position is keyed by its 64-byte board, castle '
@@ -334,10 +341,13 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
     nBatches = len(order) // batchSize
     if nBatches:
         trainer = model._trainer_for(examples.info.C)
-        for i in range(nBatches):
-            rows = slice(i * batchSize, (i + 1) * batchSize)
-            boards, value, policy = examples._batch(order[rows], None if syms is None else syms[rows])
-            trainer.step_tensors(boards, value, policy, learningRate)
+        if fused and not merge and hasattr(trainer, 'epoch_records'):
+            trainer.epoch_records(examples, order, batchSize, learningRate, sym=syms)
+        else:
+            for i in range(nBatches):
+                rows = slice(i * batchSize, (i + 1) * batchSize)
+                boards, value, policy = examples._batch(order[rows], None if syms is None else syms[rows])
+                trainer.step_tensors(boards, value, policy, learningRate)
         bad = examples.bad()  # (one look per epoch: it waits for the GPU)
         if bad:
             raise _lib.BlackbirdHipError('%d malformed example records were met in training' % bad)

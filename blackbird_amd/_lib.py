@@ -30,7 +30,8 @@ EXPORTS = (
     "bb_examples_to_batch", "bb_examples_to_batch_sym", "bb_game_symmetries",
     "bb_examples_merge_workspace", "bb_examples_merge", "bb_examples_merged_to_batch",
     "bb_arena_create", "bb_arena_begin", "bb_arena_step", "bb_arena_status", "bb_arena_fetch", "bb_arena_destroy",
-    "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_param_count", "bb_trainer_read",
+    "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_epoch", "bb_trainer_param_count",
+    "bb_trainer_read",
 )
 
 
@@ -146,6 +147,7 @@ def lib():
     L.bb_trainer_create.argtypes = [C.POINTER(TrainConfig), C.POINTER(NetWeights), C.POINTER(vp)]
     L.bb_trainer_destroy.argtypes = [vp]
     L.bb_trainer_step.argtypes = [vp, ip, vp, vp, vp, vp, C.c_double, ip, vp, vp]
+    L.bb_trainer_epoch.argtypes = [vp, ip, vp, ip, ip, vp, vp, vp, C.c_double, vp, vp, vp]
     L.bb_trainer_param_count.argtypes = [vp, C.POINTER(C.c_int64)]
     L.bb_trainer_read.argtypes = [vp, ip, vp, C.c_int64]
     for name in EXPORTS:
@@ -388,6 +390,17 @@ def trainer_step(h, n, boards, value, policy, noise=None, lr=0.0, apply=True, lo
     check(lib().bb_trainer_step(h, int(n), C.c_void_p(boards or None), C.c_void_p(value or None), C.c_void_p(policy or None),
                                 C.c_void_p(noise or None), float(lr), int(bool(apply)), C.c_void_p(loss_out or None),
                                 C.c_void_p(stream or None)))
+
+
+def trainer_epoch(h, n_records, records, n_batches, batch, order=None, sym=None, noise=None, lr=0.0, loss_out=None, bad=None,
+                  stream=0):
+    """bb_trainer_epoch: n_batches optimiser steps of `batch` rows each straight from the device records -- row j of batch i is
+    record order[i * batch + j] (None: record i * batch + j) under symmetry sym[i * batch + j] (None: the identity).  records,
+    order (int64), sym (uint8), noise (float32 [n_batches, A]; None: drawn), loss_out (float32 [n_batches, 4]) and bad (int32
+    [1]) are DEVICE addresses (ints; None/0 = absent).  Asynchronous."""
+    p = lambda a: C.c_void_p(a or None)  # noqa: E731
+    check(lib().bb_trainer_epoch(h, int(n_records), p(records), int(n_batches), int(batch), p(order), p(sym), p(noise), float(lr),
+                                 p(loss_out), p(bad), p(stream)))
 
 
 def trainer_param_count(h):

@@ -2170,9 +2170,10 @@ static void trainer_free(bb_trainer *t) {
 }
 
 template <class G>
-static int trainer_lds(bb_trainer *t) {
+static int trainer_lds(bb_trainer *t) { // (the same dynamic LDS whichever source feeds the workgroup)
     t->lds_bytes = (size_t)train_lds_floats<G>(t->lay.R) * sizeof(float);
-    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
+    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainTensors<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
+    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainRecords<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
     return BB_OK;
 }
 
@@ -2276,6 +2277,27 @@ extern "C" int bb_trainer_destroy(bb_trainer *t) {
     return BB_OK;
 }
 
+// One step's three launches on `st`, the batch read through `src` (train.hip.h): what bb_trainer_step and every batch of
+// bb_trainer_epoch enqueue.  Host state moves as the launches are made: the noise counter, Adam's step count and lr_t.
+template <class G, class Src>
+static void trainer_launch(bb_trainer *t, int n, const Src &src, const float *noise, double lr, int apply, float *loss_out, hipStream_t st) {
+    const TrainLayout &l = t->lay;
+    const float eps = t->cfg.epsilon;
+    k_train_prep<G, Src><<<1, BB_TRAIN_THREADS, 0, st>>>(n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed, t->calls,
+                                                         t->aux);
+    t->calls++;
+    k_train_grad<G, Src><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, src, n, eps, t->slabs, t->le, t->lp);
+    float rate = (float)lr;
+    if (apply) {
+        t->t++;
+        if (t->cfg.optimizer == BB_OPT_ADAM) // AdamOptimizer's lr_t (beta1 0.9, beta2 0.999)
+            rate = (float)(lr * std::sqrt(1.0 - std::pow(0.999, (double)t->t)) / (1.0 - std::pow(0.9, (double)t->t)));
+    }
+    k_train_apply<<<nblk((size_t)l.count, BB_TRAIN_THREADS) + 1, BB_TRAIN_THREADS, 0, st>>>(
+        l.count, n, l.n_l2, t->slabs, t->kind, t->prm, t->slot_m, t->slot_v, t->grads, t->cfg.optimizer, rate, t->cfg.momentum,
+        apply != 0, t->le, t->lp, t->aux, t->loss, loss_out);
+}
+
 extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const float *value, const float *policy, const float *noise,
                                double lr, int apply, float *loss_out, void *stream) {
     if (!t) return fail(BB_ERR_ARG, "null trainer");
@@ -2287,25 +2309,40 @@ extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const 
     int dev = -1;
     HIPCHK(hipGetDevice(&dev));
     if (dev != t->cfg.device) return fail(BB_ERR_ARG, "the trainer lives on device %d, the current device is %d", t->cfg.device, dev);
-    hipStream_t st = (hipStream_t)stream;
-    const TrainLayout &l = t->lay;
-    const float eps = t->cfg.epsilon;
-    k_train_prep<<<1, BB_TRAIN_THREADS, 0, st>>>(t->A, n, l.count, l.n_l2, t->prm, t->kind, policy, noise, eps, t->cfg.alpha, t->cfg.seed,
-                                                 t->calls, t->aux);
-    t->calls++;
     if (t->cfg.game == BB_GAME_CONNECT4)
-        k_train_grad<Connect4><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, boards, value, n, eps, t->slabs, t->le, t->lp);
+        trainer_launch<Connect4>(t, n, TrainTensors<Connect4>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream);
     else
-        k_train_grad<TicTacToe><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, boards, value, n, eps, t->slabs, t->le, t->lp);
-    float rate = (float)lr;
-    if (apply) {
-        t->t++;
-        if (t->cfg.optimizer == BB_OPT_ADAM) // AdamOptimizer's lr_t (beta1 0.9, beta2 0.999)
-            rate = (float)(lr * std::sqrt(1.0 - std::pow(0.999, (double)t->t)) / (1.0 - std::pow(0.9, (double)t->t)));
-    }
-    k_train_apply<<<nblk((size_t)l.count, BB_TRAIN_THREADS) + 1, BB_TRAIN_THREADS, 0, st>>>(
-        l.count, n, l.n_l2, t->slabs, t->kind, t->prm, t->slot_m, t->slot_v, t->grads, t->cfg.optimizer, rate, t->cfg.momentum,
-        apply != 0, t->le, t->lp, t->aux, t->loss, loss_out);
+        trainer_launch<TicTacToe>(t, n, TrainTensors<TicTacToe>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return BB_OK;
+}
+
+template <class G>
+static void trainer_epoch(bb_trainer *t, int n_records, const uint8_t *records, int n_batches, int batch, const int64_t *order,
+                          const uint8_t *sym, const float *noise, double lr, float *loss_out, int32_t *bad_out, hipStream_t st) {
+    for (int i = 0; i < n_batches; i++)
+        trainer_launch<G>(t, batch, TrainRecords<G>{n_records, records, order, sym, (size_t)i * (size_t)batch, bad_out},
+                          noise ? noise + (size_t)i * t->A : nullptr, lr, 1, loss_out ? loss_out + (size_t)i * 4 : nullptr, st);
+}
+
+extern "C" int bb_trainer_epoch(bb_trainer *t, int n_records, const void *records, int n_batches, int batch, const int64_t *order,
+                                const uint8_t *sym, const float *noise, double lr, float *loss_out, int32_t *bad_out, void *stream) {
+    if (!t) return fail(BB_ERR_ARG, "null trainer");
+    if (n_batches < 0 || n_records < 0) return fail(BB_ERR_ARG, "negative count (%d batches, %d records)", n_batches, n_records);
+    if (batch <= 0 || batch > t->cfg.max_batch)
+        return fail(BB_ERR_ARG, "batches of %d examples; the trainer takes 1..%d (max_batch)", batch, t->cfg.max_batch);
+    if (!std::isfinite(lr)) return fail(BB_ERR_ARG, "the learning rate is not finite");
+    if ((uintptr_t)order % sizeof(int64_t) || ((uintptr_t)noise | (uintptr_t)loss_out | (uintptr_t)bad_out) % 4)
+        return fail(BB_ERR_ARG, "order must be 8-byte aligned, noise, loss_out and bad_out 4-byte aligned");
+    if (n_batches == 0) return BB_OK;
+    if (!records || (uintptr_t)records % 16) return fail(BB_ERR_ARG, "records must be a 16-byte aligned device pointer");
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev != t->cfg.device) return fail(BB_ERR_ARG, "the trainer lives on device %d, the current device is %d", t->cfg.device, dev);
+    if (t->cfg.game == BB_GAME_CONNECT4)
+        trainer_epoch<Connect4>(t, n_records, (const uint8_t *)records, n_batches, batch, order, sym, noise, lr, loss_out, bad_out, (hipStream_t)stream);
+    else
+        trainer_epoch<TicTacToe>(t, n_records, (const uint8_t *)records, n_batches, batch, order, sym, noise, lr, loss_out, bad_out, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }

@@ -17,54 +17,91 @@
 // records are read in 16-byte units (headers and states whole); they are multiples of 16 bytes (bb_examples_fetch_games)
 static_assert(sizeof(ExampleHdr) == 16, "example header is one 16-byte load");
 
+// One row of a batch from the dense games' records, checked: record index[k] (nullptr: record k) under symmetry sym[k] (nullptr:
+// the identity).  The header and the state are one 16-byte load each, made only once the index and the symmetry have passed;
+// a caller that uses one of them only leaves the other load dead.  !ok: a malformed row -- s is 0, nothing was read, and
+// example_plane, example_share and example_value answer 0.  What k_examples_to_batch writes and what the training kernels
+// read straight from the records (train.hip.h) are these functions, so the two cannot drift apart.
+template <class G>
+struct ExampleRow {
+    static constexpr int PL = G::H * G::W * G::C;
+    static constexpr size_t OFF_VIS = sizeof(ExampleHdr) + sizeof(typename G::State), EB = OFF_VIS + 4 * G::S;
+    static_assert(sizeof(typename G::State) == 16, "grid state is one 16-byte load");
+    static_assert(EB % 16 == 0, "records are multiples of 16 bytes");
+    static_assert(G::A <= G::S, "a dense record holds the visits of every action");
+    bool ok;
+    int s; // (only a symmetry of the game reaches the maps)
+    ExampleHdr h;
+    typename G::State st;
+    const uint8_t *rec;
+};
+
+template <class G>
+__device__ __forceinline__ ExampleRow<G> example_row(int n_records, const uint8_t *records, const int64_t *index, const uint8_t *sym,
+                                                     size_t k) {
+    using Sym = Symmetries<G::GID>;
+    static_assert(Sym::H == G::H && Sym::W == G::W && Sym::A == G::A, "symmetry.h describes this game");
+    const int64_t r = index ? index[k] : (int64_t)k;
+    const uint32_t sk = sym ? sym[k] : 0u;
+    ExampleRow<G> row = {};
+    row.ok = r >= 0 && r < (int64_t)n_records && sk < (uint32_t)Sym::NSYM;
+    row.s = row.ok ? (int)sk : 0;
+    row.rec = records + (size_t)(row.ok ? r : 0) * ExampleRow<G>::EB;
+    if (row.ok) {
+        const uint4 h4 = ((const uint4 *)row.rec)[0], s4 = ((const uint4 *)row.rec)[1];
+        __builtin_memcpy(&row.h, &h4, 16);
+        __builtin_memcpy(&row.st, &s4, 16);
+        row.ok = row.h.n_children <= (uint32_t)G::S;
+    }
+    return row;
+}
+
+// element e of the row's planes [H][W][C]: a thread finds the cell its element comes FROM through the symmetry's inverse map
+template <class G>
+__device__ __forceinline__ float example_plane(const ExampleRow<G> &row, int e) {
+    const int cell = Symmetries<G::GID>::cell_inv(row.s, e / G::C); // the cell whose planes land on cell e / C
+    int8_t v[G::C] = {};
+    if (row.ok) G::encode_cell(row.st, cell / G::W, cell % G::W, v);
+    return (float)v[e % G::C];
+}
+
+// entry a of the row's policy label: divided in double and rounded once; zeros when total == 0 (the terminal example)
+template <class G>
+__device__ __forceinline__ float example_share(const ExampleRow<G> &row, int a) {
+    const int from = Symmetries<G::GID>::action_inv(row.s, a); // (both < A <= S: inside the record's visits)
+    float p = 0.f;
+    if (row.ok && row.h.total) p = (float)((double)((const uint32_t *)(row.rec + ExampleRow<G>::OFF_VIS))[from] / (double)row.h.total);
+    return p;
+}
+
+template <class G>
+__device__ __forceinline__ float example_value(const ExampleRow<G> &row) {
+    return row.ok ? (float)row.h.z : 0.f;
+}
+
 // Dense games (slot i == action i): one thread per output element, rows back to back -- a 256-thread block covers a few
 // records (Connect4: 134 floats per row, TicTacToe: 37), a wave's stores are contiguous within each of the three outputs.
-// The header and the state are one 16-byte load each; the lanes of a row read the same addresses (one fetch, broadcast).
-// A thread finds the cell or the action its element comes FROM through the symmetry's inverse maps: the stores stay as they are.
+// The lanes of a row read the same addresses (one fetch, broadcast); the stores stay as they are under a symmetry.
 // One kernel with and without sym: the only branch is the uniform one around the load of sym[k], the maps run with 0 otherwise.
 template <class G>
 __global__ void __launch_bounds__(256) k_examples_to_batch(int n_records, const uint8_t *records, int n, const int64_t *index,
                                                            const uint8_t *sym, float *boards, float *policy, float *value,
                                                            int32_t *bad) {
-    using Sym = Symmetries<G::GID>;
-    static_assert(Sym::H == G::H && Sym::W == G::W && Sym::A == G::A, "symmetry.h describes this game");
-    static_assert(sizeof(typename G::State) == 16, "grid state is one 16-byte load");
-    constexpr int PL = G::H * G::W * G::C, E = PL + G::A + 1;
-    constexpr size_t OFF_VIS = sizeof(ExampleHdr) + sizeof(typename G::State), EB = OFF_VIS + 4 * G::S;
-    static_assert(EB % 16 == 0, "records are multiples of 16 bytes");
-    static_assert(G::A <= G::S, "a dense record holds the visits of every action");
+    constexpr int PL = ExampleRow<G>::PL, E = PL + G::A + 1;
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (size_t)n * E) return;
     const size_t k = t / E;
     const int e = (int)(t % E);
-    const int64_t r = index ? index[k] : (int64_t)k;
-    const uint32_t sk = sym ? sym[k] : 0u;
-    bool ok = r >= 0 && r < (int64_t)n_records && sk < (uint32_t)Sym::NSYM;
-    const int s = ok ? (int)sk : 0; // (only a symmetry of the game reaches the maps)
-    ExampleHdr h = {};
-    typename G::State st = {};
-    const uint8_t *rec = records + (size_t)(ok ? r : 0) * EB;
-    if (ok) {
-        const uint4 h4 = ((const uint4 *)rec)[0], s4 = ((const uint4 *)rec)[1];
-        __builtin_memcpy(&h, &h4, 16);
-        __builtin_memcpy(&st, &s4, 16);
-        ok = h.n_children <= (uint32_t)G::S;
-    }
+    const ExampleRow<G> row = example_row<G>(n_records, records, index, sym, k);
     if (e < PL) {
         if (!boards) return;
-        const int cell = Sym::cell_inv(s, e / G::C); // the cell whose planes land on cell e / C
-        int8_t v[G::C] = {};
-        if (ok) G::encode_cell(st, cell / G::W, cell % G::W, v);
-        boards[k * PL + e] = (float)v[e % G::C];
+        boards[k * PL + e] = example_plane<G>(row, e);
     } else if (e < PL + G::A) {
         if (!policy) return;
-        const int a = e - PL, from = Sym::action_inv(s, a); // (both < A <= S: inside the record's visits)
-        float p = 0.f;
-        if (ok && h.total) p = (float)((double)((const uint32_t *)(rec + OFF_VIS))[from] / (double)h.total);
-        policy[k * G::A + a] = p;
+        policy[k * G::A + (e - PL)] = example_share<G>(row, e - PL);
     } else { // the row's last element: z, and the row's word in the count of rejected rows
-        if (value) value[k] = ok ? (float)h.z : 0.f;
-        if (!ok && bad) atomicAdd(bad, 1);
+        if (value) value[k] = example_value<G>(row);
+        if (!row.ok && bad) atomicAdd(bad, 1);
     }
 }
 

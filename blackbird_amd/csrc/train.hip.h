@@ -1,5 +1,5 @@
 // train.hip.h -- one optimiser step of Network.train (NetworkFactory.py:185-245) for the 16-filter networks of the dense
-// games, as three launches (bb_trainer_step):
+// games, as three launches (bb_trainer_step; bb_trainer_epoch: the same three per batch, for every batch of an epoch):
 //   k_train_prep   one workgroup: the step's Beta noise (caller's, or A Philox draws keyed by seed and step count), the
 //                  batch-wide label sum L[a] = sum_j label_j[a], log S of the policy normalisation, and the L2 loss term
 //   k_train_grad   one workgroup per example: forward with every layer's post-activation and normalised conv output in
@@ -14,7 +14,14 @@
 // The flat parameter vector is bb_net_weights' fields back to back (TrainLayout); a batch-norm block is [4][n] = gamma,
 // beta, moving_mean, moving_variance, and the moving statistics are constants (kind 0: no gradient, no update).
 // float32 throughout, every fused multiply-add explicit (-ffp-contract=off); the loss sums are taken in double.
+// The batch reaches the kernels through a source type (Src, below): the caller's three tensors (bb_trainer_step), or the
+// example records themselves (bb_trainer_epoch: prep, grad and apply enqueued for every batch of an epoch in one call, no batch
+// tensors in between).  k_train_grad never reads the policy rows -- the policy loss reaches it through L alone --, its planes
+// are a function of one 16-byte packed state and its value label is the record's z, so a step needs nothing a batch holds
+// that the records do not.  Both sources give the kernels the same floats in the same order: batch i of an epoch is, bit for
+// bit, the bb_trainer_step the per-batch loop would have made.
 #pragma once
+#include "examples.hip.h"
 #include "games.hip.h"
 #include "rng.hip.h"
 
@@ -40,10 +47,48 @@ struct TrainAux {
 
 __device__ __forceinline__ float tr_bn_inv(float var) { return 1.0f / sqrtf(var + 1e-3f); }
 
+// ---- where a step's examples come from: the Src of k_train_prep and k_train_grad, chosen at compile time ------------------
+// A source answers, for row j of the batch: label(j, a), the policy label's entry a (k_train_prep); row(j), whatever it keeps
+// of the row in registers, then plane(row, i), element i of the planes [H][W][C], and value(row) (k_train_grad); count(row,
+// tid) reports a rejected row.  TrainTensors is bb_trainer_step's three float32 tensors.  TrainRecords is bb_trainer_epoch's:
+// row j is example record order[first + j] (nullptr: record first + j) under symmetry sym[first + j] (nullptr: the identity),
+// decoded by the functions k_examples_to_batch writes its rows with (examples.hip.h) -- the same floats, never stored; a
+// malformed row is zeros there and here, and one integer atomicAdd from one thread of its workgroup counts it in *bad.
+template <class G>
+struct TrainTensors {
+    const float *__restrict__ boards, *__restrict__ value, *__restrict__ policy;
+    struct Row { int j; };
+    __device__ __forceinline__ float label(int j, int a) const { return policy[(size_t)j * G::A + a]; }
+    __device__ __forceinline__ Row row(int j) const { return {j}; }
+    __device__ __forceinline__ float plane(const Row &r, int i) const { return boards[(size_t)r.j * G::H * G::W * G::C + i]; }
+    __device__ __forceinline__ float value_of(const Row &r) const { return value[r.j]; }
+    __device__ __forceinline__ void count(const Row &, int) const {}
+};
+
+template <class G>
+struct TrainRecords {
+    int n_records;
+    const uint8_t *records;
+    const int64_t *order;
+    const uint8_t *sym;
+    size_t first;
+    int32_t *bad;
+    using Row = ExampleRow<G>;
+    __device__ __forceinline__ Row row(int j) const { return example_row<G>(n_records, records, order, sym, first + (size_t)j); }
+    __device__ __forceinline__ float label(int j, int a) const { return example_share<G>(row(j), a); }
+    __device__ __forceinline__ float plane(const Row &r, int i) const { return example_plane<G>(r, i); }
+    __device__ __forceinline__ float value_of(const Row &r) const { return example_value<G>(r); }
+    __device__ __forceinline__ void count(const Row &r, int tid) const {
+        if (tid == 0 && !r.ok && bad) atomicAdd(bad, 1);
+    }
+};
+
 // ---- k_train_prep ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_prep(int A, int n, int count, int n_l2, const float *params,
-                                                                const uint8_t *kind, const float *policy, const float *noise_in,
-                                                                float eps, float alpha, uint64_t seed, uint64_t calls, TrainAux *aux) {
+template <class G, class Src>
+__global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_prep(int n, int count, int n_l2, const float *params, const uint8_t *kind,
+                                                                Src src, const float *noise_in, float eps, float alpha, uint64_t seed,
+                                                                uint64_t calls, TrainAux *aux) {
+    constexpr int A = G::A;
     __shared__ double s_sq[BB_TRAIN_THREADS];
     __shared__ float s_part[BB_TRAIN_THREADS];
     __shared__ float s_noise[16];
@@ -59,7 +104,7 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_prep(int A, int n, i
         const int a = tid & 15, c = tid >> 4;
         float acc = 0.f;
         if (a < A)
-            for (int j = c; j < n; j += 16) acc += policy[(size_t)j * A + a];
+            for (int j = c; j < n; j += 16) acc += src.label(j, a);
         s_part[tid] = acc;
     }
     double sq = 0.0;
@@ -272,11 +317,10 @@ __host__ __device__ constexpr int train_lds_floats(int R) {
 }
 
 // ---- k_train_grad: one workgroup per example ---------------------------------------------------------------------------
-template <class G>
+template <class G, class Src>
 __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay, const float *__restrict__ prm, const TrainAux *__restrict__ aux,
-                                                                const float *__restrict__ boards, const float *__restrict__ value,
-                                                                int n, float eps, float *__restrict__ slabs, float *__restrict__ le_out,
-                                                                float *__restrict__ lp_out) {
+                                                                Src src, int n, float eps, float *__restrict__ slabs,
+                                                                float *__restrict__ le_out, float *__restrict__ lp_out) {
     constexpr int P = G::H * G::W, C = G::C, A = G::A, F = BB_TRAIN_F, LF = P * F;
     static_assert(P <= 64 && P * C <= 128 && A <= 16 && 2 * P <= 128, "head scratch sizes");
     using S = TrainSmall;
@@ -288,7 +332,9 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay
     float *slab = slabs + (size_t)b * lay.count;
 
     // ---- forward: tower ----
-    for (int i = tid; i < P * C; i += BB_TRAIN_THREADS) sm[S::brd + i] = boards[(size_t)b * P * C + i];
+    const typename Src::Row row = src.row(b);
+    src.count(row, tid);
+    for (int i = tid; i < P * C; i += BB_TRAIN_THREADS) sm[S::brd + i] = src.plane(row, i);
     tr_stage<C, false>(wst, prm + lay.conv0_k, nullptr, tid);
     __syncthreads();
     tr_conv_fwd<G, C>(sm + S::brd, wst, prm + lay.conv0_b, prm + lay.conv0_bn, nullptr, nrm, act, tid);
@@ -341,7 +387,7 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay
     if (tid == 0) { // value, softmax, the example's loss pieces, d loss / d (pre-tanh value, logits)
         float z = prm[lay.v_d2_b];
         for (int d = 0; d < D; d++) z = __builtin_fmaf(sm[S::hbuf + d], prm[lay.v_d2_k + d], z);
-        const float val = tanhf(z), diff = val - value[b];
+        const float val = tanhf(z), diff = val - src.value_of(row);
         le_out[b] = diff * diff;
         sm[S::misc + 3] = 2.0f * diff * (1.0f - val * val) / (float)n;
         float mx = sm[S::lg];

@@ -228,6 +228,49 @@ class HipTrainer:
         loss = self._launch(boards, evalLabel, policyLabel, noise, float(learningRate), True)
         return loss[0], [loss[1], loss[2], loss[3]]
 
+    def epoch_records(self, examples, order, batchSize, learningRate, sym=None, noise=None):
+        """A whole epoch of steps straight from example records (bb_trainer_epoch): batch i is the records
+        order[i * batchSize:(i + 1) * batchSize] -- each under its entry of `sym`, when given --, and the steps are, bit for
+        bit, those of `step_tensors(*examples._batch(order[rows], sym[rows]), learningRate)` batch after batch, without the batch
+        tensors and without a trip through Python per batch.  Enqueued on torch's current stream in one call and not waited
+        for; returns the device tensor [n_batches, 4] of every batch's loss and its three terms.
+
+        examples: a DeviceExamples of the trainer's game on the trainer's device (merged rows are not a records source:
+        ValueError).  order, sym: tensors as examples.index_tensor and examples.sym_tensor return them (order None: the records
+        in order), whole batches.  noise: [n_batches, A] or None to draw it.  Malformed rows count in examples.bad()."""
+        if not isinstance(examples, DeviceExamples):
+            raise ValueError('epoch_records takes a DeviceExamples (merged rows carry sums of their own and are not a records '
+                             'source), got %s' % type(examples).__name__)
+        if examples.game != self.game:
+            raise ValueError('the examples are of game %d, the trainer of game %d' % (examples.game, self.game))
+        dev = examples.records.device
+        if dev.type != 'cuda' or (dev.index if dev.index is not None else torch.cuda.current_device()) != self._index:
+            raise ValueError('the examples are on %s, the trainer on cuda:%d' % (dev, self._index))
+        batch = int(batchSize)
+        if batch < 1 or batch > self.max_batch:
+            raise ValueError('batches of %d examples; the trainer takes 1..%d (max_batch)' % (batch, self.max_batch))
+        rows = len(examples) if order is None else int(order.numel())
+        if rows % batch:
+            raise ValueError('%d rows are no whole number of batches of %d' % (rows, batch))
+        n_batches = rows // batch
+        for name, t, dtype in (('order', order, torch.int64), ('sym', sym, torch.uint8)):
+            if t is not None and (t.dtype != dtype or t.device != dev or int(t.numel()) != rows or not t.is_contiguous()):
+                raise ValueError('%s: a contiguous %s tensor of %d entries on %s is expected' % (name, dtype, rows, dev))
+        nz = None if noise is None else self._f32(noise, (n_batches, self.A))
+        loss = torch.empty((n_batches, 4), dtype=torch.float32, device=self.device)
+        if n_batches == 0:
+            return loss
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            _lib.trainer_epoch(self._h, len(examples), examples.records.data_ptr(), n_batches, batch,
+                               None if order is None else order.data_ptr(), None if sym is None else sym.data_ptr(),
+                               None if nz is None else nz.data_ptr(), float(learningRate), loss.data_ptr(),
+                               examples._bad.data_ptr(), stream.cuda_stream)
+        for t in (examples.records, examples._bad, order, sym, nz):   # asynchronous: alive until the stream has used them
+            if t is not None:
+                t.record_stream(stream)
+        return loss
+
     def last_noise(self):
         """The noise of the last step (given or drawn), read back from the device."""
         return _lib.trainer_read(self._h, _lib.TRAIN_NOISE, self.A)

@@ -524,6 +524,28 @@ int bb_trainer_destroy(bb_trainer *t);
  * BB_ERR_ARG: n <= 0, n > max_batch, a required pointer NULL, any pointer not 4-byte aligned. */
 int bb_trainer_step(bb_trainer *t, int n, const float *boards, const float *value, const float *policy,
                     const float *noise, double lr, int apply, float *loss_out, void *stream);
+/* A whole epoch of steps straight from example records: n_batches times the three launches of bb_trainer_step (apply = 1),
+ * enqueued in order as plain launches on `stream` -- no allocation, no host synchronisation, no graph capture, no stream of
+ * the trainer's own.  The kernels read the records themselves (csrc/train.hip.h: the records source); no batch tensor exists.
+ * Row j of batch i is record order[i * batch + j] under symmetry sym[i * batch + j], decoded exactly as
+ * bb_examples_to_batch_sym decodes it: batch i is, bit for bit, the bb_trainer_step the per-batch loop would have made on that
+ * call's outputs -- the noise drawn (Philox keyed by the seed and the step count, which advances once per batch, as do Adam's
+ * step count and lr_t), the parameters, both slots and the four loss words.  Afterwards BB_TRAIN_GRADS and BB_TRAIN_NOISE read
+ * the last batch's.  ALL pointers are device memory of the trainer's device, which must be the calling thread's current one:
+ *   records  [n_records][example_bytes] of the trainer's game (the bb_examples_fetch layout), 16-byte aligned
+ *   order    [n_batches * batch] int64, or NULL: record i * batch + j
+ *   sym      [n_batches * batch] uint8, each < bb_game_symmetries(game), or NULL: the identity
+ *   noise    [n_batches][A] float32, or NULL to draw it
+ *   loss_out [n_batches][4] float32 (total, evaluation, policy, parameter term of every batch), or NULL
+ *   bad_out  [1] int32, incremented by one per malformed row (the caller zeroes it), or NULL
+ * A row whose order entry is outside [0, n_records), whose sym entry is not a symmetry of the game or whose record says
+ * n_children > S is a row of zeros (planes, label and value) and one count in *bad_out: nothing a record says becomes an
+ * address before it has been checked.
+ * BB_ERR_ARG, before any device call: a null trainer, n_batches < 0, n_records < 0, batch outside 1..max_batch, a non-finite lr,
+ * a misaligned pointer, records NULL or not 16-byte aligned with n_batches > 0, another current device.  n_batches == 0: BB_OK,
+ * nothing touched. */
+int bb_trainer_epoch(bb_trainer *t, int n_records, const void *records, int n_batches, int batch, const int64_t *order,
+                     const uint8_t *sym, const float *noise, double lr, float *loss_out, int32_t *bad_out, void *stream);
 int bb_trainer_param_count(bb_trainer *t, int64_t *count_out);
 /* what = BB_TRAIN_PARAMS | GRADS | SLOT_M | SLOT_V: host_out[count] flat float32, bb_net_weights' fields back to back in their
  * order (the moving statistics included for PARAMS, zero for the others), count = bb_trainer_param_count; SLOT_M is Adam's first

@@ -9,7 +9,9 @@ examples); then one epoch over them is trained twice with the same batch size:
   device path  Blackbird.TrainWithDeviceExamples on the kept records: bb_examples_to_batch + Trainer.step_tensors per
                batch, one export and one reload at the end
   hip path     the same epoch through TrainWithDeviceExamples with NetworkConfig['training']['backend'] = 'hip' (the
-               training step as HIP kernels, bb_trainer_step), on a second model built from the same saved weights
+               training step as HIP kernels), on a second model built from the same saved weights, both ways: the per-batch
+               loop (fused=False: bb_examples_to_batch + bb_trainer_step per batch; hip_path_s) and then the epoch call
+               (bb_trainer_epoch: the step's kernels read the records themselves, one call enqueues the epoch; hip_epoch_s)
 
 and the bare DeviceExamples.batch calls of that epoch alone.  Every timed region ends in a device synchronise; one training
 step is run before any of them, per trainer (the first step pays for the library's kernel selection).  --augment: the
@@ -107,12 +109,20 @@ def main():
     device_s = time.time() - t
 
     # hip path: the same epoch (the same examples, an order drawn the same way) with the step as HIP kernels
-    hip_s = None
+    # -- both ways: the per-batch loop (fused=False: bb_examples_to_batch + bb_trainer_step per batch), then the epoch call
+    # (bb_trainer_epoch: the step's kernels read the records, one call enqueues the epoch), after one untimed batch of it
+    hip_s = hip_epoch_s = None
     if not a.skip_hip:
         t = time.time()
-        Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment)
+        Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment, fused=False)
         torch.cuda.synchronize()
         hip_s = time.time() - t
+        hip_model._trainer.epoch_records(kept, order[:B], B, a.lr)
+        torch.cuda.synchronize()
+        t = time.time()
+        Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment, fused=True)
+        torch.cuda.synchronize()
+        hip_epoch_s = time.time() - t
 
     # merged: the merge itself, the bare merged batches of an epoch, and the epoch through TrainWithDeviceExamples(merge=True)
     merge = {}
@@ -145,7 +155,8 @@ def main():
                       "host_path_s": r3(host_s), "host_decode_s": r3(decode_s),
                       "device_path_s": round(device_s, 3), "device_batches_only_s": round(batch_s, 4),
                       "host_over_device": None if host_s is None else round(host_s / device_s, 2), "hip_path_s": r3(hip_s),
-                      "device_over_hip": None if hip_s is None else round(device_s / hip_s, 2), **merge}))
+                      "device_over_hip": None if hip_s is None else round(device_s / hip_s, 2), "hip_epoch_s": r3(hip_epoch_s),
+                      "hip_over_hip_epoch": None if hip_s is None else round(hip_s / hip_epoch_s, 2), **merge}))
 
 
 if __name__ == "__main__":
