@@ -359,6 +359,39 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
     model._kept_examples = [(v, ex) for v, ex in model._kept_examples if v >= model.Version]
 
 
+def EvaluateDeviceExamples(model, examples=None, batchSize=1024):
+    """A held-out score (an extension: the reference has none): `examples` (a training.DeviceExamples, e.g. the second part of
+    DeviceExamples.split_games), or else what GenerateTrainingSamples kept for the model's current Version, scored by the model's
+    trainer -- model._trainer_for(...), made from model._weights when there is none -- with its current parameters, forward only.
+    Returns training.eval_summary's dict of Python numbers: the counts rows, policy_rows, top1, decided, sign_ok, the sums se_sum,
+    ce_sum, and the means value_mse (squared error of the value against z), policy_ce (cross entropy of the softmax policy against
+    the visit shares, over the rows that have any), top1_rate and sign_rate; a mean over zero rows is NaN.
+
+    hip backend: one HipTrainer.evaluate_records call (bb_trainer_eval reads the records themselves).  PyTorch backend:
+    examples._batch in chunks of `batchSize` through Trainer.evaluate_tensors, the counts and sums added.  No weight, no Version,
+    no batchCount changes, numpy's generator is not touched, and neither is the noise a later step draws."""
+    from .training import EVAL_COUNTS, eval_summary
+    if examples is None:
+        examples = model.KeptDeviceExamples()
+    if examples is None:
+        raise ValueError('no device examples for %s version %d: pass `examples`, or set KeepDeviceExamples before '
+                         'GenerateTrainingSamples' % (model.Name, model.Version))
+    state = np.random.get_state()      # a trainer made here draws the seed of its noise from numpy's generator, as any does:
+    trainer = model._trainer_for(examples.info.C)
+    np.random.set_state(state)         # ... the generator itself is left where it was
+    if hasattr(trainer, 'evaluate_records'):
+        out = trainer.evaluate_records(examples)
+    else:
+        index = examples.index_tensor(np.arange(len(examples)))
+        step = max(int(batchSize), 1)
+        parts = [trainer.evaluate_tensors(*examples._batch(index[i:i + step])) for i in range(0, len(examples), step)]
+        out = eval_summary(*[sum(p[k] for p in parts) for k in EVAL_COUNTS])
+    bad = examples.bad()
+    if bad:
+        raise _lib.BlackbirdHipError('%d malformed example records were met in the evaluation' % bad)
+    return out
+
+
 def TestModelsBatched(model1, model2, temp, numTests, **kw):
     """All `numTests` games of TestModels at once on the GPU (blackbird_amd/arena.py); returns an array of +1/0/-1."""
     from .arena import TestModelsBatched as run

@@ -19,6 +19,8 @@ NET_FORM_AUTO, NET_FORM_F32, NET_FORM_SPLIT = 0, 1, 2   # bb_config.net_form
 LAUNCH_AUTO, LAUNCH_LOCKSTEP, LAUNCH_ROUNDS, LAUNCH_WAVE = 0, 1, 2, 3    # bb_config.launch (LAUNCH_WAVE: the search API in one launch)
 OPT_ADAM, OPT_MOMENTUM, OPT_SGD = 0, 1, 2                # bb_train_config.optimizer
 TRAIN_PARAMS, TRAIN_GRADS, TRAIN_SLOT_M, TRAIN_SLOT_V, TRAIN_NOISE = 0, 1, 2, 3, 4   # bb_trainer_read
+ROW_HAS_POLICY, ROW_TOP1, ROW_DECIDED, ROW_SIGN_OK, ROW_COUNTED = 1, 2, 4, 8, 16     # flags byte of bb_trainer_eval
+EVAL_TOTALS_DTYPE = [(n, "<i8") for n in ("rows", "policy_rows", "top1", "decided", "sign_ok")] + [("se_sum", "<f8"), ("ce_sum", "<f8")]  # bb_eval_totals
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NAN, ERR_CAPACITY, ERR_WEIGHTS = 0, -1, -2, -3, -4, -5, -6
 
 EXPORTS = (
@@ -31,7 +33,7 @@ EXPORTS = (
     "bb_examples_merge_workspace", "bb_examples_merge", "bb_examples_merged_to_batch",
     "bb_arena_create", "bb_arena_begin", "bb_arena_step", "bb_arena_status", "bb_arena_fetch", "bb_arena_destroy",
     "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_epoch", "bb_trainer_param_count",
-    "bb_trainer_read",
+    "bb_trainer_read", "bb_trainer_eval", "bb_trainer_eval_tensors",
 )
 
 
@@ -150,6 +152,8 @@ def lib():
     L.bb_trainer_epoch.argtypes = [vp, ip, vp, ip, ip, vp, vp, vp, C.c_double, vp, vp, vp]
     L.bb_trainer_param_count.argtypes = [vp, C.POINTER(C.c_int64)]
     L.bb_trainer_read.argtypes = [vp, ip, vp, C.c_int64]
+    L.bb_trainer_eval.argtypes = [vp, ip, vp, ip, vp, vp, vp, vp, vp, vp, vp]
+    L.bb_trainer_eval_tensors.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name != "bb_last_error":
             getattr(L, name).restype = C.c_int
@@ -401,6 +405,21 @@ def trainer_epoch(h, n_records, records, n_batches, batch, order=None, sym=None,
     p = lambda a: C.c_void_p(a or None)  # noqa: E731
     check(lib().bb_trainer_epoch(h, int(n_records), p(records), int(n_batches), int(batch), p(order), p(sym), p(noise), float(lr),
                                  p(loss_out), p(bad), p(stream)))
+
+
+def trainer_eval(h, n_records, records, n, index=None, sym=None, rows_out=None, flags_out=None, totals_out=None, bad=None, stream=0):
+    """bb_trainer_eval: rows index[k] (None: record k) of the device records under sym[k] (None: the identity), scored with the
+    trainer's current parameters.  records, index (int64), sym (uint8), rows_out (float32 [n, 3]), flags_out (uint8 [n]),
+    totals_out (56 bytes, EVAL_TOTALS_DTYPE) and bad (int32 [1]) are DEVICE addresses (ints; None/0 = absent).  Asynchronous."""
+    p = lambda a: C.c_void_p(a or None)  # noqa: E731
+    check(lib().bb_trainer_eval(h, int(n_records), p(records), int(n), p(index), p(sym), p(rows_out), p(flags_out), p(totals_out),
+                                p(bad), p(stream)))
+
+
+def trainer_eval_tensors(h, n, boards, value, policy, rows_out=None, flags_out=None, totals_out=None, stream=0):
+    """bb_trainer_eval_tensors: the same for rows given as bb_trainer_step's three device tensors.  Asynchronous."""
+    p = lambda a: C.c_void_p(a or None)  # noqa: E731
+    check(lib().bb_trainer_eval_tensors(h, int(n), p(boards), p(value), p(policy), p(rows_out), p(flags_out), p(totals_out), p(stream)))
 
 
 def trainer_param_count(h):

@@ -20,6 +20,7 @@
 #include "examples_merge.hip.h"
 #include "arena.hip.h"
 #include "train.hip.h"
+#include "train_eval.hip.h"
 #include "net_pack.h"
 
 #include <cmath>
@@ -2142,6 +2143,9 @@ struct bb_trainer {
     float *prm, *slot_m, *slot_v, *grads, *slabs, *le, *lp, *loss;
     uint8_t *kind;
     TrainAux *aux;
+    float *eval_rows; // scratch of bb_trainer_eval for callers that pass no rows_out / flags_out: grows, never shrinks
+    uint8_t *eval_flags;
+    size_t eval_cap;  // rows the scratch holds
     uint64_t calls; // steps made so far, gradient-only ones included: the counter of the noise stream
     int64_t t;      // updates applied so far: AdamOptimizer's beta powers
 };
@@ -2163,7 +2167,7 @@ static TrainLayout train_layout(int C, int R, int D, int A) {
 }
 
 static void trainer_free(bb_trainer *t) {
-    void *ps[] = {t->prm, t->slot_m, t->slot_v, t->grads, t->slabs, t->le, t->lp, t->loss, t->kind, t->aux};
+    void *ps[] = {t->prm, t->slot_m, t->slot_v, t->grads, t->slabs, t->le, t->lp, t->loss, t->kind, t->aux, t->eval_rows, t->eval_flags};
     for (void *p : ps)
         if (p) (void)hipFree(p);
     delete t;
@@ -2343,6 +2347,73 @@ extern "C" int bb_trainer_epoch(bb_trainer *t, int n_records, const void *record
         trainer_epoch<Connect4>(t, n_records, (const uint8_t *)records, n_batches, batch, order, sym, noise, lr, loss_out, bad_out, (hipStream_t)stream);
     else
         trainer_epoch<TicTacToe>(t, n_records, (const uint8_t *)records, n_batches, batch, order, sym, noise, lr, loss_out, bad_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return BB_OK;
+}
+
+// ---- scoring rows with the trainer's parameters (train_eval.hip.h) ----
+static_assert(sizeof(bb_eval_totals) == sizeof(EvalTotals) && sizeof(bb_eval_totals) == 56, "bb_eval_totals is the kernels' EvalTotals");
+static_assert(BB_TRAIN_EVAL_E >= 1, "rows per workgroup");
+
+// The checks both entry points share, and the per-row outputs: the caller's, or the trainer's scratch grown to n rows.
+static int trainer_eval_prepare(bb_trainer *t, int n, float **rows, uint8_t **flags, const bb_eval_totals *totals) {
+    if (!t) return fail(BB_ERR_ARG, "null trainer");
+    if (n < 0) return fail(BB_ERR_ARG, "negative count (%d rows)", n);
+    if (!totals || (uintptr_t)totals % 8) return fail(BB_ERR_ARG, "totals_out must be an 8-byte aligned device pointer");
+    if ((uintptr_t)*rows % sizeof(float)) return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev != t->cfg.device) return fail(BB_ERR_ARG, "the trainer lives on device %d, the current device is %d", t->cfg.device, dev);
+    if ((!*rows || !*flags) && (size_t)n > t->eval_cap) {
+        if (t->eval_rows) (void)hipFree(t->eval_rows); // (hipFree waits for the device: no launch still reads the old scratch)
+        if (t->eval_flags) (void)hipFree(t->eval_flags);
+        t->eval_rows = nullptr;
+        t->eval_flags = nullptr;
+        t->eval_cap = 0;
+        if (hipMalloc(&t->eval_rows, (size_t)n * 3 * sizeof(float)) != hipSuccess || hipMalloc(&t->eval_flags, (size_t)n) != hipSuccess) {
+            (void)hipGetLastError();
+            if (t->eval_rows) (void)hipFree(t->eval_rows);
+            t->eval_rows = nullptr;
+            t->eval_flags = nullptr;
+            return fail(BB_ERR_CAPACITY, "no device memory for the per-row figures of %d rows", n);
+        }
+        t->eval_cap = (size_t)n;
+    }
+    if (!*rows) *rows = t->eval_rows;
+    if (!*flags) *flags = t->eval_flags;
+    return BB_OK;
+}
+
+template <class G, class Src>
+static void trainer_eval_launch(bb_trainer *t, int n, const Src &src, float *rows, uint8_t *flags, bb_eval_totals *totals, hipStream_t st) {
+    if (n > 0) k_train_eval<G, Src><<<nblk((size_t)n, BB_TRAIN_EVAL_E), BB_TRAIN_THREADS, 0, st>>>(t->lay, t->prm, src, n, rows, flags);
+    k_train_eval_totals<<<1, BB_TRAIN_THREADS, 0, st>>>(n, rows, flags, (EvalTotals *)totals);
+}
+
+extern "C" int bb_trainer_eval(bb_trainer *t, int n_records, const void *records, int n, const int64_t *index, const uint8_t *sym,
+                               float *rows_out, uint8_t *flags_out, bb_eval_totals *totals_out, int32_t *bad, void *stream) {
+    if (n_records < 0) return fail(BB_ERR_ARG, "negative count (%d records)", n_records);
+    if ((uintptr_t)index % sizeof(int64_t) || (uintptr_t)bad % 4) return fail(BB_ERR_ARG, "index must be 8-byte aligned, bad 4-byte aligned");
+    if (n > 0 && (!records || (uintptr_t)records % 16)) return fail(BB_ERR_ARG, "records must be a 16-byte aligned device pointer");
+    if (int rc = trainer_eval_prepare(t, n, &rows_out, &flags_out, totals_out)) return rc;
+    const uint8_t *rec = (const uint8_t *)records;
+    if (t->cfg.game == BB_GAME_CONNECT4)
+        trainer_eval_launch<Connect4>(t, n, TrainRecords<Connect4>{n_records, rec, index, sym, 0, bad}, rows_out, flags_out, totals_out, (hipStream_t)stream);
+    else
+        trainer_eval_launch<TicTacToe>(t, n, TrainRecords<TicTacToe>{n_records, rec, index, sym, 0, bad}, rows_out, flags_out, totals_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return BB_OK;
+}
+
+extern "C" int bb_trainer_eval_tensors(bb_trainer *t, int n, const float *boards, const float *value, const float *policy, float *rows_out,
+                                       uint8_t *flags_out, bb_eval_totals *totals_out, void *stream) {
+    if (n > 0 && (!boards || !value || !policy)) return fail(BB_ERR_ARG, "boards, value and policy are required");
+    if (((uintptr_t)boards | (uintptr_t)value | (uintptr_t)policy) % sizeof(float)) return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
+    if (int rc = trainer_eval_prepare(t, n, &rows_out, &flags_out, totals_out)) return rc;
+    if (t->cfg.game == BB_GAME_CONNECT4)
+        trainer_eval_launch<Connect4>(t, n, TrainTensors<Connect4>{boards, value, policy}, rows_out, flags_out, totals_out, (hipStream_t)stream);
+    else
+        trainer_eval_launch<TicTacToe>(t, n, TrainTensors<TicTacToe>{boards, value, policy}, rows_out, flags_out, totals_out, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }

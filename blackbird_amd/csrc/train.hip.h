@@ -54,6 +54,7 @@ __device__ __forceinline__ float tr_bn_inv(float var) { return 1.0f / sqrtf(var 
 // row j is example record order[first + j] (nullptr: record first + j) under symmetry sym[first + j] (nullptr: the identity),
 // decoded by the functions k_examples_to_batch writes its rows with (examples.hip.h) -- the same floats, never stored; a
 // malformed row is zeros there and here, and one integer atomicAdd from one thread of its workgroup counts it in *bad.
+// label_of(row, a) and valid(row) serve the forward-only scoring of train_eval.hip.h, which keeps the row it made.
 template <class G>
 struct TrainTensors {
     const float *__restrict__ boards, *__restrict__ value, *__restrict__ policy;
@@ -62,6 +63,8 @@ struct TrainTensors {
     __device__ __forceinline__ Row row(int j) const { return {j}; }
     __device__ __forceinline__ float plane(const Row &r, int i) const { return boards[(size_t)r.j * G::H * G::W * G::C + i]; }
     __device__ __forceinline__ float value_of(const Row &r) const { return value[r.j]; }
+    __device__ __forceinline__ float label_of(const Row &r, int a) const { return policy[(size_t)r.j * G::A + a]; }
+    __device__ __forceinline__ bool valid(const Row &) const { return true; }
     __device__ __forceinline__ void count(const Row &, int) const {}
 };
 
@@ -78,6 +81,8 @@ struct TrainRecords {
     __device__ __forceinline__ float label(int j, int a) const { return example_share<G>(row(j), a); }
     __device__ __forceinline__ float plane(const Row &r, int i) const { return example_plane<G>(r, i); }
     __device__ __forceinline__ float value_of(const Row &r) const { return example_value<G>(r); }
+    __device__ __forceinline__ float label_of(const Row &r, int a) const { return example_share<G>(r, a); }
+    __device__ __forceinline__ bool valid(const Row &r) const { return r.ok; }
     __device__ __forceinline__ void count(const Row &r, int tid) const {
         if (tid == 0 && !r.ok && bad) atomicAdd(bad, 1);
     }

@@ -133,10 +133,49 @@ class Trainer:
         self._apply(grads, float(learningRate))
         return total, parts
 
+    def evaluate_tensors(self, boards, evalLabel, policyLabel, rows=False):
+        """Score rows with the current weights, forward only (HipTrainer.evaluate_tensors' definitions in float32 torch): per row
+        the value, se = (value - z)^2 and ce = -sum_a pi[a] log_softmax(logits)[a] against the row's own label (0 for a row
+        whose label is all zeros: the terminal example) -- no noise, no batch coupling, no L2 term.  Returns eval_summary's dict;
+        rows=True adds 'per_row' [n, 3] (value, se, ce) and 'flags' [n] (uint8, _lib.ROW_*)."""
+        with torch.no_grad():
+            z, pi = evalLabel.reshape(-1), policyLabel
+            n = int(pi.shape[0])
+            if n:
+                value, logits = self.forward(boards)
+            else:
+                value, logits = z.new_zeros(0), pi.new_zeros((0, self.A))
+            has = (pi != 0).any(dim=1)
+            se = (value - z) ** 2
+            ce = torch.where(has, -(pi * torch.log_softmax(logits, dim=1)).sum(dim=1), torch.zeros_like(se))
+            top1 = has & (torch.argmax(logits, dim=1) == torch.argmax(pi, dim=1)) if n else has    # (argmax: the first maximum)
+            decided = z != 0
+            sign_ok = decided & (((value > 0) & (z > 0)) | ((value < 0) & (z < 0)))
+            out = eval_summary(n, int(has.sum()), int(top1.sum()), int(decided.sum()), int(sign_ok.sum()),
+                               float(se.double().sum()), float(ce.double().sum()))
+            if rows:
+                out['per_row'] = torch.stack([value, se, ce], dim=1)
+                out['flags'] = (has * _lib.ROW_HAS_POLICY + top1 * _lib.ROW_TOP1 + decided * _lib.ROW_DECIDED
+                                + sign_ok * _lib.ROW_SIGN_OK + _lib.ROW_COUNTED).to(torch.uint8)
+        return out
+
     def export(self):
         out = {k: v.detach().cpu().numpy().copy() for k, v in self.params.items()}
         out.update({k: v.cpu().numpy().copy() for k, v in self.consts.items()})
         return out
+
+
+def eval_summary(rows, policy_rows, top1, decided, sign_ok, se_sum, ce_sum):
+    """The dict an evaluation returns, from its counts and its two sums (Python numbers): the counts, the sums, and the means
+    value_mse = se_sum / rows, policy_ce = ce_sum / policy_rows, top1_rate = top1 / policy_rows, sign_rate = sign_ok / decided --
+    NaN over zero rows.  Counts and sums of several evaluations add; the means are then taken from the added figures."""
+    mean = lambda a, b: float(a) / float(b) if b else float('nan')  # noqa: E731
+    return {'rows': int(rows), 'policy_rows': int(policy_rows), 'top1': int(top1), 'decided': int(decided), 'sign_ok': int(sign_ok),
+            'se_sum': float(se_sum), 'ce_sum': float(ce_sum), 'value_mse': mean(se_sum, rows), 'policy_ce': mean(ce_sum, policy_rows),
+            'top1_rate': mean(top1, policy_rows), 'sign_rate': mean(sign_ok, decided)}
+
+
+EVAL_COUNTS = ('rows', 'policy_rows', 'top1', 'decided', 'sign_ok', 'se_sum', 'ce_sum')     # eval_summary's arguments, in order
 
 
 HIP_TRAINER_LIMITS = 'Connect4 or TicTacToe, 16 filters, 0 to 9 blocks, a dense width of 1 to 64'
@@ -271,6 +310,71 @@ class HipTrainer:
                 t.record_stream(stream)
         return loss
 
+    def _evaluated(self, n, launch, rows, keep):
+        """The common part of the two evaluations: the outputs, `launch(rows_ptr, flags_ptr, totals_ptr, stream)` on torch's
+        current stream, and the one synchronising read of the totals."""
+        out_rows = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        out_flags = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        totals = torch.empty(np.dtype(_lib.EVAL_TOTALS_DTYPE).itemsize, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            launch(out_rows.data_ptr(), out_flags.data_ptr(), totals.data_ptr(), stream.cuda_stream)
+        for t in keep:                                   # asynchronous: alive until the stream has used them
+            if t is not None:
+                t.record_stream(stream)
+        tot = totals.cpu().numpy().view(_lib.EVAL_TOTALS_DTYPE)[0]      # (waits for the launches)
+        out = eval_summary(*[tot[k].item() for k in EVAL_COUNTS])
+        if rows:
+            out['per_row'], out['flags'] = out_rows, out_flags
+        return out
+
+    def evaluate_records(self, examples, index=None, sym=None, rows=False):
+        """Score example records with the trainer's current device parameters (bb_trainer_eval: forward only -- no step, no noise,
+        no export; parameters, slots, gradients and the noise stream of later steps are untouched).  Row k is record index[k]
+        (None: every record, in order) under symmetry sym[k] (None: as played), decoded as `examples._batch(index, sym)` decodes
+        it.  Any number of rows: max_batch does not bound it.  Returns eval_summary's dict of Python numbers -- the counts rows,
+        policy_rows, top1, decided, sign_ok, the sums se_sum, ce_sum and the means value_mse, policy_ce, top1_rate, sign_rate (NaN
+        over zero rows) -- after one synchronising read; rows=True adds the device tensors 'per_row' [n, 3] (value, se, ce) and
+        'flags' [n] (uint8, _lib.ROW_*).
+
+        examples: a DeviceExamples of the trainer's game on the trainer's device (merged rows are not a records source:
+        ValueError).  index, sym: tensors as examples.index_tensor and examples.sym_tensor return them, or anything those take.
+        Malformed rows are zeros with flags 0, outside every total, and count in examples.bad()."""
+        if not isinstance(examples, DeviceExamples):
+            raise ValueError('evaluate_records takes a DeviceExamples (merged rows carry sums of their own and are not a records '
+                             'source), got %s' % type(examples).__name__)
+        if examples.game != self.game:
+            raise ValueError('the examples are of game %d, the trainer of game %d' % (examples.game, self.game))
+        dev = examples.records.device
+        if dev.type != 'cuda' or (dev.index if dev.index is not None else torch.cuda.current_device()) != self._index:
+            raise ValueError('the examples are on %s, the trainer on cuda:%d' % (dev, self._index))
+        if index is not None and not torch.is_tensor(index):
+            index = examples.index_tensor(index)
+        if sym is not None and not torch.is_tensor(sym):
+            sym = examples.sym_tensor(sym)
+        n = len(examples) if index is None else int(index.numel())
+        for name, t, dtype in (('index', index, torch.int64), ('sym', sym, torch.uint8)):
+            if t is not None and (t.dtype != dtype or t.device != dev or int(t.numel()) != n or not t.is_contiguous()):
+                raise ValueError('%s: a contiguous %s tensor of %d entries on %s is expected' % (name, dtype, n, dev))
+        return self._evaluated(
+            n, lambda r, f, tot, st: _lib.trainer_eval(self._h, len(examples), examples.records.data_ptr() if len(examples) else None, n,
+                                                       None if index is None else index.data_ptr(),
+                                                       None if sym is None else sym.data_ptr(), r, f, tot, examples._bad.data_ptr(), st),
+            rows, (examples.records, examples._bad, index, sym))
+
+    def evaluate_tensors(self, boards, evalLabel, policyLabel, rows=False):
+        """`evaluate_records` for rows given as the three tensors of a batch (bb_trainer_eval_tensors): boards [n,H,W,C], evalLabel
+        [n], policyLabel [n,A].  The same kernel reads either source: evaluate_records(ex, index, sym) and
+        evaluate_tensors(*ex._batch(index, sym)) give the same bits."""
+        n = int(policyLabel.shape[0]) if hasattr(policyLabel, 'shape') else len(policyLabel)
+        boards = self._f32(boards, (n, self.H, self.Wd, self.C))
+        ev = self._f32(evalLabel, (n,))
+        pl = self._f32(policyLabel, (n, self.A))
+        return self._evaluated(
+            n, lambda r, f, tot, st: _lib.trainer_eval_tensors(self._h, n, boards.data_ptr() if n else None, ev.data_ptr() if n else None,
+                                                               pl.data_ptr() if n else None, r, f, tot, st),
+            rows, (boards, ev, pl))
+
     def last_noise(self):
         """The noise of the last step (given or drawn), read back from the device."""
         return _lib.trainer_read(self._h, _lib.TRAIN_NOISE, self.A)
@@ -335,6 +439,22 @@ class DeviceExamples:
 
     def __len__(self):
         return int(self.records.shape[0])
+
+    def split_games(self, fraction, seed):
+        """(train, held): these records split by whole games, for a held-out score (HipTrainer.evaluate_records).  Games are told
+        apart by the header's game_id (bytes 0..3 of a record).  k = round(fraction * n_games) games are held out, clipped to
+        [1, n_games - 1]: the first k entries of np.random.RandomState(seed).permutation(sorted unique ids) -- numpy's global
+        generator is not touched.  Both parts keep the record order, so no game straddles the split.  ValueError with fewer than
+        two games.  Plain torch indexing on the records' own device (CPU records too), for every game: only the header is read.
+        The count of rejected rows does not carry over."""
+        ids = self.records[:, :4].contiguous().view(torch.int32).reshape(-1)
+        uniq = torch.unique(ids).cpu().numpy()                        # (sorted)
+        if len(uniq) < 2:
+            raise ValueError('split_games needs at least two games, the records hold %d' % len(uniq))
+        k = min(max(int(round(float(fraction) * len(uniq))), 1), len(uniq) - 1)
+        held_ids = np.random.RandomState(seed).permutation(uniq)[:k]
+        held = torch.isin(ids, torch.from_numpy(held_ids).to(ids.device))
+        return type(self)(self.game, self.records[~held]), type(self)(self.game, self.records[held])
 
     def index_tensor(self, index):
         """`index` (int64 tensor or anything numpy takes) as an int64 tensor on the records' device, range-checked:

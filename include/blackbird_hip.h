@@ -546,6 +546,38 @@ int bb_trainer_step(bb_trainer *t, int n, const float *boards, const float *valu
  * nothing touched. */
 int bb_trainer_epoch(bb_trainer *t, int n_records, const void *records, int n_batches, int batch, const int64_t *order,
                      const uint8_t *sym, const float *noise, double lr, float *loss_out, int32_t *bad_out, void *stream);
+/* Score rows with the trainer's current device parameters, forward only (csrc/train_eval.hip.h): no step, no noise, no
+ * export.  Nothing of the trainer is written -- not the parameters, the optimiser slots, the gradients, the last step's noise or
+ * the step counter that keys the next step's noise --, so a run that evaluates in between its steps trains the same bits.
+ * Per row k (a record row exactly as bb_trainer_epoch decodes it: record index[k] under symmetry sym[k]):
+ *   rows_out[k] = value (the network's tanh value), se = (value - z)^2, ce = -sum_a pi[a] (logit[a] - max - log sum exp(logit - max))
+ *                 with pi the row's policy label; ce is 0 for a row without one (the terminal example: total == 0)
+ *   flags_out[k]  bit 0 (BB_ROW_HAS_POLICY) the row has a policy label (some share is not zero; records: total > 0)
+ *                 bit 1 (BB_ROW_TOP1)       first maximum of the logits == first maximum of the label (meaningful with bit 0)
+ *                 bit 2 (BB_ROW_DECIDED)    z != 0
+ *                 bit 3 (BB_ROW_SIGN_OK)    value and z have the same sign (meaningful with bit 2; value == 0 disagrees)
+ *                 bit 4 (BB_ROW_COUNTED)        the row is well-formed and takes part in the totals
+ * A malformed row (bb_trainer_epoch's definition) writes zeros and flags 0, is counted once in *bad and is in no total.
+ * totals_out: counts of the rows with bit 4, bits 0, 0+1, 2, 2+3, and the sums of se over the rows with bit 4 and of ce over
+ * those with bit 0, in double: 256 strided partial sums (thread t: rows t, t + 256, ... in order), then a binary tree -- no
+ * atomics, the same call gives the same bits.  Layout, 56 bytes, 8-byte aligned: */
+typedef struct {
+    int64_t rows, policy_rows, top1, decided, sign_ok;
+    double se_sum, ce_sum;
+} bb_eval_totals;
+enum { BB_ROW_HAS_POLICY = 1, BB_ROW_TOP1 = 2, BB_ROW_DECIDED = 4, BB_ROW_SIGN_OK = 8, BB_ROW_COUNTED = 16 };
+/* ALL pointers are device memory of the trainer's device, which must be the calling thread's current one; the launches are
+ * enqueued on `stream` and not waited for.  Any n >= 0 (max_batch does not bound it: there are no slabs); n == 0 writes zero
+ * totals.  records, index, sym: as bb_trainer_epoch's records, order, sym, n entries.  rows_out [n][3] float32 or NULL, flags_out
+ * [n] or NULL: without them the per-row figures go to scratch of the trainer's own, which grows to the largest n asked for (a
+ * device allocation inside the call, BB_ERR_CAPACITY if it fails).  totals_out is required; bad: [1] int32, incremented, or NULL.
+ * BB_ERR_ARG, before any device call: a null trainer or totals_out, a negative count, a misaligned pointer (records 16 bytes,
+ * index and totals_out 8, rows_out and bad 4), records NULL with n > 0, another current device. */
+int bb_trainer_eval(bb_trainer *t, int n_records, const void *records, int n, const int64_t *index, const uint8_t *sym,
+                    float *rows_out, uint8_t *flags_out, bb_eval_totals *totals_out, int32_t *bad, void *stream);
+/* The same for rows given as bb_trainer_step's three tensors: boards [n][H][W][C], value [n], policy [n][A], required when n > 0. */
+int bb_trainer_eval_tensors(bb_trainer *t, int n, const float *boards, const float *value, const float *policy, float *rows_out,
+                            uint8_t *flags_out, bb_eval_totals *totals_out, void *stream);
 int bb_trainer_param_count(bb_trainer *t, int64_t *count_out);
 /* what = BB_TRAIN_PARAMS | GRADS | SLOT_M | SLOT_V: host_out[count] flat float32, bb_net_weights' fields back to back in their
  * order (the moving statistics included for PARAMS, zero for the others), count = bb_trainer_param_count; SLOT_M is Adam's first

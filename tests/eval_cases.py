@@ -1,0 +1,122 @@
+"""What the tests of the held-out evaluation share (not collected): the float64 statement of the network's forward pass and of the
+per-row figures bb_trainer_eval reports, for any dense game and network shape, written in numpy on its own (it shares no code
+with tests/trainer_cases.py's `statement`, which is torch autograd over einsum), and a small generator of records along random
+legal games (tests/merge_cases.py's playout_records, the helper tests/test_gpu_trainer_epoch.py uses).
+
+The definitions (include/blackbird_hip.h, bb_trainer_eval): per row value = the network's tanh value, se = (value - z)^2,
+ce = -sum_a pi[a] (logit[a] - max - log sum exp(logit - max)) with pi the row's policy label, 0 for a row without one; flags
+bit 0 the row has a label, bit 1 first maximum of the logits == first maximum of the label, bit 2 z != 0, bit 3 value and z have
+the same sign, bit 4 the row is well-formed.  No noise, no batch coupling, no L2 term."""
+import numpy as np
+
+from blackbird_amd import _lib
+from blackbird_amd import weights as W
+from tests import merge_cases as MC
+
+E = 1                 # rows per workgroup of k_train_eval (csrc/train_eval.hip.h: BB_TRAIN_EVAL_E)
+LOGIT_ROOM = 1e-4     # bit 1 is compared where the top two logits of the statement differ by more than this
+VALUE_ROOM = 1e-4     # bit 3 is compared where the statement's |value| exceeds this
+COUNTS = ("rows", "policy_rows", "top1", "decided", "sign_ok")
+
+
+def _conv(x, k, b):
+    """tf.layers.conv2d, SAME, stride 1: x [n,H,W,Cin], k [kh,kw,Cin,F]"""
+    n, H, Wd, _c = x.shape
+    kh, kw = k.shape[:2]
+    ph, pw = kh // 2, kw // 2
+    xp = np.zeros((n, H + 2 * ph, Wd + 2 * pw, x.shape[3]))
+    xp[:, ph:ph + H, pw:pw + Wd] = x
+    out = np.zeros((n, H, Wd, k.shape[3]))
+    for dy in range(kh):
+        for dx in range(kw):
+            out += xp[:, dy:dy + H, dx:dx + Wd] @ k[dy, dx]
+    return out + b
+
+
+def forward(w0, boards):
+    """(value [n], logits [n, A]) of the network `w0` (TF-named dict) on boards [n,H,W,C], in float64; batch norm in inference
+    mode, epsilon 1e-3"""
+    w = {k: np.asarray(v, dtype=np.float64) for k, v in w0.items()}
+    R = W.infer_shape(w0)[2]
+
+    def layer(x, conv, norm):
+        y = _conv(x, w[conv + "/kernel"], w[conv + "/bias"])
+        g, be, mu, var = (w[f"{norm}/{f}"] for f in W.BN_FIELDS)
+        return g * (y - mu) / np.sqrt(var + 1e-3) + be
+
+    x = np.maximum(layer(np.asarray(boards, dtype=np.float64), "resTower/conv_block/conv", "resTower/conv_block/batch_norm"), 0)
+    for i in range(R):
+        h = np.maximum(layer(x, f"resTower/block_{i}/conv_1", f"resTower/block_{i}/batch_norm_1"), 0)
+        x = np.maximum(layer(h, f"resTower/block_{i}/conv_2", f"resTower/block_{i}/batch_norm_2") + x, 0)
+    v = np.maximum(layer(x, "value/convolution", "value/batch_norm"), 0)                     # [n,H,W,1]
+    v = np.maximum((v @ w["value/dense_1/kernel"] + w["value/dense_1/bias"]).sum(axis=(1, 2)), 0)
+    value = np.tanh((v @ w["value/dense_2/kernel"] + w["value/dense_2/bias"]).sum(axis=1))
+    p = np.maximum(layer(x, "policy/convolution", "policy/batch_norm"), 0)                   # [n,H,W,2]
+    logits = (p @ w["policy/policy/kernel"] + w["policy/policy/bias"]).sum(axis=(1, 2))
+    return value, logits
+
+
+def statement(w0, boards, z, pi):
+    """The per-row figures and the totals of well-formed rows, in float64.  Returns a dict: rows [n,3] (value, se, ce), the bits
+    has, top1, decided, sign_ok [n] (bool), top1_room / sign_room [n] (bool: the statement decides the bit with room), and the
+    totals (COUNTS, se_sum, ce_sum)."""
+    z = np.asarray(z, dtype=np.float64).reshape(-1)
+    pi = np.asarray(pi, dtype=np.float64)
+    n = len(z)
+    if n == 0:
+        value, logits = np.zeros(0), np.zeros((0, pi.shape[1]))
+    else:
+        value, logits = forward(w0, boards)
+    has = (pi != 0).any(axis=1)
+    shifted = logits - logits.max(axis=1, keepdims=True)
+    logp = shifted - np.log(np.exp(shifted).sum(axis=1, keepdims=True))
+    ce = np.where(has, -(pi * logp).sum(axis=1), 0.0)
+    se = (value - z) ** 2
+    top = np.sort(logits, axis=1)
+    top1 = has & (np.argmax(logits, axis=1) == np.argmax(pi, axis=1))          # (np.argmax: the first maximum)
+    decided = z != 0
+    sign_ok = decided & (value * z > 0)
+    return {"rows": np.stack([value, se, ce], axis=1), "has": has, "top1": top1, "decided": decided, "sign_ok": sign_ok,
+            "top1_room": (top[:, -1] - top[:, -2]) > LOGIT_ROOM, "sign_room": np.abs(value) > VALUE_ROOM,
+            "totals": {"rows": n, "policy_rows": int(has.sum()), "top1": int(top1.sum()), "decided": int(decided.sum()),
+                       "sign_ok": int(sign_ok.sum()), "se_sum": float(se.sum()), "ce_sum": float(ce.sum())}}
+
+
+def bits(flags):
+    """the flags byte of bb_trainer_eval -> (has, top1, decided, sign_ok, counted) as bool arrays"""
+    f = np.asarray(flags).astype(np.int64)
+    return tuple((f & b) != 0 for b in (_lib.ROW_HAS_POLICY, _lib.ROW_TOP1, _lib.ROW_DECIDED, _lib.ROW_SIGN_OK, _lib.ROW_COUNTED))
+
+
+# ---- records ---------------------------------------------------------------------------------------------------------------------
+_records = {}
+
+
+def records(game, n=130, seed=23):
+    """n records along random legal games (several games, each ending in its terminal example: no visits, total 0), built once and
+    left unchanged; record 1 has tied top visits (its first two visited actions share the largest count)."""
+    key = (game, n, seed)
+    if key not in _records:
+        rec = MC.playout_records(game, n, seed)
+        assert (rec["total"] == 0).any() and rec["total"][1] > 0 and len(np.unique(rec["game_id"])) >= 2
+        A = MC.SHAPE[game][3]
+        v = rec["visits"][1, :A].copy()
+        live = np.flatnonzero(v > 0)
+        assert len(live) >= 2
+        v[live[0]] = v[live[1]] = int(v.max()) + 1
+        rec["visits"][1, :A] = v
+        rec["total"][1] = int(v.sum())
+        _records[key] = rec
+    return _records[key]
+
+
+def any_game_records(game, n_games, per_game, seed):
+    """headers only matter: n_games * per_game records of `game` (DragonChess too) whose game_id runs 7, 9, 11, ... in blocks of
+    per_game, every other byte random -- what DeviceExamples.split_games reads is the game id alone"""
+    rng = np.random.RandomState(seed)
+    rec = np.zeros(n_games * per_game, dtype=_lib.example_dtype(game))
+    raw = rec.view(np.uint8).reshape(len(rec), -1)
+    raw[:] = rng.randint(0, 256, raw.shape)
+    rec["game_id"] = np.repeat(7 + 2 * np.arange(n_games), per_game)
+    rec["ply"] = np.tile(np.arange(per_game), n_games)
+    return rec

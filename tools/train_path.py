@@ -1,5 +1,5 @@
 """From finished self-play games to a trained network, both ways, timed: python tools/train_path.py [--games N]
-[--play-limit P] [--batch B] [--lr LR] [--augment] [--merge] [--skip-host] [--skip-hip]
+[--play-limit P] [--batch B] [--lr LR] [--augment] [--merge] [--holdout FRACTION] [--skip-host] [--skip-hip]
 
 N Connect4 games at PlayLimit P are played once (Model.KeepDeviceExamples on, so that sqlite and the GPU hold the same
 examples); then one epoch over them is trained twice with the same batch size:
@@ -21,7 +21,15 @@ kept records are merged first (DeviceExamples.merged, bb_examples_merge): the re
 the time of merged() (its kernels and its one host look, after one untimed call on 256 records that loads the kernels) are
 printed, and one more epoch is timed on the first model through TrainWithDeviceExamples(merge=True), next to the bare merged
 batches of that epoch; every other figure is measured as without it.  --skip-host / --skip-hip leave the host path / the hip
-path out (their figures are null).  Prints one JSON line."""
+path out (their figures are null).
+
+--holdout FRACTION: a held-out score of one epoch.  The run's records are split by whole games (DeviceExamples.split_games, seed
+--seed); a third model with the hip backend, given the first model's initial weights, scores both parts (Blackbird.EvaluateDeviceExamples:
+HipTrainer.evaluate_records, bb_trainer_eval), trains one epoch on the training part alone (TrainWithDeviceExamples with --augment
+and --merge as given) and scores both parts again: value_mse, policy_ce, top1_rate and sign_rate of each are printed under
+"holdout".  Two times are taken on the held-out part, each the median of five calls after an untimed one: evaluate_records, and
+the route to the same figures without it -- trainer.export(), a fresh engine with those weights, examples._batch to the host,
+Engine.net_eval, numpy.  Every other figure is measured as without it, on all records.  Prints one JSON line."""
 import argparse
 import copy
 import json
@@ -35,11 +43,67 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from blackbird_amd import Blackbird, Connect4  # noqa: E402
-from blackbird_amd.training import epoch_order  # noqa: E402
+from blackbird_amd import Blackbird, Connect4, _lib  # noqa: E402
+from blackbird_amd import weights as W  # noqa: E402
+from blackbird_amd.training import epoch_order, eval_summary  # noqa: E402
 
 CFG = {"blocks": 4, "filters": 16, "eval": {"dense": 16}, "hasTeacher": False,
        "policy": {"dirichlet": {"alpha": 0.2, "epsilon": 0.3}}, "training": {"optimizer": "adam"}}
+
+
+MEANS = ("value_mse", "policy_ce", "top1_rate", "sign_rate")
+
+
+def host_route(trainer, examples):
+    """The held-out figures without bb_trainer_eval: the weights exported, a fresh engine loaded with them, the rows brought to
+    the host, one Engine.net_eval, and the definitions of HipTrainer.evaluate_records in numpy."""
+    eng = _lib.Engine(examples.game, n_slots=16, sims_per_move=2, evaluator=_lib.EVAL_NET)
+    try:
+        eng.load_weights(W.flatten(trainer.export()))
+        boards, z, pi = (t.cpu().numpy() for t in examples._batch(None))
+        value, logits, _policy = eng.net_eval(planes=boards.astype(np.int8))
+    finally:
+        eng.close()
+    has = (pi != 0).any(axis=1)
+    shifted = logits.astype(np.float64) - logits.max(axis=1, keepdims=True)
+    logp = shifted - np.log(np.exp(shifted).sum(axis=1, keepdims=True))
+    ce = np.where(has, -(pi * logp).sum(axis=1), 0.0)
+    top1 = has & (logits.argmax(axis=1) == pi.argmax(axis=1))
+    decided = z != 0
+    return eval_summary(len(z), has.sum(), top1.sum(), decided.sum(), (decided & (value * z > 0)).sum(),
+                        ((value.astype(np.float64) - z) ** 2).sum(), ce.sum())
+
+
+def median_time(fn, reps=5):
+    fn()                                   # untimed: kernels loaded, allocations made
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        t = time.time()
+        fn()
+        torch.cuda.synchronize()
+        times.append(time.time() - t)
+    return float(np.median(times))
+
+
+def holdout_run(a, kept, cfg, weights):
+    """--holdout: see the module's docstring"""
+    train, held = kept.split_games(a.holdout, a.seed)
+    m = Blackbird.Model(Connect4.BoardState, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, cfg)
+    m._weights, m._trainer = {k: v.copy() for k, v in weights.items()}, None
+    means = lambda d: {k: round(d[k], 5) for k in MEANS}  # noqa: E731
+    score = lambda: {"train": means(Blackbird.EvaluateDeviceExamples(m, examples=train)),  # noqa: E731
+                     "held": means(Blackbird.EvaluateDeviceExamples(m, examples=held))}
+    before = score()
+    np.random.seed(a.seed + 1)
+    Blackbird.TrainWithDeviceExamples(m, a.batch, a.lr, examples=train, augment=a.augment, merge=a.merge)
+    after = score()
+    mine, theirs = m._trainer.evaluate_records(held), host_route(m._trainer, held)
+    eval_s = median_time(lambda: m._trainer.evaluate_records(held))
+    host_s = median_time(lambda: host_route(m._trainer, held))
+    return {"fraction": a.holdout, "train_records": len(train), "held_records": len(held), "merge": bool(a.merge),
+            "before": before, "after": after, "evaluate_records_s": round(eval_s, 5), "host_route_s": round(host_s, 5),
+            "host_route_agrees": {k: round(abs(mine[k] - theirs[k]), 7) for k in MEANS}}
 
 
 def main():
@@ -51,6 +115,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--augment", action="store_true")
     ap.add_argument("--merge", action="store_true")
+    ap.add_argument("--holdout", type=float, default=None)
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--skip-hip", action="store_true")
     a = ap.parse_args()
@@ -58,6 +123,7 @@ def main():
     np.random.seed(a.seed)
     model = Blackbird.Model(Connect4.BoardState, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, CFG)
     model.KeepDeviceExamples = True
+    initial = {k: v.copy() for k, v in model._ensure_weights(3).items()}
     Blackbird.GenerateTrainingSamples(model, 64, 1.0)  # warm-up run (its examples are trained on too)
     t = time.time()
     Blackbird.GenerateTrainingSamples(model, a.games, 1.0)
@@ -149,6 +215,8 @@ def main():
                  "merge_s": round(merge_s, 5), "merged_batches": len(merged) // B, "merged_batches_only_s": round(mbatch_s, 4),
                  "device_path_merge_s": round(time.time() - t, 3)}
 
+    holdout = {} if a.holdout is None else {"holdout": holdout_run(a, kept, hip_cfg, initial)}
+
     r3 = lambda x: None if x is None else round(x, 3)  # noqa: E731
     print(json.dumps({"tool": "train_path", "game": "connect4", "games": a.games, "warmup_games": 64, "play_limit": a.play_limit,
                       "examples": n, "augment": bool(a.augment), "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
@@ -156,7 +224,7 @@ def main():
                       "device_path_s": round(device_s, 3), "device_batches_only_s": round(batch_s, 4),
                       "host_over_device": None if host_s is None else round(host_s / device_s, 2), "hip_path_s": r3(hip_s),
                       "device_over_hip": None if hip_s is None else round(device_s / hip_s, 2), "hip_epoch_s": r3(hip_epoch_s),
-                      "hip_over_hip_epoch": None if hip_s is None else round(hip_s / hip_epoch_s, 2), **merge}))
+                      "hip_over_hip_epoch": None if hip_s is None else round(hip_s / hip_epoch_s, 2), **merge, **holdout}))
 
 
 if __name__ == "__main__":
