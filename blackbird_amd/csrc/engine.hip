@@ -2173,6 +2173,21 @@ static void trainer_free(bb_trainer *t) {
     delete t;
 }
 
+// `using G = ` the trainer's game (bb_trainer_create admits these two only) around the statements given, GAME_SWITCH's way
+#define TRAINER_SWITCH(t, ...)                                                   \
+    switch ((t)->cfg.game) {                                                     \
+    case BB_GAME_CONNECT4: { using G = Connect4; __VA_ARGS__; }                  \
+    default: { using G = TicTacToe; __VA_ARGS__; }                               \
+    }
+
+// the entry points that launch do not switch devices: the caller's current device must be the trainer's
+static int trainer_on_device(const bb_trainer *t) {
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev != t->cfg.device) return fail(BB_ERR_ARG, "the trainer lives on device %d, the current device is %d", t->cfg.device, dev);
+    return BB_OK;
+}
+
 template <class G>
 static int trainer_lds(bb_trainer *t) { // (the same dynamic LDS whichever source feeds the workgroup)
     t->lds_bytes = (size_t)train_lds_floats<G>(t->lay.R) * sizeof(float);
@@ -2222,8 +2237,7 @@ static int trainer_alloc(bb_trainer *t, const bb_net_weights *w) {
         {l.p_conv_b, 2, w->p_conv_b}, {l.p_bn, 8, w->p_bn}, {l.p_d_k, 2 * t->A, w->p_d_k}, {l.p_d_b, t->A, w->p_d_b}};
     for (const auto &p : parts)
         if (p.n) HIPCHK(hipMemcpy(t->prm + p.at, p.src, (size_t)p.n * sizeof(float), hipMemcpyDefault));
-    if (t->cfg.game == BB_GAME_CONNECT4) return trainer_lds<Connect4>(t);
-    return trainer_lds<TicTacToe>(t);
+    TRAINER_SWITCH(t, return trainer_lds<G>(t));
 }
 
 extern "C" int bb_trainer_create(const bb_train_config *cfg, const bb_net_weights *w, bb_trainer **out) {
@@ -2310,13 +2324,8 @@ extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const 
     if (((uintptr_t)boards | (uintptr_t)value | (uintptr_t)policy | (uintptr_t)noise | (uintptr_t)loss_out) % sizeof(float))
         return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
     if (!std::isfinite(lr)) return fail(BB_ERR_ARG, "the learning rate is not finite");
-    int dev = -1;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev != t->cfg.device) return fail(BB_ERR_ARG, "the trainer lives on device %d, the current device is %d", t->cfg.device, dev);
-    if (t->cfg.game == BB_GAME_CONNECT4)
-        trainer_launch<Connect4>(t, n, TrainTensors<Connect4>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream);
-    else
-        trainer_launch<TicTacToe>(t, n, TrainTensors<TicTacToe>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream);
+    if (int rc = trainer_on_device(t)) return rc;
+    TRAINER_SWITCH(t, trainer_launch<G>(t, n, TrainTensors<G>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream); break);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }
@@ -2340,20 +2349,15 @@ extern "C" int bb_trainer_epoch(bb_trainer *t, int n_records, const void *record
         return fail(BB_ERR_ARG, "order must be 8-byte aligned, noise, loss_out and bad_out 4-byte aligned");
     if (n_batches == 0) return BB_OK;
     if (!records || (uintptr_t)records % 16) return fail(BB_ERR_ARG, "records must be a 16-byte aligned device pointer");
-    int dev = -1;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev != t->cfg.device) return fail(BB_ERR_ARG, "the trainer lives on device %d, the current device is %d", t->cfg.device, dev);
-    if (t->cfg.game == BB_GAME_CONNECT4)
-        trainer_epoch<Connect4>(t, n_records, (const uint8_t *)records, n_batches, batch, order, sym, noise, lr, loss_out, bad_out, (hipStream_t)stream);
-    else
-        trainer_epoch<TicTacToe>(t, n_records, (const uint8_t *)records, n_batches, batch, order, sym, noise, lr, loss_out, bad_out, (hipStream_t)stream);
+    if (int rc = trainer_on_device(t)) return rc;
+    TRAINER_SWITCH(t, trainer_epoch<G>(t, n_records, (const uint8_t *)records, n_batches, batch, order, sym, noise, lr, loss_out, bad_out, (hipStream_t)stream);
+                   break);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }
 
 // ---- scoring rows with the trainer's parameters (train_eval.hip.h) ----
 static_assert(sizeof(bb_eval_totals) == sizeof(EvalTotals) && sizeof(bb_eval_totals) == 56, "bb_eval_totals is the kernels' EvalTotals");
-static_assert(BB_TRAIN_EVAL_E >= 1, "rows per workgroup");
 
 // The checks both entry points share, and the per-row outputs: the caller's, or the trainer's scratch grown to n rows.
 static int trainer_eval_prepare(bb_trainer *t, int n, float **rows, uint8_t **flags, const bb_eval_totals *totals) {
@@ -2361,9 +2365,7 @@ static int trainer_eval_prepare(bb_trainer *t, int n, float **rows, uint8_t **fl
     if (n < 0) return fail(BB_ERR_ARG, "negative count (%d rows)", n);
     if (!totals || (uintptr_t)totals % 8) return fail(BB_ERR_ARG, "totals_out must be an 8-byte aligned device pointer");
     if ((uintptr_t)*rows % sizeof(float)) return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
-    int dev = -1;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev != t->cfg.device) return fail(BB_ERR_ARG, "the trainer lives on device %d, the current device is %d", t->cfg.device, dev);
+    if (int rc = trainer_on_device(t)) return rc;
     if ((!*rows || !*flags) && (size_t)n > t->eval_cap) {
         if (t->eval_rows) (void)hipFree(t->eval_rows); // (hipFree waits for the device: no launch still reads the old scratch)
         if (t->eval_flags) (void)hipFree(t->eval_flags);
@@ -2386,7 +2388,7 @@ static int trainer_eval_prepare(bb_trainer *t, int n, float **rows, uint8_t **fl
 
 template <class G, class Src>
 static void trainer_eval_launch(bb_trainer *t, int n, const Src &src, float *rows, uint8_t *flags, bb_eval_totals *totals, hipStream_t st) {
-    if (n > 0) k_train_eval<G, Src><<<nblk((size_t)n, BB_TRAIN_EVAL_E), BB_TRAIN_THREADS, 0, st>>>(t->lay, t->prm, src, n, rows, flags);
+    if (n > 0) k_train_eval<G, Src><<<n, BB_TRAIN_THREADS, 0, st>>>(t->lay, t->prm, src, n, rows, flags);
     k_train_eval_totals<<<1, BB_TRAIN_THREADS, 0, st>>>(n, rows, flags, (EvalTotals *)totals);
 }
 
@@ -2396,11 +2398,9 @@ extern "C" int bb_trainer_eval(bb_trainer *t, int n_records, const void *records
     if ((uintptr_t)index % sizeof(int64_t) || (uintptr_t)bad % 4) return fail(BB_ERR_ARG, "index must be 8-byte aligned, bad 4-byte aligned");
     if (n > 0 && (!records || (uintptr_t)records % 16)) return fail(BB_ERR_ARG, "records must be a 16-byte aligned device pointer");
     if (int rc = trainer_eval_prepare(t, n, &rows_out, &flags_out, totals_out)) return rc;
-    const uint8_t *rec = (const uint8_t *)records;
-    if (t->cfg.game == BB_GAME_CONNECT4)
-        trainer_eval_launch<Connect4>(t, n, TrainRecords<Connect4>{n_records, rec, index, sym, 0, bad}, rows_out, flags_out, totals_out, (hipStream_t)stream);
-    else
-        trainer_eval_launch<TicTacToe>(t, n, TrainRecords<TicTacToe>{n_records, rec, index, sym, 0, bad}, rows_out, flags_out, totals_out, (hipStream_t)stream);
+    TRAINER_SWITCH(t, trainer_eval_launch<G>(t, n, TrainRecords<G>{n_records, (const uint8_t *)records, index, sym, 0, bad}, rows_out, flags_out,
+                                             totals_out, (hipStream_t)stream);
+                   break);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }
@@ -2410,10 +2410,7 @@ extern "C" int bb_trainer_eval_tensors(bb_trainer *t, int n, const float *boards
     if (n > 0 && (!boards || !value || !policy)) return fail(BB_ERR_ARG, "boards, value and policy are required");
     if (((uintptr_t)boards | (uintptr_t)value | (uintptr_t)policy) % sizeof(float)) return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
     if (int rc = trainer_eval_prepare(t, n, &rows_out, &flags_out, totals_out)) return rc;
-    if (t->cfg.game == BB_GAME_CONNECT4)
-        trainer_eval_launch<Connect4>(t, n, TrainTensors<Connect4>{boards, value, policy}, rows_out, flags_out, totals_out, (hipStream_t)stream);
-    else
-        trainer_eval_launch<TicTacToe>(t, n, TrainTensors<TicTacToe>{boards, value, policy}, rows_out, flags_out, totals_out, (hipStream_t)stream);
+    TRAINER_SWITCH(t, trainer_eval_launch<G>(t, n, TrainTensors<G>{boards, value, policy}, rows_out, flags_out, totals_out, (hipStream_t)stream); break);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }

@@ -47,6 +47,16 @@ struct TrainAux {
 
 __device__ __forceinline__ float tr_bn_inv(float var) { return 1.0f / sqrtf(var + 1e-3f); }
 
+// The workgroup's sum of every array s[BB_TRAIN_THREADS] given (LDS), left in its [0]: [t] += [t + w] for w = 128, 64, ... 1, a
+// barrier after each level.  The caller stores the partial sums and makes the barrier before the call.  One order, so one rounding.
+template <class... T>
+__device__ __forceinline__ void tr_tree_sum(int tid, T *...s) {
+    for (int w = BB_TRAIN_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) ((s[tid] += s[tid + w]), ...);
+        __syncthreads();
+    }
+}
+
 // ---- where a step's examples come from: the Src of k_train_prep and k_train_grad, chosen at compile time ------------------
 // A source answers, for row j of the batch: label(j, a), the policy label's entry a (k_train_prep); row(j), whatever it keeps
 // of the row in registers, then plane(row, i), element i of the planes [H][W][C], and value(row) (k_train_grad); count(row,
@@ -117,10 +127,7 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_prep(int n, int coun
         if (kind[i] == 1) sq += (double)params[i] * (double)params[i];
     s_sq[tid] = sq;
     __syncthreads();
-    for (int w = BB_TRAIN_THREADS / 2; w > 0; w >>= 1) {
-        if (tid < w) s_sq[tid] += s_sq[tid + w];
-        __syncthreads();
-    }
+    tr_tree_sum(tid, s_sq);
     if (tid < 16) {
         float acc = 0.f;
         for (int c = 0; c < 16; c++) acc += s_part[c * 16 + tid];
@@ -155,8 +162,10 @@ __device__ __forceinline__ void tr_stage(float *wst, const float *k, const float
 }
 
 // conv 3x3 SAME + bias, inference batch norm, (+ residual), ReLU.  Thread (f = tid & 15, pg = tid >> 4) owns the pixels
-// pg, pg + 16, ...; the sum over (tap, ci) is one fmaf chain in that order, padding skipped.
-template <class G, int CIN>
+// pg, pg + 16, ...; the sum over (tap, ci) is one fmaf chain in that order, padding skipped.  NRM: the normalised conv output
+// is stored too (the backward pass reads it; the forward-only k_train_eval passes nrm = nullptr).  res == act is allowed: a
+// thread reads and writes its own elements only.
+template <class G, int CIN, bool NRM>
 __device__ __forceinline__ void tr_conv_fwd(const float *X, const float *wst, const float *bias, const float *bn, const float *res,
                                             float *nrm, float *act, int tid) {
     constexpr int P = G::H * G::W, NP = (P + 15) / 16;
@@ -215,7 +224,7 @@ __device__ __forceinline__ void tr_conv_fwd(const float *X, const float *wst, co
             const float xh = ((acc[k] + b) - mu) * inv;
             float y = __builtin_fmaf(g, xh, be);
             if (res) y += res[p * BB_TRAIN_F + f];
-            nrm[p * BB_TRAIN_F + f] = xh;
+            if constexpr (NRM) nrm[p * BB_TRAIN_F + f] = xh;
             act[p * BB_TRAIN_F + f] = fmaxf(y, 0.f);
         }
     }
@@ -315,6 +324,48 @@ __device__ __forceinline__ void tr_conv_dw(const float *X, const float *dy, cons
     }
 }
 
+// ---- the heads' forward pass, one output element a call: THE text of these expressions ------------------------------------
+// k_train_grad and k_train_eval (train_eval.hip.h) map the elements to their own threads and keep the results in their own
+// scratch; the arithmetic is here once, so a scored row's value and logits are the step's bits by construction.  x: the tower's
+// output [P][16]; vy [P], py [P][2]: the head convs' activations; h [D]: dense_1's.  xh: the normalised conv output, which the
+// backward pass reads and the scorer drops.
+// value/convolution (1x1, one filter), batch norm, ReLU at square p: one fmaf chain over f ascending
+__device__ __forceinline__ float tr_head_value_conv(const TrainLayout &lay, const float *prm, const float *x, int p, float &xh) {
+    float acc = 0.f;
+    for (int f = 0; f < BB_TRAIN_F; f++) acc = __builtin_fmaf(x[p * BB_TRAIN_F + f], prm[lay.v_conv_k + f], acc);
+    xh = ((acc + prm[lay.v_conv_b]) - prm[lay.v_bn + 2]) * tr_bn_inv(prm[lay.v_bn + 3]);
+    return fmaxf(__builtin_fmaf(prm[lay.v_bn], xh, prm[lay.v_bn + 1]), 0.f);
+}
+// policy/convolution (1x1, two filters), batch norm, ReLU at square p, filter j: one fmaf chain over f ascending
+__device__ __forceinline__ float tr_head_policy_conv(const TrainLayout &lay, const float *prm, const float *x, int p, int j, float &xh) {
+    float acc = 0.f;
+    for (int f = 0; f < BB_TRAIN_F; f++) acc = __builtin_fmaf(x[p * BB_TRAIN_F + f], prm[lay.p_conv_k + f * 2 + j], acc);
+    xh = ((acc + prm[lay.p_conv_b + j]) - prm[lay.p_bn + 4 + j]) * tr_bn_inv(prm[lay.p_bn + 6 + j]);
+    return fmaxf(__builtin_fmaf(prm[lay.p_bn + j], xh, prm[lay.p_bn + 2 + j]), 0.f);
+}
+// value/dense_1 on every square, summed over the squares p ascending, ReLU: unit d
+template <class G>
+__device__ __forceinline__ float tr_head_dense_1(const TrainLayout &lay, const float *prm, const float *vy, int d) {
+    const float k1 = prm[lay.v_d1_k + d], b1 = prm[lay.v_d1_b + d];
+    float acc = 0.f;
+    for (int p = 0; p < G::H * G::W; p++) acc += __builtin_fmaf(vy[p], k1, b1);
+    return fmaxf(acc, 0.f);
+}
+// policy/policy on every square, summed over the squares p ascending: the logit of action a
+template <class G>
+__device__ __forceinline__ float tr_head_logit(const TrainLayout &lay, const float *prm, const float *py, int a) {
+    const float k0 = prm[lay.p_d_k + a], k1 = prm[lay.p_d_k + G::A + a], pb = prm[lay.p_d_b + a];
+    float acc = 0.f;
+    for (int p = 0; p < G::H * G::W; p++) acc += __builtin_fmaf(py[2 * p + 1], k1, __builtin_fmaf(py[2 * p], k0, pb));
+    return acc;
+}
+// value/dense_2, one fmaf chain over d ascending from the bias, tanh: the value
+__device__ __forceinline__ float tr_head_value(const TrainLayout &lay, const float *prm, const float *h) {
+    float z = prm[lay.v_d2_b];
+    for (int d = 0; d < lay.D; d++) z = __builtin_fmaf(h[d], prm[lay.v_d2_k + d], z);
+    return tanhf(z);
+}
+
 // LDS floats of k_train_grad for R blocks
 template <class G>
 __host__ __device__ constexpr int train_lds_floats(int R) {
@@ -342,12 +393,12 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay
     for (int i = tid; i < P * C; i += BB_TRAIN_THREADS) sm[S::brd + i] = src.plane(row, i);
     tr_stage<C, false>(wst, prm + lay.conv0_k, nullptr, tid);
     __syncthreads();
-    tr_conv_fwd<G, C>(sm + S::brd, wst, prm + lay.conv0_b, prm + lay.conv0_bn, nullptr, nrm, act, tid);
+    tr_conv_fwd<G, C, true>(sm + S::brd, wst, prm + lay.conv0_b, prm + lay.conv0_bn, nullptr, nrm, act, tid);
     __syncthreads();
     for (int l = 1; l < NL; l++) { // layer l: conv_{1,2} of block (l-1)/2; conv_2 adds the block's input
         tr_stage<F, false>(wst, prm + lay.blk_k + (l - 1) * 9 * F * F, nullptr, tid);
         __syncthreads();
-        tr_conv_fwd<G, F>(act + (l - 1) * LF, wst, prm + lay.blk_b + (l - 1) * F, prm + lay.blk_bn + (l - 1) * 4 * F,
+        tr_conv_fwd<G, F, true>(act + (l - 1) * LF, wst, prm + lay.blk_b + (l - 1) * F, prm + lay.blk_bn + (l - 1) * 4 * F,
                           (l & 1) ? nullptr : act + (l - 2) * LF, nrm + l * LF, act + l * LF, tid);
         __syncthreads();
     }
@@ -355,33 +406,23 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay
 
     // ---- forward: heads ----
     const float v_s = prm[lay.v_bn] * tr_bn_inv(prm[lay.v_bn + 3]);
-    if (tid < P) { // value/convolution (1x1, one filter), batch norm, ReLU
-        float acc = 0.f;
-        for (int f = 0; f < F; f++) acc = __builtin_fmaf(x[tid * F + f], prm[lay.v_conv_k + f], acc);
-        const float xh = ((acc + prm[lay.v_conv_b]) - prm[lay.v_bn + 2]) * tr_bn_inv(prm[lay.v_bn + 3]);
+    if (tid < P) { // value/convolution
+        float xh;
+        const float y = tr_head_value_conv(lay, prm, x, tid, xh);
         sm[S::vn + tid] = xh;
-        sm[S::vy + tid] = fmaxf(__builtin_fmaf(prm[lay.v_bn], xh, prm[lay.v_bn + 1]), 0.f);
-    } else if (tid >= 64 && tid < 64 + 2 * P) { // policy/convolution (1x1, two filters)
-        const int e = tid - 64, p = e >> 1, j = e & 1;
-        float acc = 0.f;
-        for (int f = 0; f < F; f++) acc = __builtin_fmaf(x[p * F + f], prm[lay.p_conv_k + f * 2 + j], acc);
-        const float xh = ((acc + prm[lay.p_conv_b + j]) - prm[lay.p_bn + 4 + j]) * tr_bn_inv(prm[lay.p_bn + 6 + j]);
+        sm[S::vy + tid] = y;
+    } else if (tid >= 64 && tid < 64 + 2 * P) { // policy/convolution
+        const int e = tid - 64;
+        float xh;
+        const float y = tr_head_policy_conv(lay, prm, x, e >> 1, e & 1, xh);
         sm[S::pn + e] = xh;
-        sm[S::py + e] = fmaxf(__builtin_fmaf(prm[lay.p_bn + j], xh, prm[lay.p_bn + 2 + j]), 0.f);
+        sm[S::py + e] = y;
     }
     __syncthreads();
-    if (tid < D) { // value/dense_1 on every square, summed over the squares, ReLU
-        const float k1 = prm[lay.v_d1_k + tid], b1 = prm[lay.v_d1_b + tid];
-        float acc = 0.f;
-        for (int p = 0; p < P; p++) acc += __builtin_fmaf(sm[S::vy + p], k1, b1);
-        sm[S::hbuf + tid] = fmaxf(acc, 0.f);
-    } else if (tid >= 64 && tid < 64 + A) { // policy/policy on every square, summed
-        const int a = tid - 64;
-        const float k0 = prm[lay.p_d_k + a], k1 = prm[lay.p_d_k + A + a], pb = prm[lay.p_d_b + a];
-        float acc = 0.f;
-        for (int p = 0; p < P; p++)
-            acc += __builtin_fmaf(sm[S::py + 2 * p + 1], k1, __builtin_fmaf(sm[S::py + 2 * p], k0, pb));
-        sm[S::lg + a] = acc;
+    if (tid < D) { // value/dense_1
+        sm[S::hbuf + tid] = tr_head_dense_1<G>(lay, prm, sm + S::vy, tid);
+    } else if (tid >= 64 && tid < 64 + A) { // policy/policy
+        sm[S::lg + tid - 64] = tr_head_logit<G>(lay, prm, sm + S::py, tid - 64);
     } else if (tid >= 128 && tid < 131) { // sums over the squares the dense gradients need
         const int j = tid - 128;
         float acc = 0.f;
@@ -390,9 +431,7 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay
     }
     __syncthreads();
     if (tid == 0) { // value, softmax, the example's loss pieces, d loss / d (pre-tanh value, logits)
-        float z = prm[lay.v_d2_b];
-        for (int d = 0; d < D; d++) z = __builtin_fmaf(sm[S::hbuf + d], prm[lay.v_d2_k + d], z);
-        const float val = tanhf(z), diff = val - src.value_of(row);
+        const float val = tr_head_value(lay, prm, sm + S::hbuf), diff = val - src.value_of(row);
         le_out[b] = diff * diff;
         sm[S::misc + 3] = 2.0f * diff * (1.0f - val * val) / (float)n;
         float mx = sm[S::lg];
@@ -529,13 +568,7 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_apply(int count, int
         s_e[tid] = e;
         s_p[tid] = p;
         __syncthreads();
-        for (int w = BB_TRAIN_THREADS / 2; w > 0; w >>= 1) {
-            if (tid < w) {
-                s_e[tid] += s_e[tid + w];
-                s_p[tid] += s_p[tid + w];
-            }
-            __syncthreads();
-        }
+        tr_tree_sum(tid, s_e, s_p);
         if (tid == 0) {
             const float l_e = (float)(s_e[0] / (double)n), l_p = (float)(-s_p[0] / ((double)n * (double)n)), l_w = aux->l2;
             const float total = l_e + l_p + l_w;

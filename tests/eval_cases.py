@@ -13,7 +13,6 @@ from blackbird_amd import _lib
 from blackbird_amd import weights as W
 from tests import merge_cases as MC
 
-E = 1                 # rows per workgroup of k_train_eval (csrc/train_eval.hip.h: BB_TRAIN_EVAL_E)
 LOGIT_ROOM = 1e-4     # bit 1 is compared where the top two logits of the statement differ by more than this
 VALUE_ROOM = 1e-4     # bit 3 is compared where the statement's |value| exceeds this
 COUNTS = ("rows", "policy_rows", "top1", "decided", "sign_ok")
