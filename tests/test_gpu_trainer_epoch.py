@@ -14,10 +14,11 @@ import torch
 from blackbird_amd import Blackbird, Connect4, TicTacToe, _lib
 from blackbird_amd import weights as W
 from blackbird_amd.training import DeviceExamples, HipTrainer, epoch_order
+from tests import eval_cases as EC
 from tests import merge_cases as MC
 from tests import model_cases as M
 from tests.merge_cases import C4, TTT
-from tests.trainer_cases import ALPHA, EPS, close, statement
+from tests.trainer_cases import ALPHA, EPS, close, close_live, statement
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -181,6 +182,42 @@ def test_one_batch_against_the_statement(game, all_terminal):
     for k in r_grads:
         close(grads[k], r_grads[k], (game, "grad", k))
     tr.close()
+
+
+def test_live_epoch_is_the_loop_and_its_first_step_the_statement():
+    """Two batches at live inputs (tests/test_trainer_liveness_cpu.py: with the weights of the cases above the value head is
+    saturated or its ReLUs are off): the epoch is the per-batch loop bit for bit, and the loop's first step is held to the float64
+    statement per tensor within tol * max|data gradient| + 2**-23 * max|want|, tol = min(8 f, 1e-5), f the float32 statement's
+    error on the CPU (tests/trainer_cases.py: float32_figure).  Measured on the MI355X: f 2.9e-6, the kernel 7.8e-7, tol 1e-5."""
+    ref = EC.epoch_live_case()
+    game, batch, noise = ref["game"], EC.EPOCH_LIVE_CASE[3], ref["noise"]
+    ex = DeviceExamples.from_records(game, ref["rec"], DEV)
+    order = ex.index_tensor(ref["order"])
+    one, two = (HipTrainer(ref["w"], alpha=ALPHA, epsilon=EPS, optimizer="adam", momentum=0.9, device=DEV, seed=11, max_batch=17)
+                for _k in range(2))
+    losses = one.epoch_records(ex, order, batch, LR, noise=noise)
+    out = []
+    for i in range(2):
+        boards, value, policy = ex._batch(order[i * batch:(i + 1) * batch], None)
+        total, parts = two.step_tensors(boards, value, policy, LR, noise=torch.from_numpy(noise[i]).to(DEV))
+        out.append(torch.stack([total] + parts))
+        if i == 0:
+            assert np.array_equal(boards.cpu().numpy(), ref["rows"][0]) and np.array_equal(value.cpu().numpy(), ref["rows"][1])
+            grads = two._named(_lib.TRAIN_GRADS)
+    _same_bits(_state(one, losses), _state(two, torch.stack(out)))
+    assert ex.bad() == 0 and np.array_equal(one.last_noise(), noise[1])
+    r_total, r_parts, r_grads, r_data, _live = ref["want"]
+    first = out[0].cpu().numpy()
+    close(first[0], r_total, "loss")
+    for got, want, name in zip(first[1:], r_parts, ("lossEvaluation", "lossPolicy", "lossParam")):
+        close(got, want, name)
+    worst = 0.0
+    for k in r_grads:
+        close(grads[k], r_grads[k], ("grad", k))
+        worst = max(worst, close_live(grads[k], r_grads[k], float(np.abs(r_data[k]).max()), ref["tol"], ("live grad", k)))
+    print("float32 statement %.3g kernel %.3g tolerance %.3g" % (ref["figure"], worst, ref["tol"]))
+    one.close()
+    two.close()
 
 
 # ---- 4. repeatability ----------------------------------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ from tests import eval_cases as EC
 from tests import merge_cases as MC
 from tests import model_cases as M
 from tests.merge_cases import C4, TTT
-from tests.trainer_cases import ALPHA, EPS, close
+from tests.trainer_cases import ALPHA, EPS, close, close_live
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -37,14 +37,7 @@ def _examples(game):
     return DeviceExamples.from_records(game, EC.records(game), DEV)
 
 
-def _index(game, n):
-    """n record numbers: the tied-visits record, a terminal example, then the others in order; all of them in order for 130"""
-    rec = EC.records(game)
-    if n == len(rec):
-        return None
-    terminal = int(np.flatnonzero(rec["total"] == 0)[0])
-    rest = [i for i in range(len(rec)) if i not in (1, terminal)]
-    return np.array(([1, terminal] + rest)[:n], dtype=np.int64)
+_index = EC.index      # n record numbers: the tied-visits record, a terminal example, then the others; None for all 130
 
 
 def _decoded(ex, index=None, sym=None):
@@ -111,6 +104,43 @@ def test_rows_and_totals_against_the_statement(name, R, D, n):
         A = MC.SHAPE[game][3]
         assert (rec["visits"][0, :A] == rec["visits"][0, :A].max()).sum() == 2 and not want["has"].all() and want["has"].any()
     _check(got, want, (name, R, D, n))
+    assert ex.bad() == 0
+    tr.close()
+
+
+# ---- 1b. at live inputs, column by column -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", EC.LIVE_CASES, ids=str)
+def test_live_rows_against_the_statement(case):
+    """At the weights of CASES the Connect4 value head saturates (value +-1, se in {0, 1, 4}) and the three columns are compared
+    jointly at the scale of the largest cross entropy.  Here the rows are live (tests/test_trainer_liveness_cpu.py) and value, se
+    and ce are each held to tol * max|column| + 2**-23 * max|column|, tol = min(8 f, 1e-5), f the error of that column of the same
+    statement evaluated in float32 on the CPU, relative to the column's largest |entry|.
+    Measured on the MI355X, f / the kernel's error in the same measure / tol, for value, se, ce:
+      connect4 R0 D1 n1      1.3e-7/5.3e-7/1.0e-6   4.7e-8/4.4e-7/3.7e-7   7.5e-8/7.5e-8/6.0e-7
+      connect4 R9 D64 n1     9.9e-9/7.8e-8/8.0e-8   5.6e-8/5.6e-8/4.4e-7   9.0e-8/8.6e-8/7.2e-7
+      connect4 R2 D1 n2      1.3e-7/1.6e-7/1.0e-6   1.9e-7/1.0e-7/1.5e-6   7.1e-8/1.4e-7/5.6e-7
+      tictactoe R2 D64 n2    5.4e-7/6.4e-8/4.4e-6   1.6e-6/2.2e-7/1e-5     8.9e-8/3.5e-8/7.1e-7
+      tictactoe R9 D1 n2     1.3e-6/2.1e-7/1e-5     5.5e-7/8.8e-8/4.4e-6   2.3e-8/4.2e-8/1.8e-7
+      tictactoe R0 D64 n130  6.4e-7/5.3e-7/5.1e-6   4.5e-7/4.2e-7/3.6e-6   1.7e-7/1.2e-7/1.4e-6
+    With one row f is the rounding of a single number (9.9e-9 is a sixth of a unit in the last place), so there the bound is
+    mostly its 2**-23 term: se of connect4 R0 D1 n1 is at 4.4e-7 against 3.7e-7 + 1.2e-7."""
+    _name, _R, _D, n, _ws = case
+    ref = EC.live_case(case)
+    ex = _examples(ref["game"])
+    idx = None if ref["index"] is None else ex.index_tensor(ref["index"])
+    tr = HipTrainer(ref["w"], alpha=ALPHA, epsilon=EPS, optimizer="adam", momentum=0.9, device=DEV, seed=11, max_batch=17)
+    got = tr.evaluate_records(ex, idx, rows=True)
+    rows = _decoded(ex, idx)
+    assert np.array_equal(rows[0], ref["rows"][0]) and np.array_equal(rows[1], ref["rows"][1])   # the rows the host decoded
+    want = EC.statement(ref["w"], *rows)
+    assert len(want["rows"]) == n
+    _check(got, want, case)                                                                       # the joint rule still holds
+    per_row = got["per_row"].cpu().numpy()
+    for c, column in enumerate(EC.COLUMNS):
+        scale = float(np.abs(want["rows"][:, c]).max())
+        rel = close_live(per_row[:, c], want["rows"][:, c], scale, ref["tol"][c], (case, column))
+        print(case, column, "float32 statement %.3g kernel %.3g tolerance %.3g" % (ref["figure"][c], rel, ref["tol"][c]))
+    assert (np.abs(per_row[:, 0]) < 0.95).any() and (np.abs(want["rows"][:, 0]) < 0.95).any()    # not the saturated +-1
     assert ex.bad() == 0
     tr.close()
 
