@@ -302,7 +302,8 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
     or else what GenerateTrainingSamples kept for the model's current Version (model.KeepDeviceExamples).  The same steps
     in the same order -- the epoch's order drawn from numpy's generator as there (the same seed visits the same examples in
     the same batches), one optimiser step per batch --, but a batch is formed on the device (bb_examples_to_batch) and the
-    trained weights are exported and handed to the engines once, after the last batch, not after every one.  `epochs` is
+    trained weights are exported and handed to the engines once, after the last batch, not after every one (with
+    NetworkConfig['training']['handoff'] = 'device' they are not exported at all: the engines get them on the device).  `epochs` is
     accepted and ignored, as in the reference.  Raises ValueError when there is nothing to train from.
 
     augment (an extension: the reference does not augment): every visited example is presented under a symmetry of the game
@@ -351,8 +352,7 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
         bad = examples.bad()  # (one look per epoch: it waits for the GPU)
         if bad:
             raise _lib.BlackbirdHipError('%d malformed example records were met in training' % bad)
-        model._weights = trainer.export()
-        model._weights_changed()
+        model._trained()
         model.batchCount += nBatches
     model.Version += 1
     model.Conn.PutModel(model.Game.GameType, model.Name, model.Version)
@@ -489,10 +489,11 @@ class Model(MCTS, Network):
 
     def _weights_changed(self):
         Network._weights_changed(self)
-        flat = W.flatten(self._weights)
-        for eng in (self._engine, self._batch_engine):
-            if eng is not None:
-                eng.load_weights(flat)
+        engines = [eng for eng in (self._engine, self._batch_engine) if eng is not None]
+        if engines:
+            load = self._engine_loader()     # (the host route flattens once; the device route needs no host copy at all)
+            for eng in engines:
+                load(eng)
         self.SampleValue.cache_clear()
         self.GetPriors.cache_clear()
 

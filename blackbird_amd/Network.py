@@ -16,8 +16,12 @@ _GAME_BY_SHAPE = {(6, 7, 3): _lib.GAME_CONNECT4, (3, 3, 3): _lib.GAME_TICTACTOE,
 
 
 class Network:
+    HANDOFF_LIMITS = '16 filters (the fused tower; Connect4, TicTacToe, DragonChess)'
+
     def __init__(self, name, networkConstructor=None, tensorflowConfig={}):
         self.batchCount = 0
+        self._handoff = 'host'            # NetworkConfig['training']['handoff'], read when the trainer is made
+        self._weights_stale = False       # 'device' hand-off: the trainer's device parameters are ahead of the host copy
         self._netName = name
         self._constructor = networkConstructor
         self._weights = None
@@ -33,6 +37,19 @@ class Network:
                 self.saveModel(name)
 
     # ---- weights -------------------------------------------------------------------------------------
+    @property
+    def _weights(self):
+        """The host copy of the weights (TF-named dict).  With the 'device' hand-off training leaves it stale; whoever reads it
+        -- saveModel, _ensure_weights, a new engine's first load -- gets the trainer's current values, exported once."""
+        if self._weights_stale and getattr(self, '_trainer', None) is not None:
+            self._weights_host = self._trainer.export()
+        self._weights_stale = False
+        return self._weights_host
+
+    @_weights.setter
+    def _weights(self, value):
+        self._weights_host, self._weights_stale = value, False
+
     def _ensure_weights(self, in_planes):
         if self._weights is None:
             if self._constructor is None:
@@ -52,9 +69,26 @@ class Network:
             self._eval_engine.load_weights(W.flatten(self._ensure_weights(shape[2])))
         return self._eval_engine
 
+    def _engine_loader(self):
+        """What hands the current weights to an engine that has had its first load: the trainer's load_into while its device
+        parameters are ahead of the host copy ('device' hand-off), else load_weights of the host copy, flattened once."""
+        if self._weights_stale and self._trainer is not None:
+            return self._trainer.load_into
+        flat = W.flatten(self._weights)
+        return lambda eng: eng.load_weights(flat)
+
     def _weights_changed(self):
         if self._eval_engine is not None:
-            self._eval_engine.load_weights(W.flatten(self._weights))
+            self._engine_loader()(self._eval_engine)
+
+    def _trained(self):
+        """After optimiser steps: 'host' exports the trainer's parameters and reloads every engine through the host; 'device'
+        marks the host copy stale and hands the parameters to the engines on the device."""
+        if self._handoff == 'device':
+            self._weights_stale = True
+        else:
+            self._weights = self._trainer.export()
+        self._weights_changed()
 
     # ---- reference API ---------------------------------------------------------------------------------
     def getEvaluation(self, state):
@@ -76,12 +110,19 @@ class Network:
         """The optimiser over this network's weights, created on first use (optimiser kind from NetworkConfig, the graph's
         alpha and epsilon) and kept, with its slots, until other weights are loaded."""
         from . import training
-        self._ensure_weights(in_planes)
         if self._trainer is None:
+            self._ensure_weights(in_planes)     # (a trainer that exists has them; reading them would export a stale copy)
             cfg = (getattr(self._constructor, 'NetworkConfig', None) or {}).get('training') or {}
             backend = cfg.get('backend', 'torch')
             if backend not in ('torch', 'hip'):
                 raise ValueError("NetworkConfig['training']['backend'] is 'torch' or 'hip', got %r" % (backend,))
+            handoff = cfg.get('handoff', 'host')
+            if handoff not in ('host', 'device'):
+                raise ValueError("NetworkConfig['training']['handoff'] is 'host' or 'device', got %r" % (handoff,))
+            if handoff == 'device' and W.infer_shape(self._weights)[1] != 16:
+                raise ValueError("NetworkConfig['training']['handoff'] = 'device' covers %s; this network has %d filters.  Use "
+                                 "the 'host' hand-off for it." % (self.HANDOFF_LIMITS, W.infer_shape(self._weights)[1]))
+            self._handoff = handoff
             if backend == 'hip' and not training.hip_trainer_supports(self._weights):
                 raise ValueError("NetworkConfig['training']['backend'] = 'hip' covers %s; this network has shape "
                                  "(planes, filters, blocks, dense, actions) = %r.  Use the 'torch' backend for it."
@@ -99,8 +140,7 @@ class Network:
             raise NotImplementedError('policy distillation from a teacher (hasTeacher) is not supported')
         state = np.asarray(state)
         self._trainer_for(state.shape[-1]).step(state, eval, policy, learningRate)
-        self._weights = self._trainer.export()
-        self._weights_changed()
+        self._trained()
         self.batchCount += 1
 
     def saveModel(self, name=None):

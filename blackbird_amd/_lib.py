@@ -18,6 +18,7 @@ EVAL_HASH, EVAL_NET, EVAL_ROLLOUT = 0, 1, 2
 NET_FORM_AUTO, NET_FORM_F32, NET_FORM_SPLIT = 0, 1, 2   # bb_config.net_form
 LAUNCH_AUTO, LAUNCH_LOCKSTEP, LAUNCH_ROUNDS, LAUNCH_WAVE = 0, 1, 2, 3    # bb_config.launch (LAUNCH_WAVE: the search API in one launch)
 OPT_ADAM, OPT_MOMENTUM, OPT_SGD = 0, 1, 2                # bb_train_config.optimizer
+WEIGHTS_IMAGES = ("w0", "wt", "epi", "head", "x3")        # bb_weights_read's selector, BB_WEIGHTS_*: Engine.weights_image
 TRAIN_PARAMS, TRAIN_GRADS, TRAIN_SLOT_M, TRAIN_SLOT_V, TRAIN_NOISE = 0, 1, 2, 3, 4   # bb_trainer_read
 ROW_HAS_POLICY, ROW_TOP1, ROW_DECIDED, ROW_SIGN_OK, ROW_COUNTED = 1, 2, 4, 8, 16     # flags byte of bb_trainer_eval
 EVAL_TOTALS_DTYPE = [(n, "<i8") for n in ("rows", "policy_rows", "top1", "decided", "sign_ok")] + [("se_sum", "<f8"), ("ce_sum", "<f8")]  # bb_eval_totals
@@ -34,6 +35,7 @@ EXPORTS = (
     "bb_arena_create", "bb_arena_begin", "bb_arena_step", "bb_arena_status", "bb_arena_fetch", "bb_arena_destroy",
     "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_epoch", "bb_trainer_param_count",
     "bb_trainer_read", "bb_trainer_eval", "bb_trainer_eval_tensors",
+    "bb_load_weights_device", "bb_trainer_load_engine", "bb_weights_read",
 )
 
 
@@ -100,6 +102,9 @@ def lib():
     L.bb_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
     L.bb_destroy.argtypes = [vp]
     L.bb_load_weights.argtypes = [vp, C.POINTER(NetWeights)]
+    L.bb_load_weights_device.argtypes = [vp, C.POINTER(NetWeights), vp]
+    L.bb_trainer_load_engine.argtypes = [vp, vp, vp]
+    L.bb_weights_read.argtypes = [vp, ip, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.bb_get_counters.argtypes = [vp, C.POINTER(Counters)]
     L.bb_reset_counters.argtypes = [vp]
     L.bb_synchronize.argtypes = [vp]
@@ -374,6 +379,22 @@ def net_weights(H, W, flat):
     return w, keep
 
 
+def net_weights_device(H, W, C_, F, R, D, A, base, offsets):
+    """A bb_net_weights whose blocks lie in DEVICE memory: block `name` starts offsets[name] float32 after the device address
+    `base` (an int, e.g. torch.Tensor.data_ptr()).  For Engine.load_weights_device."""
+    w = NetWeights()
+    w.H, w.W, w.C, w.F, w.R, w.D, w.A = int(H), int(W), int(C_), int(F), int(R), int(D), int(A)
+    for name, _t in NetWeights._fields_[7:]:
+        setattr(w, name, C.cast(C.c_void_p(int(base) + 4 * int(offsets[name])), _FP))
+    return w
+
+
+def trainer_load_engine(h, engine, stream=0):
+    """bb_trainer_load_engine: the trainer's current parameters into `engine` (an Engine that has had load_weights), packed on
+    the device behind what `stream` holds.  Asynchronous for `stream`."""
+    check(lib().bb_trainer_load_engine(h, engine.h, C.c_void_p(stream or None)))
+
+
 def trainer_create(game, flat, H, W, optimizer, max_batch, device=0, momentum=0.9, alpha=0.2, epsilon=0.3, seed=0):
     """bb_trainer_create: a bb_trainer handle (c_void_p) over the weights `flat` (weights.flatten()) of an H x W game."""
     cfg = TrainConfig(game=int(game), optimizer=int(optimizer), max_batch=int(max_batch), device=int(device),
@@ -499,6 +520,24 @@ class Engine:
             setattr(w, name, keep[name].ctypes.data_as(_FP))
         self._weights_keep = keep
         check(lib().bb_load_weights(self.h, C.byref(w)))
+
+    def load_weights_device(self, desc, stream=0):
+        """bb_load_weights_device: `desc` a NetWeights whose pointers are device addresses on this engine's device (the
+        current device; net_weights_device builds one), `stream` a hipStream_t handle.  The engine must have had load_weights
+        with a network of the same shape: that call allocates the buffers this one fills.  What `desc` points into must stay
+        alive until `stream` has passed this call (torch: record_stream)."""
+        check(lib().bb_load_weights_device(self.h, C.byref(desc), C.c_void_p(stream or None)))
+
+    def weights_image(self, which):
+        """bb_weights_read: one operand buffer of the engine as a uint8 array -- `which` one of WEIGHTS_IMAGES (or its index):
+        the float32 'w0', 'wt', 'epi', the 'head' array, 'x3' the bf16 images back to back (empty without them).  Layouts:
+        csrc/net_pack.h."""
+        k = WEIGHTS_IMAGES.index(which) if isinstance(which, str) else int(which)
+        n = C.c_int64()
+        check(lib().bb_weights_read(self.h, k, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        check(lib().bb_weights_read(self.h, k, ptr(out), out.nbytes, C.byref(n)))
+        return out
 
     def counters(self):
         c = Counters()

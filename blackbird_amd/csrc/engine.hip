@@ -22,6 +22,7 @@
 #include "train.hip.h"
 #include "train_eval.hip.h"
 #include "net_pack.h"
+#include "net_pack.hip.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -338,6 +339,7 @@ struct bb_engine {
     int gnet_C = 0;
     size_t net_sizes[4] = {0, 0, 0, 0};
     hipStream_t stream = nullptr;
+    hipEvent_t w_event[2] = {nullptr, nullptr}; // bb_load_weights_device: the caller's stream -> the engine's, and back (no timing)
     std::vector<void *> allocs;
     int n_games_target = 0;
     StartsTable starts; // bb_selfplay_set_starts: the device copy dev.starts / view[].starts point at (starts.h); not in `allocs`
@@ -587,6 +589,7 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
     }
     HIPCHK(hipSetDevice(cfg->device));
     HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    for (hipEvent_t &ev : e->w_event) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     TreeDev &d = e->dev;
     memset(&d, 0, sizeof d);
     d.n_slots = cfg->n_slots;
@@ -665,6 +668,8 @@ extern "C" int bb_destroy(bb_engine *e) {
     for (void *p : e->allocs) (void)hipFree(p);
     if (e->starts.dev) (void)hipFree(e->starts.dev);
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->w_event)
+        if (ev) (void)hipEventDestroy(ev);
     if (e->vstream[1]) {
         (void)hipStreamSynchronize(e->vstream[1]);
         (void)hipStreamDestroy(e->vstream[1]);
@@ -945,6 +950,78 @@ extern "C" int bb_load_weights(bb_engine *e, const bb_net_weights *w) {
     e->has_weights = true;
     e->net_F = F;
     e->net_C = C;
+    return BB_OK;
+}
+
+// ---- weights that are in device memory already: pack on the device (net_pack.hip.h) into the buffers bb_load_weights made ----
+static int load_weights_device(bb_engine *e, const bb_net_weights *w, hipStream_t stream, const char *who) {
+    const bb_game_info &gi = e->info;
+    if (w->H != gi.H || w->W != gi.W || w->C != gi.C || w->A != gi.A)
+        return fail(BB_ERR_ARG, "%s: weights are for a %dx%dx%d/%d network, game needs %dx%dx%d/%d", who, w->H, w->W, w->C, w->A, gi.H,
+                    gi.W, gi.C, gi.A);
+    const float *need[] = {w->conv0_k, w->conv0_b, w->conv0_bn, w->v_conv_k, w->v_conv_b, w->v_bn, w->v_d1_k, w->v_d1_b, w->v_d2_k,
+                           w->v_d2_b, w->p_conv_k, w->p_conv_b, w->p_bn, w->p_d_k, w->p_d_b};
+    for (const float *p : need)
+        if (!p) return fail(BB_ERR_ARG, "%s: a weight block is missing", who);
+    if (w->R > 0 && (!w->blk_k || !w->blk_b || !w->blk_bn)) return fail(BB_ERR_ARG, "%s: a weight block is missing", who);
+    if (!e->has_weights || !e->net.w0 || !e->net.head)
+        return fail(BB_ERR_STATE, "%s: the engine has no weight buffers yet -- its first load is bb_load_weights, which allocates them", who);
+    if (e->general_net)
+        return fail(BB_ERR_STATE, "%s covers the fused 16-filter tower; this engine runs its %d-filter network through the "
+                    "launch-per-layer kernels", who, e->net_F);
+    const bool want3 = w->C <= 32 && e->cfg.net_form != BB_NET_FORM_F32;
+    if (w->F != 16 || e->net_F != 16 || w->C != e->net_C || w->R != e->net.R || w->D != e->net.D || w->A != e->net.A ||
+        want3 != (e->x3.w0 != nullptr))
+        return fail(BB_ERR_STATE, "%s: the engine's buffers hold a network of %d planes, %d filters, %d blocks, dense %d, %d actions "
+                    "(%s); the weights given have %d, %d, %d, %d, %d", who, e->net_C, e->net_F, e->net.R, e->net.D, e->net.A,
+                    e->x3.w0 ? "split form" : "float32 form", w->C, w->F, w->R, w->D, w->A);
+    NetDev &nd = e->net;
+    const NetHeadOff off = head_offsets(16, w->D, w->A);
+    if (off.floats != nd.head_floats || (size_t)off.floats != e->net_sizes[3])
+        return fail(BB_ERR_STATE, "%s: the head array holds %d floats, these weights need %d", who, nd.head_floats, off.floats);
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev != e->cfg.device)
+        return fail(BB_ERR_ARG, "%s: the engine lives on device %d, the current device (the stream's and the weights') is %d", who,
+                    e->cfg.device, dev);
+    HIPCHK(sync_all(e)); // weights must not change under a running search: the engine's own streams only, never `stream`
+    // behind whatever `stream` has queued (the steps that made these weights) ...
+    HIPCHK(hipEventRecord(e->w_event[0], stream));
+    HIPCHK(hipStreamWaitEvent(e->stream, e->w_event[0], 0));
+    // ... no evaluation outlives the weights it was made with ...
+    if (e->eval_cache_bytes) HIPCHK(hipMemsetAsync(e->dev.eval_cache, 0, e->eval_cache_bytes, e->stream));
+    auto blocks = [](int threads) { return (unsigned)((threads + NET_PACK_THREADS - 1) / NET_PACK_THREADS); };
+    k_pack_f32<<<blocks(pack_f32_threads(w->C, w->R)), NET_PACK_THREADS, 0, e->stream>>>(*w, (float *)nd.w0, (float *)nd.wt, (float *)nd.epi);
+    k_pack_head<<<blocks(off.floats), NET_PACK_THREADS, 0, e->stream>>>(*w, off, (float *)nd.head);
+    if (e->x3.w0)
+        k_pack_x3<<<blocks(pack_x3_threads(w->C, w->R)), NET_PACK_THREADS, 0, e->stream>>>(
+            *w, (uint16_t *)e->x3.w0, (uint16_t *)e->x3.wt12, (uint16_t *)e->x3.wt3, (uint16_t *)e->x3.wt8, (uint16_t *)e->x3.wh);
+    HIPCHK(hipGetLastError());
+    // ... and everything else waits for the images: the engine's second stream, and `stream` itself, so that the weights may be
+    // freed or stepped on as soon as `stream` has come this far
+    HIPCHK(hipEventRecord(e->w_event[1], e->stream));
+    if (e->vstream[1]) HIPCHK(hipStreamWaitEvent(e->vstream[1], e->w_event[1], 0));
+    HIPCHK(hipStreamWaitEvent(stream, e->w_event[1], 0));
+    return BB_OK;
+}
+
+extern "C" int bb_load_weights_device(bb_engine *e, const bb_net_weights *w_dev, void *stream) {
+    if (!e || !w_dev) return fail(BB_ERR_ARG, "null argument");
+    return load_weights_device(e, w_dev, (hipStream_t)stream, "bb_load_weights_device");
+}
+
+extern "C" int bb_weights_read(bb_engine *e, int which, void *host_out, int64_t capacity, int64_t *bytes_out) {
+    if (!e || (!host_out && !bytes_out)) return fail(BB_ERR_ARG, "null argument");
+    if (which < BB_WEIGHTS_W0 || which > BB_WEIGHTS_X3) return fail(BB_ERR_ARG, "unknown image %d", which);
+    if (!e->has_weights) return fail(BB_ERR_WEIGHTS, "bb_load_weights has not been called");
+    const void *src[5] = {e->net.w0, e->net.wt, e->net.epi, e->net.head, e->x3.w0};
+    const int64_t bytes = which == BB_WEIGHTS_X3 ? (e->x3.w0 ? (int64_t)e->x3_bytes : 0) : (int64_t)(e->net_sizes[which] * sizeof(float));
+    if (bytes_out) *bytes_out = bytes;
+    if (!host_out) return BB_OK;
+    if (capacity < bytes) return fail(BB_ERR_ARG, "image %d has %lld bytes, the buffer %lld", which, (long long)bytes, (long long)capacity);
+    HIPCHK(hipSetDevice(e->cfg.device));
+    HIPCHK(sync_all(e));
+    if (bytes) HIPCHK(hipMemcpy(host_out, src[which], (size_t)bytes, hipMemcpyDeviceToHost));
     return BB_OK;
 }
 
@@ -2442,6 +2519,24 @@ extern "C" int bb_trainer_read(bb_trainer *t, int what, float *host_out, int64_t
     (void)hipSetDevice(prev);
     if (e != hipSuccess) return fail(BB_ERR_HIP, "reading the trainer failed: %s", hipGetErrorString(e));
     return BB_OK;
+}
+
+// The trainer's parameters are bb_net_weights' fields back to back (TrainLayout): a descriptor into them, packed on the device.
+extern "C" int bb_trainer_load_engine(bb_trainer *t, bb_engine *e, void *stream) {
+    if (!t || !e) return fail(BB_ERR_ARG, "null argument");
+    if (t->cfg.game != e->cfg.game) return fail(BB_ERR_ARG, "the trainer is of game %d, the engine of game %d", t->cfg.game, e->cfg.game);
+    if (t->cfg.device != e->cfg.device)
+        return fail(BB_ERR_ARG, "the trainer lives on device %d, the engine on device %d", t->cfg.device, e->cfg.device);
+    const TrainLayout &l = t->lay;
+    const float *p = t->prm;
+    bb_net_weights w = {};
+    w.H = e->info.H; w.W = e->info.W; w.C = t->C; w.F = BB_TRAIN_F; w.R = l.R; w.D = l.D; w.A = t->A;
+    w.conv0_k = p + l.conv0_k; w.conv0_b = p + l.conv0_b; w.conv0_bn = p + l.conv0_bn;
+    w.blk_k = p + l.blk_k; w.blk_b = p + l.blk_b; w.blk_bn = p + l.blk_bn;
+    w.v_conv_k = p + l.v_conv_k; w.v_conv_b = p + l.v_conv_b; w.v_bn = p + l.v_bn;
+    w.v_d1_k = p + l.v_d1_k; w.v_d1_b = p + l.v_d1_b; w.v_d2_k = p + l.v_d2_k; w.v_d2_b = p + l.v_d2_b;
+    w.p_conv_k = p + l.p_conv_k; w.p_conv_b = p + l.p_conv_b; w.p_bn = p + l.p_bn; w.p_d_k = p + l.p_d_k; w.p_d_b = p + l.p_d_b;
+    return load_weights_device(e, &w, (hipStream_t)stream, "bb_trainer_load_engine");
 }
 
 extern "C" int bb_timing_net(bb_engine *e, int iters, int noise, int ablate, double *ms_per_launch_out) {

@@ -159,6 +159,47 @@ class Trainer:
                                 + sign_ok * _lib.ROW_SIGN_OK + _lib.ROW_COUNTED).to(torch.uint8)
         return out
 
+    def _flat_device(self):
+        """The weights as ONE float32 device tensor in weights.flatten's order (weights.flat_fields), constants included, and
+        {bb_net_weights field: its offset in floats}: what bb_load_weights_device's descriptor points into."""
+        bn = lambda prefix: [self._get(f'{prefix}/{f}').detach().reshape(-1) for f in W.BN_FIELDS]  # noqa: E731
+        one = lambda name: [self._get(name).detach().reshape(-1)]                                    # noqa: E731
+        blocks = [(i, j) for i in range(self.R) for j in (1, 2)]
+        parts = {
+            'conv0_k': one('resTower/conv_block/conv/kernel'), 'conv0_b': one('resTower/conv_block/conv/bias'),
+            'conv0_bn': bn('resTower/conv_block/batch_norm'),
+            'blk_k': [t for i, j in blocks for t in one(f'resTower/block_{i}/conv_{j}/kernel')],
+            'blk_b': [t for i, j in blocks for t in one(f'resTower/block_{i}/conv_{j}/bias')],
+            'blk_bn': [t for i, j in blocks for t in bn(f'resTower/block_{i}/batch_norm_{j}')],
+            'v_conv_k': one('value/convolution/kernel'), 'v_conv_b': one('value/convolution/bias'), 'v_bn': bn('value/batch_norm'),
+            'v_d1_k': one('value/dense_1/kernel'), 'v_d1_b': one('value/dense_1/bias'),
+            'v_d2_k': one('value/dense_2/kernel'), 'v_d2_b': one('value/dense_2/bias'),
+            'p_conv_k': one('policy/convolution/kernel'), 'p_conv_b': one('policy/convolution/bias'), 'p_bn': bn('policy/batch_norm'),
+            'p_d_k': one('policy/policy/kernel'), 'p_d_b': one('policy/policy/bias'),
+        }
+        offsets, tensors, at = {}, [], 0
+        for name, shape in W.flat_fields(self.C, self.F, self.R, self.D, self.A):
+            offsets[name] = at
+            tensors += parts[name]
+            at += int(np.prod(shape))
+        flat = torch.cat([t.to(torch.float32) for t in tensors])
+        assert int(flat.numel()) == at, (int(flat.numel()), at)
+        return flat, offsets
+
+    def load_into(self, engine):
+        """Hand the current weights to `engine` (an _lib.Engine that has had load_weights with a network of this shape) on the
+        device: one torch.cat into a flat tensor, a descriptor into it, bb_load_weights_device on torch's current stream -- no
+        export, no host packing.  16 filters, every game (DragonChess too); the engine refuses anything else (AssertionError
+        for a shape that is not what it holds, ValueError for another game)."""
+        if self.device.type != 'cuda':
+            raise _lib.BlackbirdHipError('load_into hands weights over on the GPU; this trainer is on %s' % self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            flat, offsets = self._flat_device()
+            desc = _lib.net_weights_device(engine.info.H, engine.info.W, self.C, self.F, self.R, self.D, self.A, flat.data_ptr(), offsets)
+            engine.load_weights_device(desc, stream.cuda_stream)
+        flat.record_stream(stream)      # the kernels read it after this returns; `stream` waits for them
+
     def export(self):
         out = {k: v.detach().cpu().numpy().copy() for k, v in self.params.items()}
         out.update({k: v.cpu().numpy().copy() for k, v in self.consts.items()})
@@ -386,6 +427,15 @@ class HipTrainer:
 
     def export(self):
         return self._named(_lib.TRAIN_PARAMS)
+
+    def load_into(self, engine):
+        """Hand the current parameters to `engine` (an _lib.Engine of the trainer's game that has had load_weights with a
+        network of this shape) on the device (bb_trainer_load_engine on torch's current stream): the operand images are packed
+        by kernels straight from the parameter buffer, behind the steps already queued -- no export, no host packing.  The
+        engine refuses what it cannot take: AssertionError for a shape that is not what it holds or an engine without
+        weights, ValueError for another game or device."""
+        with torch.cuda.device(self.device):
+            _lib.trainer_load_engine(self._h, engine, torch.cuda.current_stream(self.device).cuda_stream)
 
 
 def epoch_order(n, batchSize):

@@ -195,6 +195,26 @@ int bb_fit_slots(const bb_config *cfg, int *n_slots_out, uint64_t *bytes_per_slo
 int bb_destroy(bb_engine *e);
 /* Network.__init__/loadModel (Network.py:10-28, 100-112): install weights for BB_EVAL_NET */
 int bb_load_weights(bb_engine *e, const bb_net_weights *w);
+/* bb_load_weights for weights that are in DEVICE memory (on request: nothing calls it unless asked).  w_dev's shape fields are
+ * as for bb_load_weights; its pointers are device pointers on the engine's device, which must be the current device, and need to
+ * stay valid only until `stream` (a hipStream_t; NULL: the default stream) has run what this call queued on it.  The operand
+ * images are packed by kernels (csrc/net_pack.hip.h: the bodies of csrc/net_pack.h, one thread per call) into the buffers the
+ * engine's last bb_load_weights made, and are those a bb_load_weights of the same values would upload, byte for byte.
+ * Ordering: the kernels run on the engine's stream behind everything `stream` held at the call (an event), after the clearing of
+ * the evaluation cache that bb_load_weights does; the engine's other stream and `stream` itself wait for them.  The call waits on
+ * the host for the ENGINE's streams first (weights do not change under a running search); it does not synchronise `stream`,
+ * copies nothing to the host and allocates nothing.
+ * Scope: 16 filters, every game, the fused tower in both net forms (BB_NET_FORM_F32: no bf16 images).  BB_ERR_STATE: an engine
+ * that never had bb_load_weights (that call allocates the buffers), one whose loaded shape (C, R, D, A, net form) is not w_dev's,
+ * one on the launch-per-layer path (more than 16 filters, bb_config.general_net).  BB_ERR_ARG: a null argument or weight block, a
+ * shape that is not the game's, another current device.  Every check comes before any device work; a refused call changes nothing. */
+int bb_load_weights_device(bb_engine *e, const bb_net_weights *w_dev, void *stream);
+/* Diagnostic: one of the engine's operand buffers copied to the host as it stands (after waiting for the engine's streams) --
+ * the float32 first convolution, tower and epilogue records, the head array, or the bf16 images back to back (0 bytes on an
+ * engine without them).  *bytes_out (may be NULL) receives the image's size; host_out == NULL: the size only; else capacity, the
+ * bytes host_out holds, must cover it (BB_ERR_ARG).  BB_ERR_WEIGHTS before bb_load_weights.  Layouts: csrc/net_pack.h. */
+enum { BB_WEIGHTS_W0 = 0, BB_WEIGHTS_WT = 1, BB_WEIGHTS_EPI = 2, BB_WEIGHTS_HEAD = 3, BB_WEIGHTS_X3 = 4 };
+int bb_weights_read(bb_engine *e, int which, void *host_out, int64_t capacity, int64_t *bytes_out);
 int bb_get_counters(bb_engine *e, bb_counters *out);
 int bb_reset_counters(bb_engine *e);
 int bb_synchronize(bb_engine *e);
@@ -584,6 +604,11 @@ int bb_trainer_param_count(bb_trainer *t, int64_t *count_out);
  * moment or Momentum's accumulator, SLOT_V Adam's second moment.  BB_TRAIN_NOISE: the last step's noise, count = A.
  * Synchronises the device.  BB_ERR_ARG for any other `what` or count. */
 int bb_trainer_read(bb_trainer *t, int what, float *host_out, int64_t count);
+/* bb_load_weights_device with the trainer's own parameter buffer as w_dev: the engine gets the trainer's current weights without
+ * a trip through the host, ordered behind the steps queued on `stream` (the stream those steps were given).  Later steps on
+ * `stream` wait for the packing.  BB_ERR_ARG, before any device call: a null argument, a trainer and an engine of different games or
+ * devices; otherwise bb_load_weights_device's answers. */
+int bb_trainer_load_engine(bb_trainer *t, bb_engine *e, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 """From finished self-play games to a trained network, both ways, timed: python tools/train_path.py [--games N]
-[--play-limit P] [--batch B] [--lr LR] [--augment] [--merge] [--holdout FRACTION] [--skip-host] [--skip-hip]
+[--play-limit P] [--batch B] [--lr LR] [--augment] [--merge] [--holdout FRACTION] [--skip-host] [--skip-device] [--skip-hip]
+[--handoff host|device]
 
 N Connect4 games at PlayLimit P are played once (Model.KeepDeviceExamples on, so that sqlite and the GPU hold the same
 examples); then one epoch over them is trained twice with the same batch size:
@@ -22,6 +23,14 @@ the time of merged() (its kernels and its one host look, after one untimed call 
 printed, and one more epoch is timed on the first model through TrainWithDeviceExamples(merge=True), next to the bare merged
 batches of that epoch; every other figure is measured as without it.  --skip-host / --skip-hip leave the host path / the hip
 path out (their figures are null).
+
+--handoff host|device: NetworkConfig['training']['handoff'] of the hip model (default host: export and reload through the host).
+Either way the hip model is given the engines a playing, training model owns -- its evaluation engine and, after a warm-up run
+of 64 games, its self-play engine -- and two more legs are timed on it: train_loop_s, the reference API's shape, Model.train
+once per batch of the epoch on host arrays staged beforehand (a step, then every engine reloaded: where the hand-off matters),
+and handoff_s against export_load_s, the median of five calls of one HipTrainer.load_into of the evaluation engine against one
+export() + flatten + load_weights of it (handoff_s is null on a build without load_into).  --skip-device leaves the PyTorch
+trainer's device path out.
 
 --holdout FRACTION: a held-out score of one epoch.  The run's records are split by whole games (DeviceExamples.split_games, seed
 --seed); a third model with the hip backend, given the first model's initial weights, scores both parts (Blackbird.EvaluateDeviceExamples:
@@ -118,6 +127,8 @@ def main():
     ap.add_argument("--holdout", type=float, default=None)
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--skip-hip", action="store_true")
+    ap.add_argument("--skip-device", action="store_true")
+    ap.add_argument("--handoff", choices=("host", "device"), default="host")
     a = ap.parse_args()
     os.chdir(tempfile.mkdtemp())  # the sqlite file and the saved networks of this run
     np.random.seed(a.seed)
@@ -134,10 +145,16 @@ def main():
     # the second model: the weights the first one saved when it was made, the hip backend
     hip_cfg = copy.deepcopy(CFG)
     hip_cfg["training"]["backend"] = "hip"
+    if a.handoff != "host":
+        hip_cfg["training"]["handoff"] = a.handoff
     hip_model = Blackbird.Model(Connect4.BoardState, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, hip_cfg)
     assert all(np.array_equal(hip_model._weights[k], model._weights[k]) for k in model._weights)
     model.train(boards, value, policy, a.lr)  # warm-up step
     if not a.skip_hip:
+        hip_model.getEvaluation(boards[:1].astype(np.int8))     # the engines a playing, training model owns: evaluation ...
+        state = np.random.get_state()
+        Blackbird.GenerateTrainingSamples(hip_model, 64, 1.0)    # ... and self-play (numpy's generator left where it was)
+        np.random.set_state(state)
         hip_model.train(boards, value, policy, a.lr)
     torch.cuda.synchronize()
 
@@ -169,10 +186,12 @@ def main():
         host_s = time.time() - t
 
     # device path
-    t = time.time()
-    Blackbird.TrainWithDeviceExamples(model, B, a.lr, examples=kept, augment=a.augment)
-    torch.cuda.synchronize()
-    device_s = time.time() - t
+    device_s = None
+    if not a.skip_device:
+        t = time.time()
+        Blackbird.TrainWithDeviceExamples(model, B, a.lr, examples=kept, augment=a.augment)
+        torch.cuda.synchronize()
+        device_s = time.time() - t
 
     # hip path: the same epoch (the same examples, an order drawn the same way) with the step as HIP kernels
     # -- both ways: the per-batch loop (fused=False: bb_examples_to_batch + bb_trainer_step per batch), then the epoch call
@@ -189,6 +208,22 @@ def main():
         Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment, fused=True)
         torch.cuda.synchronize()
         hip_epoch_s = time.time() - t
+
+    # the reference API's shape on the hip model: Model.train per batch (a step, then every engine the model owns reloaded), on
+    # host arrays staged beforehand; then one hand-off alone against one export + load_weights, on the evaluation engine
+    loop_s = handoff_s = export_load_s = None
+    if not a.skip_hip:
+        staged = [tuple(x.cpu().numpy() for x in kept._batch(order[i * B:(i + 1) * B])) for i in range(len(order) // B)]
+        torch.cuda.synchronize()
+        t = time.time()
+        for b, v, p in staged:
+            hip_model.train(b, v, p, a.lr)
+        torch.cuda.synchronize()
+        loop_s = time.time() - t
+        tr, eng = hip_model._trainer, hip_model._eval_engine
+        export_load_s = median_time(lambda: eng.load_weights(W.flatten(tr.export())))
+        if hasattr(tr, "load_into"):
+            handoff_s = median_time(lambda: (tr.load_into(eng), eng.synchronize()))
 
     # merged: the merge itself, the bare merged batches of an epoch, and the epoch through TrainWithDeviceExamples(merge=True)
     merge = {}
@@ -221,10 +256,14 @@ def main():
     print(json.dumps({"tool": "train_path", "game": "connect4", "games": a.games, "warmup_games": 64, "play_limit": a.play_limit,
                       "examples": n, "augment": bool(a.augment), "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
                       "host_path_s": r3(host_s), "host_decode_s": r3(decode_s),
-                      "device_path_s": round(device_s, 3), "device_batches_only_s": round(batch_s, 4),
-                      "host_over_device": None if host_s is None else round(host_s / device_s, 2), "hip_path_s": r3(hip_s),
-                      "device_over_hip": None if hip_s is None else round(device_s / hip_s, 2), "hip_epoch_s": r3(hip_epoch_s),
-                      "hip_over_hip_epoch": None if hip_s is None else round(hip_s / hip_epoch_s, 2), **merge, **holdout}))
+                      "device_path_s": r3(device_s), "device_batches_only_s": round(batch_s, 4),
+                      "host_over_device": None if host_s is None or device_s is None else round(host_s / device_s, 2),
+                      "hip_path_s": r3(hip_s),
+                      "device_over_hip": None if hip_s is None or device_s is None else round(device_s / hip_s, 2),
+                      "hip_epoch_s": r3(hip_epoch_s), "hip_over_hip_epoch": None if hip_s is None else round(hip_s / hip_epoch_s, 2),
+                      "handoff": a.handoff, "train_loop_s": r3(loop_s),
+                      "handoff_s": None if handoff_s is None else round(handoff_s, 6),
+                      "export_load_s": None if export_load_s is None else round(export_load_s, 6), **merge, **holdout}))
 
 
 if __name__ == "__main__":
