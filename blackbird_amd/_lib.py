@@ -9,6 +9,8 @@ import os
 
 import numpy as np
 
+from .weights import FIELDS as _weight_fields
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libblackbird_hip.so")
 
@@ -48,9 +50,7 @@ _FP = C.POINTER(C.c_float)
 
 class NetWeights(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("H", "W", "C", "F", "R", "D", "A")] + [
-        (n, _FP) for n in ("conv0_k", "conv0_b", "conv0_bn", "blk_k", "blk_b", "blk_bn", "v_conv_k", "v_conv_b",
-                           "v_bn", "v_d1_k", "v_d1_b", "v_d2_k", "v_d2_b", "p_conv_k", "p_conv_b", "p_bn", "p_d_k",
-                           "p_d_b")]
+        (n, _FP) for n in _weight_fields]
 
 
 class Config(C.Structure):
@@ -509,16 +509,7 @@ class Engine:
 
     def load_weights(self, flat):
         """flat: dict from blackbird_amd.weights.flatten()."""
-        gi = self.info
-        w = NetWeights()
-        k0 = flat["conv0_k"]
-        w.H, w.W, w.C, w.F = gi.H, gi.W, k0.shape[2], k0.shape[3]
-        w.R, w.D, w.A = flat["blk_k"].shape[0], flat["v_d1_k"].shape[0], flat["p_d_b"].shape[0]
-        keep = {}
-        for name, _t in NetWeights._fields_[7:]:
-            keep[name] = np.ascontiguousarray(flat[name], dtype=np.float32)
-            setattr(w, name, keep[name].ctypes.data_as(_FP))
-        self._weights_keep = keep
+        w, self._weights_keep = net_weights(self.info.H, self.info.W, flat)
         check(lib().bb_load_weights(self.h, C.byref(w)))
 
     def load_weights_device(self, desc, stream=0):

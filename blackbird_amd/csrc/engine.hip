@@ -21,9 +21,11 @@
 #include "arena.hip.h"
 #include "train.hip.h"
 #include "train_eval.hip.h"
+#include "net_blocks.h"
 #include "net_pack.h"
 #include "net_pack.hip.h"
 
+#include <cassert>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -880,12 +882,20 @@ static int launch_gnet(bb_engine *e, int n_max, const int *n_ptr, const int *slo
     return BB_OK;
 }
 
+// What every entry point asks of a bb_net_weights before anything else: the game's planes and actions, and every block the
+// shape needs (net_blocks.h).  `who`, where given, goes in front of the message.
+static int check_weights(const bb_net_weights *w, const bb_game_info &gi, const char *who = nullptr) {
+    const std::string pre = who ? std::string(who) + ": " : "";
+    if (w->H != gi.H || w->W != gi.W || w->C != gi.C || w->A != gi.A)
+        return fail(BB_ERR_ARG, "%sweights are for a %dx%dx%d/%d network, game needs %dx%dx%d/%d", pre.c_str(), w->H, w->W, w->C, w->A,
+                    gi.H, gi.W, gi.C, gi.A);
+    if (net_block_missing(*w)) return fail(BB_ERR_ARG, "%sa weight block is missing", pre.c_str());
+    return BB_OK;
+}
+
 extern "C" int bb_load_weights(bb_engine *e, const bb_net_weights *w) {
     if (!e || !w) return fail(BB_ERR_ARG, "null argument");
-    const bb_game_info &gi = e->info;
-    if (w->H != gi.H || w->W != gi.W || w->C != gi.C || w->A != gi.A)
-        return fail(BB_ERR_ARG, "weights are for a %dx%dx%d/%d network, game needs %dx%dx%d/%d", w->H, w->W, w->C,
-                    w->A, gi.H, gi.W, gi.C, gi.A);
+    if (int rc = check_weights(w, e->info)) return rc;
     if (w->F <= 0 || w->F % 16 != 0 || w->F > 1024)
         return fail(BB_ERR_ARG, "filters must be a multiple of 16 (MFMA tile), got %d", w->F);
     if (w->D <= 0 || w->D > 64 || w->R < 0) return fail(BB_ERR_ARG, "unsupported dense/blocks");
@@ -955,15 +965,7 @@ extern "C" int bb_load_weights(bb_engine *e, const bb_net_weights *w) {
 
 // ---- weights that are in device memory already: pack on the device (net_pack.hip.h) into the buffers bb_load_weights made ----
 static int load_weights_device(bb_engine *e, const bb_net_weights *w, hipStream_t stream, const char *who) {
-    const bb_game_info &gi = e->info;
-    if (w->H != gi.H || w->W != gi.W || w->C != gi.C || w->A != gi.A)
-        return fail(BB_ERR_ARG, "%s: weights are for a %dx%dx%d/%d network, game needs %dx%dx%d/%d", who, w->H, w->W, w->C, w->A, gi.H,
-                    gi.W, gi.C, gi.A);
-    const float *need[] = {w->conv0_k, w->conv0_b, w->conv0_bn, w->v_conv_k, w->v_conv_b, w->v_bn, w->v_d1_k, w->v_d1_b, w->v_d2_k,
-                           w->v_d2_b, w->p_conv_k, w->p_conv_b, w->p_bn, w->p_d_k, w->p_d_b};
-    for (const float *p : need)
-        if (!p) return fail(BB_ERR_ARG, "%s: a weight block is missing", who);
-    if (w->R > 0 && (!w->blk_k || !w->blk_b || !w->blk_bn)) return fail(BB_ERR_ARG, "%s: a weight block is missing", who);
+    if (int rc = check_weights(w, e->info, who)) return rc;
     if (!e->has_weights || !e->net.w0 || !e->net.head)
         return fail(BB_ERR_STATE, "%s: the engine has no weight buffers yet -- its first load is bb_load_weights, which allocates them", who);
     if (e->general_net)
@@ -2228,18 +2230,15 @@ struct bb_trainer {
 };
 
 static TrainLayout train_layout(int C, int R, int D, int A) {
+    const NetBlocks t = net_blocks(C, BB_TRAIN_F, R, D, A);
     TrainLayout l = {};
-    int o = 0;
-    auto take = [&](int n) { int at = o; o += n; return at; };
-    const int F = BB_TRAIN_F;
     l.R = R; l.D = D;
-    l.conv0_k = take(9 * C * F); l.conv0_b = take(F); l.conv0_bn = take(4 * F);
-    l.blk_k = take(R * 2 * 9 * F * F); l.blk_b = take(R * 2 * F); l.blk_bn = take(R * 2 * 4 * F);
-    l.v_conv_k = take(F); l.v_conv_b = take(1); l.v_bn = take(4);
-    l.v_d1_k = take(D); l.v_d1_b = take(D); l.v_d2_k = take(D); l.v_d2_b = take(1);
-    l.p_conv_k = take(2 * F); l.p_conv_b = take(2); l.p_bn = take(8); l.p_d_k = take(2 * A); l.p_d_b = take(A);
-    l.count = o;
-    l.n_l2 = 12 + 6 * R; // kernel, gamma, beta of 1 + 2R tower convs and of the two head convs; dense_1, dense_2, policy kernels
+#define X(name, kind, units, per) l.name = t.b[NET_BLOCK_##name].at;
+    BB_NET_BLOCKS(X)
+#undef X
+    l.count = t.count;
+    l.n_l2 = net_blocks_l2(t);
+    assert(l.n_l2 == 12 + 6 * R); // kernel, gamma, beta of 1 + 2R tower convs and of the two head convs; dense_1, dense_2, policy kernels
     return l;
 }
 
@@ -2296,24 +2295,12 @@ static int trainer_alloc(bb_trainer *t, const bb_net_weights *w) {
     HIPCHK(hipMemset(t->grads, 0, cb));
     HIPCHK(hipMemset(t->loss, 0, 4 * sizeof(float)));
     HIPCHK(hipMemset(t->aux, 0, sizeof(TrainAux)));
-    // variable kinds: 1 trainable and in the L2 mean, 2 trainable bias, 0 moving statistics
-    std::vector<uint8_t> kind((size_t)l.count, 1);
-    auto mark = [&](int at, int n, uint8_t k) { std::fill(kind.begin() + at, kind.begin() + at + n, k); };
-    const int F = BB_TRAIN_F, R = l.R, D = l.D;
-    mark(l.conv0_b, F, 2); mark(l.blk_b, R * 2 * F, 2); mark(l.v_conv_b, 1, 2); mark(l.v_d1_b, D, 2); mark(l.v_d2_b, 1, 2);
-    mark(l.p_conv_b, 2, 2); mark(l.p_d_b, t->A, 2);
-    mark(l.conv0_bn + 2 * F, 2 * F, 0);
-    for (int i = 0; i < 2 * R; i++) mark(l.blk_bn + i * 4 * F + 2 * F, 2 * F, 0);
-    mark(l.v_bn + 2, 2, 0); mark(l.p_bn + 4, 4, 0);
+    const NetBlocks tb = net_blocks(t->C, BB_TRAIN_F, l.R, l.D, t->A); // (what train_layout took l from)
+    const std::vector<uint8_t> kind = net_block_kinds(tb);
     HIPCHK(hipMemcpy(t->kind, kind.data(), kind.size(), hipMemcpyHostToDevice));
-    const struct { int at, n; const float *src; } parts[] = {
-        {l.conv0_k, 9 * t->C * F, w->conv0_k}, {l.conv0_b, F, w->conv0_b}, {l.conv0_bn, 4 * F, w->conv0_bn},
-        {l.blk_k, R * 2 * 9 * F * F, w->blk_k}, {l.blk_b, R * 2 * F, w->blk_b}, {l.blk_bn, R * 2 * 4 * F, w->blk_bn},
-        {l.v_conv_k, F, w->v_conv_k}, {l.v_conv_b, 1, w->v_conv_b}, {l.v_bn, 4, w->v_bn}, {l.v_d1_k, D, w->v_d1_k},
-        {l.v_d1_b, D, w->v_d1_b}, {l.v_d2_k, D, w->v_d2_k}, {l.v_d2_b, 1, w->v_d2_b}, {l.p_conv_k, 2 * F, w->p_conv_k},
-        {l.p_conv_b, 2, w->p_conv_b}, {l.p_bn, 8, w->p_bn}, {l.p_d_k, 2 * t->A, w->p_d_k}, {l.p_d_b, t->A, w->p_d_b}};
-    for (const auto &p : parts)
-        if (p.n) HIPCHK(hipMemcpy(t->prm + p.at, p.src, (size_t)p.n * sizeof(float), hipMemcpyDefault));
+    for (int i = 0; i < NET_BLOCKS; i++)
+        if (const int n = tb.b[i].count())
+            HIPCHK(hipMemcpy(t->prm + tb.b[i].at, net_block(*w, i), (size_t)n * sizeof(float), hipMemcpyDefault));
     TRAINER_SWITCH(t, return trainer_lds<G>(t));
 }
 
@@ -2324,9 +2311,7 @@ extern "C" int bb_trainer_create(const bb_train_config *cfg, const bb_net_weight
         return fail(BB_ERR_ARG, "the HIP trainer covers Connect4 and TicTacToe, not game %d", cfg->game);
     bb_game_info gi;
     bb_game_info_get(cfg->game, &gi);
-    if (w->H != gi.H || w->W != gi.W || w->C != gi.C || w->A != gi.A)
-        return fail(BB_ERR_ARG, "weights are for a %dx%dx%d/%d network, game needs %dx%dx%d/%d", w->H, w->W, w->C, w->A, gi.H, gi.W,
-                    gi.C, gi.A);
+    if (int rc = check_weights(w, gi)) return rc;
     if (w->F != BB_TRAIN_F || w->R < 0 || w->R > 9 || w->D < 1 || w->D > 64)
         return fail(BB_ERR_ARG, "the HIP trainer covers 16 filters, 0..9 blocks and a dense width of 1..64; got %d filters, %d blocks, "
                     "dense %d", w->F, w->R, w->D);
@@ -2335,11 +2320,6 @@ extern "C" int bb_trainer_create(const bb_train_config *cfg, const bb_net_weight
     if (cfg->max_batch <= 0 || cfg->max_batch > (1 << 20)) return fail(BB_ERR_ARG, "max_batch %d out of range", cfg->max_batch);
     if (!(cfg->epsilon >= 0.f && cfg->epsilon <= 1.f) || (cfg->epsilon != 0.f && !(cfg->alpha > 0.f && cfg->alpha < 1.f)))
         return fail(BB_ERR_ARG, "epsilon must lie in [0, 1] and alpha in (0, 1)");
-    const float *need[] = {w->conv0_k, w->conv0_b, w->conv0_bn, w->v_conv_k, w->v_conv_b, w->v_bn, w->v_d1_k, w->v_d1_b, w->v_d2_k,
-                           w->v_d2_b, w->p_conv_k, w->p_conv_b, w->p_bn, w->p_d_k, w->p_d_b};
-    for (const float *p : need)
-        if (!p) return fail(BB_ERR_ARG, "a weight block is missing");
-    if (w->R > 0 && (!w->blk_k || !w->blk_b || !w->blk_bn)) return fail(BB_ERR_ARG, "a weight block is missing");
     const int ndev = bb_device_count();
     if (ndev <= 0) return fail(BB_ERR_HIP, "no HIP device available (this library has no CPU fallback)");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(BB_ERR_ARG, "device %d out of range", cfg->device);
@@ -2531,11 +2511,9 @@ extern "C" int bb_trainer_load_engine(bb_trainer *t, bb_engine *e, void *stream)
     const float *p = t->prm;
     bb_net_weights w = {};
     w.H = e->info.H; w.W = e->info.W; w.C = t->C; w.F = BB_TRAIN_F; w.R = l.R; w.D = l.D; w.A = t->A;
-    w.conv0_k = p + l.conv0_k; w.conv0_b = p + l.conv0_b; w.conv0_bn = p + l.conv0_bn;
-    w.blk_k = p + l.blk_k; w.blk_b = p + l.blk_b; w.blk_bn = p + l.blk_bn;
-    w.v_conv_k = p + l.v_conv_k; w.v_conv_b = p + l.v_conv_b; w.v_bn = p + l.v_bn;
-    w.v_d1_k = p + l.v_d1_k; w.v_d1_b = p + l.v_d1_b; w.v_d2_k = p + l.v_d2_k; w.v_d2_b = p + l.v_d2_b;
-    w.p_conv_k = p + l.p_conv_k; w.p_conv_b = p + l.p_conv_b; w.p_bn = p + l.p_bn; w.p_d_k = p + l.p_d_k; w.p_d_b = p + l.p_d_b;
+#define X(name, kind, units, per) w.name = p + l.name;
+    BB_NET_BLOCKS(X)
+#undef X
     return load_weights_device(e, &w, (hipStream_t)stream, "bb_trainer_load_engine");
 }
 

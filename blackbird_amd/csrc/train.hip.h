@@ -21,6 +21,7 @@
 // that the records do not.  Both sources give the kernels the same floats in the same order: batch i of an epoch is, bit for
 // bit, the bb_trainer_step the per-batch loop would have made.
 #pragma once
+#include "../../include/blackbird_hip.h"
 #include "examples.hip.h"
 #include "games.hip.h"
 #include "rng.hip.h"
@@ -33,8 +34,11 @@
 
 struct TrainLayout {
     int R, D;
-    int conv0_k, conv0_b, conv0_bn, blk_k, blk_b, blk_bn, v_conv_k, v_conv_b, v_bn, v_d1_k, v_d1_b, v_d2_k, v_d2_b, p_conv_k,
-        p_conv_b, p_bn, p_d_k, p_d_b, count;
+    // where each block starts, in floats: one member per row of BB_NET_BLOCKS (blackbird_hip.h), named like its field
+#define X(name, kind, units, per) int name;
+    BB_NET_BLOCKS(X)
+#undef X
+    int count;
     int n_l2; // trainable variables whose name does not contain `bias`: the N of the L2 mean
 };
 

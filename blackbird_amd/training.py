@@ -162,25 +162,10 @@ class Trainer:
     def _flat_device(self):
         """The weights as ONE float32 device tensor in weights.flatten's order (weights.flat_fields), constants included, and
         {bb_net_weights field: its offset in floats}: what bb_load_weights_device's descriptor points into."""
-        bn = lambda prefix: [self._get(f'{prefix}/{f}').detach().reshape(-1) for f in W.BN_FIELDS]  # noqa: E731
-        one = lambda name: [self._get(name).detach().reshape(-1)]                                    # noqa: E731
-        blocks = [(i, j) for i in range(self.R) for j in (1, 2)]
-        parts = {
-            'conv0_k': one('resTower/conv_block/conv/kernel'), 'conv0_b': one('resTower/conv_block/conv/bias'),
-            'conv0_bn': bn('resTower/conv_block/batch_norm'),
-            'blk_k': [t for i, j in blocks for t in one(f'resTower/block_{i}/conv_{j}/kernel')],
-            'blk_b': [t for i, j in blocks for t in one(f'resTower/block_{i}/conv_{j}/bias')],
-            'blk_bn': [t for i, j in blocks for t in bn(f'resTower/block_{i}/batch_norm_{j}')],
-            'v_conv_k': one('value/convolution/kernel'), 'v_conv_b': one('value/convolution/bias'), 'v_bn': bn('value/batch_norm'),
-            'v_d1_k': one('value/dense_1/kernel'), 'v_d1_b': one('value/dense_1/bias'),
-            'v_d2_k': one('value/dense_2/kernel'), 'v_d2_b': one('value/dense_2/bias'),
-            'p_conv_k': one('policy/convolution/kernel'), 'p_conv_b': one('policy/convolution/bias'), 'p_bn': bn('policy/batch_norm'),
-            'p_d_k': one('policy/policy/kernel'), 'p_d_b': one('policy/policy/bias'),
-        }
         offsets, tensors, at = {}, [], 0
-        for name, shape in W.flat_fields(self.C, self.F, self.R, self.D, self.A):
-            offsets[name] = at
-            tensors += parts[name]
+        for field, shape, names, _ in W.blocks(self.C, self.F, self.R, self.D, self.A):
+            offsets[field] = at
+            tensors += [self._get(name).detach().reshape(-1) for name in names]
             at += int(np.prod(shape))
         flat = torch.cat([t.to(torch.float32) for t in tensors])
         assert int(flat.numel()) == at, (int(flat.numel()), at)

@@ -6,6 +6,8 @@ Variables carry the names the reference's TensorFlow graph gives them
 (SURVEY.md 2.3 / 8f-f4).  `flatten()` regroups them into the contiguous float32 blocks the C ABI
 (include/blackbird_hip.h: bb_net_weights) takes.
 """
+import re
+
 import numpy as np
 
 BN_FIELDS = ("gamma", "beta", "moving_mean", "moving_variance")
@@ -93,84 +95,78 @@ def infer_shape(w):
     return C, F, R, D, A
 
 
+# One row per float block of bb_net_weights, in the struct's order: the field, the block's shape in the letters of
+# infer_shape(), the TF variables it is made of back to back -- `{i}`, `{j}`: one per residual block i and convolution j = 1, 2
+# of it; `/*`: the four BN_FIELDS, in their order -- and the TF shape of one of those variables where it is not the block's own
+# shape behind the dimensions the expansions account for ([R][2] and [4]).
+BLOCKS = (
+    ("conv0_k", (3, 3, "C", "F"), "resTower/conv_block/conv/kernel", None),
+    ("conv0_b", ("F",), "resTower/conv_block/conv/bias", None),
+    ("conv0_bn", (4, "F"), "resTower/conv_block/batch_norm/*", None),
+    ("blk_k", ("R", 2, 3, 3, "F", "F"), "resTower/block_{i}/conv_{j}/kernel", None),
+    ("blk_b", ("R", 2, "F"), "resTower/block_{i}/conv_{j}/bias", None),
+    ("blk_bn", ("R", 2, 4, "F"), "resTower/block_{i}/batch_norm_{j}/*", None),
+    ("v_conv_k", ("F",), "value/convolution/kernel", (1, 1, "F", 1)),
+    ("v_conv_b", (1,), "value/convolution/bias", None),
+    ("v_bn", (4, 1), "value/batch_norm/*", None),
+    ("v_d1_k", ("D",), "value/dense_1/kernel", (1, "D")),
+    ("v_d1_b", ("D",), "value/dense_1/bias", None),
+    ("v_d2_k", ("D",), "value/dense_2/kernel", ("D", 1)),
+    ("v_d2_b", (1,), "value/dense_2/bias", None),
+    ("p_conv_k", ("F", 2), "policy/convolution/kernel", (1, 1, "F", 2)),
+    ("p_conv_b", (2,), "policy/convolution/bias", None),
+    ("p_bn", (4, 2), "policy/batch_norm/*", None),
+    ("p_d_k", (2, "A"), "policy/policy/kernel", None),
+    ("p_d_b", ("A",), "policy/policy/bias", None),
+)
+FIELDS = tuple(row[0] for row in BLOCKS)
+
+
+def blocks(C, F, R, D, A):
+    """BLOCKS at one shape: [(field, the block's shape, its TF variables in order, the TF shape of one of them)]."""
+    dims = dict(C=C, F=F, R=R, D=D, A=A)
+    rows = []
+    for field, shape, pattern, var_shape in BLOCKS:
+        shape = tuple(dims.get(n, n) for n in shape)
+        per_block, bn = "{i}" in pattern, pattern.endswith("/*")
+        names = [pattern.format(i=i, j=j) for i in range(R) for j in (1, 2)] if per_block else [pattern]
+        if bn:
+            names = [n[:-1] + f for n in names for f in BN_FIELDS]
+        var_shape = tuple(dims.get(n, n) for n in var_shape) if var_shape else shape[2 * per_block + bn:]
+        rows.append((field, shape, names, var_shape))
+    return rows
+
+
 def flatten(w):
     """TF-named dict -> dict of contiguous float32 blocks named like bb_net_weights' fields."""
-    C, F, R, D, A = infer_shape(w)
-
-    def bn(prefix):
-        return np.stack([np.asarray(w[f"{prefix}/{f}"], np.float32).ravel() for f in BN_FIELDS])
-
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-    out = {
-        "conv0_k": f32(w["resTower/conv_block/conv/kernel"]),
-        "conv0_b": f32(w["resTower/conv_block/conv/bias"]),
-        "conv0_bn": f32(bn("resTower/conv_block/batch_norm")),
-        "blk_k": f32(np.stack([np.stack([w[f"resTower/block_{i}/conv_{j}/kernel"] for j in (1, 2)])
-                               for i in range(R)]) if R else np.zeros((0, 2, 3, 3, F, F))),
-        "blk_b": f32(np.stack([np.stack([w[f"resTower/block_{i}/conv_{j}/bias"] for j in (1, 2)])
-                               for i in range(R)]) if R else np.zeros((0, 2, F))),
-        "blk_bn": f32(np.stack([np.stack([bn(f"resTower/block_{i}/batch_norm_{j}") for j in (1, 2)])
-                                for i in range(R)]) if R else np.zeros((0, 2, 4, F))),
-        "v_conv_k": f32(w["value/convolution/kernel"]).reshape(F),
-        "v_conv_b": f32(w["value/convolution/bias"]).reshape(1),
-        "v_bn": f32(bn("value/batch_norm")),
-        "v_d1_k": f32(w["value/dense_1/kernel"]).reshape(D),
-        "v_d1_b": f32(w["value/dense_1/bias"]).reshape(D),
-        "v_d2_k": f32(w["value/dense_2/kernel"]).reshape(D),
-        "v_d2_b": f32(w["value/dense_2/bias"]).reshape(1),
-        "p_conv_k": f32(w["policy/convolution/kernel"]).reshape(F, 2),
-        "p_conv_b": f32(w["policy/convolution/bias"]).reshape(2),
-        "p_bn": f32(bn("policy/batch_norm")),
-        "p_d_k": f32(w["policy/policy/kernel"]).reshape(2, A),
-        "p_d_b": f32(w["policy/policy/bias"]).reshape(A),
-    }
+    out = {}
+    for field, shape, names, _ in blocks(*infer_shape(w)):
+        parts = [np.ascontiguousarray(w[n], dtype=np.float32) for n in names]
+        if len(parts) != 1:   # (one variable: the block is that variable, reshaped)
+            parts = [np.concatenate([np.zeros(0, np.float32)] + [p.ravel() for p in parts])]
+        out[field] = parts[0].reshape(shape)
     return out
 
 
 def flat_fields(C, F, R, D, A):
     """(bb_net_weights field, shape) in the struct's order: how bb_trainer_read lays one flat vector out."""
-    return [("conv0_k", (3, 3, C, F)), ("conv0_b", (F,)), ("conv0_bn", (4, F)), ("blk_k", (R, 2, 3, 3, F, F)),
-            ("blk_b", (R, 2, F)), ("blk_bn", (R, 2, 4, F)), ("v_conv_k", (F,)), ("v_conv_b", (1,)), ("v_bn", (4, 1)),
-            ("v_d1_k", (D,)), ("v_d1_b", (D,)), ("v_d2_k", (D,)), ("v_d2_b", (1,)), ("p_conv_k", (F, 2)), ("p_conv_b", (2,)),
-            ("p_bn", (4, 2)), ("p_d_k", (2, A)), ("p_d_b", (A,))]
+    return [(field, shape) for field, shape, _, _ in blocks(C, F, R, D, A)]
 
 
 def unflatten(vec, C, F, R, D, A):
     """The inverse of flatten() for one flat float32 vector in flat_fields' order: the TF-named dict, fresh arrays."""
     vec = np.asarray(vec)
-    blocks, at = {}, 0
-    for name, shape in flat_fields(C, F, R, D, A):
-        n = int(np.prod(shape))
-        blocks[name] = vec[at:at + n].reshape(shape)
-        at += n
+    w, at = {}, 0
+    for _, _, names, var_shape in blocks(C, F, R, D, A):
+        n = int(np.prod(var_shape))
+        for name in names:
+            w[name] = vec[at:at + n].reshape(var_shape).copy()
+            at += n
     assert at == vec.size, (at, vec.size)
-    w = {}
-
-    def bn(prefix, block):
-        for i, f in enumerate(BN_FIELDS):
-            w[f"{prefix}/{f}"] = block[i].copy()
-
-    w["resTower/conv_block/conv/kernel"] = blocks["conv0_k"].copy()
-    w["resTower/conv_block/conv/bias"] = blocks["conv0_b"].copy()
-    bn("resTower/conv_block/batch_norm", blocks["conv0_bn"])
-    for i in range(R):
-        for j in (1, 2):
-            w[f"resTower/block_{i}/conv_{j}/kernel"] = blocks["blk_k"][i, j - 1].copy()
-            w[f"resTower/block_{i}/conv_{j}/bias"] = blocks["blk_b"][i, j - 1].copy()
-            bn(f"resTower/block_{i}/batch_norm_{j}", blocks["blk_bn"][i, j - 1])
-    w["value/convolution/kernel"] = blocks["v_conv_k"].reshape(1, 1, F, 1).copy()
-    w["value/convolution/bias"] = blocks["v_conv_b"].copy()
-    bn("value/batch_norm", blocks["v_bn"])
-    w["value/dense_1/kernel"] = blocks["v_d1_k"].reshape(1, D).copy()
-    w["value/dense_1/bias"] = blocks["v_d1_b"].copy()
-    w["value/dense_2/kernel"] = blocks["v_d2_k"].reshape(D, 1).copy()
-    w["value/dense_2/bias"] = blocks["v_d2_b"].copy()
-    w["policy/convolution/kernel"] = blocks["p_conv_k"].reshape(1, 1, F, 2).copy()
-    w["policy/convolution/bias"] = blocks["p_conv_b"].copy()
-    bn("policy/batch_norm", blocks["p_bn"])
-    w["policy/policy/kernel"] = blocks["p_d_k"].copy()
-    w["policy/policy/bias"] = blocks["p_d_b"].copy()
-    return w
+    # in init_weights' order: a residual block's variables stand together, where the struct has all kernels, then all biases ...
+    block_of = lambda name: [int(x) for x in re.findall(r"_(\d+)/", name)] if "/block_" in name else None  # noqa: E731
+    tower = iter(sorted((name for name in w if block_of(name)), key=block_of))   # (stable: kernel, bias, batch norm of each i, j)
+    return {name: w[name] for name in (next(tower) if block_of(name) else name for name in w)}
 
 
 def save_npz(path, w):

@@ -114,6 +114,31 @@ typedef struct {
     const float *p_d_b;    /* [A] */
 } bb_net_weights;
 
+/* The float blocks of bb_net_weights once more, as a table in the struct's order: X(field, kind, units, floats per unit).  A
+ * block is `units` equal pieces back to back; the counts are in terms of the shape fields, which the place that expands the
+ * table names C, F, R, D, A.  A kernel unit is one variable of the L2 term, a bias unit one that is not, and a batch-norm unit
+ * is [4][n]: its first half (gamma, beta) two trainable variables, its second half (moving mean, variance) constants. */
+enum { BB_BLOCK_KERNEL = 0, BB_BLOCK_BIAS = 1, BB_BLOCK_BN = 2 };
+#define BB_NET_BLOCKS(X)                          \
+    X(conv0_k,  BB_BLOCK_KERNEL, 1,     9 * C * F) \
+    X(conv0_b,  BB_BLOCK_BIAS,   1,     F)         \
+    X(conv0_bn, BB_BLOCK_BN,     1,     4 * F)     \
+    X(blk_k,    BB_BLOCK_KERNEL, 2 * R, 9 * F * F) \
+    X(blk_b,    BB_BLOCK_BIAS,   2 * R, F)         \
+    X(blk_bn,   BB_BLOCK_BN,     2 * R, 4 * F)     \
+    X(v_conv_k, BB_BLOCK_KERNEL, 1,     F)         \
+    X(v_conv_b, BB_BLOCK_BIAS,   1,     1)         \
+    X(v_bn,     BB_BLOCK_BN,     1,     4 * 1)     \
+    X(v_d1_k,   BB_BLOCK_KERNEL, 1,     D)         \
+    X(v_d1_b,   BB_BLOCK_BIAS,   1,     D)         \
+    X(v_d2_k,   BB_BLOCK_KERNEL, 1,     D)         \
+    X(v_d2_b,   BB_BLOCK_BIAS,   1,     1)         \
+    X(p_conv_k, BB_BLOCK_KERNEL, 1,     F * 2)     \
+    X(p_conv_b, BB_BLOCK_BIAS,   1,     2)         \
+    X(p_bn,     BB_BLOCK_BN,     1,     4 * 2)     \
+    X(p_d_k,    BB_BLOCK_KERNEL, 1,     2 * A)     \
+    X(p_d_b,    BB_BLOCK_BIAS,   1,     A)
+
 /* ---- engine -------------------------------------------------------------------------------- */
 typedef struct {
     int32_t game;          /* BB_GAME_* */
@@ -193,7 +218,8 @@ int bb_create(const bb_config *cfg, bb_engine **out);
  * the batched GenerateTrainingSamples uses this to cap its concurrency.  BB_ERR_CAPACITY if not even one slot fits. */
 int bb_fit_slots(const bb_config *cfg, int *n_slots_out, uint64_t *bytes_per_slot_out);
 int bb_destroy(bb_engine *e);
-/* Network.__init__/loadModel (Network.py:10-28, 100-112): install weights for BB_EVAL_NET */
+/* Network.__init__/loadModel (Network.py:10-28, 100-112): install weights for BB_EVAL_NET.  BB_ERR_ARG, the engine left as it
+ * was: a shape that is not the game's or out of range, a null weight block (blk_* may be null where R == 0) */
 int bb_load_weights(bb_engine *e, const bb_net_weights *w);
 /* bb_load_weights for weights that are in DEVICE memory (on request: nothing calls it unless asked).  w_dev's shape fields are
  * as for bb_load_weights; its pointers are device pointers on the engine's device, which must be the current device, and need to

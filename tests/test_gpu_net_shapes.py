@@ -319,8 +319,13 @@ def test_refused_shapes_leave_the_engine_as_it_was():
         before = eng.net_eval(states=st)
         mode = eng.selfplay_mode()
         big = W.flatten(_weights(C4, 4, 64, F=32))  # (arrays large enough for whatever a refused shape names)
-        for shape in (dict(F=24), dict(F=0), dict(D=0), dict(D=65), dict(R=-1)):
+        cases = [(s, ()) for s in (dict(F=24), dict(F=0), dict(D=0), dict(D=65), dict(R=-1))]
+        cases += [(dict(), ("p_bn",)), (dict(R=4), ("blk_k",))]  # a block the shape needs, not given
+        for shape, missing in cases:
             w, keep = _struct(gi, big, **shape)
+            for name in missing:
+                setattr(w, name, None)
+                shape = dict(shape, missing=missing)
             rc = _lib.lib().bb_load_weights(eng.h, ctypes.byref(w))
             assert rc == _lib.ERR_ARG, (shape, rc)
             assert _lib.last_error(), shape
@@ -330,5 +335,14 @@ def test_refused_shapes_leave_the_engine_as_it_was():
             assert all(np.array_equal(x, y) for x, y in zip(before, after)), shape
             assert eng.selfplay_mode() == mode and eng.net_form() == 2, shape
             del keep
+        # without residual blocks there is nothing in blk_*: accepted with all three null, and the network they leave out of
+        flat0 = W.flatten(_weights(C4, 0, 16))
+        w, keep = _struct(gi, flat0)
+        for name in ("blk_k", "blk_b", "blk_bn"):
+            setattr(w, name, None)
+        assert w.R == 0 and _lib.lib().bb_load_weights(eng.h, ctypes.byref(w)) == _lib.OK, _lib.last_error()
+        got = eng.net_eval(states=st)
+        eng.load_weights(flat0)
+        assert all(np.array_equal(x, y) for x, y in zip(got, eng.net_eval(states=st)))
     finally:
         eng.close()

@@ -50,6 +50,12 @@ def test_unflatten_inverts_flatten():
         assert list(back) == list(w)
         for k in w:
             assert back[k].shape == w[k].shape and np.array_equal(back[k], w[k]), k
+        if R in (0, 2):  # the PyTorch trainer's flat tensor (Trainer.load_into's descriptor points into it): the same vector
+            from blackbird_amd.training import Trainer
+            t_flat, offsets = Trainer(w, device="cpu")._flat_device()
+            assert t_flat.dtype.is_floating_point and t_flat.element_size() == 4 and np.array_equal(t_flat.numpy(), vec)
+            sums = np.cumsum([0] + [flat[n].size for n, _s in fields])
+            assert offsets == {n: int(at) for (n, _s), at in zip(fields, sums)} and sums[-1] == vec.size
 
 
 # ---- bb_trainer_create: arguments, and no GPU ---------------------------------------------------------------------------
