@@ -18,6 +18,7 @@ GAME_CONNECT4, GAME_TICTACTOE, GAME_DRAGONCHESS = 0, 1, 2
 MCTS_DYNAMIC, MCTS_FIXED = 0, 1
 EVAL_HASH, EVAL_NET, EVAL_ROLLOUT = 0, 1, 2
 NET_FORM_AUTO, NET_FORM_F32, NET_FORM_SPLIT = 0, 1, 2   # bb_config.net_form
+NET_EVAL_FUSED, NET_EVAL_SMALL, NET_EVAL_BATCH = 0, 1, 2   # bb_net_eval_structure
 LAUNCH_AUTO, LAUNCH_LOCKSTEP, LAUNCH_ROUNDS, LAUNCH_WAVE = 0, 1, 2, 3    # bb_config.launch (LAUNCH_WAVE: the search API in one launch)
 OPT_ADAM, OPT_MOMENTUM, OPT_SGD = 0, 1, 2                # bb_train_config.optimizer
 WEIGHTS_IMAGES = ("w0", "wt", "epi", "head", "x3")        # bb_weights_read's selector, BB_WEIGHTS_*: Engine.weights_image
@@ -29,7 +30,7 @@ OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NAN, ERR_CAPACITY, ERR_WEIGHTS = 0, -1, -2,
 EXPORTS = (
     "bb_game_info_get", "bb_last_error", "bb_device_count", "bb_game_legal", "bb_game_apply", "bb_game_winner",
     "bb_game_encode", "bb_game_initial", "bb_create", "bb_destroy", "bb_load_weights", "bb_get_counters",
-    "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked", "bb_run_sims_structure", "bb_search_rollouts", "bb_selfplay_rollouts",
+    "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval_structure", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked", "bb_run_sims_structure", "bb_search_rollouts", "bb_selfplay_rollouts",
     "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_set_starts", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
     "bb_examples_to_batch", "bb_examples_to_batch_sym", "bb_game_symmetries",
@@ -114,6 +115,7 @@ def lib():
     L.bb_timing_net.argtypes = [vp, ip, ip, ip, C.POINTER(C.c_double)]
     L.bb_selfplay_mode.argtypes = [vp]
     L.bb_net_form.argtypes = [vp]
+    L.bb_net_eval_structure.argtypes = [vp, ip, C.POINTER(C.c_int32)]
     L.bb_net_eval.argtypes = [vp, ip, vp, vp, vp, vp, vp, ip]
     L.bb_net_eval_keyed.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp, vp]
     L.bb_set_rng_stream.argtypes = [vp, C.c_uint64, C.c_uint32]
@@ -559,6 +561,13 @@ class Engine:
         """0 float32-MFMA fused tower, 1 general-filter launches, 2 fused tower on the bf16 matrix pipe (float32 by operand
         splitting), 3 general-filter launches with such tower layers (bb_net_form)."""
         return check(lib().bb_net_form(self.h))
+
+    def net_eval_structure(self, n):
+        """bb_net_eval_structure: NET_EVAL_FUSED, or for the launch-per-layer network NET_EVAL_SMALL / NET_EVAL_BATCH -- how a
+        net_eval call of n positions is cut into launches (the same bits either way).  Launches nothing."""
+        out = C.c_int32(-1)
+        check(lib().bb_net_eval_structure(self.h, int(n), C.byref(out)))
+        return out.value
 
     def timing_net(self, iters=50, noise=True, ablate=0):
         ms = C.c_double()

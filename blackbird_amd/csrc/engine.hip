@@ -821,6 +821,12 @@ static int load_general_weights(bb_engine *e, const bb_net_weights *w, const Net
     return BB_OK;
 }
 
+// How launch_gnet cuts a call of up to n_max positions at NCB filter blocks -- the ONE place that decides it.  Small batch: one
+// position x one filter block per wave (latency of a lone evaluation: 40 layers x ~25 us instead of x ~170 us at 256 filters);
+// every larger call, and every call whose size lives on the device (n_ptr), takes PPB positions x FBW filter blocks per wave.
+// bb_net_eval_structure reports it for a host-sized call.
+static bool gnet_small_launch(int n_max, int NCB, const int *n_ptr) { return (long)n_max * NCB <= 2048 && !n_ptr; }
+
 // n_ptr != nullptr: the batch size lives in device memory (<= n_max); slot_list maps batch entries to mailbox slots
 template <class G>
 static int launch_gnet(bb_engine *e, int n_max, const int *n_ptr, const int *slot_list, const typename G::State *states,
@@ -848,9 +854,7 @@ static int launch_gnet(bb_engine *e, int n_max, const int *n_ptr, const int *slo
         gx.act3[0] += (size_t)buf_offset * pos_bytes;
         gx.act3[1] += (size_t)buf_offset * pos_bytes;
     }
-    // small batch: one position x one filter block per wave (latency of a lone evaluation: 40 layers x ~25 us
-    // instead of x ~170 us at 256 filters)
-    const bool small = (long)n_max * g.NCB <= 2048 && !n_ptr;
+    const bool small = gnet_small_launch(n_max, g.NCB, n_ptr);
     constexpr int FBW3 = 4;
     // a workgroup's four waves take `per` neighbours along y (filter blocks, or groups of FBW of them) and 4 / per along x
     // (positions, or groups of PPB of them)
@@ -1097,6 +1101,13 @@ extern "C" int bb_net_eval(bb_engine *e, int n, const void *states, const int8_t
     if (!e->has_weights) return fail(BB_ERR_WEIGHTS, "bb_load_weights has not been called");
     HIPCHK(hipSetDevice(e->cfg.device));
     GAME_SWITCH(e->cfg.game, return net_eval<G>(e, n, states, planes, value_out, logits_out, policy_out, noise));
+}
+
+extern "C" int bb_net_eval_structure(bb_engine *e, int n, int32_t *out) {
+    if (!e || !out || n < 0) return fail(BB_ERR_ARG, "bb_net_eval_structure: an engine, n >= 0 and a place for the answer");
+    if (!e->has_weights) return fail(BB_ERR_WEIGHTS, "bb_load_weights has not been called");
+    *out = !e->general_net ? BB_NET_EVAL_FUSED : gnet_small_launch(n, e->gnet.NCB, nullptr) ? BB_NET_EVAL_SMALL : BB_NET_EVAL_BATCH;
+    return BB_OK;
 }
 
 extern "C" int bb_net_eval_keyed(bb_engine *e, int n, const void *states, const int8_t *planes, const uint32_t *game_ids,

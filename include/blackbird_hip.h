@@ -279,6 +279,16 @@ int bb_selfplay_rollouts(bb_engine *e, int on);
  * bit-identical; bb_config.net_form = BB_NET_FORM_F32 selects form 0 instead); 3 the launch-per-layer network with its tower
  * layers in the split-operand form of 2 (BB_NET_FORM_F32: form 1).  Negative: BB_ERR_*. */
 int bb_net_form(bb_engine *e);
+/* How a bb_net_eval / bb_net_eval_keyed call of n positions is cut into launches by the engine as it stands (after
+ * bb_load_weights): *out = BB_NET_EVAL_FUSED (bb_net_form 0 / 2), or, for the launch-per-layer network (bb_net_form 1 / 3),
+ * BB_NET_EVAL_SMALL (one position x one filter block per wave: the latency of few positions) or BB_NET_EVAL_BATCH (several
+ * positions x several filter blocks per wave: throughput).  Both give the same bits; self-play rounds, whose batch size lives
+ * on the device, always take BB_NET_EVAL_BATCH.  Launches nothing.  BB_ERR_ARG: a null argument or n < 0; BB_ERR_WEIGHTS:
+ * before bb_load_weights. */
+#define BB_NET_EVAL_FUSED 0
+#define BB_NET_EVAL_SMALL 1
+#define BB_NET_EVAL_BATCH 2
+int bb_net_eval_structure(bb_engine *e, int n, int32_t *out);
 
 /* Network.getEvaluation + getPolicy for n positions (Network.py:48-64; graph NetworkFactory.py:22-183).
  * Exactly one of states (packed) / planes (int8 [n][H][W][C], what AsInputArray returns) is non-NULL.

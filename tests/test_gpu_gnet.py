@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib, weights as W
-from tests.net_cases import boards_for
+from tests.net_cases import boards_for, dragonchess_positions
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -79,13 +79,7 @@ def test_dragonchess_general_filters(orc):
     flat = W.flatten(W.init_weights(17, 32, 2, 16, 4032, seed=13, perturb=True))
     eng = _lib.Engine(game, n_slots=2, sims_per_move=2, evaluator=_lib.EVAL_NET, max_plies=8)
     eng.load_weights(flat)
-    rng = np.random.RandomState(5)
-    n = 7
-    boards = np.zeros((n, 8, 8), dtype=np.int8)
-    for i in range(n):
-        m = rng.rand(8, 8) < 0.35
-        boards[i][m] = rng.choice([-6, -5, -4, -3, -2, -1, 1, 2], m.sum())
-    st = _lib.pack_dc(boards, rng.randint(1, 3, n), rng.randint(0, 3, n), rng.randint(0, 2, (n, 4)))
+    st = dragonchess_positions(np.random.RandomState(5), 7)
     planes = _lib.game_encode(game, st)
     v1, l1, p1 = eng.net_eval(states=st)
     ov, ol, op = orc.net_forward(orc.NetWeights(8, 8, 17, 32, 2, 16, 4032, flat), planes)

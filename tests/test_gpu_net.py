@@ -8,7 +8,7 @@ import pytest
 
 from blackbird_amd import _lib, weights as W
 
-from tests.net_cases import TOL, boards_for, selfplay_vs_oracle_tree as _selfplay_vs_oracle_tree
+from tests.net_cases import TOL, boards_for, dragonchess_positions, selfplay_vs_oracle_tree as _selfplay_vs_oracle_tree
 
 pytestmark = pytest.mark.gpu
 
@@ -57,13 +57,7 @@ def test_net_dc_vs_oracle(orc, form):
     eng = _lib.Engine(game, n_slots=2, sims_per_move=2, evaluator=_lib.EVAL_NET, max_plies=8, net_form=form)
     eng.load_weights(flat)
     assert eng.net_form() == (2 if form == _lib.NET_FORM_AUTO else 0)
-    rng = np.random.RandomState(5)
-    n = 11
-    boards = np.zeros((n, 8, 8), dtype=np.int8)
-    for i in range(n):
-        m = rng.rand(8, 8) < 0.35
-        boards[i][m] = rng.choice([-6, -5, -4, -3, -2, -1, 1, 2], m.sum())
-    st = _lib.pack_dc(boards, rng.randint(1, 3, n), rng.randint(0, 3, n), rng.randint(0, 2, (n, 4)))
+    st = dragonchess_positions(np.random.RandomState(5), 11)
     planes = _lib.game_encode(game, st)
     v1, l1, p1 = eng.net_eval(states=st)
     v2, l2, p2 = eng.net_eval(planes=planes)
@@ -278,11 +272,7 @@ def test_split_operand_envelope(orc, game):
         b, pl = boards_for(game, rng, 24)
         st = _lib.pack_grid(game, b, pl)
     else:
-        boards = np.zeros((8, 8, 8), dtype=np.int8)
-        for i in range(8):
-            m = rng.rand(8, 8) < 0.35
-            boards[i][m] = rng.choice([-6, -5, -4, -3, -2, -1, 1, 2], m.sum())
-        st = _lib.pack_dc(boards, rng.randint(1, 3, 8), rng.randint(0, 3, 8), rng.randint(0, 2, (8, 4)))
+        st = dragonchess_positions(rng, 8)
     planes = _lib.game_encode(game, st)
 
     def run(wts, what, tol=TOL, c64=4.0):

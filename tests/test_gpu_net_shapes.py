@@ -18,11 +18,10 @@ import numpy as np
 import pytest
 
 from blackbird_amd import _lib, weights as W
-from tests.net_cases import boards_for
+from tests.net_cases import eval_forms as _eval_forms, oracle_forward as _oracle, positions as _positions, within as _within
 from tests import selfplay_cases as SP
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
 ALPHA, EPS = 0.2, 0.3
 C4, TTT, DC = _lib.GAME_CONNECT4, _lib.GAME_TICTACTOE, _lib.GAME_DRAGONCHESS
 OG = {C4: 0, TTT: 1}
@@ -33,52 +32,6 @@ N_POS = 7  # positions per bb_net_eval call (and 1: the first of them alone)
 def _weights(game, R, D, F=16, seed=21):
     gi = _lib.game_info(game)
     return W.init_weights(gi.C, F, R, D, gi.A, seed=seed, perturb=True)
-
-
-def _positions(game, n, seed=5):
-    rng = np.random.RandomState(seed)
-    if game == DC:
-        boards = np.zeros((n, 8, 8), dtype=np.int8)
-        for i in range(n):
-            m = rng.rand(8, 8) < 0.35
-            boards[i][m] = rng.choice([-6, -5, -4, -3, -2, -1, 1, 2], m.sum())
-        return _lib.pack_dc(boards, rng.randint(1, 3, n), rng.randint(0, 3, n), rng.randint(0, 2, (n, 4)))
-    b, pl = boards_for(game, rng, n)
-    return _lib.pack_grid(game, b, pl)
-
-
-def _oracle(orc, game, flat, planes):
-    gi = _lib.game_info(game)
-    F, R, D = flat["conv0_k"].shape[3], flat["blk_k"].shape[0], flat["v_d1_k"].shape[0]
-    return orc.net_forward(orc.NetWeights(gi.H, gi.W, gi.C, F, R, D, gi.A, flat), planes)
-
-
-def _within(got, ref, what):
-    (v, l, p), (ov, ol, op) = got, ref
-    ev, ep = float(np.max(np.abs(v - ov))), float(np.max(np.abs(p - op)))
-    el = float(np.max(np.abs(l - ol) / np.maximum(1.0, np.abs(ol))))
-    print(f"{what}: value {ev:.2e} logits {el:.2e} policy {ep:.2e}")
-    assert ev <= TOL and el <= TOL and ep <= TOL, what
-
-
-def _eval_forms(orc, game, flat, forms, st):
-    """bb_net_eval of st and of st[:1] on one engine per form, each against the oracle (computed once); {name: outputs}"""
-    planes = _lib.game_encode(game, st)
-    ref = _oracle(orc, game, flat, planes)
-    outs = {}
-    for name, kw, net_form in forms:
-        eng = _lib.Engine(game, n_slots=4, sims_per_move=2, evaluator=_lib.EVAL_NET, max_plies=8, **kw)
-        try:
-            eng.load_weights(flat)
-            assert eng.net_form() == net_form, name
-            outs[name] = eng.net_eval(states=st)
-            one = eng.net_eval(states=st[:1])
-        finally:
-            eng.close()
-        _within(outs[name], ref, name)
-        _within(one, tuple(a[:1] for a in ref), name + ", n = 1")
-        assert all(np.array_equal(a, b[:1]) for a, b in zip(one, outs[name])), name  # (a position alone: the same bits)
-    return outs
 
 
 SHAPES = [(2, 1), (2, 15), (2, 16), (2, 17), (2, 32), (2, 33), (2, 64), (0, 16), (5, 16), (9, 16)]  # (R, D)
