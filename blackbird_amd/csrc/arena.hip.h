@@ -1,6 +1,6 @@
 // arena.hip.h -- the match loop of Blackbird.TestModels (Blackbird.py:177-216) on the device: what the arena keeps per game and the
 // two small kernels that stand where the host loop of blackbird_amd/arena.py reads results back.  Everything that touches a search
-// tree is an existing launch of the two engines (set_roots, k_add_sims, the search, sample, move_roots: engine.hip enqueues them on
+// tree is an existing launch of the two engines (set_roots, k_add_sims, the search, sample, move_roots: host_arena.hip.h enqueues them on
 // the engines' own streams); the kernels here only read the engines' out_action rows and write the arena's own arrays, which are
 // then the arguments of those launches.  One thread per slot, plain stores: a game is owned by one thread.
 #pragma once

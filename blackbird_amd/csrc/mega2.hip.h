@@ -21,7 +21,7 @@
 #define MEGA_RMAX 4          // residual blocks whose weights fit the 160 KiB LDS next to the activations
 // packed head parameters that fit next to them.  Every array of NetDev::head is padded to 4 floats (bb_load_weights), so a 16-filter
 // network packs 88 + 3 * pad4(D) floats for Connect4 and 96 + 3 * pad4(D) for TicTacToe: 136 / 144 at the default D = 16, and
-// D <= 32 fits (Connect4 184; TicTacToe exactly 192 at D = 29 .. 32).  D >= 33 plays as rounds (engine.hip selfplay_structure).
+// D <= 32 fits (Connect4 184; TicTacToe exactly 192 at D = 29 .. 32).  D >= 33 plays as rounds (host_selfplay.hip.h selfplay_structure).
 #define MEGA_HEAD_FLOATS 192
 
 // Waves of the workgroup = NETW network waves + the tree waves.  float32-MFMA network: 12 waves (8 + 4) at 168 VGPRs;

@@ -185,7 +185,7 @@ __device__ __forceinline__ void wide_head_stats(WideHead &h, PK pdk, PK pdb, int
 // Every lane ends with the same bits; the tree does not depend on how positions are packed into waves.
 __device__ __forceinline__ float pooled_sum(float v) { return wave_sum_f32(v); }
 
-// ---- evaluation cache (persistent kernels: Connect4 here, DragonChess below; the table is device memory of the engine: engine.hip) ----
+// ---- evaluation cache (persistent kernels: Connect4 here, DragonChess below; the table is device memory of the engine: host_engine.hip.h) ----
 // Two-way set-associative: 2^log2 entries of 64 bytes in buckets of two, a bucket is ONE 128-byte line and is picked by the top
 // bits of bb_mix64(G::cache_key).  An entry (a "way") is four 16-byte chunks {u64 key, f32, f32} that hold [value, p0 .. p6], the
 // network's value and its priors BEFORE the prior noise: chunk c carries floats 2c and 2c + 1.  Every chunk is written and read

@@ -16,7 +16,7 @@
 // or no simulations left: nothing changes that before the move) ends the ply's simulations, and a slot without a game (it has
 // played its last one: only its own move refills a slot) ends the call.
 //
-// `move` = 0 is the host's split of ONE ply that is longer than a launch may be (selfplay_wave_rollout, engine.hip): `sims` steps
+// `move` = 0 is the host's split of ONE ply that is longer than a launch may be (selfplay_wave_rollout, host_selfplay.hip.h): `sims` steps
 // and no move, the last leaf stays pending in the mailbox exactly as it does between two lock-step launches, and the next launch's
 // first phase_apply takes it.
 #pragma once

@@ -62,7 +62,7 @@ struct ExampleHdr { // 16 bytes, then packed state, then u32 visits[S]
 // ---- every array that has one run of elements per game slot, declared ONCE: a new one is one new row --------------------
 // A row is X(type, name, per): `per` elements per slot, in names the expanding context defines -- S = G::S, MP = G::MAXPATH,
 // PS = the policy stride (G::A for DragonChess, else G::S), ANC = the ancestor stride (max_plies + 2) * (DragonChess ? 2 : 1).
-// TreeDev's pointer members, the allocation and the slot-range views (engine.hip) and the persistent kernels' LDS shadows
+// TreeDev's pointer members, the allocation and the slot-range views (host_engine.hip.h) and the persistent kernels' LDS shadows
 // (mega2.hip.h, mega_dc.hip.h) are generated from the rows.  The lists are the runs of arrays between TreeDev's other members,
 // in its order: TreeDev is an argument of every kernel, and moving a member changes SGPR counts and spills of a dozen of them.
 // Macros B / Q / R: kept in LDS by both persistent kernels / the Connect4 queue kernel only / the same in its REC form only.

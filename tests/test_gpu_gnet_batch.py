@@ -1,4 +1,4 @@
-"""-m gpu: the BATCH launch of the launch-per-layer network (gnet.hip.h, gnet_x3.hip.h, launch_gnet in engine.hip) for every
+"""-m gpu: the BATCH launch of the launch-per-layer network (gnet.hip.h, gnet_x3.hip.h, launch_gnet in host_weights.hip.h) for every
 game, width and form.
 
 launch_gnet cuts a call one of two ways: one position x one filter block per wave (small launch), or PPB positions x FBW

@@ -2,7 +2,7 @@
 
 bb_load_weights takes any D in 1 .. 64 and any R >= 0.  Every network path ends in head_one (net.hip.h), which puts dense unit d
 on lane d behind `lane < D` and folds dense_2 over row 0 of the wave at D <= 16 and over the whole wave above; and
-selfplay_structure (engine.hip) leaves the persistent kernels when the network does not fit their LDS copy: R > 4 or more
+selfplay_structure (host_selfplay.hip.h) leaves the persistent kernels when the network does not fit their LDS copy: R > 4 or more
 than 192 packed head parameters for Connect4 / TicTacToe (D >= 33), R > 8 or more than 12288 for DragonChess (D >= 41).
 Here:
   * bb_net_eval against the oracle (1e-5, the bounds of test_gpu_gnet._check) over D and R, in every form of the network;

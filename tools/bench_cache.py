@@ -29,7 +29,7 @@ class Engine(_lib.Engine):
         if rounds:
             kw["launch"] = _lib.LAUNCH_ROUNDS
         super().__init__(*a, **kw)
-        # the table this engine owns, as engine.hip eval_cache_log2_of sizes it (the defaults are those of the in-tree build)
+        # the table this engine owns, as eval_cache_log2_of (csrc/host_engine.hip.h) sizes it (the defaults are those of the in-tree build)
         dc = self.game == _lib.GAME_DRAGONCHESS
         k = min(max(int(os.environ.get("BB_EVAL_CACHE_LOG2") or (24 if dc else 27)), 10), 32)
         if os.environ.get("BB_EVAL_CACHE", "1").strip() in ("0", ""):
