@@ -320,7 +320,9 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
     whole epoch is one call, HipTrainer.epoch_records (bb_trainer_epoch): the step's kernels read the records themselves, no
     batch tensor is formed and Python is not visited per batch -- the same steps bit for bit, numpy's generator consumed alike.
     It is not the default because it measured no faster on the MI355X than the per-batch loop, whose launches already queue
-    ahead of the GPU (README, training row).  merge=True and the PyTorch trainer take the per-batch loop whatever it says."""
+    ahead of the GPU (README, training row).  merge=True and the PyTorch trainer take the per-batch loop whatever it says.  A
+    DragonChess model with the hip backend (NetworkConfig['training']['hip_games'] = 'all') trains through the per-batch loop;
+    fused=True is a ValueError for it (the records source does not cover the game), raised before any step is made."""
     from .training import epoch_order
     if merge and (model.Game.GAME_ID if examples is None else examples.game) not in _lib.GRID:
         raise ValueError('merge=True covers Connect4 and TicTacToe: a DragonChess position is keyed by its 64-byte board, castle '

@@ -2,7 +2,8 @@
 tower (bb_net_eval) on the int8 planes AsInputArray returns; weights live in an .npz with the
 reference's TensorFlow variable names instead of a TF checkpoint.  train() is the step right after
 the hot path: PyTorch-ROCm optimiser over the same parameters (or, with
-NetworkConfig['training']['backend'] = 'hip', the HIP training kernels), then the new weights are
+NetworkConfig['training']['backend'] = 'hip', the HIP training kernels -- Connect4 and TicTacToe; DragonChess too with
+NetworkConfig['training']['hip_games'] = 'all'), then the new weights are
 pushed back into the engine."""
 import os
 
@@ -122,11 +123,15 @@ class Network:
             if handoff == 'device' and W.infer_shape(self._weights)[1] != 16:
                 raise ValueError("NetworkConfig['training']['handoff'] = 'device' covers %s; this network has %d filters.  Use "
                                  "the 'host' hand-off for it." % (self.HANDOFF_LIMITS, W.infer_shape(self._weights)[1]))
+            hip_games = cfg.get('hip_games', 'dense')
+            if hip_games not in training.HIP_GAMES:
+                raise ValueError("NetworkConfig['training']['hip_games'] is 'dense' or 'all', got %r" % (hip_games,))
             self._handoff = handoff
-            if backend == 'hip' and not training.hip_trainer_supports(self._weights):
+            if backend == 'hip' and not training.hip_trainer_supports(self._weights, hip_games):
                 raise ValueError("NetworkConfig['training']['backend'] = 'hip' covers %s; this network has shape "
                                  "(planes, filters, blocks, dense, actions) = %r.  Use the 'torch' backend for it."
-                                 % (training.HIP_TRAINER_LIMITS, W.infer_shape(self._weights)))
+                                 % (training.HIP_TRAINER_LIMITS if hip_games == 'dense' else training.HIP_TRAINER_LIMITS_ALL,
+                                    W.infer_shape(self._weights)))
             make = training.HipTrainer if backend == 'hip' else training.Trainer
             self._trainer = make(self._weights, alpha=self.alpha, epsilon=self.epsilon,
                                  optimizer=cfg.get('optimizer', 'adam'), momentum=cfg.get('momentum', 0.9))

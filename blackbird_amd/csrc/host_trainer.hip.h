@@ -10,6 +10,7 @@ struct bb_trainer {
     float *prm, *slot_m, *slot_v, *grads, *slabs, *le, *lp, *loss;
     uint8_t *kind;
     TrainAux *aux;
+    float *aux_wide; // DragonChess only: noise[A], then L[A] (k_train_prep_wide); null for the dense games
     float *eval_rows; // scratch of bb_trainer_eval for callers that pass no rows_out / flags_out: grows, never shrinks
     uint8_t *eval_flags;
     size_t eval_cap;  // rows the scratch holds
@@ -30,12 +31,21 @@ static TrainLayout train_layout(int C, int R, int D, int A) {
     return l;
 }
 
-// `using G = ` the trainer's game (bb_trainer_create admits these two only) around the statements given, GAME_SWITCH's way
+// `using G = ` the trainer's dense game around the statements given, GAME_SWITCH's way.  DragonChess (trainer_is_wide) has a
+// dispatch of its own wherever it is covered, so that neither TrainRecords<DragonChess> nor k_train_eval<DragonChess, ...> is made.
 #define TRAINER_SWITCH(t, ...)                                                   \
     switch ((t)->cfg.game) {                                                     \
     case BB_GAME_CONNECT4: { using G = Connect4; __VA_ARGS__; }                  \
     default: { using G = TicTacToe; __VA_ARGS__; }                               \
     }
+
+static bool trainer_is_wide(const bb_trainer *t) { return t->cfg.game == BB_GAME_DRAGONCHESS; }
+static int trainer_not_wide(const bb_trainer *t, const char *who) {
+    if (trainer_is_wide(t))
+        return fail(BB_ERR_ARG, "%s: the records source and the scorer do not cover DragonChess (compact child lists: a row's share of "
+                    "an action is a search); step it from batch tensors with bb_trainer_step", who);
+    return BB_OK;
+}
 
 // the entry points that launch do not switch devices: the caller's current device must be the trainer's
 static int trainer_on_device(const bb_trainer *t) {
@@ -50,6 +60,13 @@ static int trainer_lds(bb_trainer *t) { // (the same dynamic LDS whichever sourc
     t->lds_bytes = (size_t)train_lds_floats<G>(t->lay.R) * sizeof(float);
     HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainTensors<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
     HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainRecords<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
+    return BB_OK;
+}
+
+static int trainer_lds_wide(bb_trainer *t) {
+    using G = DragonChess;
+    t->lds_bytes = (size_t)train_lds_floats<G>(t->lay.R) * sizeof(float);
+    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad_wide<G, TrainTensors<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
     return BB_OK;
 }
 
@@ -71,26 +88,34 @@ static int trainer_alloc(bb_trainer *t, const bb_net_weights *w) {
     HIPCHK(hipMemset(t->grads, 0, cb));
     HIPCHK(hipMemset(t->loss, 0, 4 * sizeof(float)));
     HIPCHK(hipMemset(t->aux, 0, sizeof(TrainAux)));
+    if (trainer_is_wide(t)) {
+        if (take(t->aux_wide, 2 * (size_t)t->A)) return BB_ERR_HIP;
+        HIPCHK(hipMemset(t->aux_wide, 0, 2 * (size_t)t->A * sizeof(float)));
+    }
     const NetBlocks tb = net_blocks(t->C, BB_TRAIN_F, l.R, l.D, t->A); // (what train_layout took l from)
     const std::vector<uint8_t> kind = net_block_kinds(tb);
     HIPCHK(hipMemcpy(t->kind, kind.data(), kind.size(), hipMemcpyHostToDevice));
     for (int i = 0; i < NET_BLOCKS; i++)
         if (const int n = tb.b[i].count())
             HIPCHK(hipMemcpy(t->prm + tb.b[i].at, net_block(*w, i), (size_t)n * sizeof(float), hipMemcpyDefault));
+    if (trainer_is_wide(t)) return trainer_lds_wide(t);
     TRAINER_SWITCH(t, return trainer_lds<G>(t));
 }
 
 extern "C" int bb_trainer_create(const bb_train_config *cfg, const bb_net_weights *w, bb_trainer **out) {
     if (!cfg || !w || !out) return fail(BB_ERR_ARG, "null argument");
     *out = nullptr;
-    if (cfg->game != BB_GAME_CONNECT4 && cfg->game != BB_GAME_TICTACTOE)
-        return fail(BB_ERR_ARG, "the HIP trainer covers Connect4 and TicTacToe, not game %d", cfg->game);
+    if (cfg->game != BB_GAME_CONNECT4 && cfg->game != BB_GAME_TICTACTOE && cfg->game != BB_GAME_DRAGONCHESS)
+        return fail(BB_ERR_ARG, "the HIP trainer covers Connect4, TicTacToe and DragonChess, not game %d", cfg->game);
     bb_game_info gi;
     bb_game_info_get(cfg->game, &gi);
     if (int rc = check_weights(w, gi)) return rc;
-    if (w->F != BB_TRAIN_F || w->R < 0 || w->R > 9 || w->D < 1 || w->D > 64)
-        return fail(BB_ERR_ARG, "the HIP trainer covers 16 filters, 0..9 blocks and a dense width of 1..64; got %d filters, %d blocks, "
-                    "dense %d", w->F, w->R, w->D);
+    // DragonChess: the blocks whose k_train_grad_wide workgroup fits a CU's LDS (train_max_blocks, train.hip.h)
+    const int max_blocks = cfg->game == BB_GAME_DRAGONCHESS ? train_max_blocks<DragonChess>() : 9;
+    if (w->F != BB_TRAIN_F || w->R < 0 || w->R > max_blocks || w->D < 1 || w->D > 64)
+        return fail(BB_ERR_ARG, "the HIP trainer covers 16 filters, 0..%d blocks%s and a dense width of 1..64; got %d filters, %d blocks, "
+                    "dense %d", max_blocks, cfg->game == BB_GAME_DRAGONCHESS ? " (DragonChess: the 160 KB of LDS of a CU)" : "", w->F,
+                    w->R, w->D);
     if (cfg->optimizer != BB_OPT_ADAM && cfg->optimizer != BB_OPT_MOMENTUM && cfg->optimizer != BB_OPT_SGD)
         return fail(BB_ERR_ARG, "unknown optimizer %d", cfg->optimizer);
     if (cfg->max_batch <= 0 || cfg->max_batch > (1 << 20)) return fail(BB_ERR_ARG, "max_batch %d out of range", cfg->max_batch);
@@ -124,16 +149,9 @@ extern "C" int bb_trainer_destroy(bb_trainer *t) {
     return BB_OK;
 }
 
-// One step's three launches on `st`, the batch read through `src` (train.hip.h): what bb_trainer_step and every batch of
-// bb_trainer_epoch enqueue.  Host state moves as the launches are made: the noise counter, Adam's step count and lr_t.
-template <class G, class Src>
-static void trainer_launch(bb_trainer *t, int n, const Src &src, const float *noise, double lr, int apply, float *loss_out, hipStream_t st) {
+// The last of a step's three launches: Adam's step count and lr_t move here, as the launch is made.
+static void trainer_launch_apply(bb_trainer *t, int n, double lr, int apply, float *loss_out, hipStream_t st) {
     const TrainLayout &l = t->lay;
-    const float eps = t->cfg.epsilon;
-    k_train_prep<G, Src><<<1, BB_TRAIN_THREADS, 0, st>>>(n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed, t->calls,
-                                                         t->aux);
-    t->calls++;
-    k_train_grad<G, Src><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, src, n, eps, t->slabs, t->le, t->lp);
     float rate = (float)lr;
     if (apply) {
         t->t++;
@@ -145,6 +163,34 @@ static void trainer_launch(bb_trainer *t, int n, const Src &src, const float *no
         apply != 0, t->le, t->lp, t->aux, t->loss, loss_out);
 }
 
+// One step's three launches on `st`, the batch read through `src` (train.hip.h): what bb_trainer_step and every batch of
+// bb_trainer_epoch enqueue.  Host state moves as the launches are made: the noise counter, Adam's step count and lr_t.
+template <class G, class Src>
+static void trainer_launch(bb_trainer *t, int n, const Src &src, const float *noise, double lr, int apply, float *loss_out, hipStream_t st) {
+    const TrainLayout &l = t->lay;
+    const float eps = t->cfg.epsilon;
+    k_train_prep<G, Src><<<1, BB_TRAIN_THREADS, 0, st>>>(n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed, t->calls,
+                                                         t->aux);
+    t->calls++;
+    k_train_grad<G, Src><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, src, n, eps, t->slabs, t->le, t->lp);
+    trainer_launch_apply(t, n, lr, apply, loss_out, st);
+}
+
+// The DragonChess step: k_train_prep_wide on 1 + ceil(A / 256) workgroups, k_train_grad_wide, then the same k_train_apply.
+static void trainer_launch_wide(bb_trainer *t, int n, const TrainTensors<DragonChess> &src, const float *noise, double lr, int apply,
+                                float *loss_out, hipStream_t st) {
+    using G = DragonChess;
+    const TrainLayout &l = t->lay;
+    const float eps = t->cfg.epsilon;
+    float *aux_noise = t->aux_wide, *aux_L = t->aux_wide + G::A;
+    k_train_prep_wide<G, TrainTensors<G>><<<1 + nblk((size_t)G::A, BB_TRAIN_THREADS), BB_TRAIN_THREADS, 0, st>>>(
+        n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed, t->calls, t->aux, aux_noise, aux_L);
+    t->calls++;
+    k_train_grad_wide<G, TrainTensors<G>><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, aux_noise, aux_L, src, n, eps, t->slabs,
+                                                                                   t->le, t->lp);
+    trainer_launch_apply(t, n, lr, apply, loss_out, st);
+}
+
 extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const float *value, const float *policy, const float *noise,
                                double lr, int apply, float *loss_out, void *stream) {
     if (!t) return fail(BB_ERR_ARG, "null trainer");
@@ -154,7 +200,10 @@ extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const 
         return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
     if (!std::isfinite(lr)) return fail(BB_ERR_ARG, "the learning rate is not finite");
     if (int rc = trainer_on_device(t)) return rc;
-    TRAINER_SWITCH(t, trainer_launch<G>(t, n, TrainTensors<G>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream); break);
+    if (trainer_is_wide(t))
+        trainer_launch_wide(t, n, TrainTensors<DragonChess>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream);
+    else
+        TRAINER_SWITCH(t, trainer_launch<G>(t, n, TrainTensors<G>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream); break);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }
@@ -170,6 +219,7 @@ static void trainer_epoch(bb_trainer *t, int n_records, const uint8_t *records, 
 extern "C" int bb_trainer_epoch(bb_trainer *t, int n_records, const void *records, int n_batches, int batch, const int64_t *order,
                                 const uint8_t *sym, const float *noise, double lr, float *loss_out, int32_t *bad_out, void *stream) {
     if (!t) return fail(BB_ERR_ARG, "null trainer");
+    if (int rc = trainer_not_wide(t, "bb_trainer_epoch")) return rc;
     if (n_batches < 0 || n_records < 0) return fail(BB_ERR_ARG, "negative count (%d batches, %d records)", n_batches, n_records);
     if (batch <= 0 || batch > t->cfg.max_batch)
         return fail(BB_ERR_ARG, "batches of %d examples; the trainer takes 1..%d (max_batch)", batch, t->cfg.max_batch);
@@ -191,6 +241,7 @@ static_assert(sizeof(bb_eval_totals) == sizeof(EvalTotals) && sizeof(bb_eval_tot
 // The checks both entry points share, and the per-row outputs: the caller's, or the trainer's scratch grown to n rows.
 static int trainer_eval_prepare(bb_trainer *t, int n, float **rows, uint8_t **flags, const bb_eval_totals *totals) {
     if (!t) return fail(BB_ERR_ARG, "null trainer");
+    if (int rc = trainer_not_wide(t, "bb_trainer_eval")) return rc;
     if (n < 0) return fail(BB_ERR_ARG, "negative count (%d rows)", n);
     if (!totals || (uintptr_t)totals % 8) return fail(BB_ERR_ARG, "totals_out must be an 8-byte aligned device pointer");
     if ((uintptr_t)*rows % sizeof(float)) return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
@@ -258,7 +309,7 @@ extern "C" int bb_trainer_read(bb_trainer *t, int what, float *host_out, int64_t
     case BB_TRAIN_GRADS: src = t->grads; break;
     case BB_TRAIN_SLOT_M: src = t->slot_m; break;
     case BB_TRAIN_SLOT_V: src = t->slot_v; break;
-    case BB_TRAIN_NOISE: src = t->aux->noise; want = t->A; break;
+    case BB_TRAIN_NOISE: src = trainer_is_wide(t) ? t->aux_wide : t->aux->noise; want = t->A; break;
     default: return fail(BB_ERR_ARG, "unknown selector %d", what);
     }
     if (count != want) return fail(BB_ERR_ARG, "count %lld, expected %lld", (long long)count, (long long)want);

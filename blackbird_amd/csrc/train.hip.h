@@ -20,6 +20,10 @@
 // are a function of one 16-byte packed state and its value label is the record's z, so a step needs nothing a batch holds
 // that the records do not.  Both sources give the kernels the same floats in the same order: batch i of an epoch is, bit for
 // bit, the bb_trainer_step the per-batch loop would have made.
+// DragonChess (17 planes, 4032 actions; 0 .. train_max_blocks<DragonChess>() = 8 blocks) takes the same three launches with a
+// prep and a grad kernel of its own (k_train_prep_wide, k_train_grad_wide, below k_train_grad: the policy head spread over the
+// workgroup, its sum orders written there) and k_train_apply as it is; it is fed by the tensors source only -- the records
+// source and the scorer (train_eval.hip.h) are not instantiated for it.
 #pragma once
 #include "../../include/blackbird_hip.h"
 #include "examples.hip.h"
@@ -292,28 +296,34 @@ __device__ __forceinline__ void tr_conv_dx(const float *dy, const float *wst, co
 // gradients of one conv layer's variables from dy (gradient at the batch-norm output, ReLU mask applied):
 //   kernel[tap][ci][f] = scale[f] * sum_p X[p + off(tap)][ci] dy[p][f]   thread (f = tid & 15, ci = tid >> 4), p ascending
 //   gamma[f] = sum_p dy xhat, beta[f] = sum_p dy, bias[f] = scale[f] * beta[f]                       threads 0..15
+// CIN > 16 (DragonChess's 17 planes): the channels ci = c0 + (tid >> 4) for c0 = 0, 16, ..., one pass each -- every (ci, f) pair
+// is written, and the chain of a pair is the same p-ascending one whichever pass holds it.
 template <class G, int CIN>
 __device__ __forceinline__ void tr_conv_dw(const float *X, const float *dy, const float *nrm, const float *bn, float *slab_k,
                                            float *slab_b, float *slab_bn, int tid) {
     constexpr int P = G::H * G::W;
-    const int f = tid & 15, ci = tid >> 4;
+    const int f = tid & 15;
     const float s = bn[f] * tr_bn_inv(bn[3 * BB_TRAIN_F + f]);
-    if (ci < CIN) {
-        float acc[9];
 #pragma unroll
-        for (int t = 0; t < 9; t++) acc[t] = 0.f;
-        for (int r = 0; r < G::H; r++)
-            for (int c = 0; c < G::W; c++) {
-                const float d = dy[(r * G::W + c) * BB_TRAIN_F + f];
+    for (int c0 = 0; c0 < CIN; c0 += BB_TRAIN_THREADS / 16) {
+        const int ci = c0 + (tid >> 4);
+        if (ci < CIN) {
+            float acc[9];
 #pragma unroll
-                for (int t = 0; t < 9; t++) {
-                    const int rr = r + t / 3 - 1, cc = c + t % 3 - 1;
-                    if (rr >= 0 && rr < G::H && cc >= 0 && cc < G::W)
-                        acc[t] = __builtin_fmaf(X[(rr * G::W + cc) * CIN + ci], d, acc[t]);
+            for (int t = 0; t < 9; t++) acc[t] = 0.f;
+            for (int r = 0; r < G::H; r++)
+                for (int c = 0; c < G::W; c++) {
+                    const float d = dy[(r * G::W + c) * BB_TRAIN_F + f];
+#pragma unroll
+                    for (int t = 0; t < 9; t++) {
+                        const int rr = r + t / 3 - 1, cc = c + t % 3 - 1;
+                        if (rr >= 0 && rr < G::H && cc >= 0 && cc < G::W)
+                            acc[t] = __builtin_fmaf(X[(rr * G::W + cc) * CIN + ci], d, acc[t]);
+                    }
                 }
-            }
 #pragma unroll
-        for (int t = 0; t < 9; t++) slab_k[(t * CIN + ci) * BB_TRAIN_F + f] = acc[t] * s;
+            for (int t = 0; t < 9; t++) slab_k[(t * CIN + ci) * BB_TRAIN_F + f] = acc[t] * s;
+        }
     }
     if (tid < BB_TRAIN_F) {
         float dg = 0.f, db = 0.f;
@@ -370,11 +380,36 @@ __device__ __forceinline__ float tr_head_value(const TrainLayout &lay, const flo
     return tanhf(z);
 }
 
-// LDS floats of k_train_grad for R blocks
+// LDS floats of k_train_grad (dense games) / k_train_grad_wide (DragonChess) for R blocks: the activations and normalised conv
+// outputs of 2R + 1 layers, gA, gB, the staged conv kernel and the scratch behind it.
+// The staged kernel is 9 * max(C, F) rows of BB_TRAIN_WROW floats (tr_stage<C> writes 9 * C rows), in whole float4s: 2448 floats
+// for 3 planes, 2604 for DragonChess's 17.
+template <class G>
+__host__ __device__ constexpr int train_wst_floats() {
+    return (9 * (G::C > BB_TRAIN_F ? G::C : BB_TRAIN_F) * BB_TRAIN_WROW + 3) / 4 * 4;
+}
+// Behind it: the dense games' TrainSmall (planes and head scratch, offsets fixed); the wide game keeps only its planes there
+// (H * W * C floats: 1088) -- its head scratch lies in gB and its reduction scratch in gA, both idle until the backward pass.
+template <class G>
+__host__ __device__ constexpr int train_small_floats() {
+    return G::A <= 16 ? BB_TRAIN_SMALL : (G::H * G::W * G::C + 3) / 4 * 4;
+}
 template <class G>
 __host__ __device__ constexpr int train_lds_floats(int R) {
-    return (2 * (2 * R + 1) + 2) * G::H * G::W * BB_TRAIN_F + 9 * BB_TRAIN_F * BB_TRAIN_WROW + BB_TRAIN_SMALL;
+    return (2 * (2 * R + 1) + 2) * G::H * G::W * BB_TRAIN_F + train_wst_floats<G>() + train_small_floats<G>();
 }
+// The largest R whose workgroup fits the 160 KB of LDS a gfx950 CU has (one workgroup may take all of it).  DragonChess:
+// (4R + 4) * 4096 + 4 * (2604 + 1088) bytes = 162 224 at R = 8 and 178 608 at R = 9, so 8.
+#define BB_TRAIN_LDS_BYTES (160 * 1024)
+template <class G>
+__host__ __device__ constexpr int train_max_blocks() {
+    int R = 0;
+    while ((size_t)train_lds_floats<G>(R + 1) * sizeof(float) <= BB_TRAIN_LDS_BYTES) R++;
+    return R;
+}
+static_assert(train_lds_floats<Connect4>(0) == 4 * 42 * 16 + 2448 + 896 && train_lds_floats<TicTacToe>(9) == 40 * 9 * 16 + 2448 + 896,
+              "the dense games' layout does not move");
+static_assert(train_max_blocks<DragonChess>() >= 6, "the DragonChess step covers at least 6 blocks");
 
 // ---- k_train_grad: one workgroup per example ---------------------------------------------------------------------------
 template <class G, class Src>
@@ -551,6 +586,298 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay
     for (int e = tid; e < LF; e += BB_TRAIN_THREADS) gA[e] = act[e] > 0.f ? gA[e] : 0.f;
     __syncthreads();
     tr_conv_dw<G, C>(sm + S::brd, gA, nrm, prm + lay.conv0_bn, slab + lay.conv0_k, slab + lay.conv0_b, slab + lay.conv0_bn, tid);
+}
+
+// ---- the wide game (DragonChess: 17 planes, 4032 actions) ------------------------------------------------------------------
+// The same step with the policy head spread over the workgroup.  TrainAux keeps logS and l2 (k_train_apply reads them); the
+// noise and L are A floats each in an allocation of their own (bb_trainer.aux_wide: noise[A], then L[A]).
+//
+// k_train_prep_wide, 1 + ceil(A / 256) workgroups:
+//   workgroup 0      noise[a] for a = tid, tid + 256, ... (the caller's, or the Philox draw keyed (seed, calls, a)); the noise sum:
+//                    each thread its own a ascending, then tr_tree_sum; log S; the L2 term as k_train_prep takes it
+//   workgroup 1 + w  L[a] for a = 256 w + tid: the rows j = 0 .. n-1 ascending, one thread per action (loads contiguous along a)
+// k_train_grad_wide, one workgroup per example: k_train_grad's tower, value head and backward pass; the policy head as follows.
+//   thread tid owns the actions a = tid + 256 k, k = 0 .. 15 (4032 = 15.75 * 256: a < A guards the last 192 threads' k = 15);
+//   logit[a] from tr_head_logit, kept in registers
+//   max: each thread over its k ascending, then tr_tree_max;  sum of exp, the loss piece sum_a L[a] (log q[a] - log S) (an fmaf
+//   chain, entries with L[a] = 0 skipped) and t = sum_a L[a] r[a] (an fmaf chain): each thread over its k ascending, then tr_tree_sum
+//   d logit[a] as k_train_grad forms it; policy/policy's kernel and bias gradients from it, stored along a
+//   g_j = sum_a d logit[a] K[j][a], the gradient at every square's policy/convolution activation j before its ReLU mask: an fmaf
+//   chain per thread over its k ascending, then tr_tree_sum -- it does not depend on the square
+// LDS: train_lds_floats.  The head scratch (TrainWideSmall, 720 floats) lies in gB and the four reduction arrays [256] in gA: the
+// forward pass and the heads do not use either, the gradient at the tower's output is written to gA after the last reduction
+// was read (a barrier in between), and gB is first written by the backward tower.  The planes keep a place of their own, because
+// the last weight gradient reads them.  The staged 17-plane kernel has rows of BB_TRAIN_WROW = 17 floats and the planes of a
+// pixel are 17 floats apart: both odd, so neither walk stays on one bank.
+__device__ __forceinline__ void tr_tree_max(int tid, float *s) { // tr_tree_sum's shape with fmaxf
+    for (int w = BB_TRAIN_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) s[tid] = fmaxf(s[tid], s[tid + w]);
+        __syncthreads();
+    }
+}
+
+template <class G, class Src>
+__global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_prep_wide(int n, int count, int n_l2, const float *params, const uint8_t *kind,
+                                                                     Src src, const float *noise_in, float eps, float alpha, uint64_t seed,
+                                                                     uint64_t calls, TrainAux *aux, float *aux_noise, float *aux_L) {
+    constexpr int A = G::A;
+    const int tid = threadIdx.x;
+    if (blockIdx.x > 0) { // L[a]: rows ascending
+        const int a = ((int)blockIdx.x - 1) * BB_TRAIN_THREADS + tid;
+        if (a < A) {
+            float acc = 0.f;
+            for (int j = 0; j < n; j++) acc += src.label(j, a);
+            aux_L[a] = acc;
+        }
+        return;
+    }
+    __shared__ double s_sq[BB_TRAIN_THREADS];
+    __shared__ float s_noise[BB_TRAIN_THREADS];
+    float sn = 0.f;
+    for (int a = tid; a < A; a += BB_TRAIN_THREADS) {
+        float z = 0.f;
+        if (eps != 0.f) z = noise_in ? noise_in[a] : bb_beta_noise(seed, (uint32_t)calls, (uint32_t)(calls >> 32), (uint32_t)a, alpha);
+        aux_noise[a] = z;
+        sn += z;
+    }
+    s_noise[tid] = sn;
+    double sq = 0.0;
+    for (int i = tid; i < count; i += BB_TRAIN_THREADS)
+        if (kind[i] == 1) sq += (double)params[i] * (double)params[i];
+    s_sq[tid] = sq;
+    __syncthreads();
+    tr_tree_sum(tid, s_sq, s_noise);
+    if (tid == 0) {
+        const float S = (float)n * (1.0f - eps) + (float)n * eps * s_noise[0];
+        aux->logS = logf(S);
+        aux->l2 = (float)(0.5 * s_sq[0] / (double)n_l2);
+    }
+}
+
+template <class G>
+struct TrainWideSmall { // offsets into the head scratch of k_train_grad_wide (in gB)
+    static constexpr int P = G::H * G::W;
+    static constexpr int vn = 0, vy = P, pn = 2 * P, py = 4 * P, dvy = 6 * P, dpy = 7 * P, hbuf = 9 * P, tmp = hbuf + 64, misc = tmp + 64,
+                         end = misc + 16; // misc: 0 svy, 1..2 spy, 3 dz
+};
+
+template <class G, class Src>
+__global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad_wide(TrainLayout lay, const float *__restrict__ prm, const TrainAux *__restrict__ aux,
+                                                                     const float *__restrict__ aux_noise, const float *__restrict__ aux_L, Src src,
+                                                                     int n, float eps, float *__restrict__ slabs, float *__restrict__ le_out,
+                                                                     float *__restrict__ lp_out) {
+    constexpr int P = G::H * G::W, C = G::C, A = G::A, F = BB_TRAIN_F, LF = P * F, T = BB_TRAIN_THREADS, NK = (A + T - 1) / T;
+    using S = TrainWideSmall<G>;
+    static_assert(P <= 64 && 2 * P <= 128 && S::end <= LF && 4 * T <= LF && A >= T, "the head scratch fits gB, the reductions gA");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    if (b >= n) return;
+    const int R = lay.R, D = lay.D, NL = 2 * R + 1;
+    float *act = lds, *nrm = act + NL * LF, *gA = nrm + NL * LF, *gB = gA + LF, *wst = gB + LF, *brd = wst + train_wst_floats<G>();
+    float *sm = gB, *red0 = gA, *red1 = gA + T, *red2 = gA + 2 * T, *red3 = gA + 3 * T;
+    float *slab = slabs + (size_t)b * lay.count;
+
+    // ---- forward: tower ----
+    const typename Src::Row row = src.row(b);
+    src.count(row, tid);
+    for (int i = tid; i < P * C; i += T) brd[i] = src.plane(row, i);
+    tr_stage<C, false>(wst, prm + lay.conv0_k, nullptr, tid);
+    __syncthreads();
+    tr_conv_fwd<G, C, true>(brd, wst, prm + lay.conv0_b, prm + lay.conv0_bn, nullptr, nrm, act, tid);
+    __syncthreads();
+    for (int l = 1; l < NL; l++) { // layer l: conv_{1,2} of block (l-1)/2; conv_2 adds the block's input
+        tr_stage<F, false>(wst, prm + lay.blk_k + (l - 1) * 9 * F * F, nullptr, tid);
+        __syncthreads();
+        tr_conv_fwd<G, F, true>(act + (l - 1) * LF, wst, prm + lay.blk_b + (l - 1) * F, prm + lay.blk_bn + (l - 1) * 4 * F,
+                          (l & 1) ? nullptr : act + (l - 2) * LF, nrm + l * LF, act + l * LF, tid);
+        __syncthreads();
+    }
+    const float *x = act + (NL - 1) * LF;
+
+    // ---- forward: heads ----
+    const float v_s = prm[lay.v_bn] * tr_bn_inv(prm[lay.v_bn + 3]);
+    if (tid < P) { // value/convolution
+        float xh;
+        const float y = tr_head_value_conv(lay, prm, x, tid, xh);
+        sm[S::vn + tid] = xh;
+        sm[S::vy + tid] = y;
+    } else if (tid >= 64 && tid < 64 + 2 * P) { // policy/convolution
+        const int e = tid - 64;
+        float xh;
+        const float y = tr_head_policy_conv(lay, prm, x, e >> 1, e & 1, xh);
+        sm[S::pn + e] = xh;
+        sm[S::py + e] = y;
+    }
+    __syncthreads();
+    float e[NK]; // the thread's logits, then their exponentials, then its softmax entries
+#pragma unroll
+    for (int k = 0; k < NK; k++) { // policy/policy
+        const int a = tid + T * k;
+        e[k] = a < A ? tr_head_logit<G>(lay, prm, sm + S::py, a) : 0.f;
+    }
+    if (tid < D) { // value/dense_1
+        sm[S::hbuf + tid] = tr_head_dense_1<G>(lay, prm, sm + S::vy, tid);
+    } else if (tid >= 128 && tid < 131) { // sums over the squares the dense gradients need
+        const int j = tid - 128;
+        float acc = 0.f;
+        for (int p = 0; p < P; p++) acc += j == 0 ? sm[S::vy + p] : sm[S::py + 2 * p + (j - 1)];
+        sm[S::misc + j] = acc;
+    }
+    {
+        float mx = e[0]; // (A >= T: every thread owns action tid)
+#pragma unroll
+        for (int k = 1; k < NK; k++)
+            if (tid + T * k < A) mx = fmaxf(mx, e[k]);
+        red0[tid] = mx;
+    }
+    __syncthreads();
+    tr_tree_max(tid, red0);
+    if (tid == 0) { // value, the example's value loss piece, d loss / d pre-tanh value
+        const float val = tr_head_value(lay, prm, sm + S::hbuf), diff = val - src.value_of(row);
+        le_out[b] = diff * diff;
+        sm[S::misc + 3] = 2.0f * diff * (1.0f - val * val) / (float)n;
+    }
+    {
+        const float mx = red0[0];
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; k++)
+            if (tid + T * k < A) {
+                e[k] = expf(e[k] - mx);
+                se += e[k];
+            }
+        red1[tid] = se;
+    }
+    __syncthreads();
+    tr_tree_sum(tid, red1);
+    float m[NK]; // L[a] * r[a]
+    {
+        const float sum = red1[0], logS = aux->logS;
+        float lp = 0.f, t = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; k++) {
+            const int a = tid + T * k;
+            m[k] = 0.f;
+            if (a < A) {
+                e[k] = e[k] / sum; // softmax
+                const float q = __builtin_fmaf(eps, aux_noise[a], (1.0f - eps) * e[k]), La = aux_L[a];
+                if (La != 0.f) lp = __builtin_fmaf(La, logf(q) - logS, lp);
+                const float r = q > 0.f ? (1.0f - eps) * e[k] / q : 0.f;
+                t = __builtin_fmaf(La, r, t);
+                m[k] = La * r;
+            }
+        }
+        red2[tid] = lp;
+        red3[tid] = t;
+    }
+    __syncthreads();
+    tr_tree_sum(tid, red2, red3);
+    if (tid == 0) lp_out[b] = red2[0];
+
+    // ---- backward: heads ----
+    {
+        const float t = red3[0], inv_n2 = 1.0f / ((float)n * (float)n), spy0 = sm[S::misc + 1], spy1 = sm[S::misc + 2];
+        float g0 = 0.f, g1 = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; k++) {
+            const int a = tid + T * k;
+            if (a < A) {
+                const float dl = -inv_n2 * (m[k] - e[k] * t);
+                slab[lay.p_d_b + a] = dl * (float)P;
+                slab[lay.p_d_k + a] = dl * spy0;
+                slab[lay.p_d_k + A + a] = dl * spy1;
+                g0 = __builtin_fmaf(dl, prm[lay.p_d_k + a], g0);
+                g1 = __builtin_fmaf(dl, prm[lay.p_d_k + A + a], g1);
+            }
+        }
+        red0[tid] = g0;
+        red1[tid] = g1;
+    }
+    __syncthreads();
+    tr_tree_sum(tid, red0, red1);
+    const float dz = sm[S::misc + 3];
+    if (tid < D) {
+        const float h = sm[S::hbuf + tid], dh = h > 0.f ? dz * prm[lay.v_d2_k + tid] : 0.f;
+        slab[lay.v_d2_k + tid] = dz * h;
+        slab[lay.v_d1_k + tid] = dh * sm[S::misc];
+        slab[lay.v_d1_b + tid] = dh * (float)P;
+        sm[S::tmp + tid] = dh * prm[lay.v_d1_k + tid];
+    } else if (tid == 128) {
+        slab[lay.v_d2_b] = dz;
+    }
+    __syncthreads();
+    if (tid < P) { // every square's value-head activation gets the same gradient, through its own ReLU
+        float g1 = 0.f;
+        for (int d = 0; d < D; d++) g1 += sm[S::tmp + d];
+        sm[S::dvy + tid] = sm[S::vy + tid] > 0.f ? g1 : 0.f;
+    } else if (tid >= 64 && tid < 64 + 2 * P) { // ... and every square's policy-head activation j the same g_j
+        const int el = tid - 64;
+        const float g = (el & 1) ? red1[0] : red0[0];
+        sm[S::dpy + el] = sm[S::py + el] > 0.f ? g : 0.f;
+    }
+    __syncthreads();
+    const float p_s0 = prm[lay.p_bn] * tr_bn_inv(prm[lay.p_bn + 6]), p_s1 = prm[lay.p_bn + 1] * tr_bn_inv(prm[lay.p_bn + 7]);
+    if (tid == 0) {
+        float dg = 0.f, db = 0.f;
+        for (int p = 0; p < P; p++) {
+            dg = __builtin_fmaf(sm[S::dvy + p], sm[S::vn + p], dg);
+            db += sm[S::dvy + p];
+        }
+        slab[lay.v_bn] = dg;
+        slab[lay.v_bn + 1] = db;
+        slab[lay.v_conv_b] = db * v_s;
+    } else if (tid < 3) {
+        const int j = tid - 1;
+        float dg = 0.f, db = 0.f;
+        for (int p = 0; p < P; p++) {
+            dg = __builtin_fmaf(sm[S::dpy + 2 * p + j], sm[S::pn + 2 * p + j], dg);
+            db += sm[S::dpy + 2 * p + j];
+        }
+        slab[lay.p_bn + j] = dg;
+        slab[lay.p_bn + 2 + j] = db;
+        slab[lay.p_conv_b + j] = db * (j ? p_s1 : p_s0);
+    } else if (tid >= 16 && tid < 32) {
+        const int f = tid - 16;
+        float acc = 0.f;
+        for (int p = 0; p < P; p++) acc = __builtin_fmaf(sm[S::dvy + p], x[p * F + f], acc);
+        slab[lay.v_conv_k + f] = acc * v_s;
+    } else if (tid >= 32 && tid < 64) {
+        const int el = tid - 32, f = el >> 1, j = el & 1;
+        float acc = 0.f;
+        for (int p = 0; p < P; p++) acc = __builtin_fmaf(sm[S::dpy + 2 * p + j], x[p * F + f], acc);
+        slab[lay.p_conv_k + el] = acc * (j ? p_s1 : p_s0);
+    }
+    for (int el = tid; el < LF; el += T) { // gradient at the tower's output (gA: the reductions are over)
+        const int p = el / F, f = el % F;
+        float g = (sm[S::dvy + p] * v_s) * prm[lay.v_conv_k + f];
+        g = __builtin_fmaf(sm[S::dpy + 2 * p] * p_s0, prm[lay.p_conv_k + 2 * f], g);
+        g = __builtin_fmaf(sm[S::dpy + 2 * p + 1] * p_s1, prm[lay.p_conv_k + 2 * f + 1], g);
+        gA[el] = g;
+    }
+    __syncthreads();
+
+    // ---- backward: tower.  gA: gradient at the current block's output; gB is free from here (the head scratch is done) ----
+    for (int i = R - 1; i >= 0; i--) {
+        const int l1 = 1 + 2 * i, l2 = 2 + 2 * i; // layers of conv_1 and conv_2; the block's input is layer l1 - 1
+        const float *k1 = prm + lay.blk_k + (l1 - 1) * 9 * F * F, *k2 = prm + lay.blk_k + (l2 - 1) * 9 * F * F;
+        const float *bn1 = prm + lay.blk_bn + (l1 - 1) * 4 * F, *bn2 = prm + lay.blk_bn + (l2 - 1) * 4 * F;
+        for (int el = tid; el < LF; el += T) gA[el] = act[l2 * LF + el] > 0.f ? gA[el] : 0.f;
+        tr_stage<F, true>(wst, k2, bn2, tid);
+        __syncthreads();
+        tr_conv_dw<G, F>(act + l1 * LF, gA, nrm + l2 * LF, bn2, slab + lay.blk_k + (l2 - 1) * 9 * F * F, slab + lay.blk_b + (l2 - 1) * F,
+                         slab + lay.blk_bn + (l2 - 1) * 4 * F, tid);
+        tr_conv_dx<G, true>(gA, wst, act + l1 * LF, gB, tid);
+        __syncthreads();
+        tr_stage<F, true>(wst, k1, bn1, tid);
+        tr_conv_dw<G, F>(act + (l1 - 1) * LF, gB, nrm + l1 * LF, bn1, slab + lay.blk_k + (l1 - 1) * 9 * F * F,
+                         slab + lay.blk_b + (l1 - 1) * F, slab + lay.blk_bn + (l1 - 1) * 4 * F, tid);
+        __syncthreads();
+        tr_conv_dx<G, false>(gB, wst, nullptr, gA, tid);
+        __syncthreads();
+    }
+    for (int el = tid; el < LF; el += T) gA[el] = act[el] > 0.f ? gA[el] : 0.f;
+    __syncthreads();
+    tr_conv_dw<G, C>(brd, gA, nrm, prm + lay.conv0_bn, slab + lay.conv0_k, slab + lay.conv0_b, slab + lay.conv0_bn, tid);
 }
 
 // ---- k_train_apply ---------------------------------------------------------------------------------------------------

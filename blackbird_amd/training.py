@@ -205,21 +205,34 @@ EVAL_COUNTS = ('rows', 'policy_rows', 'top1', 'decided', 'sign_ok', 'se_sum', 'c
 
 
 HIP_TRAINER_LIMITS = 'Connect4 or TicTacToe, 16 filters, 0 to 9 blocks, a dense width of 1 to 64'
-_GAME_BY_PLANES = {(7, 3): (_lib.GAME_CONNECT4, 6, 7), (9, 3): (_lib.GAME_TICTACTOE, 3, 3)}   # (A, C) -> game, H, W
+HIP_TRAINER_DC_BLOCKS = 8     # train_max_blocks<DragonChess>() of csrc/train.hip.h: the blocks whose workgroup fits a CU's 160 KB of LDS
+HIP_TRAINER_LIMITS_ALL = ('Connect4 or TicTacToe (0 to 9 blocks) or DragonChess (0 to %d blocks: the LDS of a CU; batch tensors only, no '
+                          'records source, no scorer), 16 filters, a dense width of 1 to 64' % HIP_TRAINER_DC_BLOCKS)
+HIP_GAMES = ('dense', 'all')  # NetworkConfig['training']['hip_games']: what backend 'hip' may be asked for
+_GAME_BY_PLANES = {(7, 3): (_lib.GAME_CONNECT4, 6, 7), (9, 3): (_lib.GAME_TICTACTOE, 3, 3),
+                   (4032, 17): (_lib.GAME_DRAGONCHESS, 8, 8)}   # (A, C) -> game, H, W
 _OPTIMIZERS = {'adam': _lib.OPT_ADAM, 'momentum': _lib.OPT_MOMENTUM, 'sgd': _lib.OPT_SGD}
 
 
-def hip_trainer_supports(weights):
-    """Whether `weights` (TF-named dict) is a network the HIP training kernels cover (HIP_TRAINER_LIMITS)."""
+def hip_trainer_supports(weights, games='dense'):
+    """Whether `weights` (TF-named dict) is a network the HIP training kernels cover: games='dense', Connect4 and TicTacToe
+    (HIP_TRAINER_LIMITS); games='all', DragonChess too (HIP_TRAINER_LIMITS_ALL)."""
+    if games not in HIP_GAMES:
+        raise ValueError("hip_games is 'dense' or 'all', got %r" % (games,))
     C, F, R, D, A = W.infer_shape(weights)
-    return (A, C) in _GAME_BY_PLANES and F == 16 and 0 <= R <= 9 and 1 <= D <= 64
+    if (A, C) not in _GAME_BY_PLANES or F != 16 or not 1 <= D <= 64:
+        return False
+    if _GAME_BY_PLANES[(A, C)][0] == _lib.GAME_DRAGONCHESS:
+        return games == 'all' and 0 <= R <= HIP_TRAINER_DC_BLOCKS
+    return 0 <= R <= 9
 
 
 class HipTrainer:
     """`Trainer` with the step as HIP kernels of libblackbird_hip.so (bb_trainer_*, csrc/train.hip.h): the same loss, the
     same optimiser rules, the same interface -- chosen with NetworkConfig['training']['backend'] = 'hip'.  Parameters,
     optimiser slots and gradients live in the library's own device buffers; `export` reads the parameters back.  Covers
-    HIP_TRAINER_LIMITS; anything else raises ValueError.  `seed` keys the Beta noise a step draws when none is given
+    HIP_TRAINER_LIMITS_ALL; anything else raises ValueError.  A DragonChess trainer (`wide`) steps from batch tensors only:
+    epoch_records, evaluate_records and evaluate_tensors raise ValueError for it.  `seed` keys the Beta noise a step draws when none is given
     (None: from numpy's generator, as the engines do); `max_batch` bounds the examples of one step."""
 
     def __init__(self, weights, alpha=0.2, epsilon=0.3, optimizer='adam', momentum=0.9, device=None, seed=None, max_batch=1024):
@@ -228,13 +241,14 @@ class HipTrainer:
             raise _lib.BlackbirdHipError('HipTrainer runs on the GPU only (device %s)' % self.device)
         self.alpha, self.epsilon = float(alpha), float(epsilon)
         self.C, self.F, self.R, self.D, self.A = W.infer_shape(weights)
-        if not hip_trainer_supports(weights):
+        if not hip_trainer_supports(weights, 'all'):
             raise ValueError('the hip training backend covers %s; got %d input planes, %d actions, %d filters, %d blocks, '
-                             'dense %d' % (HIP_TRAINER_LIMITS, self.C, self.A, self.F, self.R, self.D))
+                             'dense %d' % (HIP_TRAINER_LIMITS_ALL, self.C, self.A, self.F, self.R, self.D))
         if optimizer not in _OPTIMIZERS:   # (Trainer treats any other name as sgd; the kernels are asked by number)
             optimizer = 'sgd'
         self.kind, self.momentum = optimizer, float(momentum)
         self.game, self.H, self.Wd = _GAME_BY_PLANES[(self.A, self.C)]
+        self.wide = self.game == _lib.GAME_DRAGONCHESS
         self.max_batch = int(max_batch)
         if seed is None:
             from .MCTS import _seed_from_numpy
@@ -272,6 +286,11 @@ class HipTrainer:
                 t.record_stream(torch.cuda.current_stream(self.device))
         return loss
 
+    def _not_wide(self, who):
+        if self.wide:
+            raise ValueError('%s: the records source and the scorer of the hip training backend cover Connect4 and TicTacToe; a '
+                             'DragonChess trainer steps from batch tensors (step, step_tensors, gradients)' % who)
+
     def _named(self, what):
         return W.unflatten(_lib.trainer_read(self._h, what), self.C, self.F, self.R, self.D, self.A)
 
@@ -303,6 +322,7 @@ class HipTrainer:
         examples: a DeviceExamples of the trainer's game on the trainer's device (merged rows are not a records source:
         ValueError).  order, sym: tensors as examples.index_tensor and examples.sym_tensor return them (order None: the records
         in order), whole batches.  noise: [n_batches, A] or None to draw it.  Malformed rows count in examples.bad()."""
+        self._not_wide('epoch_records')
         if not isinstance(examples, DeviceExamples):
             raise ValueError('epoch_records takes a DeviceExamples (merged rows carry sums of their own and are not a records '
                              'source), got %s' % type(examples).__name__)
@@ -366,6 +386,7 @@ class HipTrainer:
         examples: a DeviceExamples of the trainer's game on the trainer's device (merged rows are not a records source:
         ValueError).  index, sym: tensors as examples.index_tensor and examples.sym_tensor return them, or anything those take.
         Malformed rows are zeros with flags 0, outside every total, and count in examples.bad()."""
+        self._not_wide('evaluate_records')
         if not isinstance(examples, DeviceExamples):
             raise ValueError('evaluate_records takes a DeviceExamples (merged rows carry sums of their own and are not a records '
                              'source), got %s' % type(examples).__name__)
@@ -392,6 +413,7 @@ class HipTrainer:
         """`evaluate_records` for rows given as the three tensors of a batch (bb_trainer_eval_tensors): boards [n,H,W,C], evalLabel
         [n], policyLabel [n,A].  The same kernel reads either source: evaluate_records(ex, index, sym) and
         evaluate_tensors(*ex._batch(index, sym)) give the same bits."""
+        self._not_wide('evaluate_tensors')
         n = int(policyLabel.shape[0]) if hasattr(policyLabel, 'shape') else len(policyLabel)
         boards = self._f32(boards, (n, self.H, self.Wd, self.C))
         ev = self._f32(evalLabel, (n,))

@@ -556,11 +556,16 @@ int bb_examples_merged_to_batch(int game, int n_records, const void *records, in
  * label sum and L2 term; one workgroup per example (forward, loss pieces, backward, the gradients of every trainable variable
  * into the example's own slab); per parameter element the slabs summed in example order, + v / N for the non-bias variables,
  * and the TF1 update (Adam with epsilon outside the bias correction, Momentum, GradientDescent) in place.  No float atomics:
- * the same steps give the same bits.  Batch norm is in inference mode: the moving statistics are constants. */
+ * the same steps give the same bits.  Batch norm is in inference mode: the moving statistics are constants.
+ * DragonChess (17 planes, 4032 actions) is covered too, with 16 filters, a dense width of 1..64 and 0..8 blocks -- the most whose
+ * per-example workgroup fits the 160 KB of LDS of a CU; bb_trainer_create's refusal names the figure.  Such a trainer steps from
+ * batch tensors only: bb_trainer_step, bb_trainer_read (BB_TRAIN_NOISE: 4032 floats), bb_trainer_param_count,
+ * bb_trainer_load_engine and bb_trainer_destroy work for it; bb_trainer_epoch, bb_trainer_eval and bb_trainer_eval_tensors
+ * return BB_ERR_ARG (a DragonChess record holds a compact child list: the records source and the scorer do not cover it). */
 enum { BB_OPT_ADAM = 0, BB_OPT_MOMENTUM = 1, BB_OPT_SGD = 2 };
 enum { BB_TRAIN_PARAMS = 0, BB_TRAIN_GRADS = 1, BB_TRAIN_SLOT_M = 2, BB_TRAIN_SLOT_V = 3, BB_TRAIN_NOISE = 4 };
 typedef struct {
-    int32_t game;      /* BB_GAME_CONNECT4 | BB_GAME_TICTACTOE */
+    int32_t game;      /* BB_GAME_CONNECT4 | BB_GAME_TICTACTOE | BB_GAME_DRAGONCHESS */
     int32_t optimizer; /* BB_OPT_* */
     int32_t max_batch; /* examples per step at most: one gradient slab each is allocated */
     int32_t device;    /* HIP device ordinal */

@@ -1,6 +1,10 @@
 """From finished self-play games to a trained network, both ways, timed: python tools/train_path.py [--games N]
 [--play-limit P] [--batch B] [--lr LR] [--augment] [--merge] [--holdout FRACTION] [--skip-host] [--skip-device] [--skip-hip]
-[--handoff host|device]
+[--handoff host|device] [--game connect4|dragonchess] [--warmup-games W]
+
+--game dragonchess: the same on DragonChess (17 planes, 4032 actions), the hip model with NetworkConfig['training']['hip_games'] =
+'all'.  The records source and the scorer do not cover that game, so hip_epoch_s is null and --holdout and --merge are refused;
+--warmup-games (default 64) bounds the untimed warm-up runs, whose games are long there.
 
 N Connect4 games at PlayLimit P are played once (Model.KeepDeviceExamples on, so that sqlite and the GPU hold the same
 examples); then one epoch over them is trained twice with the same batch size:
@@ -52,7 +56,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from blackbird_amd import Blackbird, Connect4, _lib  # noqa: E402
+from blackbird_amd import Blackbird, Connect4, DragonChess, _lib  # noqa: E402
 from blackbird_amd import weights as W  # noqa: E402
 from blackbird_amd.training import epoch_order, eval_summary  # noqa: E402
 
@@ -129,13 +133,20 @@ def main():
     ap.add_argument("--skip-hip", action="store_true")
     ap.add_argument("--skip-device", action="store_true")
     ap.add_argument("--handoff", choices=("host", "device"), default="host")
+    ap.add_argument("--game", choices=("connect4", "dragonchess"), default="connect4")
+    ap.add_argument("--warmup-games", type=int, default=64)
     a = ap.parse_args()
+    dc = a.game == "dragonchess"
+    if dc and (a.merge or a.holdout is not None or a.augment):
+        ap.error("--merge, --augment and --holdout cover Connect4 only")
+    board = DragonChess.BoardState if dc else Connect4.BoardState
+    planes = _lib.game_info(board.GAME_ID).C
     os.chdir(tempfile.mkdtemp())  # the sqlite file and the saved networks of this run
     np.random.seed(a.seed)
-    model = Blackbird.Model(Connect4.BoardState, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, CFG)
+    model = Blackbird.Model(board, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, CFG)
     model.KeepDeviceExamples = True
-    initial = {k: v.copy() for k, v in model._ensure_weights(3).items()}
-    Blackbird.GenerateTrainingSamples(model, 64, 1.0)  # warm-up run (its examples are trained on too)
+    initial = {k: v.copy() for k, v in model._ensure_weights(planes).items()}
+    Blackbird.GenerateTrainingSamples(model, a.warmup_games, 1.0)  # warm-up run (its examples are trained on too)
     t = time.time()
     Blackbird.GenerateTrainingSamples(model, a.games, 1.0)
     selfplay_s = time.time() - t
@@ -145,15 +156,17 @@ def main():
     # the second model: the weights the first one saved when it was made, the hip backend
     hip_cfg = copy.deepcopy(CFG)
     hip_cfg["training"]["backend"] = "hip"
+    if dc:
+        hip_cfg["training"]["hip_games"] = "all"
     if a.handoff != "host":
         hip_cfg["training"]["handoff"] = a.handoff
-    hip_model = Blackbird.Model(Connect4.BoardState, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, hip_cfg)
+    hip_model = Blackbird.Model(board, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, hip_cfg)
     assert all(np.array_equal(hip_model._weights[k], model._weights[k]) for k in model._weights)
     model.train(boards, value, policy, a.lr)  # warm-up step
     if not a.skip_hip:
         hip_model.getEvaluation(boards[:1].astype(np.int8))     # the engines a playing, training model owns: evaluation ...
         state = np.random.get_state()
-        Blackbird.GenerateTrainingSamples(hip_model, 64, 1.0)    # ... and self-play (numpy's generator left where it was)
+        Blackbird.GenerateTrainingSamples(hip_model, a.warmup_games, 1.0)    # ... and self-play (numpy's generator left where it was)
         np.random.set_state(state)
         hip_model.train(boards, value, policy, a.lr)
     torch.cuda.synchronize()
@@ -202,12 +215,13 @@ def main():
         Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment, fused=False)
         torch.cuda.synchronize()
         hip_s = time.time() - t
-        hip_model._trainer.epoch_records(kept, order[:B], B, a.lr)
-        torch.cuda.synchronize()
-        t = time.time()
-        Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment, fused=True)
-        torch.cuda.synchronize()
-        hip_epoch_s = time.time() - t
+        if not dc:
+            hip_model._trainer.epoch_records(kept, order[:B], B, a.lr)
+            torch.cuda.synchronize()
+            t = time.time()
+            Blackbird.TrainWithDeviceExamples(hip_model, B, a.lr, examples=kept, augment=a.augment, fused=True)
+            torch.cuda.synchronize()
+            hip_epoch_s = time.time() - t
 
     # the reference API's shape on the hip model: Model.train per batch (a step, then every engine the model owns reloaded), on
     # host arrays staged beforehand; then one hand-off alone against one export + load_weights, on the evaluation engine
@@ -253,14 +267,14 @@ def main():
     holdout = {} if a.holdout is None else {"holdout": holdout_run(a, kept, hip_cfg, initial)}
 
     r3 = lambda x: None if x is None else round(x, 3)  # noqa: E731
-    print(json.dumps({"tool": "train_path", "game": "connect4", "games": a.games, "warmup_games": 64, "play_limit": a.play_limit,
+    print(json.dumps({"tool": "train_path", "game": a.game, "games": a.games, "warmup_games": a.warmup_games, "play_limit": a.play_limit,
                       "examples": n, "augment": bool(a.augment), "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
                       "host_path_s": r3(host_s), "host_decode_s": r3(decode_s),
                       "device_path_s": r3(device_s), "device_batches_only_s": round(batch_s, 4),
                       "host_over_device": None if host_s is None or device_s is None else round(host_s / device_s, 2),
                       "hip_path_s": r3(hip_s),
                       "device_over_hip": None if hip_s is None or device_s is None else round(device_s / hip_s, 2),
-                      "hip_epoch_s": r3(hip_epoch_s), "hip_over_hip_epoch": None if hip_s is None else round(hip_s / hip_epoch_s, 2),
+                      "hip_epoch_s": r3(hip_epoch_s), "hip_over_hip_epoch": None if hip_s is None or hip_epoch_s is None else round(hip_s / hip_epoch_s, 2),
                       "handoff": a.handoff, "train_loop_s": r3(loop_s),
                       "handoff_s": None if handoff_s is None else round(handoff_s, 6),
                       "export_load_s": None if export_load_s is None else round(export_load_s, 6), **merge, **holdout}))
