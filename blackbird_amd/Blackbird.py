@@ -361,7 +361,7 @@ def TrainWithDeviceExamples(model, batchSize, learningRate, epochs=1, examples=N
     model._kept_examples = [(v, ex) for v, ex in model._kept_examples if v >= model.Version]
 
 
-def EvaluateDeviceExamples(model, examples=None, batchSize=1024):
+def EvaluateDeviceExamples(model, examples=None, batchSize=1024, scorer='trainer'):
     """A held-out score (an extension: the reference has none): `examples` (a training.DeviceExamples, e.g. the second part of
     DeviceExamples.split_games), or else what GenerateTrainingSamples kept for the model's current Version, scored by the model's
     trainer -- model._trainer_for(...), made from model._weights when there is none -- with its current parameters, forward only.
@@ -371,13 +371,30 @@ def EvaluateDeviceExamples(model, examples=None, batchSize=1024):
 
     hip backend: one HipTrainer.evaluate_records call (bb_trainer_eval reads the records themselves).  PyTorch backend:
     examples._batch in chunks of `batchSize` through Trainer.evaluate_tensors, the counts and sums added.  No weight, no Version,
-    no batchCount changes, numpy's generator is not touched, and neither is the noise a later step draws."""
+    no batchCount changes, numpy's generator is not touched, and neither is the noise a later step draws.
+
+    scorer='engine' (any other value but 'trainer': ValueError): the records are scored by the model's evaluation engine
+    instead -- the one behind getEvaluation, created and loaded as getEvaluation creates it and kept up to date by the reload
+    that follows every training call --, in the arithmetic that evaluates positions in self-play (DeviceExamples.score_with,
+    bb_examples_score).  Every game, every network width, both training backends; no trainer is made.  `batchSize` is the
+    number of rows per network launch then.  Merged rows are not a records source: ValueError."""
     from .training import EVAL_COUNTS, eval_summary
+    if scorer not in ('trainer', 'engine'):
+        raise ValueError("scorer is 'trainer' or 'engine', got %r" % (scorer,))
     if examples is None:
         examples = model.KeptDeviceExamples()
     if examples is None:
         raise ValueError('no device examples for %s version %d: pass `examples`, or set KeepDeviceExamples before '
                          'GenerateTrainingSamples' % (model.Name, model.Version))
+    if scorer == 'engine':
+        state = np.random.get_state()  # an engine made here draws the seed of its noise from numpy's generator, as any does:
+        engine = model._engine_for((examples.info.H, examples.info.W, examples.info.C))
+        np.random.set_state(state)     # ... the generator itself is left where it was
+        out = examples.score_with(engine, chunk_rows=max(int(batchSize), 1))
+        bad = examples.bad()
+        if bad:
+            raise _lib.BlackbirdHipError('%d malformed example records were met in the evaluation' % bad)
+        return out
     state = np.random.get_state()      # a trainer made here draws the seed of its noise from numpy's generator, as any does:
     trainer = model._trainer_for(examples.info.C)
     np.random.set_state(state)         # ... the generator itself is left where it was

@@ -39,6 +39,7 @@ EXPORTS = (
     "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_epoch", "bb_trainer_param_count",
     "bb_trainer_read", "bb_trainer_eval", "bb_trainer_eval_tensors",
     "bb_load_weights_device", "bb_trainer_load_engine", "bb_weights_read",
+    "bb_examples_score_workspace", "bb_examples_score",
 )
 
 
@@ -161,6 +162,8 @@ def lib():
     L.bb_trainer_read.argtypes = [vp, ip, vp, C.c_int64]
     L.bb_trainer_eval.argtypes = [vp, ip, vp, ip, vp, vp, vp, vp, vp, vp, vp]
     L.bb_trainer_eval_tensors.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp, vp]
+    L.bb_examples_score_workspace.argtypes = [vp, ip, C.POINTER(C.c_uint64)]
+    L.bb_examples_score.argtypes = [vp, ip, vp, ip, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]
     for name in EXPORTS:
         if name != "bb_last_error":
             getattr(L, name).restype = C.c_int
@@ -751,6 +754,24 @@ class Engine:
         win = np.zeros(len(ids), dtype=np.int8)
         k = check(lib().bb_examples_fetch_games(self.h, len(ids), ptr(ids), ptr(rec), cap, ptr(offs), ptr(win)))
         return rec[:k], offs, win
+
+    def score_workspace(self, rows_per_chunk):
+        """bb_examples_score_workspace: the bytes of scratch memory score_examples needs for chunks of rows_per_chunk rows.  Host
+        only."""
+        out = C.c_uint64(0)
+        check(lib().bb_examples_score_workspace(self.h, int(rows_per_chunk), C.byref(out)))
+        return int(out.value)
+
+    def score_examples(self, n_records, records, n, index=None, rows_out=None, flags_out=None, totals_out=None, bad=None,
+                       workspace=None, workspace_bytes=0, stream=0):
+        """bb_examples_score: rows index[k] (None: record k) of the device records scored with the network this engine holds --
+        any game, width and net form.  records, index (int64), rows_out (float32 [n, 3]), flags_out (uint8 [n]), totals_out (56
+        bytes, EVAL_TOTALS_DTYPE), bad (int32 [1]) and workspace (score_workspace bytes for the chunk size wanted) are DEVICE
+        addresses on the engine's device (ints; None/0 = absent).  Waits for the engine's own streams, then runs behind what
+        `stream` holds; `stream` waits for the figures.  Asynchronous for `stream`."""
+        p = lambda a: C.c_void_p(a or None)  # noqa: E731
+        check(lib().bb_examples_score(self.h, int(n_records), p(records), int(n), p(index), p(rows_out), p(flags_out), p(totals_out),
+                                      p(bad), p(workspace), int(workspace_bytes), p(stream)))
 
     def examples_device(self):
         """bb_examples_device: (records device pointer, bytes, record bytes, game header device pointer)."""

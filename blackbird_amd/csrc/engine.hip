@@ -12,6 +12,7 @@
 //   host_arena.hip.h     bb_arena
 //   host_trainer.hip.h   bb_trainer
 //   host_timing.hip.h    bb_timing_*, the stamp entry points of diagnostic builds
+//   host_score.hip.h     bb_examples_score: records scored with the engine's network (last: nothing before it moves)
 // Device memory, streams and events have one owner per object (dev_mem.h: DevOwner); a call's scratch is a Staged<T>.
 //   simulation  = k_tree_step (apply previous leaf: expand+backup; select next leaf)  ->  evaluator kernel
 //   move        = k_selfplay_move (apply last leaf; sample; record example; re-root; game over -> next game)
@@ -37,6 +38,7 @@
 #include "net_blocks.h"
 #include "net_pack.h"
 #include "net_pack.hip.h"
+#include "examples_score.hip.h"
 
 #include "host_common.hip.h"
 #include "host_launch.hip.h"
@@ -49,3 +51,4 @@
 #include "host_arena.hip.h"
 #include "host_trainer.hip.h"
 #include "host_timing.hip.h"
+#include "host_score.hip.h"

@@ -574,6 +574,52 @@ class DeviceExamples:
                                        torch.cuda.current_stream(dev).cuda_stream)
         return boards, value, policy
 
+    def score_with(self, engine, index=None, rows=False, chunk_rows=4096):
+        """Score these records with the network `engine` (an _lib.Engine of this game, on the records' device, with weights
+        loaded) holds -- bb_examples_score: the engine's own network launch, whatever its game, width and net form, so the
+        figures are those of the arithmetic that evaluates positions in self-play.  Row k is record index[k] (None: every
+        record, in order).  Returns eval_summary's dict of Python numbers, HipTrainer.evaluate_records' keys with the same
+        meaning, after one synchronising read; rows=True adds the device tensors 'per_row' [n, 3] (value, se, ce) and 'flags' [n]
+        (uint8, _lib.ROW_*).  chunk_rows: the rows per network launch; the workspace (states, values and logits of one chunk:
+        bb_examples_score_workspace) is a torch tensor kept with the records and reused while it is large enough.  The chunk
+        size does not change a bit of the result.  The engine's trees, counters, evaluation cache and weights are untouched; the
+        call waits for the engine's own streams first.  Malformed rows are zeros with flags 0, outside every total, and count in
+        bad()."""
+        if not isinstance(engine, _lib.Engine):
+            raise ValueError('score_with takes an _lib.Engine, got %s' % type(engine).__name__)
+        if engine.game != self.game:
+            raise ValueError('the examples are of game %d, the engine of game %d' % (self.game, engine.game))
+        dev = self.records.device
+        if dev.type != 'cuda' or (dev.index if dev.index is not None else torch.cuda.current_device()) != int(engine.cfg.device):
+            raise ValueError('the examples are on %s, the engine on cuda:%d' % (dev, int(engine.cfg.device)))
+        if index is not None and not torch.is_tensor(index):
+            index = self.index_tensor(index)
+        n = len(self) if index is None else int(index.numel())
+        if index is not None and (index.dtype != torch.int64 or index.device != dev or not index.is_contiguous()):
+            raise ValueError('index: a contiguous %s tensor on %s is expected' % (torch.int64, dev))
+        chunk = min(max(int(chunk_rows), 1), max(n, 1))
+        nbytes = engine.score_workspace(chunk)
+        work = getattr(self, '_score_work', None)
+        if work is None or int(work.numel()) < nbytes:
+            work = self._score_work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out_rows = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        out_flags = torch.empty((n,), dtype=torch.uint8, device=dev)
+        totals = torch.empty(np.dtype(_lib.EVAL_TOTALS_DTYPE).itemsize, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            engine.score_examples(len(self), self.records.data_ptr() if len(self) else None, n,
+                                  None if index is None else index.data_ptr(), out_rows.data_ptr() if n else None,
+                                  out_flags.data_ptr() if n else None, totals.data_ptr(), self._bad.data_ptr(),
+                                  work.data_ptr(), nbytes, stream.cuda_stream)
+        for t in (self.records, self._bad, index, work, out_rows, out_flags, totals):   # the engine's stream uses them: alive until `stream` is past its wait
+            if t is not None:
+                t.record_stream(stream)
+        tot = totals.cpu().numpy().view(_lib.EVAL_TOTALS_DTYPE)[0]      # (waits for the launches)
+        out = eval_summary(*[tot[k].item() for k in EVAL_COUNTS])
+        if rows:
+            out['per_row'], out['flags'] = out_rows, out_flags
+        return out
+
     def bad(self):
         """Rows that bb_examples_to_batch rejected (and wrote as zeros) since this object was made: malformed records.
         Waits for the GPU -- look at it once per epoch, not once per batch."""
@@ -702,6 +748,11 @@ class MergedExamples:
                                           None if sym is None else sym.data_ptr(), boards.data_ptr(), policy.data_ptr(),
                                           value.data_ptr(), self._bad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         return boards, value, policy
+
+    def score_with(self, engine, index=None, rows=False, chunk_rows=4096):
+        """Merged rows carry sums of their own and are not a records source: ValueError, as HipTrainer.evaluate_records answers."""
+        raise ValueError('score_with takes a DeviceExamples (merged rows carry sums of their own and are not a records source), '
+                         'got %s' % type(self).__name__)
 
     def bad(self):
         """Malformed records that the merge left out, plus rows that `batch` rejected (and wrote as zeros) since.  Waits for

@@ -651,6 +651,45 @@ int bb_trainer_read(bb_trainer *t, int what, float *host_out, int64_t count);
  * devices; otherwise bb_load_weights_device's answers. */
 int bb_trainer_load_engine(bb_trainer *t, bb_engine *e, void *stream);
 
+/* ---- example records scored with the network an engine holds ------------------------------------ */
+/* An extension (the reference has no held-out score), like bb_trainer_eval, which covers the trainer's float32 network of the
+ * dense games with 16 filters only.  This call scores records with whatever network the ENGINE evaluates positions with -- the
+ * one behind Network.getEvaluation (Network.py:48-54) and the search: the fused 16-filter tower or the launch-per-layer network,
+ * in the split-operand or the float32-MFMA form (bb_net_form), for every game -- so the figures are those of the arithmetic
+ * that chooses the moves.  csrc/examples_score.hip.h: per chunk of rows a gather of the records' packed states, the engine's own
+ * network launch (no noise, no keys, no evaluation cache) and one wave per row for the figures; then bb_trainer_eval's totals
+ * launch, unchanged.  Per row k (record index[k]; NULL: record k), as bb_trainer_eval defines them:
+ *   rows_out[k] = value (the engine's, unchanged), se = (value - z)^2, ce = -sum_a pi[a] (logit[a] - max - log sum exp(logit - max))
+ *                 over all A logits, pi[a] = (float)((double)visits / (double)total); DragonChess takes pi from the record's
+ *                 compact list (visits[j] at action[j], j < n_children) and forms no 4032-wide label row; ce is 0 without a label
+ *   flags_out[k]  BB_ROW_*; BB_ROW_HAS_POLICY: total != 0 and some visit count is not zero; BB_ROW_TOP1: first maximum of the
+ *                 logits == first maximum of the label in action order (DragonChess: the child with the largest share, ties to
+ *                 the smallest action id wherever it stands in the list; duplicate actions are no error, every entry counts)
+ * A malformed row -- index[k] outside [0, n_records), n_children > S, a compact action[j] >= A -- is {0, 0, 0} with flags 0, one
+ * count in *bad (when non-NULL) and in no total; the network sees the game's initial position in its place, and nothing a record
+ * says becomes an address before it has been checked.  All sums run in a fixed order without float atomics: the same call gives
+ * the same bits, whatever the chunk size.
+ * The scratch memory for chunks of rows_per_chunk rows, in bytes: the gathered states, value[chunk] and logits[chunk][A]; it grows
+ * with rows_per_chunk and is a multiple of 16.  Host only: no device call.  BB_ERR_ARG: a null argument, rows_per_chunk < 0. */
+int bb_examples_score_workspace(bb_engine *e, int rows_per_chunk, uint64_t *bytes_out);
+/* ALL pointers are device memory of the engine's device, which must be the calling thread's current one.  records
+ * [n_records][example_bytes] (the bb_examples_fetch layout), index [n] int64 or NULL, rows_out [n][3] float32, flags_out [n],
+ * totals_out (56 bytes), bad [1] int32 (incremented; the caller zeroes it) or NULL.  The chunk size is the number of rows the
+ * given workspace holds (at most n): any workspace that holds one row gives the same bytes.
+ * Ordering: the call waits on the host for the engine's own streams (a score never runs beside a search), makes the engine's
+ * stream wait for what `stream` (a hipStream_t; 0 = the default stream) has queued, enqueues everything on the engine's stream and
+ * makes `stream` wait for the end.  It does not synchronise `stream`, copies nothing to the host and allocates nothing -- but for
+ * the activation buffers of the launch-per-layer network, which grow (and wait) as for any larger batch.  Trees, slots,
+ * counters, the evaluation cache and its counters, the random streams and the weights are left alone.
+ * n == 0: BB_OK, and the totals launch writes zero totals (there is a GPU: an engine exists).  BB_ERR_ARG, before any device
+ * call: a null engine or totals_out, n < 0, n_records < 0, a misaligned pointer (records and workspace 16 bytes, index and
+ * totals_out 8, rows_out and bad 4), with n > 0 a null records, rows_out, flags_out or workspace, or a workspace too small for one
+ * row.  BB_ERR_WEIGHTS: an engine without loaded weights, or whose evaluator is not the network.  BB_ERR_ARG: another current
+ * device. */
+int bb_examples_score(bb_engine *e, int n_records, const void *records, int n, const int64_t *index, float *rows_out,
+                      uint8_t *flags_out, bb_eval_totals *totals_out, int32_t *bad, void *workspace, uint64_t workspace_bytes,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

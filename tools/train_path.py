@@ -1,6 +1,6 @@
 """From finished self-play games to a trained network, both ways, timed: python tools/train_path.py [--games N]
 [--play-limit P] [--batch B] [--lr LR] [--augment] [--merge] [--holdout FRACTION] [--skip-host] [--skip-device] [--skip-hip]
-[--handoff host|device] [--game connect4|dragonchess] [--warmup-games W]
+[--handoff host|device] [--game connect4|dragonchess] [--warmup-games W] [--score-engine]
 
 --game dragonchess: the same on DragonChess (17 planes, 4032 actions), the hip model with NetworkConfig['training']['hip_games'] =
 'all'.  The records source and the scorer do not cover that game, so hip_epoch_s is null and --holdout and --merge are refused;
@@ -42,7 +42,15 @@ HipTrainer.evaluate_records, bb_trainer_eval), trains one epoch on the training 
 and --merge as given) and scores both parts again: value_mse, policy_ce, top1_rate and sign_rate of each are printed under
 "holdout".  Two times are taken on the held-out part, each the median of five calls after an untimed one: evaluate_records, and
 the route to the same figures without it -- trainer.export(), a fresh engine with those weights, examples._batch to the host,
-Engine.net_eval, numpy.  Every other figure is measured as without it, on all records.  Prints one JSON line."""
+Engine.net_eval, numpy.  Every other figure is measured as without it, on all records.
+
+--score-engine (with --holdout): the held-out part is also scored by the model's evaluation engine
+(Blackbird.EvaluateDeviceExamples(scorer='engine'): DeviceExamples.score_with, bb_examples_score -- the network in the arithmetic
+self-play uses), timed the same way next to the other routes (score_engine_s; score_with_s is the score_with call alone), with
+its figures and their distance from evaluate_records'.  With --game dragonchess --holdout is accepted together with
+--score-engine only: a model with the PyTorch trainer scores the held-out part both ways -- Trainer.evaluate_tensors over
+examples._batch chunks (torch_route_s), which was the only route for that game, and scorer='engine' -- and nothing is trained.
+Prints one JSON line."""
 import argparse
 import copy
 import json
@@ -114,9 +122,32 @@ def holdout_run(a, kept, cfg, weights):
     mine, theirs = m._trainer.evaluate_records(held), host_route(m._trainer, held)
     eval_s = median_time(lambda: m._trainer.evaluate_records(held))
     host_s = median_time(lambda: host_route(m._trainer, held))
-    return {"fraction": a.holdout, "train_records": len(train), "held_records": len(held), "merge": bool(a.merge),
-            "before": before, "after": after, "evaluate_records_s": round(eval_s, 5), "host_route_s": round(host_s, 5),
-            "host_route_agrees": {k: round(abs(mine[k] - theirs[k]), 7) for k in MEANS}}
+    out = {"fraction": a.holdout, "train_records": len(train), "held_records": len(held), "merge": bool(a.merge),
+           "before": before, "after": after, "evaluate_records_s": round(eval_s, 5), "host_route_s": round(host_s, 5),
+           "host_route_agrees": {k: round(abs(mine[k] - theirs[k]), 7) for k in MEANS}}
+    if a.score_engine:
+        out.update(engine_scores(m, held, mine))
+    return out
+
+
+def engine_scores(m, held, other):
+    """--score-engine: the held-out part scored by the model's evaluation engine, timed, against the figures `other`"""
+    got = Blackbird.EvaluateDeviceExamples(m, examples=held, scorer="engine")
+    front_s = median_time(lambda: Blackbird.EvaluateDeviceExamples(m, examples=held, scorer="engine"))
+    eng = m._eval_engine
+    call_s = median_time(lambda: held.score_with(eng))
+    return {"score_engine": {k: round(got[k], 5) for k in MEANS}, "score_engine_s": round(front_s, 5), "score_with_s": round(call_s, 5),
+            "score_engine_net_form": eng.net_form(), "score_engine_agrees": {k: round(abs(got[k] - other[k]), 7) for k in MEANS}}
+
+
+def holdout_run_dc(a, kept, board):
+    """--game dragonchess --holdout --score-engine: see the module's docstring"""
+    _train, held = kept.split_games(a.holdout, a.seed)
+    m = Blackbird.Model(board, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, CFG)
+    theirs = Blackbird.EvaluateDeviceExamples(m, examples=held)
+    torch_s = median_time(lambda: Blackbird.EvaluateDeviceExamples(m, examples=held))
+    return {"fraction": a.holdout, "held_records": len(held), "torch_route": {k: round(theirs[k], 5) for k in MEANS},
+            "torch_route_s": round(torch_s, 5), **engine_scores(m, held, theirs)}
 
 
 def main():
@@ -135,10 +166,13 @@ def main():
     ap.add_argument("--handoff", choices=("host", "device"), default="host")
     ap.add_argument("--game", choices=("connect4", "dragonchess"), default="connect4")
     ap.add_argument("--warmup-games", type=int, default=64)
+    ap.add_argument("--score-engine", action="store_true")
     a = ap.parse_args()
     dc = a.game == "dragonchess"
-    if dc and (a.merge or a.holdout is not None or a.augment):
-        ap.error("--merge, --augment and --holdout cover Connect4 only")
+    if a.score_engine and a.holdout is None:
+        ap.error("--score-engine goes with --holdout")
+    if dc and (a.merge or a.augment or (a.holdout is not None and not a.score_engine)):
+        ap.error("--merge and --augment cover Connect4 only, --holdout on DragonChess needs --score-engine")
     board = DragonChess.BoardState if dc else Connect4.BoardState
     planes = _lib.game_info(board.GAME_ID).C
     os.chdir(tempfile.mkdtemp())  # the sqlite file and the saved networks of this run
@@ -264,7 +298,7 @@ def main():
                  "merge_s": round(merge_s, 5), "merged_batches": len(merged) // B, "merged_batches_only_s": round(mbatch_s, 4),
                  "device_path_merge_s": round(time.time() - t, 3)}
 
-    holdout = {} if a.holdout is None else {"holdout": holdout_run(a, kept, hip_cfg, initial)}
+    holdout = {} if a.holdout is None else {"holdout": holdout_run_dc(a, kept, board) if dc else holdout_run(a, kept, hip_cfg, initial)}
 
     r3 = lambda x: None if x is None else round(x, 3)  # noqa: E731
     print(json.dumps({"tool": "train_path", "game": a.game, "games": a.games, "warmup_games": a.warmup_games, "play_limit": a.play_limit,
