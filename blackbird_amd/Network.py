@@ -126,6 +126,7 @@ class Network:
             hip_games = cfg.get('hip_games', 'dense')
             if hip_games not in training.HIP_GAMES:
                 raise ValueError("NetworkConfig['training']['hip_games'] is 'dense' or 'all', got %r" % (hip_games,))
+            loss, l2 = training.check_loss(cfg.get('loss', 'reference'), cfg.get('l2', 1e-4))   # (ValueError, as for the keys above)
             self._handoff = handoff
             if backend == 'hip' and not training.hip_trainer_supports(self._weights, hip_games):
                 raise ValueError("NetworkConfig['training']['backend'] = 'hip' covers %s; this network has shape "
@@ -134,7 +135,7 @@ class Network:
                                     W.infer_shape(self._weights)))
             make = training.HipTrainer if backend == 'hip' else training.Trainer
             self._trainer = make(self._weights, alpha=self.alpha, epsilon=self.epsilon,
-                                 optimizer=cfg.get('optimizer', 'adam'), momentum=cfg.get('momentum', 0.9))
+                                 optimizer=cfg.get('optimizer', 'adam'), momentum=cfg.get('momentum', 0.9), loss=loss, l2=l2)
         return self._trainer
 
     def train(self, state, eval, policy, learningRate=0.01, teacher=None):

@@ -21,6 +21,7 @@ NET_FORM_AUTO, NET_FORM_F32, NET_FORM_SPLIT = 0, 1, 2   # bb_config.net_form
 NET_EVAL_FUSED, NET_EVAL_SMALL, NET_EVAL_BATCH = 0, 1, 2   # bb_net_eval_structure
 LAUNCH_AUTO, LAUNCH_LOCKSTEP, LAUNCH_ROUNDS, LAUNCH_WAVE = 0, 1, 2, 3    # bb_config.launch (LAUNCH_WAVE: the search API in one launch)
 OPT_ADAM, OPT_MOMENTUM, OPT_SGD = 0, 1, 2                # bb_train_config.optimizer
+LOSS_REFERENCE, LOSS_PER_EXAMPLE = 0, 1                  # bb_trainer_set_loss
 WEIGHTS_IMAGES = ("w0", "wt", "epi", "head", "x3")        # bb_weights_read's selector, BB_WEIGHTS_*: Engine.weights_image
 TRAIN_PARAMS, TRAIN_GRADS, TRAIN_SLOT_M, TRAIN_SLOT_V, TRAIN_NOISE = 0, 1, 2, 3, 4   # bb_trainer_read
 ROW_HAS_POLICY, ROW_TOP1, ROW_DECIDED, ROW_SIGN_OK, ROW_COUNTED = 1, 2, 4, 8, 16     # flags byte of bb_trainer_eval
@@ -37,7 +38,7 @@ EXPORTS = (
     "bb_examples_merge_workspace", "bb_examples_merge", "bb_examples_merged_to_batch",
     "bb_arena_create", "bb_arena_begin", "bb_arena_step", "bb_arena_status", "bb_arena_fetch", "bb_arena_destroy",
     "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_epoch", "bb_trainer_param_count",
-    "bb_trainer_read", "bb_trainer_eval", "bb_trainer_eval_tensors",
+    "bb_trainer_read", "bb_trainer_eval", "bb_trainer_eval_tensors", "bb_trainer_set_loss",
     "bb_load_weights_device", "bb_trainer_load_engine", "bb_weights_read",
     "bb_examples_score_workspace", "bb_examples_score",
 )
@@ -156,6 +157,7 @@ def lib():
     L.bb_arena_destroy.argtypes = [vp]
     L.bb_trainer_create.argtypes = [C.POINTER(TrainConfig), C.POINTER(NetWeights), C.POINTER(vp)]
     L.bb_trainer_destroy.argtypes = [vp]
+    L.bb_trainer_set_loss.argtypes = [vp, ip, C.c_double]
     L.bb_trainer_step.argtypes = [vp, ip, vp, vp, vp, vp, C.c_double, ip, vp, vp]
     L.bb_trainer_epoch.argtypes = [vp, ip, vp, ip, ip, vp, vp, vp, C.c_double, vp, vp, vp]
     L.bb_trainer_param_count.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -413,6 +415,11 @@ def trainer_create(game, flat, H, W, optimizer, max_batch, device=0, momentum=0.
 def trainer_destroy(h):
     if h is not None and h.value:
         lib().bb_trainer_destroy(h)
+
+
+def trainer_set_loss(h, loss, l2=0.0):
+    """bb_trainer_set_loss: LOSS_REFERENCE or LOSS_PER_EXAMPLE (with the coefficient `l2` of its L2 term) for the steps that follow."""
+    check(lib().bb_trainer_set_loss(h, int(loss), float(l2)))
 
 
 def trainer_step(h, n, boards, value, policy, noise=None, lr=0.0, apply=True, loss_out=None, stream=0):

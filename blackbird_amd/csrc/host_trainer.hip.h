@@ -16,6 +16,8 @@ struct bb_trainer {
     size_t eval_cap;  // rows the scratch holds
     uint64_t calls; // steps made so far, gradient-only ones included: the counter of the noise stream
     int64_t t;      // updates applied so far: AdamOptimizer's beta powers
+    int loss_kind = BB_LOSS_REFERENCE; // BB_LOSS_*: which loss the next step takes (bb_trainer_set_loss)
+    float l2 = 0.f;               // BB_LOSS_PER_EXAMPLE: the coefficient of the L2 term
 };
 
 static TrainLayout train_layout(int C, int R, int D, int A) {
@@ -60,6 +62,10 @@ static int trainer_lds(bb_trainer *t) { // (the same dynamic LDS whichever sourc
     t->lds_bytes = (size_t)train_lds_floats<G>(t->lay.R) * sizeof(float);
     HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainTensors<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
     HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainRecords<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
+    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainTensors<G>, BB_LOSS_PER_EXAMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)t->lds_bytes));
+    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainRecords<G>, BB_LOSS_PER_EXAMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)t->lds_bytes));
     return BB_OK;
 }
 
@@ -67,6 +73,8 @@ static int trainer_lds_wide(bb_trainer *t) {
     using G = DragonChess;
     t->lds_bytes = (size_t)train_lds_floats<G>(t->lay.R) * sizeof(float);
     HIPCHK(hipFuncSetAttribute((const void *)k_train_grad_wide<G, TrainTensors<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
+    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad_wide<G, TrainTensors<G>, BB_LOSS_PER_EXAMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)t->lds_bytes));
     return BB_OK;
 }
 
@@ -139,6 +147,24 @@ extern "C" int bb_trainer_create(const bb_train_config *cfg, const bb_net_weight
     return BB_OK;
 }
 
+// Which loss the steps after this call take: host state only -- no launch, no allocation, nothing of the device touched.
+extern "C" int bb_trainer_set_loss(bb_trainer *t, int loss, double l2) {
+    if (loss != BB_LOSS_REFERENCE && loss != BB_LOSS_PER_EXAMPLE)
+        return fail(BB_ERR_ARG, "unknown loss %d (BB_LOSS_REFERENCE = 0, BB_LOSS_PER_EXAMPLE = 1)", loss);
+    if (!(l2 >= 0.0) || !std::isfinite(l2) || !std::isfinite((float)l2)) return fail(BB_ERR_ARG, "l2 must be a finite number >= 0, got %g", l2);
+    if (!t) return fail(BB_ERR_ARG, "null trainer");
+    t->loss_kind = loss;
+    t->l2 = (float)l2;
+    return BB_OK;
+}
+
+// the per-example loss has no noise term: a caller that passes one has mistaken the mode
+static int trainer_noise_ok(const bb_trainer *t, const float *noise, const char *who) {
+    if (noise && t->loss_kind == BB_LOSS_PER_EXAMPLE)
+        return fail(BB_ERR_ARG, "%s: the per-example loss (BB_LOSS_PER_EXAMPLE) takes no noise; pass NULL", who);
+    return BB_OK;
+}
+
 extern "C" int bb_trainer_destroy(bb_trainer *t) {
     if (!t) return BB_OK;
     int prev = 0;
@@ -159,36 +185,56 @@ static void trainer_launch_apply(bb_trainer *t, int n, double lr, int apply, flo
             rate = (float)(lr * std::sqrt(1.0 - std::pow(0.999, (double)t->t)) / (1.0 - std::pow(0.9, (double)t->t)));
     }
     k_train_apply<<<nblk((size_t)l.count, BB_TRAIN_THREADS) + 1, BB_TRAIN_THREADS, 0, st>>>(
-        l.count, n, l.n_l2, t->slabs, t->kind, t->prm, t->slot_m, t->slot_v, t->grads, t->cfg.optimizer, rate, t->cfg.momentum,
+        l.count, n, l.n_l2, t->loss_kind, t->l2, t->slabs, t->kind, t->prm, t->slot_m, t->slot_v, t->grads, t->cfg.optimizer, rate, t->cfg.momentum,
         apply != 0, t->le, t->lp, t->aux, t->loss, loss_out);
 }
 
 // One step's three launches on `st`, the batch read through `src` (train.hip.h): what bb_trainer_step and every batch of
 // bb_trainer_epoch enqueue.  Host state moves as the launches are made: the noise counter, Adam's step count and lr_t.
-template <class G, class Src>
-static void trainer_launch(bb_trainer *t, int n, const Src &src, const float *noise, double lr, int apply, float *loss_out, hipStream_t st) {
+// The loss is a template argument of prep and grad (train.hip.h): the per-example step takes the same launches with other kernels.
+template <class G, class Src, int LOSS>
+static void trainer_launch_as(bb_trainer *t, int n, const Src &src, const float *noise, double lr, int apply, float *loss_out, hipStream_t st) {
     const TrainLayout &l = t->lay;
     const float eps = t->cfg.epsilon;
-    k_train_prep<G, Src><<<1, BB_TRAIN_THREADS, 0, st>>>(n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed, t->calls,
-                                                         t->aux);
+    k_train_prep<G, Src, LOSS><<<1, BB_TRAIN_THREADS, 0, st>>>(n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed,
+                                                               t->calls, t->l2, t->aux);
     t->calls++;
-    k_train_grad<G, Src><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, src, n, eps, t->slabs, t->le, t->lp);
+    k_train_grad<G, Src, LOSS><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, src, n, eps, t->slabs, t->le, t->lp);
     trainer_launch_apply(t, n, lr, apply, loss_out, st);
 }
 
-// The DragonChess step: k_train_prep_wide on 1 + ceil(A / 256) workgroups, k_train_grad_wide, then the same k_train_apply.
-static void trainer_launch_wide(bb_trainer *t, int n, const TrainTensors<DragonChess> &src, const float *noise, double lr, int apply,
-                                float *loss_out, hipStream_t st) {
+template <class G, class Src>
+static void trainer_launch(bb_trainer *t, int n, const Src &src, const float *noise, double lr, int apply, float *loss_out, hipStream_t st) {
+    if (t->loss_kind == BB_LOSS_PER_EXAMPLE)
+        trainer_launch_as<G, Src, BB_LOSS_PER_EXAMPLE>(t, n, src, noise, lr, apply, loss_out, st);
+    else
+        trainer_launch_as<G, Src, BB_LOSS_REFERENCE>(t, n, src, noise, lr, apply, loss_out, st);
+}
+
+// The DragonChess step: k_train_prep_wide on 1 + ceil(A / 256) workgroups (per example: one -- there is no label sweep),
+// k_train_grad_wide, then the same k_train_apply.
+template <int LOSS>
+static void trainer_launch_wide_as(bb_trainer *t, int n, const TrainTensors<DragonChess> &src, const float *noise, double lr, int apply,
+                                   float *loss_out, hipStream_t st) {
     using G = DragonChess;
     const TrainLayout &l = t->lay;
     const float eps = t->cfg.epsilon;
     float *aux_noise = t->aux_wide, *aux_L = t->aux_wide + G::A;
-    k_train_prep_wide<G, TrainTensors<G>><<<1 + nblk((size_t)G::A, BB_TRAIN_THREADS), BB_TRAIN_THREADS, 0, st>>>(
-        n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed, t->calls, t->aux, aux_noise, aux_L);
+    const unsigned groups = LOSS == BB_LOSS_PER_EXAMPLE ? 1u : 1u + (unsigned)nblk((size_t)G::A, BB_TRAIN_THREADS);
+    k_train_prep_wide<G, TrainTensors<G>, LOSS><<<groups, BB_TRAIN_THREADS, 0, st>>>(
+        n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed, t->calls, t->l2, t->aux, aux_noise, aux_L);
     t->calls++;
-    k_train_grad_wide<G, TrainTensors<G>><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, aux_noise, aux_L, src, n, eps, t->slabs,
-                                                                                   t->le, t->lp);
+    k_train_grad_wide<G, TrainTensors<G>, LOSS><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, aux_noise, aux_L, src, n, eps,
+                                                                                         t->slabs, t->le, t->lp);
     trainer_launch_apply(t, n, lr, apply, loss_out, st);
+}
+
+static void trainer_launch_wide(bb_trainer *t, int n, const TrainTensors<DragonChess> &src, const float *noise, double lr, int apply,
+                                float *loss_out, hipStream_t st) {
+    if (t->loss_kind == BB_LOSS_PER_EXAMPLE)
+        trainer_launch_wide_as<BB_LOSS_PER_EXAMPLE>(t, n, src, noise, lr, apply, loss_out, st);
+    else
+        trainer_launch_wide_as<BB_LOSS_REFERENCE>(t, n, src, noise, lr, apply, loss_out, st);
 }
 
 extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const float *value, const float *policy, const float *noise,
@@ -199,6 +245,7 @@ extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const 
     if (((uintptr_t)boards | (uintptr_t)value | (uintptr_t)policy | (uintptr_t)noise | (uintptr_t)loss_out) % sizeof(float))
         return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
     if (!std::isfinite(lr)) return fail(BB_ERR_ARG, "the learning rate is not finite");
+    if (int rc = trainer_noise_ok(t, noise, "bb_trainer_step")) return rc;
     if (int rc = trainer_on_device(t)) return rc;
     if (trainer_is_wide(t))
         trainer_launch_wide(t, n, TrainTensors<DragonChess>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream);
@@ -226,6 +273,7 @@ extern "C" int bb_trainer_epoch(bb_trainer *t, int n_records, const void *record
     if (!std::isfinite(lr)) return fail(BB_ERR_ARG, "the learning rate is not finite");
     if ((uintptr_t)order % sizeof(int64_t) || ((uintptr_t)noise | (uintptr_t)loss_out | (uintptr_t)bad_out) % 4)
         return fail(BB_ERR_ARG, "order must be 8-byte aligned, noise, loss_out and bad_out 4-byte aligned");
+    if (int rc = trainer_noise_ok(t, noise, "bb_trainer_epoch")) return rc;
     if (n_batches == 0) return BB_OK;
     if (!records || (uintptr_t)records % 16) return fail(BB_ERR_ARG, "records must be a 16-byte aligned device pointer");
     if (int rc = trainer_on_device(t)) return rc;

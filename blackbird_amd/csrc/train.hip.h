@@ -24,6 +24,17 @@
 // prep and a grad kernel of its own (k_train_prep_wide, k_train_grad_wide, below k_train_grad: the policy head spread over the
 // workgroup, its sum orders written there) and k_train_apply as it is; it is fed by the tensors source only -- the records
 // source and the scorer (train_eval.hip.h) are not instantiated for it.
+// The per-example loss (BB_LOSS_PER_EXAMPLE, bb_trainer_set_loss; opt-in) is a compile-time argument LOSS of the prep and grad
+// kernels; the BB_LOSS_REFERENCE instances are the text above, untouched by it.  With it
+//   lossPolicy = -(1/n) sum_b sum_a pi_b[a] log_softmax(lg_b)[a],   d loss / d lg_b[a] = (softmax_b[a] T_b - pi_b[a]) / n,   T_b = sum_a pi_b[a]
+//   lossParam  = l2 * sum over the kind-1 variables of sum(v^2) / 2,   its gradient l2 * v (k_train_apply, a run-time argument there)
+// so a row reads its OWN label (Src::label_of, both sources), nothing couples the rows, and the prep kernels form the L2 sum
+// alone: no noise, no L (k_train_prep_wide runs one workgroup instead of 17: its 4032 x n label sweep is gone).  Dense games: lane
+// 0's head block, the serial orders of k_train_eval (max, sum of expf, lse, an fmaf chain for the loss piece and for T, a
+// ascending).  Wide game: thread tid's 16 labels a = tid + 256 k take the place of m[] (no register is added), the loss piece
+// sum_a pi[a] (lg[a] - max), T and the sum of expf are per-thread chains over k ascending in one pass and one tr_tree_sum;
+// the row's piece is that sum - lse T (both terms of one sign: nothing cancels).  A row without a label adds 0 and has d lg = 0.
+// No float atomics here either.  The step counter that keys the noise stream still advances once per step.
 #pragma once
 #include "../../include/blackbird_hip.h"
 #include "examples.hip.h"
@@ -107,15 +118,32 @@ struct TrainRecords {
 };
 
 // ---- k_train_prep ---------------------------------------------------------------------------------------------------
-template <class G, class Src>
+template <class G, class Src, int LOSS = BB_LOSS_REFERENCE>
 __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_prep(int n, int count, int n_l2, const float *params, const uint8_t *kind,
                                                                 Src src, const float *noise_in, float eps, float alpha, uint64_t seed,
-                                                                uint64_t calls, TrainAux *aux) {
+                                                                uint64_t calls, float l2c, TrainAux *aux) {
     constexpr int A = G::A;
     __shared__ double s_sq[BB_TRAIN_THREADS];
+    const int tid = threadIdx.x;
+    if constexpr (LOSS == BB_LOSS_PER_EXAMPLE) { // no noise, no label sum: the L2 term alone
+        double sq = 0.0;
+        for (int i = tid; i < count; i += BB_TRAIN_THREADS)
+            if (kind[i] == 1) sq += (double)params[i] * (double)params[i];
+        s_sq[tid] = sq;
+        __syncthreads();
+        tr_tree_sum(tid, s_sq);
+        if (tid < 16) {
+            aux->noise[tid] = 0.f;
+            aux->L[tid] = 0.f;
+        }
+        if (tid == 0) {
+            aux->logS = 0.f;
+            aux->l2 = (float)((double)l2c * (0.5 * s_sq[0]));
+        }
+        return;
+    }
     __shared__ float s_part[BB_TRAIN_THREADS];
     __shared__ float s_noise[16];
-    const int tid = threadIdx.x;
     if (tid < 16) {
         float z = 0.f;
         if (tid < A && eps != 0.f)
@@ -412,7 +440,7 @@ static_assert(train_lds_floats<Connect4>(0) == 4 * 42 * 16 + 2448 + 896 && train
 static_assert(train_max_blocks<DragonChess>() >= 6, "the DragonChess step covers at least 6 blocks");
 
 // ---- k_train_grad: one workgroup per example ---------------------------------------------------------------------------
-template <class G, class Src>
+template <class G, class Src, int LOSS = BB_LOSS_REFERENCE>
 __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay, const float *__restrict__ prm, const TrainAux *__restrict__ aux,
                                                                 Src src, int n, float eps, float *__restrict__ slabs,
                                                                 float *__restrict__ le_out, float *__restrict__ lp_out) {
@@ -480,17 +508,29 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad(TrainLayout lay
             e[a] = expf(sm[S::lg + a] - mx);
             sum += e[a];
         }
-        float lp = 0.f, t = 0.f, r[A];
-        for (int a = 0; a < A; a++) {
-            e[a] = e[a] / sum; // softmax
-            const float q = __builtin_fmaf(eps, aux->noise[a], (1.0f - eps) * e[a]), La = aux->L[a];
-            if (La != 0.f) lp = __builtin_fmaf(La, logf(q) - aux->logS, lp);
-            r[a] = q > 0.f ? (1.0f - eps) * e[a] / q : 0.f;
-            t = __builtin_fmaf(La, r[a], t);
+        if constexpr (LOSS == BB_LOSS_PER_EXAMPLE) { // the row's own label: k_train_eval's ce, and T = sum_a pi[a]
+            const float lse = logf(sum);
+            float pi[A], lp = 0.f, t = 0.f;
+            for (int a = 0; a < A; a++) {
+                pi[a] = src.label_of(row, a);
+                lp = __builtin_fmaf(pi[a], (sm[S::lg + a] - mx) - lse, lp);
+                t = __builtin_fmaf(pi[a], 1.0f, t);
+            }
+            lp_out[b] = t != 0.f ? lp : 0.f; // (a row without a label -- the terminal example -- adds 0)
+            for (int a = 0; a < A; a++) sm[S::dlg + a] = ((e[a] / sum) * t - pi[a]) / (float)n;
+        } else {
+            float lp = 0.f, t = 0.f, r[A];
+            for (int a = 0; a < A; a++) {
+                e[a] = e[a] / sum; // softmax
+                const float q = __builtin_fmaf(eps, aux->noise[a], (1.0f - eps) * e[a]), La = aux->L[a];
+                if (La != 0.f) lp = __builtin_fmaf(La, logf(q) - aux->logS, lp);
+                r[a] = q > 0.f ? (1.0f - eps) * e[a] / q : 0.f;
+                t = __builtin_fmaf(La, r[a], t);
+            }
+            lp_out[b] = lp;
+            const float inv_n2 = 1.0f / ((float)n * (float)n);
+            for (int a = 0; a < A; a++) sm[S::dlg + a] = -inv_n2 * (aux->L[a] * r[a] - e[a] * t);
         }
-        lp_out[b] = lp;
-        const float inv_n2 = 1.0f / ((float)n * (float)n);
-        for (int a = 0; a < A; a++) sm[S::dlg + a] = -inv_n2 * (aux->L[a] * r[a] - e[a] * t);
     }
     __syncthreads();
 
@@ -616,12 +656,28 @@ __device__ __forceinline__ void tr_tree_max(int tid, float *s) { // tr_tree_sum'
     }
 }
 
-template <class G, class Src>
+template <class G, class Src, int LOSS = BB_LOSS_REFERENCE>
 __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_prep_wide(int n, int count, int n_l2, const float *params, const uint8_t *kind,
                                                                      Src src, const float *noise_in, float eps, float alpha, uint64_t seed,
-                                                                     uint64_t calls, TrainAux *aux, float *aux_noise, float *aux_L) {
+                                                                     uint64_t calls, float l2c, TrainAux *aux, float *aux_noise, float *aux_L) {
     constexpr int A = G::A;
     const int tid = threadIdx.x;
+    if constexpr (LOSS == BB_LOSS_PER_EXAMPLE) { // one workgroup: no noise, no label sweep; the L2 term alone
+        if (blockIdx.x > 0) return;
+        __shared__ double s_sq1[BB_TRAIN_THREADS];
+        for (int a = tid; a < A; a += BB_TRAIN_THREADS) aux_noise[a] = 0.f;
+        double sq = 0.0;
+        for (int i = tid; i < count; i += BB_TRAIN_THREADS)
+            if (kind[i] == 1) sq += (double)params[i] * (double)params[i];
+        s_sq1[tid] = sq;
+        __syncthreads();
+        tr_tree_sum(tid, s_sq1);
+        if (tid == 0) {
+            aux->logS = 0.f;
+            aux->l2 = (float)((double)l2c * (0.5 * s_sq1[0]));
+        }
+        return;
+    }
     if (blockIdx.x > 0) { // L[a]: rows ascending
         const int a = ((int)blockIdx.x - 1) * BB_TRAIN_THREADS + tid;
         if (a < A) {
@@ -661,7 +717,7 @@ struct TrainWideSmall { // offsets into the head scratch of k_train_grad_wide (i
                          end = misc + 16; // misc: 0 svy, 1..2 spy, 3 dz
 };
 
-template <class G, class Src>
+template <class G, class Src, int LOSS = BB_LOSS_REFERENCE>
 __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad_wide(TrainLayout lay, const float *__restrict__ prm, const TrainAux *__restrict__ aux,
                                                                      const float *__restrict__ aux_noise, const float *__restrict__ aux_L, Src src,
                                                                      int n, float eps, float *__restrict__ slabs, float *__restrict__ le_out,
@@ -737,52 +793,85 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad_wide(TrainLayou
         le_out[b] = diff * diff;
         sm[S::misc + 3] = 2.0f * diff * (1.0f - val * val) / (float)n;
     }
-    {
+    float m[NK]; // reference: L[a] * r[a]; per example: the row's label pi[a]
+    if constexpr (LOSS == BB_LOSS_PER_EXAMPLE) {
+        // the sum of exp, the loss piece and T in one pass over the thread's k ascending (each an fmaf chain or a plain sum), then
+        // one tr_tree_sum: sum_a pi[a] ((logit[a] - mx) - lse) = sum_a pi[a] (logit[a] - mx) - lse T, both terms of one sign
         const float mx = red0[0];
-        float se = 0.f;
-#pragma unroll
-        for (int k = 0; k < NK; k++)
-            if (tid + T * k < A) {
-                e[k] = expf(e[k] - mx);
-                se += e[k];
-            }
-        red1[tid] = se;
-    }
-    __syncthreads();
-    tr_tree_sum(tid, red1);
-    float m[NK]; // L[a] * r[a]
-    {
-        const float sum = red1[0], logS = aux->logS;
-        float lp = 0.f, t = 0.f;
+        float se = 0.f, lp = 0.f, t = 0.f;
 #pragma unroll
         for (int k = 0; k < NK; k++) {
             const int a = tid + T * k;
             m[k] = 0.f;
             if (a < A) {
-                e[k] = e[k] / sum; // softmax
-                const float q = __builtin_fmaf(eps, aux_noise[a], (1.0f - eps) * e[k]), La = aux_L[a];
-                if (La != 0.f) lp = __builtin_fmaf(La, logf(q) - logS, lp);
-                const float r = q > 0.f ? (1.0f - eps) * e[k] / q : 0.f;
-                t = __builtin_fmaf(La, r, t);
-                m[k] = La * r;
+                const float d = e[k] - mx;
+                m[k] = src.label_of(row, a);
+                lp = __builtin_fmaf(m[k], d, lp);
+                t = __builtin_fmaf(m[k], 1.0f, t);
+                e[k] = expf(d);
+                se += e[k];
             }
         }
+        red1[tid] = se;
         red2[tid] = lp;
         red3[tid] = t;
+        __syncthreads();
+        tr_tree_sum(tid, red1, red2, red3);
+        if (tid == 0) lp_out[b] = red3[0] != 0.f ? red2[0] - logf(red1[0]) * red3[0] : 0.f; // (no label: the row adds 0)
+    } else {
+        {
+            const float mx = red0[0];
+            float se = 0.f;
+#pragma unroll
+            for (int k = 0; k < NK; k++)
+                if (tid + T * k < A) {
+                    e[k] = expf(e[k] - mx);
+                    se += e[k];
+                }
+            red1[tid] = se;
+        }
+        __syncthreads();
+        tr_tree_sum(tid, red1);
+        {
+            const float sum = red1[0], logS = aux->logS;
+            float lp = 0.f, t = 0.f;
+#pragma unroll
+            for (int k = 0; k < NK; k++) {
+                const int a = tid + T * k;
+                m[k] = 0.f;
+                if (a < A) {
+                    e[k] = e[k] / sum; // softmax
+                    const float q = __builtin_fmaf(eps, aux_noise[a], (1.0f - eps) * e[k]), La = aux_L[a];
+                    if (La != 0.f) lp = __builtin_fmaf(La, logf(q) - logS, lp);
+                    const float r = q > 0.f ? (1.0f - eps) * e[k] / q : 0.f;
+                    t = __builtin_fmaf(La, r, t);
+                    m[k] = La * r;
+                }
+            }
+            red2[tid] = lp;
+            red3[tid] = t;
+        }
+        __syncthreads();
+        tr_tree_sum(tid, red2, red3);
+        if (tid == 0) lp_out[b] = red2[0];
     }
-    __syncthreads();
-    tr_tree_sum(tid, red2, red3);
-    if (tid == 0) lp_out[b] = red2[0];
 
     // ---- backward: heads ----
+    // g_1's partial sums: red1 -- per example red2, because other waves may still be reading the sum of exp in red1[0] (red2[0] is
+    // read by thread 0 alone, which is the one that writes it here)
+    float *rg1 = LOSS == BB_LOSS_PER_EXAMPLE ? red2 : red1;
     {
-        const float t = red3[0], inv_n2 = 1.0f / ((float)n * (float)n), spy0 = sm[S::misc + 1], spy1 = sm[S::misc + 2];
+        const float t = red3[0], sum = red1[0], inv_n2 = 1.0f / ((float)n * (float)n), spy0 = sm[S::misc + 1], spy1 = sm[S::misc + 2];
         float g0 = 0.f, g1 = 0.f;
 #pragma unroll
         for (int k = 0; k < NK; k++) {
             const int a = tid + T * k;
             if (a < A) {
-                const float dl = -inv_n2 * (m[k] - e[k] * t);
+                float dl;
+                if constexpr (LOSS == BB_LOSS_PER_EXAMPLE)
+                    dl = ((e[k] / sum) * t - m[k]) / (float)n;
+                else
+                    dl = -inv_n2 * (m[k] - e[k] * t);
                 slab[lay.p_d_b + a] = dl * (float)P;
                 slab[lay.p_d_k + a] = dl * spy0;
                 slab[lay.p_d_k + A + a] = dl * spy1;
@@ -791,10 +880,10 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad_wide(TrainLayou
             }
         }
         red0[tid] = g0;
-        red1[tid] = g1;
+        rg1[tid] = g1;
     }
     __syncthreads();
-    tr_tree_sum(tid, red0, red1);
+    tr_tree_sum(tid, red0, rg1);
     const float dz = sm[S::misc + 3];
     if (tid < D) {
         const float h = sm[S::hbuf + tid], dh = h > 0.f ? dz * prm[lay.v_d2_k + tid] : 0.f;
@@ -812,7 +901,7 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad_wide(TrainLayou
         sm[S::dvy + tid] = sm[S::vy + tid] > 0.f ? g1 : 0.f;
     } else if (tid >= 64 && tid < 64 + 2 * P) { // ... and every square's policy-head activation j the same g_j
         const int el = tid - 64;
-        const float g = (el & 1) ? red1[0] : red0[0];
+        const float g = (el & 1) ? rg1[0] : red0[0];
         sm[S::dpy + el] = sm[S::py + el] > 0.f ? g : 0.f;
     }
     __syncthreads();
@@ -883,7 +972,7 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_grad_wide(TrainLayou
 // ---- k_train_apply ---------------------------------------------------------------------------------------------------
 // One thread per parameter element: slabs summed b = 0 .. n-1, the L2 part, the update.  The workgroup after the last
 // element reduces the loss pieces: loss[4] = total, evaluation, policy, parameter term.
-__global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_apply(int count, int n, int n_l2, const float *__restrict__ slabs,
+__global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_apply(int count, int n, int n_l2, int loss_kind, float l2c, const float *__restrict__ slabs,
                                                                  const uint8_t *__restrict__ kind, float *__restrict__ prm,
                                                                  float *__restrict__ slot_m, float *__restrict__ slot_v, float *__restrict__ grads,
                                                                  int opt, float lr, float momentum, int apply, const float *le,
@@ -901,7 +990,9 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_apply(int count, int
         __syncthreads();
         tr_tree_sum(tid, s_e, s_p);
         if (tid == 0) {
-            const float l_e = (float)(s_e[0] / (double)n), l_p = (float)(-s_p[0] / ((double)n * (double)n)), l_w = aux->l2;
+            // reference: the B x B cross matrix's mean; per example: the mean over the rows
+            const float l_e = (float)(s_e[0] / (double)n), l_w = aux->l2,
+                        l_p = (float)(-s_p[0] / (loss_kind == BB_LOSS_PER_EXAMPLE ? (double)n : (double)n * (double)n));
             const float total = l_e + l_p + l_w;
             loss[0] = total; loss[1] = l_e; loss[2] = l_p; loss[3] = l_w;
             if (loss_out) {
@@ -920,7 +1011,7 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_apply(int count, int
     float g = 0.f;
     for (int b = 0; b < n; b++) g += slabs[(size_t)b * count + i];
     const float p = prm[i];
-    if (kd == 1) g += p / (float)n_l2;
+    if (kd == 1) g += loss_kind == BB_LOSS_PER_EXAMPLE ? l2c * p : p / (float)n_l2;
     grads[i] = g;
     if (!apply) return;
     if (opt == BB_OPT_ADAM) { // lr is lr_t = lr sqrt(1 - b2^t) / (1 - b1^t); epsilon outside the bias correction (TF1)

@@ -11,6 +11,13 @@ Reproduced exactly as written in the reference graph, quirks included:
   * optimiser: tf.compat.v1.train Adam / Momentum / GradientDescent by config, their update rules written out
     in `Trainer._apply` (TF1's Adam puts epsilon outside the bias correction; torch.optim.Adam does not)  (:234-242)
 The teacher term (:205-218) calls the removed `tf.log` in the reference and cannot run there; Network.train refuses it.
+
+An extension, opt-in (loss='per_example'; NetworkConfig['training']['loss']): the ordinary AlphaZero loss.  The cross matrix above
+trains every row towards the batch's summed label; this one trains a row towards its own:
+  * value loss  = as above
+  * policy loss = -(1/n) sum_b sum_a pi_b[a] log_softmax(logits_b)[a]; a row whose label is all zeros (the terminal example) adds 0
+  * L2 term     = l2 * sum over the same variables of sum(v^2)/2
+  * no noise (alpha and epsilon are not used; a noise= argument is refused)
 """
 import numpy as np
 import torch
@@ -20,8 +27,30 @@ from . import _lib
 from . import weights as W
 
 
+LOSSES = ('reference', 'per_example')  # NetworkConfig['training']['loss']
+
+
+def check_loss(loss, l2):
+    """The two loss arguments of both trainers, validated: (loss, float(l2)) or ValueError."""
+    if loss not in LOSSES:
+        raise ValueError("loss is 'reference' or 'per_example', got %r" % (loss,))
+    try:
+        value = float(l2)
+    except (TypeError, ValueError):
+        raise ValueError('l2 must be a finite number >= 0, got %r' % (l2,))
+    if not 0.0 <= value <= float(np.finfo(np.float32).max):      # (NaN fails both; the kernels take it as a float32)
+        raise ValueError('l2 must be a finite number >= 0, got %r' % (l2,))
+    return loss, value
+
+
+def _no_noise(loss, noise):
+    if loss == 'per_example' and noise is not None:
+        raise ValueError("the per-example loss has no noise term: noise= must be None with loss='per_example'")
+
+
 class Trainer:
-    def __init__(self, weights, alpha=0.2, epsilon=0.3, optimizer='adam', momentum=0.9, device=None):
+    def __init__(self, weights, alpha=0.2, epsilon=0.3, optimizer='adam', momentum=0.9, device=None, loss='reference', l2=1e-4):
+        self.loss_kind, self.l2 = check_loss(loss, l2)
         self.device = torch.device(device or ('cuda' if torch.cuda.is_available() else 'cpu'))
         self.alpha, self.epsilon = float(alpha), float(epsilon)
         self.C, self.F, self.R, self.D, self.A = W.infer_shape(weights)
@@ -89,7 +118,14 @@ class Trainer:
         return value, logits
 
     def loss(self, boards, evalLabel, policyLabel, noise=None):
+        _no_noise(self.loss_kind, noise)
         value, logits = self.forward(boards)
+        if self.loss_kind == 'per_example':
+            lossEvaluation = torch.mean((value - evalLabel) ** 2)
+            # (a row of zeros contributes 0 * log_softmax = 0 and has no gradient)
+            lossPolicy = -(policyLabel * torch.log_softmax(logits, dim=1)).sum() / policyLabel.shape[0]
+            lossParam = self.l2 * torch.stack([0.5 * (p ** 2).sum() for k, p in self.params.items() if 'bias' not in k]).sum()
+            return lossEvaluation + lossPolicy + lossParam, (lossEvaluation, lossPolicy, lossParam)
         base = torch.softmax(logits, dim=1)
         if noise is None:  # A independent Beta(alpha, 1-alpha) draws shared across the batch
             noise = torch.distributions.Beta(self.alpha, 1.0 - self.alpha).sample((self.A,)).to(self.device)
@@ -233,9 +269,12 @@ class HipTrainer:
     optimiser slots and gradients live in the library's own device buffers; `export` reads the parameters back.  Covers
     HIP_TRAINER_LIMITS_ALL; anything else raises ValueError.  A DragonChess trainer (`wide`) steps from batch tensors only:
     epoch_records, evaluate_records and evaluate_tensors raise ValueError for it.  `seed` keys the Beta noise a step draws when none is given
-    (None: from numpy's generator, as the engines do); `max_batch` bounds the examples of one step."""
+    (None: from numpy's generator, as the engines do); `max_batch` bounds the examples of one step.  loss='per_example' (with its
+    coefficient `l2`) makes every step the per-example loss of the module's docstring (bb_trainer_set_loss), from either source."""
 
-    def __init__(self, weights, alpha=0.2, epsilon=0.3, optimizer='adam', momentum=0.9, device=None, seed=None, max_batch=1024):
+    def __init__(self, weights, alpha=0.2, epsilon=0.3, optimizer='adam', momentum=0.9, device=None, seed=None, max_batch=1024,
+                 loss='reference', l2=1e-4):
+        self.loss_kind, self.l2 = check_loss(loss, l2)
         self.device = torch.device(device or 'cuda')
         if self.device.type != 'cuda':
             raise _lib.BlackbirdHipError('HipTrainer runs on the GPU only (device %s)' % self.device)
@@ -258,6 +297,8 @@ class HipTrainer:
                                       device=self._index, momentum=self.momentum, alpha=self.alpha, epsilon=self.epsilon,
                                       seed=seed)
         self.count = _lib.trainer_param_count(self._h)
+        if self.loss_kind != 'reference':      # (a trainer is created with the reference loss)
+            _lib.trainer_set_loss(self._h, _lib.LOSS_PER_EXAMPLE, self.l2)
 
     def close(self):
         h, self._h = getattr(self, '_h', None), None
@@ -272,6 +313,7 @@ class HipTrainer:
 
     def _launch(self, boards, evalLabel, policyLabel, noise, lr, apply):
         """One bb_trainer_step on torch's current stream; returns the device tensor [4] of the loss and its terms."""
+        _no_noise(self.loss_kind, noise)
         n = int(policyLabel.shape[0]) if hasattr(policyLabel, 'shape') else len(policyLabel)
         boards = self._f32(boards, (n, self.H, self.Wd, self.C))
         ev = self._f32(evalLabel, (n,))
@@ -323,6 +365,7 @@ class HipTrainer:
         ValueError).  order, sym: tensors as examples.index_tensor and examples.sym_tensor return them (order None: the records
         in order), whole batches.  noise: [n_batches, A] or None to draw it.  Malformed rows count in examples.bad()."""
         self._not_wide('epoch_records')
+        _no_noise(self.loss_kind, noise)
         if not isinstance(examples, DeviceExamples):
             raise ValueError('epoch_records takes a DeviceExamples (merged rows carry sums of their own and are not a records '
                              'source), got %s' % type(examples).__name__)

@@ -578,6 +578,20 @@ typedef struct bb_trainer bb_trainer;
  * above -- checked before any device call; BB_ERR_HIP without a GPU; BB_ERR_CAPACITY if the slabs do not fit the free memory. */
 int bb_trainer_create(const bb_train_config *cfg, const bb_net_weights *w, bb_trainer **out);
 int bb_trainer_destroy(bb_trainer *t);
+/* The loss of the steps made after this call (an extension; a trainer is created with BB_LOSS_REFERENCE, the reference graph's
+ * loss described above, and behaves bit for bit as before until this is called).  BB_LOSS_PER_EXAMPLE, for a batch of n rows with
+ * value v_b, logits lg_b, policy label pi_b and outcome z_b:
+ *   lossEvaluation = (1/n) sum_b (v_b - z_b)^2                                  (as the reference's)
+ *   lossPolicy     = -(1/n) sum_b sum_a pi_b[a] log_softmax(lg_b)[a]            a row whose label is all zeros adds 0
+ *   lossParam      = l2 * sum over the trainable non-bias variables of sum(v^2)/2
+ *   d loss / d lg_b[a] = (softmax_b[a] T_b - pi_b[a]) / n, T_b = sum_a pi_b[a];  d lossParam / d v = l2 * v
+ * No noise: alpha and epsilon are not used, nothing is drawn (BB_TRAIN_NOISE reads zeros), and bb_trainer_step / bb_trainer_epoch
+ * return BB_ERR_ARG for a noise pointer.  The same three launches with the loss as a compile-time argument of the kernels
+ * (csrc/train.hip.h), no float atomics: the same steps give the same bits.  l2 is read with BB_LOSS_PER_EXAMPLE only.  Host state
+ * alone: callable at any time between steps, no device call, no allocation; optimiser slots and step counts carry over.
+ * BB_ERR_ARG: an unknown loss, an l2 that is negative or not finite (as a float32 too), a null trainer. */
+enum { BB_LOSS_REFERENCE = 0, BB_LOSS_PER_EXAMPLE = 1 };
+int bb_trainer_set_loss(bb_trainer *t, int loss, double l2);
 /* boards [n][H][W][C], value [n], policy [n][A], noise [A] or NULL: float32 DEVICE pointers of the trainer's device, which must
  * be the calling thread's current one; loss_out: device float[4] = total, evaluation, policy, parameter term, or NULL.
  * noise == NULL and epsilon != 0: A Beta(alpha, 1-alpha) values are drawn (readable afterwards, BB_TRAIN_NOISE).

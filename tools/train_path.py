@@ -1,6 +1,6 @@
 """From finished self-play games to a trained network, both ways, timed: python tools/train_path.py [--games N]
 [--play-limit P] [--batch B] [--lr LR] [--augment] [--merge] [--holdout FRACTION] [--skip-host] [--skip-device] [--skip-hip]
-[--handoff host|device] [--game connect4|dragonchess] [--warmup-games W] [--score-engine]
+[--handoff host|device] [--game connect4|dragonchess] [--warmup-games W] [--score-engine] [--loss reference|per_example]
 
 --game dragonchess: the same on DragonChess (17 planes, 4032 actions), the hip model with NetworkConfig['training']['hip_games'] =
 'all'.  The records source and the scorer do not cover that game, so hip_epoch_s is null and --holdout and --merge are refused;
@@ -50,6 +50,10 @@ self-play uses), timed the same way next to the other routes (score_engine_s; sc
 its figures and their distance from evaluate_records'.  With --game dragonchess --holdout is accepted together with
 --score-engine only: a model with the PyTorch trainer scores the held-out part both ways -- Trainer.evaluate_tensors over
 examples._batch chunks (torch_route_s), which was the only route for that game, and scorer='engine' -- and nothing is trained.
+
+--loss reference|per_example (default reference): NetworkConfig['training']['loss'] of every model of the run -- the PyTorch
+trainer, the hip model and the --holdout model alike; per_example is the ordinary AlphaZero loss (each row's own label, l2 1e-4,
+no noise).  Every figure is measured as without it.
 Prints one JSON line."""
 import argparse
 import copy
@@ -167,7 +171,10 @@ def main():
     ap.add_argument("--game", choices=("connect4", "dragonchess"), default="connect4")
     ap.add_argument("--warmup-games", type=int, default=64)
     ap.add_argument("--score-engine", action="store_true")
+    ap.add_argument("--loss", choices=("reference", "per_example"), default="reference")
     a = ap.parse_args()
+    if a.loss != "reference":
+        CFG["training"]["loss"] = a.loss  # (every model of the run is made from CFG or a copy of it)
     dc = a.game == "dragonchess"
     if a.score_engine and a.holdout is None:
         ap.error("--score-engine goes with --holdout")
@@ -301,7 +308,7 @@ def main():
     holdout = {} if a.holdout is None else {"holdout": holdout_run_dc(a, kept, board) if dc else holdout_run(a, kept, hip_cfg, initial)}
 
     r3 = lambda x: None if x is None else round(x, 3)  # noqa: E731
-    print(json.dumps({"tool": "train_path", "game": a.game, "games": a.games, "warmup_games": a.warmup_games, "play_limit": a.play_limit,
+    print(json.dumps({"tool": "train_path", "game": a.game, "loss": a.loss, "games": a.games, "warmup_games": a.warmup_games, "play_limit": a.play_limit,
                       "examples": n, "augment": bool(a.augment), "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
                       "host_path_s": r3(host_s), "host_decode_s": r3(decode_s),
                       "device_path_s": r3(device_s), "device_batches_only_s": round(batch_s, 4),
