@@ -78,11 +78,12 @@ def _packed_starts(model, startStates):
     return np.ascontiguousarray(np.concatenate([s._packed() for s in startStates], axis=0))
 
 
-def _timed_selfplay(model, nGames, temp, startStates=None):
+def _timed_selfplay(model, nGames, temp, startStates=None, schedule=None):
     """GenerateTrainingSamples when the searcher has a wall-clock limit per move (mcts.timeLimit, MCTS.py:173-182, :298):
     the reference's loop (FindMove, example, MoveRoot, Winner) for all games of a wave at once through the lock-step entry
     points -- every move, all live games are searched together until `TimeLimit` seconds have passed (and no further than
-    PlayLimit simulations when that is set too), then each samples its move with numpy's next uniform."""
+    PlayLimit simulations when that is set too), then each samples its move with numpy's next uniform.  schedule: (plies,
+    lateTemp) or None; all games of a wave are on the same ply, so the loop picks each ply's temperature (_lib.temp_at)."""
     from time import time
     game_cls = model.Game
     game = game_cls.GAME_ID
@@ -124,7 +125,8 @@ def _timed_selfplay(model, nGames, temp, startStates=None):
                     raise _lib.BlackbirdHipError('search tree outgrew the node pool')
                 u = np.zeros(n_slots)
                 u[live] = np.random.random_sample(len(live))
-                out = eng.sample_moves(temp, u if temp != 0 else None)
+                now = _lib.temp_at(temp, schedule, _ply)
+                out = eng.sample_moves(now, u if now != 0 else None)
                 planes = _lib.game_encode(game, states[live])
                 acts = np.full(n_slots, -1, dtype=np.int32)
                 for k, gidx in enumerate(live):
@@ -168,17 +170,21 @@ def _side_to_move(game, packed):
     return int((int(np.asarray(packed).view(np.uint64).reshape(-1)[0]) >> 56) & 3)
 
 
-def _parked_without_probabilities(eng, temp):
-    """Whether a slot of a stopped self-play run sits on a root whose visit counts give no probabilities at `temp`: N ** (1 / temp)
-    overflowed (inf / inf), which parks the slot (bb_selfplay_begin) where the reference's np.random.choice raises ValueError."""
-    if temp == 0:
-        return False
-    for slot in range(eng.n_slots):
-        plays = eng.node_edges(slot)['plays'].astype(np.float64)
-        with np.errstate(over='ignore'):
-            if plays.sum() > 0 and not np.isfinite(np.sum(plays ** (1.0 / temp))):
-                return True
-    return False
+def _parked_without_probabilities(eng, temp, schedule=None):
+    """The temperature at which a slot of a stopped self-play run sits on a root whose visit counts give no probabilities -- N **
+    (1 / temp) overflowed (inf / inf), which parks the slot (bb_selfplay_begin) where the reference's np.random.choice raises
+    ValueError -- or None.  Under a schedule (plies, lateTemp) either temperature may be the one: both are tried, the run's own
+    first.  (A parked slot keeps its root, but its ply counter is not readable from here, so the temperature is found by what
+    overflows; where both would, the earlier one is named.)"""
+    for t in (temp,) if schedule is None else (temp, schedule[1]):
+        if t == 0:
+            continue
+        for slot in range(eng.n_slots):
+            plays = eng.node_edges(slot)['plays'].astype(np.float64)
+            with np.errstate(over='ignore'):
+                if plays.sum() > 0 and not np.isfinite(np.sum(plays ** (1.0 / t))):
+                    return t
+    return None
 
 
 def GenerateTrainingSamples(model, nGames, temp, startStates=None):
@@ -187,15 +193,22 @@ def GenerateTrainingSamples(model, nGames, temp, startStates=None):
     startStates (beyond the reference, which starts every game from model.Game()): a sequence of model.Game states; the k-th
     game of the call, in game-id order, starts from startStates[k % len(startStates)], its examples count plies from there and
     its first example is that state.  None or empty: the initial position.  ValueError, with nothing stored, for a state no
-    game can start from (already over, no legal move, or a DragonChess position with more moves than a tree node holds)."""
+    game can start from (already over, no legal move, or a DragonChess position with more moves than a tree node holds).
+    model.SelfPlayTempSchedule (beyond the reference, which plays a game at one temperature; an attribute like
+    KeepDeviceExamples, so that this function's signature stays the reference's plus startStates): (plies, lateTemp) -- the
+    move out of ply p, counted from the game's start position, is drawn at `temp` while p < plies and at lateTemp from there on
+    (0: the PUCT arg-max move).  None, the default: every move at `temp`.  ValueError before any engine is made for anything
+    but a pair of an integer and a finite lateTemp >= 0."""
     if nGames <= 0:
         raise ValueError('Use a positive integer for number of games.')
+    schedule = _lib.temp_schedule(getattr(model, 'SelfPlayTempSchedule', None))
     game_cls = model.Game
     if model.TimeLimit is not None:
-        return _timed_selfplay(model, nGames, temp, startStates)
+        return _timed_selfplay(model, nGames, temp, startStates, schedule)
     starts = _packed_starts(model, startStates)
     eng = model._selfplay_engine(nGames)
     eng.selfplay_set_starts(starts)  # (None clears what an earlier call left on the engine it shares with this one)
+    eng.selfplay_set_temp_schedule(*(schedule or (-1, 0.0)))  # (and so does "off")
     # every call is a fresh draw, as in the reference (new numpy choices and new graph noise each time): a new Philox
     # key from numpy's generator (advancing it) and game ids that continue where the model's last run stopped
     eng.set_rng_stream(int(np.random.randint(0, 2 ** 62, dtype=np.int64)), model._games_played)
@@ -260,8 +273,10 @@ def GenerateTrainingSamples(model, nGames, temp, startStates=None):
                 pending = None
             hdr = eng.selfplay_headers(0, nGames)   # (waits for the launch)
             if eng.counters()['overflow']:  # pool exhausted, a parked slot or an aborted launch: the games would never finish
-                if _parked_without_probabilities(eng, temp):
-                    raise ValueError('probabilities contain NaN')   # np.random.choice in the reference's FindMove
+                hot = _parked_without_probabilities(eng, temp, schedule)
+                if hot is not None:                                 # np.random.choice in the reference's FindMove
+                    raise ValueError('probabilities contain NaN' + (' (at the schedule\'s late temperature %r)' % hot
+                                                                    if schedule is not None and hot != temp else ''))
                 raise _lib.BlackbirdHipError('self-play stopped: a search tree outgrew its node pool or a launch was aborted')
             new = np.nonzero((hdr[:, 3] != 0) & ~seen)[0]
             if len(new):
@@ -417,45 +432,45 @@ def TestModelsBatched(model1, model2, temp, numTests, **kw):
     return run(model1, model2, temp, numTests, **kw)
 
 
-def TestModels(model1, model2, temp, numTests):
+def TestModels(model1, model2, temp, numTests, tempSchedule=None):
     """Blackbird.py:177-216: one head-to-head game, +1 / 0 / -1 for model1's win / draw / loss.  (The reference's
     loop over numTests returns at the end of its first game, so one game is what a call plays.)  The game itself --
     coin toss for the first move, FindMove on the mover's turns, MoveRoot for both after every move -- runs in the
-    batched arena with a batch of one."""
+    batched arena with a batch of one.  tempSchedule: as TestModelsBatched takes it."""
     if numTests <= 0:
         return None
-    return int(TestModelsBatched(model1, model2, temp, 1)[0])
+    return int(TestModelsBatched(model1, model2, temp, 1, tempSchedule=tempSchedule)[0])
 
 
-def _tally(model, opponent, temp, numTests, opName, opVersion=0):
+def _tally(model, opponent, temp, numTests, opName, opVersion=0, tempSchedule=None):
     """The Test* wrappers (Blackbird.py:84-174): numTests games, every result logged, counts returned.  All games are
     played concurrently by the batched arena; results are logged in game order."""
     stats = defaultdict(int)
     if numTests <= 0:
         return stats
     names = {1: 'wins', 0: 'draws', -1: 'losses'}
-    for result in TestModelsBatched(model, opponent, temp, numTests):
+    for result in TestModelsBatched(model, opponent, temp, numTests, tempSchedule=tempSchedule):
         stats[names.get(int(result), 'indeterminant')] += 1
         model.Conn.PutTrainingStatistic(int(result), model.Name, model.Version, opName, opVersion)
     return stats
 
 
-def TestRandom(model, temp, numTests):
+def TestRandom(model, temp, numTests, tempSchedule=None):
     """Blackbird.py:84-111"""
-    return _tally(model, RandomMCTS(), temp, numTests, 'RANDOM')
+    return _tally(model, RandomMCTS(), temp, numTests, 'RANDOM', tempSchedule=tempSchedule)
 
 
-def TestPrevious(model, temp, numTests):
+def TestPrevious(model, temp, numTests, tempSchedule=None):
     """Blackbird.py:114-143"""
     oldModel = model.LastVersion()
-    return _tally(model, oldModel, temp, numTests, oldModel.Name, oldModel.Version)
+    return _tally(model, oldModel, temp, numTests, oldModel.Name, oldModel.Version, tempSchedule=tempSchedule)
 
 
-def TestGood(model, temp, numTests):
+def TestGood(model, temp, numTests, tempSchedule=None):
     """Blackbird.py:146-174"""
     good = FixedMCTS(maxDepth=10, explorationRate=0.85, timeLimit=1)
     good.Game = model.Game
-    return _tally(model, good, temp, numTests, 'MCTS')
+    return _tally(model, good, temp, numTests, 'MCTS', tempSchedule=tempSchedule)
 
 
 class Model(MCTS, Network):
@@ -474,6 +489,8 @@ class Model(MCTS, Network):
         # the Version they were played by, for TrainWithDeviceExamples; sqlite receives every game either way.  Runs under a
         # time limit (mcts.timeLimit: _timed_selfplay) search in lock step and leave no engine records: nothing is kept
         self.KeepDeviceExamples = False
+        # opt-in: GenerateTrainingSamples plays under a temperature schedule by ply, (plies, lateTemp); None: one temperature
+        self.SelfPlayTempSchedule = None
         self._kept_examples = []
         MCTS.__init__(self, **mctsConfig)
         factory = None

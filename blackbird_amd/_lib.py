@@ -32,11 +32,11 @@ EXPORTS = (
     "bb_game_info_get", "bb_last_error", "bb_device_count", "bb_game_legal", "bb_game_apply", "bb_game_winner",
     "bb_game_encode", "bb_game_initial", "bb_create", "bb_destroy", "bb_load_weights", "bb_get_counters",
     "bb_reset_counters", "bb_synchronize", "bb_set_sims_per_move", "bb_timing_enable", "bb_timing_read", "bb_timing_net", "bb_selfplay_mode", "bb_net_form", "bb_net_eval_structure", "bb_net_eval", "bb_hash_eval", "bb_set_roots", "bb_run_sims", "bb_run_sims_masked", "bb_run_sims_structure", "bb_search_rollouts", "bb_selfplay_rollouts",
-    "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_set_starts", "bb_selfplay_step",
+    "bb_sample_moves", "bb_move_roots", "bb_get_root_states", "bb_selfplay_begin", "bb_selfplay_set_starts", "bb_selfplay_set_temp_schedule", "bb_selfplay_step",
     "bb_selfplay_done", "bb_examples_fetch", "bb_examples_device", "bb_selfplay_headers", "bb_examples_fetch_games", "bb_reset_roots", "bb_node_view", "bb_node_edges", "bb_net_eval_keyed", "bb_set_rng_stream", "bb_fit_slots",
     "bb_examples_to_batch", "bb_examples_to_batch_sym", "bb_game_symmetries",
     "bb_examples_merge_workspace", "bb_examples_merge", "bb_examples_merged_to_batch",
-    "bb_arena_create", "bb_arena_begin", "bb_arena_step", "bb_arena_status", "bb_arena_fetch", "bb_arena_destroy",
+    "bb_arena_create", "bb_arena_begin", "bb_arena_set_temp_schedule", "bb_arena_step", "bb_arena_status", "bb_arena_fetch", "bb_arena_destroy",
     "bb_trainer_create", "bb_trainer_destroy", "bb_trainer_step", "bb_trainer_epoch", "bb_trainer_param_count",
     "bb_trainer_read", "bb_trainer_eval", "bb_trainer_eval_tensors", "bb_trainer_set_loss",
     "bb_load_weights_device", "bb_trainer_load_engine", "bb_weights_read",
@@ -134,6 +134,7 @@ def lib():
     L.bb_get_root_states.argtypes = [vp, vp]
     L.bb_selfplay_begin.argtypes = [vp, ip, C.c_double]
     L.bb_selfplay_set_starts.argtypes = [vp, ip, vp]
+    L.bb_selfplay_set_temp_schedule.argtypes = [vp, ip, C.c_double]
     L.bb_selfplay_step.argtypes = [vp, ip]
     L.bb_selfplay_done.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
     L.bb_examples_fetch.argtypes = [vp, ip, ip, vp, ip, vp, vp]
@@ -151,6 +152,7 @@ def lib():
     L.bb_examples_merged_to_batch.argtypes = [ip, ip, vp, ip, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]
     L.bb_arena_create.argtypes = [vp, vp, ip, C.POINTER(vp)]
     L.bb_arena_begin.argtypes = [vp, ip, vp, vp, C.c_double]
+    L.bb_arena_set_temp_schedule.argtypes = [vp, ip, C.c_double]
     L.bb_arena_step.argtypes = [vp, ip]
     L.bb_arena_status.argtypes = [vp, C.POINTER(ip)]
     L.bb_arena_fetch.argtypes = [vp, vp, vp, vp, vp]
@@ -470,6 +472,29 @@ def trainer_read(h, what, count=None):
     return out
 
 
+def temp_schedule(tempSchedule):
+    """Model.SelfPlayTempSchedule / tempSchedule= of TestModelsBatched as (plies, lateTemp), or None for None.  ValueError for
+    anything but a pair of an integer and a finite temperature >= 0 -- raised before any engine is made.  plies < 0 is the
+    C ABI's "off": None."""
+    if tempSchedule is None:
+        return None
+    try:
+        plies, late = tempSchedule
+    except (TypeError, ValueError):
+        raise ValueError('tempSchedule must be a pair (plies, lateTemp), not {!r}'.format(tempSchedule)) from None
+    if isinstance(plies, (bool, np.bool_)) or not isinstance(plies, (int, np.integer)):
+        raise ValueError('tempSchedule: plies must be an integer, not {!r}'.format(plies))
+    if isinstance(late, (bool, np.bool_)) or not isinstance(late, (int, float, np.integer, np.floating)) \
+            or not (late >= 0 and np.isfinite(late)):
+        raise ValueError('tempSchedule: lateTemp must be a finite temperature >= 0, not {!r}'.format(late))
+    return (int(plies), float(late)) if plies >= 0 else None
+
+
+def temp_at(temp, schedule, ply):
+    """The temperature of the move out of ply `ply` under schedule (plies, lateTemp) or None."""
+    return temp if schedule is None or ply < schedule[0] else schedule[1]
+
+
 def fit_slots(game, n_slots, sims_per_move, *, mcts_kind=MCTS_DYNAMIC, max_depth=10, max_plies=None, max_games=None,
               node_capacity=0, device=0):
     """bb_fit_slots: (largest slot count <= n_slots whose pools fit the device's free memory, bytes per slot)."""
@@ -727,6 +752,11 @@ class Engine:
             raise ValueError("start states: %d bytes for %d states of %d bytes each" % (states.nbytes, n, self.info.state_bytes))
         check(lib().bb_selfplay_set_starts(self.h, n, ptr(states)))
 
+    def selfplay_set_temp_schedule(self, plies, temp_late=0.0):
+        """bb_selfplay_set_temp_schedule: in every later selfplay_begin the move out of ply p (counted from the game's start
+        position) is drawn at begin's temp while p < plies and at temp_late from there on.  plies < 0 (or None) turns it off."""
+        check(lib().bb_selfplay_set_temp_schedule(self.h, -1 if plies is None else int(plies), float(temp_late)))
+
     def selfplay_step(self, plies=1):
         check(lib().bb_selfplay_step(self.h, int(plies)))
 
@@ -816,6 +846,11 @@ class Arena:
                 raise ValueError("start states: %d bytes for %d games of %d bytes each" % (start_states.nbytes, n, self.a.info.state_bytes))
         check(lib().bb_arena_begin(self.h, n, ptr(first), ptr(start_states), float(temp)))
         self.n_games = n
+
+    def set_temp_schedule(self, plies, temp_late=0.0):
+        """bb_arena_set_temp_schedule, before begin(): ply p of the match is sampled at begin's temp while p < plies, at temp_late
+        from there on.  plies < 0 (or None) turns it off."""
+        check(lib().bb_arena_set_temp_schedule(self.h, -1 if plies is None else int(plies), float(temp_late)))
 
     def step(self, plies=1):
         check(lib().bb_arena_step(self.h, int(plies)))

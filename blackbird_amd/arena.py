@@ -96,10 +96,12 @@ def _choose_loop(model1, model2, playLimit, uniforms, loop):
     return loop
 
 
-def _device_arena(sides, game_id, temp, numTests, first, starts):
-    """The match loop on the device: create, begin, step + status until nobody is alive, fetch."""
+def _device_arena(sides, game_id, temp, numTests, first, starts, schedule=None):
+    """The match loop on the device: create, (schedule,) begin, step + status until nobody is alive, fetch."""
     arena = _lib.Arena(sides[0].engine, sides[1].engine, log_plies=0)
     try:
+        if schedule is not None:
+            arena.set_temp_schedule(*schedule)
         arena.begin(first, temp, starts)
         while True:
             arena.step(_STEP_PLIES)
@@ -110,7 +112,8 @@ def _device_arena(sides, game_id, temp, numTests, first, starts):
         arena.close()
 
 
-def TestModelsBatched(model1, model2, temp, numTests, playLimit=None, first=None, uniforms=None, loop=None, startStates=None):
+def TestModelsBatched(model1, model2, temp, numTests, playLimit=None, first=None, uniforms=None, loop=None, startStates=None,
+                      tempSchedule=None):
     """Play `numTests` games of model1 against model2 concurrently; returns an int array of +1 / 0 / -1 (model1's
     wins / draws / losses), one entry per game, in game order.
 
@@ -122,10 +125,15 @@ def TestModelsBatched(model1, model2, temp, numTests, playLimit=None, first=None
                host loop only
     loop       'host' or 'device' (module docstring); None takes model1.ArenaLoop as a preference.  `last_loop` says which
                loop played.  An explicit 'device' that is not possible raises ValueError naming the reason
-    startStates  device loop only: a list of numTests GameStates the games start from instead of `Game()`"""
+    startStates  device loop only: a list of numTests GameStates the games start from instead of `Game()`
+    tempSchedule (plies, lateTemp): ply p of the match -- 0 for each game's first move -- is played at `temp` while p < plies and
+               at lateTemp from there on (0: the PUCT arg-max move): varied openings, then each side's best play.  Both loops;
+               a RandomMCTS side takes no temperature.  ValueError, before any engine is made, for anything but a pair of an
+               integer and a finite lateTemp >= 0"""
     global last_loop
     if numTests <= 0:
         raise ValueError('Use a positive integer for number of tests.')
+    schedule = _lib.temp_schedule(tempSchedule)
     which = _choose_loop(model1, model2, playLimit, uniforms, loop)
     last_loop = which
     starts = None
@@ -153,13 +161,16 @@ def TestModelsBatched(model1, model2, temp, numTests, playLimit=None, first=None
         sides.append(_Searcher(m, game_id, numTests, sims, seconds))
     try:
         if which == 'device':
-            return _device_arena(sides, game_id, temp, numTests, first, starts)
+            return _device_arena(sides, game_id, temp, numTests, first, starts, schedule)
         states = np.repeat(_lib.game_initial(game_id), numTests, axis=0)   # packed boards, host side
         alive = np.ones(numTests, dtype=bool)
         result = np.zeros(numTests, dtype=np.int32)
         to_move1 = first.copy()
         model1_player = np.where(first, 1, 2)
+        ply = -1
         while alive.any():
+            ply += 1                                              # every live game is on this ply of the match
+            now = _lib.temp_at(temp, schedule, ply)
             actions = np.full(numTests, -1, dtype=np.int32)
             for k, side in enumerate(sides):
                 mine = alive & (to_move1 if k == 0 else ~to_move1)
@@ -180,9 +191,9 @@ def TestModelsBatched(model1, model2, temp, numTests, playLimit=None, first=None
                 if eng.counters()['overflow']:
                     raise _lib.BlackbirdHipError('search tree outgrew the node pool')
                 u = np.zeros(numTests, dtype=np.float64)
-                if temp != 0:
+                if now != 0:
                     u[idx] = draw(len(idx))
-                out = eng.sample_moves(temp, u if temp != 0 else None)
+                out = eng.sample_moves(now, u if now != 0 else None)
                 if (out['action'][idx] < 0).any():
                     raise ValueError('probabilities contain NaN')
                 actions[idx] = out['action'][idx]

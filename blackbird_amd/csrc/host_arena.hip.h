@@ -7,6 +7,10 @@ struct bb_arena {
     DevOwner own{HIP_OPS}; // dev's arrays and the events
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // prep done (a), b sampled, moved (a), b's roots moved
     double temp = 0.0;
+    int sched_plies = -1;    // bb_arena_set_temp_schedule (host state; < 0: no schedule): what the next bb_arena_begin takes ...
+    double sched_late = 0.0;
+    int run_plies = -1;      // ... and what the run begun last plays under: ply p of the match samples at scheduled_temp(.., p)
+    double run_late = 0.0;
     int enqueued = 0; // plies enqueued since bb_arena_begin
     bool begun = false;
 };
@@ -93,6 +97,15 @@ static int arena_begin(bb_arena *ar, int n_games, const uint8_t *a_first, const 
     return BB_OK;
 }
 
+extern "C" int bb_arena_set_temp_schedule(bb_arena *ar, int plies, double temp_late) {
+    if (!ar) return fail(BB_ERR_ARG, "bb_arena_set_temp_schedule: null arena");
+    if (!(temp_late >= 0.0 && temp_late < INFINITY))
+        return fail(BB_ERR_ARG, "bb_arena_set_temp_schedule: temp_late must be finite and >= 0");
+    ar->sched_plies = plies < 0 ? -1 : plies;
+    ar->sched_late = temp_late;
+    return BB_OK;
+}
+
 extern "C" int bb_arena_begin(bb_arena *ar, int n_games, const uint8_t *a_first, const void *start_states, double temp) {
     if (!ar || !a_first) return fail(BB_ERR_ARG, "bb_arena_begin: null argument");
     if (n_games < 1 || n_games > ar->dev.n_slots)
@@ -100,7 +113,7 @@ extern "C" int bb_arena_begin(bb_arena *ar, int n_games, const uint8_t *a_first,
     if (!(temp >= 0)) return fail(BB_ERR_ARG, "bb_arena_begin: temp must be >= 0");
     for (bb_engine *e : {ar->a, ar->b}) {
         if (int rc = check_eval(e)) return rc;
-        if (e->sims_now < 2 && temp != 0.0) // (bb_selfplay_begin's rule)
+        if (e->sims_now < 2 && (temp != 0.0 || (ar->sched_plies >= 0 && ar->sched_late != 0.0))) // (bb_selfplay_begin's rule)
             return fail(BB_ERR_ARG, "probabilities contain NaN (a fresh root needs >= 2 simulations, MCTS.py:336-338)");
     }
     HIPCHK(hipSetDevice(ar->a->cfg.device));
@@ -113,6 +126,8 @@ extern "C" int bb_arena_begin(bb_arena *ar, int n_games, const uint8_t *a_first,
     });
     ar->dev.n_games = n_games;
     ar->temp = temp;
+    ar->run_plies = ar->sched_plies;
+    ar->run_late = ar->sched_late;
     ar->enqueued = 0;
     ar->begun = true;
     return BB_OK;
@@ -130,6 +145,8 @@ static int arena_ply(bb_arena *ar) {
     const ArenaDev &d = ar->dev;
     hipStream_t sa = a->stream, sb = b->stream;
     const int blocks = nblk(d.n_slots);
+    // every live game is on ply `enqueued` of the match (they all began at bb_arena_begin): the schedule is chosen here, per ply
+    const double temp = scheduled_temp(ar->temp, ar->run_plies, ar->run_late, ar->enqueued);
     if (ar->enqueued > 0) HIPCHK(hipStreamWaitEvent(sa, ar->ev[3], 0));
     k_arena_prep<<<blocks, 256, 0, sa>>>(d);
     HIPCHK(hipGetLastError());
@@ -146,7 +163,7 @@ static int arena_ply(bb_arena *ar) {
         if (int rc = enqueue_sims(e, e->sims_now, s.mask)) return rc;
         TreeDev t = e->dev;
         t.in_u = nullptr; // the Philox draw of (seed, game id, ply), as bb_sample_moves with u == NULL
-        Launch<G>::sample(t, e->edges, e->stream, ar->temp, e->d_child_action);
+        Launch<G>::sample(t, e->edges, e->stream, temp, e->d_child_action);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(ar->ev[1], sb));

@@ -4,6 +4,7 @@
 #include "dev_mem.h"
 
 #include <cassert>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>

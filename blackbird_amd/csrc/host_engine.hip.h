@@ -39,6 +39,8 @@ struct bb_engine {
     hipEvent_t w_event[2] = {nullptr, nullptr}; // bb_load_weights_device: the caller's stream -> the engine's, and back (no timing)
     int n_games_target = 0;
     StartsTable starts; // bb_selfplay_set_starts: the device copy dev.starts / view[].starts point at (starts.h); not in `own`
+    int sched_plies = -1;    // bb_selfplay_set_temp_schedule: plies at the run's own temperature (< 0: no schedule) and the
+    double sched_late = 0.0; // temperature from there on; host state, copied into dev / view[] by bb_selfplay_begin
     int sims_now = 0;
     size_t node_bytes = 0;
     double *d_u = nullptr;
@@ -310,6 +312,8 @@ extern "C" int bb_create(const bb_config *cfg, bb_engine **out) {
     const bool rounds_kernels = e->plan == PLAY_ROUNDS || e->plan == PLAY_QUEUE; // (a queue engine plays rounds when its network does not fit)
     if (int v = env_int("BB_TREE_GPW", 0); v >= 1 && v <= 64 / e->info.S) d.gpw = v;
     d.temp = 1.0;
+    d.temp_late = 1.0;
+    d.temp_plies = INT_MAX; // no schedule
     GAME_SWITCH(cfg->game, rc = engine_alloc<G>(e); break);
     if (!rc) { // (a configuration that owns a table plays through a structure that probes it: eval_cache_log2_of asks selfplay_plan)
         if (const int k = eval_cache_log2_of(cfg)) {

@@ -67,6 +67,19 @@ extern "C" int bb_selfplay_set_starts(bb_engine *e, int n, const void *states) {
     return BB_OK;
 }
 
+// The temperature of the move out of ply `ply` under the schedule (plies, late); plies < 0: no schedule.  The host's copy of the
+// select in selfplay_move_body / dc_selfplay_move_body (the arena picks per enqueued ply with it).
+static double scheduled_temp(double temp, int plies, double late, int ply) { return plies < 0 || ply < plies ? temp : late; }
+
+extern "C" int bb_selfplay_set_temp_schedule(bb_engine *e, int plies, double temp_late) {
+    if (!e) return fail(BB_ERR_ARG, "null engine");
+    if (!(temp_late >= 0.0 && temp_late < INFINITY))
+        return fail(BB_ERR_ARG, "bb_selfplay_set_temp_schedule: temp_late must be finite and >= 0");
+    e->sched_plies = plies < 0 ? -1 : plies; // (host state: the next bb_selfplay_begin copies it next to temp)
+    e->sched_late = temp_late;
+    return BB_OK;
+}
+
 extern "C" int bb_selfplay_begin(bb_engine *e, int n_games, double temp) {
     if (!e) return fail(BB_ERR_ARG, "null engine");
     if (n_games <= 0) return fail(BB_ERR_ARG, "Use a positive integer for number of games."); // Blackbird.py:235-236
@@ -74,7 +87,8 @@ extern "C" int bb_selfplay_begin(bb_engine *e, int n_games, double temp) {
         return fail(BB_ERR_STATE, "DragonChess self-play does not keep ancestor chains: create the engine without track_ancestors");
     if (n_games > e->cfg.max_games)
         return fail(BB_ERR_CAPACITY, "n_games %d exceeds the engine's max_games %d", n_games, e->cfg.max_games);
-    if (e->sims_now < 2 && temp != 0.0)
+    const bool sched = e->sched_plies >= 0;
+    if (e->sims_now < 2 && (temp != 0.0 || (sched && e->sched_late != 0.0))) // (either temperature of a schedule)
         return fail(BB_ERR_NAN, "probabilities contain NaN (a fresh root needs >= 2 simulations, MCTS.py:336-338)");
     int rc = check_eval(e);
     if (rc) return rc;
@@ -82,6 +96,12 @@ extern "C" int bb_selfplay_begin(bb_engine *e, int n_games, double temp) {
     e->n_games_target = n_games;
     e->dev.n_games_target = n_games;
     e->dev.temp = temp;
+    e->dev.temp_late = sched ? e->sched_late : temp;
+    e->dev.temp_plies = sched ? e->sched_plies : INT_MAX;
+    for (int v = 0; v < 2; v++) {
+        e->view[v].temp_late = e->dev.temp_late;
+        e->view[v].temp_plies = e->dev.temp_plies;
+    }
     HIPCHK(sync_all(e));
     HIPCHK(hipMemsetAsync(e->dev.game_hdr, 0, (size_t)e->cfg.max_games * 16, e->stream));
     HIPCHK(hipMemsetAsync(e->dev.resume_cur, 0xFF, (size_t)e->dev.n_slots * 4, e->stream));

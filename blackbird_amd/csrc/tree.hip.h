@@ -150,6 +150,11 @@ struct TreeDev {
     // see the note on member order above.)
     const void *starts;
     int n_starts;
+    // temperature schedule by ply (bb_selfplay_set_temp_schedule): the move out of a position at ply p is drawn at `temp` while
+    // p < temp_plies and at temp_late from there on.  No schedule: temp_plies = INT_MAX, so the select in the two move bodies always
+    // yields `temp`.  (Last members, like the start table.)
+    double temp_late;
+    int temp_plies;
 };
 
 // ---- group (G::S lanes) collectives ---------------------------------------------------------
@@ -923,7 +928,7 @@ __device__ __forceinline__ void selfplay_move_body(const TreeDev &d, int g, int 
     double u = bb_u53(d.seed, gid, (uint32_t)ply);
     int total, Ni;
     float Wi;
-    int act = choose_move<G>(d, g, lane, d.temp, u, total, Ni, Wi);
+    int act = choose_move<G>(d, g, lane, ply < d.temp_plies ? d.temp : d.temp_late, u, total, Ni, Wi);
     if (act < 0) { // no probabilities (choose_move: N^(1/temp) overflowed; 0 / 0 needs sims_per_move < 2, which bb_selfplay_begin refuses): park the slot
         if (lane == 0) {
             d.game_lid[g] = -1;

@@ -1137,7 +1137,7 @@ __device__ void dc_selfplay_move_body(const TreeDev &d, const DCEdges &E, int g,
     int ply = d.ply[g];
     double u = bb_u53(d.seed, gid, (uint32_t)ply);
     int total, eo;
-    int act = dc_choose_move<COPY>(d, E, g, lane, d.temp, u, total, eo);
+    int act = dc_choose_move<COPY>(d, E, g, lane, ply < d.temp_plies ? d.temp : d.temp_late, u, total, eo);
     if (act < 0) {
         if (lane == 0) {
             d.game_lid[g] = -1;

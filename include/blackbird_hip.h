@@ -394,6 +394,18 @@ int bb_selfplay_begin(bb_engine *e, int n_games, double temp);
  * For use BETWEEN runs only: the call waits for everything the engine has queued before it swaps the table; calling it while
  * a run started by bb_selfplay_begin is unfinished is not supported (slots refilled later would start from the new table). */
 int bb_selfplay_set_starts(bb_engine *e, int n, const void *states);
+/* A temperature schedule by ply for self-play -- an extension: the reference plays a whole game at one temperature.  The move out
+ * of a position whose record carries ply p is drawn at bb_selfplay_begin's `temp` when p < plies and at temp_late otherwise.  p is
+ * the engine's own ply counter, the value in the record header and in the key of the move's draw: ply counts from the game's start
+ * position -- 0 for every game, also for one that starts from a bb_selfplay_set_starts state, and 0 again when a slot is refilled
+ * with its next game.  temp_late == 0 is the PUCT arg-max move, exactly as temp == 0.  Nothing else about a move changes: the
+ * draw of (seed, game id, ply), the record, the re-rooting, and the rule that a move without probabilities (N ^ (1 / temp_late)
+ * overflows) stops the slot without a record and counts in bb_counters.overflow.  Every launch structure honours it.
+ * plies < 0 turns the schedule off; plies == 0 plays every move at temp_late.  An engine that never had a schedule, has it turned
+ * off, or has temp_late == temp plays exactly as without this call.
+ * Host state only: it takes effect at the next bb_selfplay_begin, which refuses (BB_ERR_NAN) an engine with fewer than 2
+ * simulations per move when EITHER temperature is non-zero.  BB_ERR_ARG: a null engine, temp_late negative or not finite. */
+int bb_selfplay_set_temp_schedule(bb_engine *e, int plies, double temp_late);
 /* Advance the self-play by `plies` moves' worth of search per active slot (a move: sims_per_move simulations, sample, record
  * the example, MoveRoot, Winner(); finished games hand their slot to the next game id).  Asynchronous.  In the lock-step and
  * rounds structures every slot makes exactly `plies` moves.  The persistent kernels hand out plies x sims_per_move tree visits
@@ -452,6 +464,12 @@ int bb_arena_create(bb_engine *a, bb_engine *b, int log_plies, bb_arena **out);
  * BB_ERR_WEIGHTS: a network engine without weights.  BB_ERR_ARG: an engine with fewer than 2 simulations per move and
  * temp != 0 (MCTS.py:336-338, the rule of bb_selfplay_begin), or any argument outside the above. */
 int bb_arena_begin(bb_arena *ar, int n_games, const uint8_t *a_first, const void *start_states, double temp);
+/* bb_selfplay_set_temp_schedule for the arena: ply p of the match (0 for each game's first move -- ply counts from the game's
+ * start position, given or initial; every live game is on the same ply) is sampled as bb_sample_moves(e, p < plies ? temp :
+ * temp_late, u = NULL) does.  Call it before bb_arena_begin: a run keeps the schedule it began with.  plies < 0 turns it off.  With
+ * a schedule on, bb_arena_begin's rule about fewer than 2 simulations per move looks at both temperatures.
+ * BB_ERR_ARG: a null arena, temp_late negative or not finite. */
+int bb_arena_set_temp_schedule(bb_arena *ar, int plies, double temp_late);
 /* Enqueue `plies` plies of every live game (Blackbird.py:195-203).  Asynchronous: no host synchronisation inside or between the
  * plies; a finished game costs masked-out lanes only. */
 int bb_arena_step(bb_arena *ar, int plies);

@@ -1,6 +1,7 @@
 """From finished self-play games to a trained network, both ways, timed: python tools/train_path.py [--games N]
 [--play-limit P] [--batch B] [--lr LR] [--augment] [--merge] [--holdout FRACTION] [--skip-host] [--skip-device] [--skip-hip]
 [--handoff host|device] [--game connect4|dragonchess] [--warmup-games W] [--score-engine] [--loss reference|per_example]
+[--temp-schedule PLIES,TEMP]
 
 --game dragonchess: the same on DragonChess (17 planes, 4032 actions), the hip model with NetworkConfig['training']['hip_games'] =
 'all'.  The records source and the scorer do not cover that game, so hip_epoch_s is null and --holdout and --merge are refused;
@@ -54,6 +55,11 @@ examples._batch chunks (torch_route_s), which was the only route for that game, 
 --loss reference|per_example (default reference): NetworkConfig['training']['loss'] of every model of the run -- the PyTorch
 trainer, the hip model and the --holdout model alike; per_example is the ordinary AlphaZero loss (each row's own label, l2 1e-4,
 no noise).  Every figure is measured as without it.
+
+--temp-schedule PLIES,TEMP: every self-play run of the tool (the warm-up runs too) plays the first PLIES plies of a game at
+temperature 1 and the rest at TEMP (Model.SelfPlayTempSchedule; 0: the PUCT arg-max move).  Without it every move is
+drawn at temperature 1, as before.  Connect4 runs also print duplicate_share: the share of the kept records that are a further
+copy of a position already among them (1 - groups / records of DeviceExamples.merged), counted after everything that is timed.
 Prints one JSON line."""
 import argparse
 import copy
@@ -172,7 +178,15 @@ def main():
     ap.add_argument("--warmup-games", type=int, default=64)
     ap.add_argument("--score-engine", action="store_true")
     ap.add_argument("--loss", choices=("reference", "per_example"), default="reference")
+    ap.add_argument("--temp-schedule", default=None, metavar="PLIES,TEMP")
     a = ap.parse_args()
+    schedule = None
+    if a.temp_schedule is not None:
+        try:
+            plies, late = a.temp_schedule.split(",")
+            schedule = _lib.temp_schedule((int(plies), float(late)))
+        except ValueError as err:
+            ap.error("--temp-schedule PLIES,TEMP: %s" % err)
     if a.loss != "reference":
         CFG["training"]["loss"] = a.loss  # (every model of the run is made from CFG or a copy of it)
     dc = a.game == "dragonchess"
@@ -187,6 +201,7 @@ def main():
     model = Blackbird.Model(board, "train_path", {"explorationRate": 0.85, "playLimit": a.play_limit}, CFG)
     model.KeepDeviceExamples = True
     initial = {k: v.copy() for k, v in model._ensure_weights(planes).items()}
+    model.SelfPlayTempSchedule = schedule
     Blackbird.GenerateTrainingSamples(model, a.warmup_games, 1.0)  # warm-up run (its examples are trained on too)
     t = time.time()
     Blackbird.GenerateTrainingSamples(model, a.games, 1.0)
@@ -207,6 +222,7 @@ def main():
     if not a.skip_hip:
         hip_model.getEvaluation(boards[:1].astype(np.int8))     # the engines a playing, training model owns: evaluation ...
         state = np.random.get_state()
+        hip_model.SelfPlayTempSchedule = schedule
         Blackbird.GenerateTrainingSamples(hip_model, a.warmup_games, 1.0)    # ... and self-play (numpy's generator left where it was)
         np.random.set_state(state)
         hip_model.train(boards, value, policy, a.lr)
@@ -307,8 +323,10 @@ def main():
 
     holdout = {} if a.holdout is None else {"holdout": holdout_run_dc(a, kept, board) if dc else holdout_run(a, kept, hip_cfg, initial)}
 
+    duplicate_share = None if dc else round(1.0 - len(kept.merged()) / float(n), 5)
     r3 = lambda x: None if x is None else round(x, 3)  # noqa: E731
     print(json.dumps({"tool": "train_path", "game": a.game, "loss": a.loss, "games": a.games, "warmup_games": a.warmup_games, "play_limit": a.play_limit,
+                      "temp_schedule": None if schedule is None else list(schedule), "duplicate_share": duplicate_share,
                       "examples": n, "augment": bool(a.augment), "batch_size": B, "batches": n // B, "selfplay_s": round(selfplay_s, 3),
                       "host_path_s": r3(host_s), "host_decode_s": r3(decode_s),
                       "device_path_s": r3(device_s), "device_batches_only_s": round(batch_s, 4),
