@@ -10,7 +10,7 @@ struct bb_trainer {
     float *prm, *slot_m, *slot_v, *grads, *slabs, *le, *lp, *loss;
     uint8_t *kind;
     TrainAux *aux;
-    float *aux_wide; // DragonChess only: noise[A], then L[A] (k_train_prep_wide); null for the dense games
+    float *noise, *L; // A floats each: the dense games' lie in *aux, DragonChess's in one allocation of 2 A floats (k_train_prep_wide)
     float *eval_rows; // scratch of bb_trainer_eval for callers that pass no rows_out / flags_out: grows, never shrinks
     uint8_t *eval_flags;
     size_t eval_cap;  // rows the scratch holds
@@ -33,10 +33,17 @@ static TrainLayout train_layout(int C, int R, int D, int A) {
     return l;
 }
 
-// `using G = ` the trainer's dense game around the statements given, GAME_SWITCH's way.  DragonChess (trainer_is_wide) has a
-// dispatch of its own wherever it is covered, so that neither TrainRecords<DragonChess> nor k_train_eval<DragonChess, ...> is made.
+// `using G = ` the trainer's dense game around the statements given, GAME_SWITCH's way: the dispatch of the records source and the
+// scorer, which DragonChess (trainer_is_wide) never reaches (trainer_not_wide), so that neither TrainRecords<DragonChess> nor
+// k_train_eval<DragonChess, ...> is made.  TRAINER_SWITCH_TENSORS: every game -- what is fed by batch tensors alone (the step).
 #define TRAINER_SWITCH(t, ...)                                                   \
     switch ((t)->cfg.game) {                                                     \
+    case BB_GAME_CONNECT4: { using G = Connect4; __VA_ARGS__; }                  \
+    default: { using G = TicTacToe; __VA_ARGS__; }                               \
+    }
+#define TRAINER_SWITCH_TENSORS(t, ...)                                           \
+    switch ((t)->cfg.game) {                                                     \
+    case BB_GAME_DRAGONCHESS: { using G = DragonChess; __VA_ARGS__; }            \
     case BB_GAME_CONNECT4: { using G = Connect4; __VA_ARGS__; }                  \
     default: { using G = TicTacToe; __VA_ARGS__; }                               \
     }
@@ -58,23 +65,15 @@ static int trainer_on_device(const bb_trainer *t) {
 }
 
 template <class G>
-static int trainer_lds(bb_trainer *t) { // (the same dynamic LDS whichever source feeds the workgroup)
+static int trainer_lds(bb_trainer *t) { // (the same dynamic LDS whichever source feeds the workgroup and whichever loss it takes)
     t->lds_bytes = (size_t)train_lds_floats<G>(t->lay.R) * sizeof(float);
-    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainTensors<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
-    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainRecords<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
-    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainTensors<G>, BB_LOSS_PER_EXAMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)t->lds_bytes));
-    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainRecords<G>, BB_LOSS_PER_EXAMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)t->lds_bytes));
-    return BB_OK;
-}
-
-static int trainer_lds_wide(bb_trainer *t) {
-    using G = DragonChess;
-    t->lds_bytes = (size_t)train_lds_floats<G>(t->lay.R) * sizeof(float);
-    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad_wide<G, TrainTensors<G>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_bytes));
-    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad_wide<G, TrainTensors<G>, BB_LOSS_PER_EXAMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)t->lds_bytes));
+    const int bytes = (int)t->lds_bytes;
+    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainTensors<G>, BB_LOSS_REFERENCE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainTensors<G>, BB_LOSS_PER_EXAMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    if constexpr (TrainScratch<G>::dense) { // the records source: the dense games alone (TRAINER_SWITCH)
+        HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainRecords<G>, BB_LOSS_REFERENCE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        HIPCHK(hipFuncSetAttribute((const void *)k_train_grad<G, TrainRecords<G>, BB_LOSS_PER_EXAMPLE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    }
     return BB_OK;
 }
 
@@ -97,8 +96,12 @@ static int trainer_alloc(bb_trainer *t, const bb_net_weights *w) {
     HIPCHK(hipMemset(t->loss, 0, 4 * sizeof(float)));
     HIPCHK(hipMemset(t->aux, 0, sizeof(TrainAux)));
     if (trainer_is_wide(t)) {
-        if (take(t->aux_wide, 2 * (size_t)t->A)) return BB_ERR_HIP;
-        HIPCHK(hipMemset(t->aux_wide, 0, 2 * (size_t)t->A * sizeof(float)));
+        if (take(t->noise, 2 * (size_t)t->A)) return BB_ERR_HIP;
+        HIPCHK(hipMemset(t->noise, 0, 2 * (size_t)t->A * sizeof(float)));
+        t->L = t->noise + t->A;
+    } else {
+        t->noise = (float *)t->aux + offsetof(TrainAux, noise) / sizeof(float); // (addresses inside the device's TrainAux)
+        t->L = (float *)t->aux + offsetof(TrainAux, L) / sizeof(float);
     }
     const NetBlocks tb = net_blocks(t->C, BB_TRAIN_F, l.R, l.D, t->A); // (what train_layout took l from)
     const std::vector<uint8_t> kind = net_block_kinds(tb);
@@ -106,8 +109,7 @@ static int trainer_alloc(bb_trainer *t, const bb_net_weights *w) {
     for (int i = 0; i < NET_BLOCKS; i++)
         if (const int n = tb.b[i].count())
             HIPCHK(hipMemcpy(t->prm + tb.b[i].at, net_block(*w, i), (size_t)n * sizeof(float), hipMemcpyDefault));
-    if (trainer_is_wide(t)) return trainer_lds_wide(t);
-    TRAINER_SWITCH(t, return trainer_lds<G>(t));
+    TRAINER_SWITCH_TENSORS(t, return trainer_lds<G>(t));
 }
 
 extern "C" int bb_trainer_create(const bb_train_config *cfg, const bb_net_weights *w, bb_trainer **out) {
@@ -118,7 +120,7 @@ extern "C" int bb_trainer_create(const bb_train_config *cfg, const bb_net_weight
     bb_game_info gi;
     bb_game_info_get(cfg->game, &gi);
     if (int rc = check_weights(w, gi)) return rc;
-    // DragonChess: the blocks whose k_train_grad_wide workgroup fits a CU's LDS (train_max_blocks, train.hip.h)
+    // DragonChess: the blocks whose k_train_grad workgroup fits a CU's LDS (train_max_blocks, train.hip.h)
     const int max_blocks = cfg->game == BB_GAME_DRAGONCHESS ? train_max_blocks<DragonChess>() : 9;
     if (w->F != BB_TRAIN_F || w->R < 0 || w->R > max_blocks || w->D < 1 || w->D > 64)
         return fail(BB_ERR_ARG, "the HIP trainer covers 16 filters, 0..%d blocks%s and a dense width of 1..64; got %d filters, %d blocks, "
@@ -192,14 +194,22 @@ static void trainer_launch_apply(bb_trainer *t, int n, double lr, int apply, flo
 // One step's three launches on `st`, the batch read through `src` (train.hip.h): what bb_trainer_step and every batch of
 // bb_trainer_epoch enqueue.  Host state moves as the launches are made: the noise counter, Adam's step count and lr_t.
 // The loss is a template argument of prep and grad (train.hip.h): the per-example step takes the same launches with other kernels.
+// The prep kernel is the game family's: one workgroup for the dense games, 1 + ceil(A / 256) for DragonChess (per example: one --
+// there is no label sweep).
 template <class G, class Src, int LOSS>
 static void trainer_launch_as(bb_trainer *t, int n, const Src &src, const float *noise, double lr, int apply, float *loss_out, hipStream_t st) {
     const TrainLayout &l = t->lay;
     const float eps = t->cfg.epsilon;
-    k_train_prep<G, Src, LOSS><<<1, BB_TRAIN_THREADS, 0, st>>>(n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed,
-                                                               t->calls, t->l2, t->aux);
+    if constexpr (TrainScratch<G>::dense) {
+        k_train_prep<G, Src, LOSS><<<1, BB_TRAIN_THREADS, 0, st>>>(n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed,
+                                                                   t->calls, t->l2, t->aux);
+    } else {
+        const unsigned groups = LOSS == BB_LOSS_PER_EXAMPLE ? 1u : 1u + (unsigned)nblk((size_t)G::A, BB_TRAIN_THREADS);
+        k_train_prep_wide<G, Src, LOSS><<<groups, BB_TRAIN_THREADS, 0, st>>>(n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha,
+                                                                             t->cfg.seed, t->calls, t->l2, t->aux, t->noise, t->L);
+    }
     t->calls++;
-    k_train_grad<G, Src, LOSS><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, src, n, eps, t->slabs, t->le, t->lp);
+    k_train_grad<G, Src, LOSS><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, t->noise, t->L, src, n, eps, t->slabs, t->le, t->lp);
     trainer_launch_apply(t, n, lr, apply, loss_out, st);
 }
 
@@ -209,32 +219,6 @@ static void trainer_launch(bb_trainer *t, int n, const Src &src, const float *no
         trainer_launch_as<G, Src, BB_LOSS_PER_EXAMPLE>(t, n, src, noise, lr, apply, loss_out, st);
     else
         trainer_launch_as<G, Src, BB_LOSS_REFERENCE>(t, n, src, noise, lr, apply, loss_out, st);
-}
-
-// The DragonChess step: k_train_prep_wide on 1 + ceil(A / 256) workgroups (per example: one -- there is no label sweep),
-// k_train_grad_wide, then the same k_train_apply.
-template <int LOSS>
-static void trainer_launch_wide_as(bb_trainer *t, int n, const TrainTensors<DragonChess> &src, const float *noise, double lr, int apply,
-                                   float *loss_out, hipStream_t st) {
-    using G = DragonChess;
-    const TrainLayout &l = t->lay;
-    const float eps = t->cfg.epsilon;
-    float *aux_noise = t->aux_wide, *aux_L = t->aux_wide + G::A;
-    const unsigned groups = LOSS == BB_LOSS_PER_EXAMPLE ? 1u : 1u + (unsigned)nblk((size_t)G::A, BB_TRAIN_THREADS);
-    k_train_prep_wide<G, TrainTensors<G>, LOSS><<<groups, BB_TRAIN_THREADS, 0, st>>>(
-        n, l.count, l.n_l2, t->prm, t->kind, src, noise, eps, t->cfg.alpha, t->cfg.seed, t->calls, t->l2, t->aux, aux_noise, aux_L);
-    t->calls++;
-    k_train_grad_wide<G, TrainTensors<G>, LOSS><<<n, BB_TRAIN_THREADS, t->lds_bytes, st>>>(l, t->prm, t->aux, aux_noise, aux_L, src, n, eps,
-                                                                                         t->slabs, t->le, t->lp);
-    trainer_launch_apply(t, n, lr, apply, loss_out, st);
-}
-
-static void trainer_launch_wide(bb_trainer *t, int n, const TrainTensors<DragonChess> &src, const float *noise, double lr, int apply,
-                                float *loss_out, hipStream_t st) {
-    if (t->loss_kind == BB_LOSS_PER_EXAMPLE)
-        trainer_launch_wide_as<BB_LOSS_PER_EXAMPLE>(t, n, src, noise, lr, apply, loss_out, st);
-    else
-        trainer_launch_wide_as<BB_LOSS_REFERENCE>(t, n, src, noise, lr, apply, loss_out, st);
 }
 
 extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const float *value, const float *policy, const float *noise,
@@ -247,10 +231,7 @@ extern "C" int bb_trainer_step(bb_trainer *t, int n, const float *boards, const 
     if (!std::isfinite(lr)) return fail(BB_ERR_ARG, "the learning rate is not finite");
     if (int rc = trainer_noise_ok(t, noise, "bb_trainer_step")) return rc;
     if (int rc = trainer_on_device(t)) return rc;
-    if (trainer_is_wide(t))
-        trainer_launch_wide(t, n, TrainTensors<DragonChess>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream);
-    else
-        TRAINER_SWITCH(t, trainer_launch<G>(t, n, TrainTensors<G>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream); break);
+    TRAINER_SWITCH_TENSORS(t, trainer_launch<G>(t, n, TrainTensors<G>{boards, value, policy}, noise, lr, apply, loss_out, (hipStream_t)stream); break);
     HIPCHK(hipGetLastError());
     return BB_OK;
 }
@@ -357,7 +338,7 @@ extern "C" int bb_trainer_read(bb_trainer *t, int what, float *host_out, int64_t
     case BB_TRAIN_GRADS: src = t->grads; break;
     case BB_TRAIN_SLOT_M: src = t->slot_m; break;
     case BB_TRAIN_SLOT_V: src = t->slot_v; break;
-    case BB_TRAIN_NOISE: src = trainer_is_wide(t) ? t->aux_wide : t->aux->noise; want = t->A; break;
+    case BB_TRAIN_NOISE: src = t->noise; want = t->A; break;
     default: return fail(BB_ERR_ARG, "unknown selector %d", what);
     }
     if (count != want) return fail(BB_ERR_ARG, "count %lld, expected %lld", (long long)count, (long long)want);

@@ -1,5 +1,5 @@
 """-m gpu: the DragonChess training step as HIP kernels (training.HipTrainer over bb_trainer_*; k_train_prep_wide and
-k_train_grad_wide of csrc/train.hip.h) against the float64 statement of tests/trainer_cases.py on the batches of
+k_train_grad with its wide policy head, csrc/train.hip.h) against the float64 statement of tests/trainer_cases.py on the batches of
 tests/dc_trainer_cases.py (tests/test_hip_trainer_dc_cpu.py checks both): the loss terms and the gradient of every variable
 over the shapes, at live inputs, two steps per optimiser, bit-repeatability, the drawn noise, an all-terminal batch, the same
 training as the PyTorch trainer over real self-play records, the hand-off to an engine, the front end and the refusals.

@@ -1,5 +1,5 @@
 """-m gpu: the per-example policy loss as HIP kernels (training.HipTrainer(loss='per_example') over bb_trainer_set_loss; the
-BB_LOSS_PER_EXAMPLE instantiations of k_train_prep / k_train_grad and their wide twins, csrc/train.hip.h) against the float64
+BB_LOSS_PER_EXAMPLE instantiations of k_train_prep / k_train_prep_wide and k_train_grad, csrc/train.hip.h) against the float64
 statement of tests/per_example_cases.py: the loss terms and the gradient of every variable over the shapes where the kernels
 can go wrong, at live inputs, two steps per optimiser, the PyTorch trainer on the same batches, bit-repeatability, the epoch
 straight from records, the step's reported terms against the scorer, the untouched reference loss, and the front end.
