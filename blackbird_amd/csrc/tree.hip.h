@@ -289,31 +289,49 @@ __device__ __forceinline__ double child_q(const TreeDev &d, float Qi, float Wi, 
     return Ni > 0 ? (double)Wi / (double)Ni : 0.0;
 }
 
+// The word a path or an ancestor chain keeps of one edge: node << 6 | Player of the node << 4 | action
+__device__ __forceinline__ uint32_t path_word(int node, int player, int a) {
+    return ((uint32_t)node << 6) | ((uint32_t)player << 4) | (uint32_t)a;
+}
+
 // MCTS._backProp (MCTS.py:238-258): one (parent, action) edge of the recorded path per lane; v01 is the
 // value for `prev` (= leaf.State.PreviousPlayer).  Refreshes Q and sqrt(1+sum N) of the rows it touches.
-template <class G>
+// REC: N, W and sum(N) of every edge come from what the descent recorded of it (TreeDev::path_N / path_W / path_all) and the backup
+// is stores only.  Nothing else touches a game's tree between the descent of a simulation and its backup, so the recorded numbers
+// ARE the memory's.  Only the persistent kernel records (async_game<G, true>), and its backups do not walk the ancestor chain:
+// the walk is the plain form's alone.  NOT guaranteed by the host: selfplay_plan (host_engine.hip.h) does not look at
+// track_ancestors, so a track_anc engine can play through that kernel, and the rows above its root then miss those simulations
+// (open: ADVICE.md).
+template <class G, bool REC = false>
 __device__ __forceinline__ void backup_path(const TreeDev &d, int g, int lane, DenseNode<G> *pool, int plen, float v01,
                                             int prev) {
     constexpr int S = G::S;
-    float vflip = 1.0f - v01;
-    const uint32_t *path = d.path + (size_t)g * G::MAXPATH;
-    auto edge = [&](uint32_t e) __attribute__((always_inline)) {
-        int a = e & 15, pl = (e >> 4) & 3;
+    const float vflip = 1.0f - v01;
+    const size_t p0 = (size_t)g * G::MAXPATH;
+    auto edge = [&](uint32_t e, int k) __attribute__((always_inline)) { // k: the edge's place in the path (REC only)
+        const int a = e & 15, pl = (e >> 4) & 3;
         DenseNode<G> *pn = pool + (e >> 6);
-        int n = pn->N[a] + 1, all = pn->all + 1;
-        float w = pn->W[a] + ((pl == prev) ? v01 : vflip);
+        int n, all; // child.Plays of the edge, sum(ChildPlays) of its node
+        float w;    // child.Value of the edge
+        if constexpr (REC) { n = d.path_N[p0 + k]; all = d.path_all[p0 + k]; w = d.path_W[p0 + k]; }
+        else { n = pn->N[a]; all = pn->all; w = pn->W[a]; }
+        n += 1;
+        all += 1;
+        w += (pl == prev) ? v01 : vflip;
         pn->N[a] = n;
         pn->W[a] = w;
         pn->Q[a] = __fdiv_rn(w, (float)n);
         pn->all = all;
         pn->sq = __dsqrt_rn(1.0 + (double)all);
     };
-    for (int k = lane; k < plen; k += S) edge(path[k]);
-    if (d.track_anc) { // the reference's recursion does not stop at the current root: the edges above it (MCTS.py:252-258)
-        const uint32_t *anc = d.anc + (size_t)g * (d.max_plies + 2);
-        const int na = d.anc_len[g];
-        for (int k = lane; k < na; k += S) edge(anc[k]);
-        if (lane == 0) d.top_N[g] += 1;
+    for (int k = lane; k < plen; k += S) edge(d.path[p0 + k], k);
+    if constexpr (!REC) {
+        if (d.track_anc) { // the reference's recursion does not stop at the current root: the edges above it (MCTS.py:252-258)
+            const uint32_t *anc = d.anc + (size_t)g * (d.max_plies + 2);
+            const int na = d.anc_len[g];
+            for (int k = lane; k < na; k += S) edge(anc[k], 0);
+            if (lane == 0) d.top_N[g] += 1;
+        }
     }
     if (lane == 0) {
         d.root_N[g] += 1;
@@ -323,91 +341,31 @@ __device__ __forceinline__ void backup_path(const TreeDev &d, int g, int lane, D
 }
 
 // ---- phase A: apply the evaluator's answer for the pending leaf (expand + backup) -------------
-template <class G>
+// REC: the leaf was posted with its flags word and its path's statistics (LEAF_RECORDED): no loads from the tree at all.  Only
+// float32 evaluators reach that form, so the rollout evaluator's branches are not in it.
+template <class G, bool REC = false>
 __device__ __forceinline__ void phase_apply(const TreeDev &d, int g, int lane) {
-    using Node = DenseNode<G>;
-    constexpr int S = G::S, A = G::A;
-    int leaf = d.pend_leaf[g];
-    if (leaf < 0) return;
-    Node *pool = (Node *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
-    Node *node = pool + leaf;
-    typename G::State st = ((const typename G::State *)d.leaf_state)[g]; // posted by phase_select
-    float v = d.eval_value[g];
-    if (d.pend_expand[g]) { // AddChildren with evaluator priors
-        uint32_t mask = G::legal_mask(st);
-        double x = 0.0;
-        if (lane < A) x = (double)d.eval_policy[(size_t)g * S + lane] * (double)((mask >> lane) & 1u);
-        double tot = grp_np_sum<A, S>(x);
-        node->N[lane] = 0;
-        node->Q[lane] = 0.f;
-        node->W[lane] = 0.f;
-        node->child[lane] = CHILD_NONE;
-        node->cP[lane] = (lane < A) ? d.c_puct * __ddiv_rn(x, tot) : 0.0;
-        if (lane == 0) {
-            node->flags |= NODE_EXPANDED;
-            node->legal_mask = mask;
-            node->all = 0;
-            node->sq = 1.0;
-        }
-    }
-    int player = gs_player(st), prev = gs_prev(st);
-    float v01;
-    if (d.evaluator == 2) {
-        v01 = v; // rollout kernel already returns the value for `prev`
-    } else {
-        v01 = (v + 1.0f) * 0.5f; // Model.SampleValue: float32 arithmetic
-        if (player != prev) v01 = 1.0f - v01;
-    }
-    if (d.evaluator != 2 && !d.pend_expand[g] && (node->flags & NODE_TERMINAL) && lane == 0) { // remember a terminal leaf's value
-        node->pad0 = (double)v01;
-        node->flags |= NODE_CACHED;
-    }
-    backup_path<G>(d, g, lane, pool, d.path_len[g], v01, prev);
-    if (lane == 0) d.pend_leaf[g] = -1;
-}
-
-// The same backup from what the descent recorded of every edge (TreeDev::path_N / path_W / path_all): stores only.  Nothing else
-// touches a game's tree between the descent of a simulation and its backup, so the recorded numbers ARE the memory's.
-template <class G>
-__device__ __forceinline__ void backup_path_rec(const TreeDev &d, int g, int lane, DenseNode<G> *pool, int plen, float v01, int prev) {
-    constexpr int S = G::S;
-    const float vflip = 1.0f - v01;
-    const uint32_t *path = d.path + (size_t)g * G::MAXPATH;
-    const int32_t *pN = d.path_N + (size_t)g * G::MAXPATH, *pA = d.path_all + (size_t)g * G::MAXPATH;
-    const float *pW = d.path_W + (size_t)g * G::MAXPATH;
-    for (int k = lane; k < plen; k += S) {
-        const uint32_t e = path[k];
-        const int a = e & 15, pl = (e >> 4) & 3;
-        DenseNode<G> *pn = pool + (e >> 6);
-        const int n = pN[k] + 1, all = pA[k] + 1;
-        const float w = pW[k] + ((pl == prev) ? v01 : vflip);
-        pn->N[a] = n;
-        pn->W[a] = w;
-        pn->Q[a] = __fdiv_rn(w, (float)n);
-        pn->all = all;
-        pn->sq = __dsqrt_rn(1.0 + (double)all);
-    }
-    if (lane == 0) {
-        d.root_N[g] += 1;
-        int pp = d.root_pp[g];
-        if (pp) d.root_W[g] += (pp == prev) ? v01 : vflip;
-    }
-}
-
-// phase_apply for a leaf posted with its flags word and path statistics recorded (LEAF_RECORDED): no loads from the tree at all.
-template <class G>
-__device__ __forceinline__ void phase_apply_rec(const TreeDev &d, int g, int lane) {
     using Node = DenseNode<G>;
     constexpr int S = G::S, A = G::A;
     const int leaf = d.pend_leaf[g];
     if (leaf < 0) return;
-    const int lf = d.leaf_flags[g] & ~LEAF_RECORDED;
+    int lf = 0; // REC: the leaf's flags word, as posted
+    if constexpr (REC) lf = d.leaf_flags[g] & ~LEAF_RECORDED;
     Node *pool = (Node *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
     Node *node = pool + leaf;
-    const typename G::State st = ((const typename G::State *)d.leaf_state)[g];
+    auto add_flag = [&](int bit) __attribute__((always_inline)) {
+        if constexpr (REC) node->flags = lf | bit;
+        else node->flags |= bit;
+    };
+    const typename G::State st = ((const typename G::State *)d.leaf_state)[g]; // posted by post_leaf
     const float v = d.eval_value[g];
-    const int expand = d.pend_expand[g];
-    if (expand) { // AddChildren with evaluator priors
+    // pend_expand: the recorded form reads it once; the plain form reads it at each of its two uses, the one piece kept as it was
+    // before the two were one text.  Read once there, five kernels change registers (k_search_wave<Connect4, cached> spills 109
+    // SGPRs for 105) and the one-launch rollout search leaves the two-read build's range: FindMove 15.95 ms against 15.39 - 15.50,
+    // an arena ply 20.86 against 20.49 - 20.61.
+    const int expand_rec = REC ? d.pend_expand[g] : 0;
+    auto expand = [&]() __attribute__((always_inline)) { return REC ? expand_rec : d.pend_expand[g]; };
+    if (expand()) { // AddChildren with evaluator priors
         const uint32_t mask = G::legal_mask(st);
         double x = 0.0;
         if (lane < A) x = (double)d.eval_policy[(size_t)g * S + lane] * (double)((mask >> lane) & 1u);
@@ -418,20 +376,24 @@ __device__ __forceinline__ void phase_apply_rec(const TreeDev &d, int g, int lan
         node->child[lane] = CHILD_NONE;
         node->cP[lane] = (lane < A) ? d.c_puct * __ddiv_rn(x, tot) : 0.0;
         if (lane == 0) {
-            node->flags = lf | NODE_EXPANDED;
+            add_flag(NODE_EXPANDED);
             node->legal_mask = mask;
             node->all = 0;
             node->sq = 1.0;
         }
     }
     const int player = gs_player(st), prev = gs_prev(st);
-    float v01 = (v + 1.0f) * 0.5f; // Model.SampleValue: float32 arithmetic
-    if (player != prev) v01 = 1.0f - v01;
-    if (!expand && (lf & NODE_TERMINAL) && lane == 0) { // remember a terminal leaf's value
-        node->pad0 = (double)v01;
-        node->flags = lf | NODE_CACHED;
+    const bool f32_eval = REC || d.evaluator != 2;
+    float v01 = v; // the rollout kernel already returns the value for `prev`
+    if (f32_eval) {
+        v01 = (v + 1.0f) * 0.5f; // Model.SampleValue: float32 arithmetic
+        if (player != prev) v01 = 1.0f - v01;
     }
-    backup_path_rec<G>(d, g, lane, pool, d.path_len[g], v01, prev);
+    if (f32_eval && !expand() && ((REC ? lf : node->flags) & NODE_TERMINAL) && lane == 0) { // remember a terminal leaf's value
+        node->pad0 = (double)v01;
+        add_flag(NODE_CACHED);
+    }
+    backup_path<G, REC>(d, g, lane, pool, d.path_len[g], v01, prev);
     if (lane == 0) d.pend_leaf[g] = -1;
 }
 
@@ -483,6 +445,22 @@ __device__ __forceinline__ uint32_t expand_ones(const TreeDev &d, DenseNode<G> *
         node->sq = 1.0;
     }
     return mask;
+}
+
+// The mailbox of a leaf that goes to the evaluator (one lane writes it): node `cur` with state `st`, reached over `depth` edges.
+// flags_word: the node's flags | LEAF_RECORDED from a descent that recorded its path's statistics, 0 from every other.
+template <class G>
+__device__ __forceinline__ void post_leaf(const TreeDev &d, int g, int cur, const typename G::State &st, int flags_word, int expand,
+                                          int depth) {
+    ((typename G::State *)d.leaf_state)[g] = st;
+    d.leaf_game_id[g] = d.first_game_id + (uint32_t)d.game_lid[g];
+    d.leaf_serial[g] = cur;
+    d.pend_leaf[g] = cur;
+    if (d.leaf_flags) d.leaf_flags[g] = flags_word;
+    d.pend_expand[g] = expand;
+    d.path_len[g] = depth;
+    d.sim_serial[g] += 1;
+    d.evals[g] += 1;
 }
 
 // ---- phase B: one _findLeaf descent; leaves the leaf in the evaluator mailbox ------------------
@@ -544,28 +522,20 @@ __device__ void phase_select(const TreeDev &d, int g, int lane) {
             bool terminal;
             child = create_child<G>(d, g, pool, node, st, a, lane, nn, st2, terminal);
             if (child == CHILD_NONE) { overflow = 1; break; }
-            if (lane == 0) path[depth] = ((uint32_t)cur << 6) | ((uint32_t)((flags >> 4) & 3) << 4) | (uint32_t)a;
+            if (lane == 0) path[depth] = path_word(cur, (flags >> 4) & 3, a);
             st = st2;
             flags = (terminal ? NODE_TERMINAL : 0) | (gs_player(st2) << 4);
             have = true;
         } else {
-            if (lane == 0) path[depth] = ((uint32_t)cur << 6) | ((uint32_t)((flags >> 4) & 3) << 4) | (uint32_t)a;
+            if (lane == 0) path[depth] = path_word(cur, (flags >> 4) & 3, a);
         }
         depth++;
         cur = child & ~CHILD_TERM_BIT;
     }
     if (lane == 0) {
         IF_STAMPS(stamp_add(d.stamps, TS_ROW_LOAD, acc_load); stamp_add(d.stamps, TS_ITERATIONS, acc_iter); stamp_add(d.stamps, TS_DESCENTS, 1);)
-        ((typename G::State *)d.leaf_state)[g] = st;
-        d.leaf_game_id[g] = d.first_game_id + (uint32_t)d.game_lid[g];
-        d.leaf_serial[g] = cur;
-        d.pend_leaf[g] = cur;
-        if (d.leaf_flags) d.leaf_flags[g] = 0;
-        d.pend_expand[g] = expand;
-        d.path_len[g] = depth;
+        post_leaf<G>(d, g, cur, st, 0, expand, depth);
         d.sims_left[g] -= 1;
-        d.sim_serial[g] += 1;
-        d.evals[g] += 1;
         uint64_t *c = d.ctr + (size_t)g * 8;
         c[0] += 1;
         c[1] += (uint64_t)depth;
@@ -742,7 +712,7 @@ __device__ __forceinline__ void advance_root(const TreeDev &d, int g, int lane, 
                 d.anc_len[g] = 0;
                 d.top_N[g] = 0;
             } else if (d.anc_len[g] < d.max_plies + 2) {
-                d.anc[(size_t)g * (d.max_plies + 2) + d.anc_len[g]] = ((uint32_t)d.root[g] << 6) | ((uint32_t)gs_player(st) << 4) | (uint32_t)a;
+                d.anc[(size_t)g * (d.max_plies + 2) + d.anc_len[g]] = path_word(d.root[g], gs_player(st), a);
                 d.anc_len[g] += 1;
             }
         }
@@ -1003,7 +973,7 @@ __global__ void __launch_bounds__(256) k_selfplay_move(TreeDev d) {
 // Per game the sequence of simulations is exactly the sequential one, so results do not depend on the
 // schedule (tests/test_gpu_mcts.py: self-play == oracle, example by example).
 // REC (persistent kernel with the recorded-path arrays in LDS): the descent notes N, W and sum(N) of every edge it takes and the
-// backups are stores only (backup_path_rec / phase_apply_rec).
+// backups are stores only (the REC instances of backup_path / phase_apply).
 // on_post(g, lane): called by every lane of the game's group right after the leaf's mailbox has been written -- the persistent
 // kernel hands the leaf to its network waves THERE (mega2.hip.h), not when the call returns: a wave's call lasts as long as
 // the slowest of its games' descents.
@@ -1018,7 +988,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
     Node *pool = (Node *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
     LevelStamps light; // (diagnostic: empty in the product build, stamps.hip.h)
     if (d.pend_leaf[g] >= 0) {
-        if (REC && (d.leaf_flags[g] & LEAF_RECORDED)) phase_apply_rec<G>(d, g, lane);
+        if (REC && (d.leaf_flags[g] & LEAF_RECORDED)) phase_apply<G, true>(d, g, lane);
         else phase_apply<G>(d, g, lane);
         if (lane == 0) d.sims_left[g] -= 1;
         __threadfence_block();
@@ -1075,8 +1045,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
                     if (flags & NODE_CACHED) { // value already known: finish this simulation here
                         float v01 = (float)cached;
                         __threadfence_block(); // path stores of this descent
-                        if (REC) backup_path_rec<G>(d, g, lane, pool, depth, v01, gs_prev(st));
-                        else backup_path<G>(d, g, lane, pool, depth, v01, gs_prev(st));
+                        backup_path<G, REC>(d, g, lane, pool, depth, v01, gs_prev(st));
                         if (lane == 0) d.sims_left[g] -= 1;
                         __threadfence_block();
                         sims_done++;
@@ -1097,7 +1066,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
             int child = ci;
             int a = grp_argmax_puct<S>(Qi, cPi, sq, Ni, lane < A && ((mask >> lane) & 1u), child);
             IF_STAMPS_LIGHT(asm volatile("" ::"v"(a), "v"(child)); light.puct += (int)clock64() - lt_b;)
-            if (lane == 0) path[depth] = ((uint32_t)cur << 6) | ((uint32_t)((flags >> 4) & 3) << 4) | (uint32_t)a;
+            if (lane == 0) path[depth] = path_word(cur, (flags >> 4) & 3, a);
             if (REC) { // what the backup of this edge will start from
                 if (lane == 0) d.path_all[(size_t)g * G::MAXPATH + depth] = all_l;
                 if (lane == a) {
@@ -1132,15 +1101,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
             continue;
         }
         if (lane == 0) {             // post the leaf for the evaluator
-            ((typename G::State *)d.leaf_state)[g] = st;
-            d.leaf_game_id[g] = d.first_game_id + (uint32_t)d.game_lid[g];
-            d.leaf_serial[g] = cur;
-            d.pend_leaf[g] = cur;
-            if (d.leaf_flags) d.leaf_flags[g] = REC ? (flags | LEAF_RECORDED) : 0;
-            d.pend_expand[g] = (fl & F_EXPAND) ? 1 : 0;
-            d.path_len[g] = depth;
-            d.sim_serial[g] += 1;
-            d.evals[g] += 1;
+            post_leaf<G>(d, g, cur, st, REC ? (flags | LEAF_RECORDED) : 0, (fl & F_EXPAND) ? 1 : 0, depth);
             d.ctr[(size_t)g * 8 + 6] += (uint64_t)((fl & F_OVERFLOW) ? 1 : 0);
         }
         on_post(g, lane);
