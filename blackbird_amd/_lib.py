@@ -20,6 +20,9 @@ EVAL_HASH, EVAL_NET, EVAL_ROLLOUT = 0, 1, 2
 NET_FORM_AUTO, NET_FORM_F32, NET_FORM_SPLIT = 0, 1, 2   # bb_config.net_form
 NET_EVAL_FUSED, NET_EVAL_SMALL, NET_EVAL_BATCH = 0, 1, 2   # bb_net_eval_structure
 LAUNCH_AUTO, LAUNCH_LOCKSTEP, LAUNCH_ROUNDS, LAUNCH_WAVE = 0, 1, 2, 3    # bb_config.launch (LAUNCH_WAVE: the search API in one launch)
+PLAY_LOCKSTEP, PLAY_ROUNDS, PLAY_QUEUE, PLAY_DC_FUSED, PLAY_WAVE_ROLLOUT = 0, 1, 3, 5, 6   # bb_selfplay_mode
+NODE_EXPANDED, NODE_TERMINAL = 1, 2                      # bits of the flags word of bb_node_view / bb_node_edges
+CHILD_NONE, CHILD_TERM_BIT = -1, 0x40000000              # their child words: no node yet; pool index | CHILD_TERM_BIT for a terminal child
 OPT_ADAM, OPT_MOMENTUM, OPT_SGD = 0, 1, 2                # bb_train_config.optimizer
 LOSS_REFERENCE, LOSS_PER_EXAMPLE = 0, 1                  # bb_trainer_set_loss
 WEIGHTS_IMAGES = ("w0", "wt", "epi", "head", "x3")        # bb_weights_read's selector, BB_WEIGHTS_*: Engine.weights_image

@@ -5,13 +5,18 @@
 // k_tree_async rounds + evaluator; persistent per-CU kernel with an LDS work queue (mega2.hip.h); DragonChess: mega_dc.hip.h; the
 // rollout evaluator of every game after bb_selfplay_rollouts(e, 1): one launch per step, a wave per slot (selfplay_wave.hip.h)
 enum { PLAY_LOCKSTEP = 0, PLAY_ROUNDS = 1, PLAY_QUEUE = 3, PLAY_DC_FUSED = 5, PLAY_WAVE_ROLLOUT = 6 };
-// What a configuration asks for -- the ONE place that reads mcts_kind / evaluator / launch / game for this.  (Whether the
-// network fits a persistent kernel's LDS is known only at bb_load_weights: selfplay_structure.)
+// What a configuration asks for -- the ONE place that reads mcts_kind / evaluator / launch / game / track_ancestors for this.
+// (Whether the network fits a persistent kernel's LDS is known only at bb_load_weights: selfplay_structure.)
+// track_ancestors: the persistent queue kernel backs a recorded leaf up with stores only (backup_path<G, true>, tree.hip.h), which
+// never walks the ancestor chain, and in either form that kernel indexes per-slot arrays with the workgroup-local slot number, which
+// is right only for the rows it shadows in LDS -- anc / anc_len / top_N are not among them (mega2.hip.h BB_QUEUE_SHADOWED).  So a
+// dense engine that keeps the chain never plans for that kernel: it plays the rounds, whose plain async_game<G> walks the chain,
+// with the same network kernels and the same records byte for byte.  (DragonChess self-play refuses such an engine: bb_selfplay_begin.)
 static int selfplay_plan(const bb_config *cfg) {
     const bool net_auto = cfg->evaluator == BB_EVAL_NET && cfg->launch == BB_LAUNCH_AUTO;
     if (cfg->mcts_kind != BB_MCTS_DYNAMIC) return PLAY_LOCKSTEP;
     if (cfg->game == BB_GAME_DRAGONCHESS) return net_auto ? PLAY_DC_FUSED : PLAY_LOCKSTEP;
-    if (net_auto) return PLAY_QUEUE; // (else rounds, for the deterministic evaluators)
+    if (net_auto) return cfg->track_ancestors ? PLAY_ROUNDS : PLAY_QUEUE; // (else rounds, for the deterministic evaluators)
     return cfg->evaluator != BB_EVAL_ROLLOUT && (cfg->launch == BB_LAUNCH_AUTO || cfg->launch == BB_LAUNCH_ROUNDS) ? PLAY_ROUNDS : PLAY_LOCKSTEP;
 }
 

@@ -213,8 +213,7 @@ extern "C" int bb_reset_roots(bb_engine *e) {
     if (!e) return fail(BB_ERR_ARG, "null engine");
     if (!e->dev.track_anc) return fail(BB_ERR_STATE, "this engine does not keep the ancestors of its roots (bb_config.track_ancestors)");
     HIPCHK(hipSetDevice(e->cfg.device));
-    if (e->cfg.game == BB_GAME_DRAGONCHESS) {
-        // a slot whose chain outgrew its max_plies + 2 entries cannot find its top-most ancestor (tree_dc.hip.h DC_ANC_BROKEN)
+    { // every game: a slot whose chain outgrew its max_plies + 2 entries cannot find its top-most ancestor (tree.hip.h ANC_BROKEN)
         std::vector<int32_t> na((size_t)e->dev.n_slots);
         HIPCHK(sync_all(e));
         HIPCHK(hipMemcpy(na.data(), e->dev.anc_len, na.size() * 4, hipMemcpyDeviceToHost));

@@ -293,15 +293,17 @@ __device__ __forceinline__ double child_q(const TreeDev &d, float Qi, float Wi, 
 __device__ __forceinline__ uint32_t path_word(int node, int player, int a) {
     return ((uint32_t)node << 6) | ((uint32_t)player << 4) | (uint32_t)a;
 }
+#define ANC_BROKEN (-1) // anc_len of a slot whose chain outgrew max_plies + 2 entries: bb_reset_roots refuses it (every game)
 
 // MCTS._backProp (MCTS.py:238-258): one (parent, action) edge of the recorded path per lane; v01 is the
 // value for `prev` (= leaf.State.PreviousPlayer).  Refreshes Q and sqrt(1+sum N) of the rows it touches.
 // REC: N, W and sum(N) of every edge come from what the descent recorded of it (TreeDev::path_N / path_W / path_all) and the backup
 // is stores only.  Nothing else touches a game's tree between the descent of a simulation and its backup, so the recorded numbers
 // ARE the memory's.  Only the persistent kernel records (async_game<G, true>), and its backups do not walk the ancestor chain:
-// the walk is the plain form's alone.  NOT guaranteed by the host: selfplay_plan (host_engine.hip.h) does not look at
-// track_ancestors, so a track_anc engine can play through that kernel, and the rows above its root then miss those simulations
-// (open: ADVICE.md).
+// the walk is the plain form's alone.  The host guarantees that no track_anc engine plays through that kernel: selfplay_plan
+// (host_engine.hip.h) sends a dense engine that keeps the chain to the rounds, whose async_game<G> is the plain form.
+// The walk reads the chain's length as it stands: a broken chain (ANC_BROKEN, advance_root) has a negative one, so `k < na` is
+// false for every lane and nothing above the root is touched -- top_N still counts, and bb_reset_roots refuses the slot.
 template <class G, bool REC = false>
 __device__ __forceinline__ void backup_path(const TreeDev &d, int g, int lane, DenseNode<G> *pool, int plen, float v01,
                                             int prev) {
@@ -659,7 +661,11 @@ __global__ void __launch_bounds__(256) k_sample(TreeDev d, double temp) {
 }
 
 // _moveRoot by action.  Lane-0 state updates; all lanes of the group call it.
-template <class G>
+// CHAIN = false: the caller never runs for an engine that keeps ancestor chains -- the recorded persistent kernel alone, which
+// the host keeps such engines away from (selfplay_plan).  Its instance keeps the chain's push as it was before chains could
+// break, never reached there, so that the kernel's code stays the code it was measured with: its register allocation follows
+// every line in it (with the new push: 148 spilled SGPRs for 146, 16 spilled VGPRs for 17 in k_selfplay_queue<Connect4, 8, true, 12>).
+template <class G, bool CHAIN = true>
 __device__ __forceinline__ void advance_root(const TreeDev &d, int g, int lane, int a, typename G::State &new_st) {
     using Node = DenseNode<G>;
     Node *pool = (Node *)d.nodes + (size_t)(g + d.pool_g0) * d.node_cap;
@@ -678,7 +684,7 @@ __device__ __forceinline__ void advance_root(const TreeDev &d, int g, int lane, 
             d.root_N[g] = 0;
             d.root_W[g] = 0.f;
             d.root_pp[g] = 0;
-            if (d.track_anc) { // a new root without a parent
+            if (d.track_anc) { // a new root without a parent: a new chain (ANC_BROKEN is forgotten with the old one)
                 d.anc_len[g] = 0;
                 d.top_N[g] = 0;
             }
@@ -709,11 +715,22 @@ __device__ __forceinline__ void advance_root(const TreeDev &d, int g, int lane, 
     if (lane == 0) {
         if (d.track_anc) {
             if (child == 0 && cn == 0 && d.n_nodes[g] == 1) { // (the pool was exhausted above: the tree restarted)
-                d.anc_len[g] = 0;
+                d.anc_len[g] = 0;                             // -- and with it the chain, a broken one's mark included
                 d.top_N[g] = 0;
-            } else if (d.anc_len[g] < d.max_plies + 2) {
-                d.anc[(size_t)g * (d.max_plies + 2) + d.anc_len[g]] = path_word(d.root[g], gs_player(st), a);
-                d.anc_len[g] += 1;
+            } else if constexpr (!CHAIN) { // (the push as it was before chains could break; no chain ever comes here)
+                if (d.anc_len[g] < d.max_plies + 2) {
+                    d.anc[(size_t)g * (d.max_plies + 2) + d.anc_len[g]] = path_word(d.root[g], gs_player(st), a);
+                    d.anc_len[g] += 1;
+                }
+            } else { // push only while 0 <= length < capacity; a full chain is marked, never cut short (later backups would miss
+                     // the edges below the cut), and a marked one is never resumed (its length is negative: no index)
+                const int na = d.anc_len[g], cap = d.max_plies + 2;
+                if (na >= 0 && na < cap) {
+                    d.anc[(size_t)g * cap + na] = path_word(d.root[g], gs_player(st), a);
+                    d.anc_len[g] = na + 1;
+                } else {
+                    d.anc_len[g] = ANC_BROKEN;
+                }
             }
         }
         d.root[g] = child & ~CHILD_TERM_BIT;
@@ -723,11 +740,33 @@ __device__ __forceinline__ void advance_root(const TreeDev &d, int g, int lane, 
     }
 }
 
-// MCTS.ResetRoot (MCTS.py:214-225): the root goes back to its top-most ancestor; nothing is forgotten.
+// MCTS.ResetRoot (MCTS.py:214-225): the root goes back to its top-most ancestor; nothing is forgotten.  (A broken chain,
+// ANC_BROKEN, is refused by the host before the launch: bb_reset_roots.)
 template <class G>
 __global__ void __launch_bounds__(256) k_reset_roots(TreeDev d) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= d.n_slots || !d.track_anc || d.game_lid[g] < 0 || d.anc_len[g] <= 0) return;
+    // A simulation in flight -- a posted leaf that is not applied yet, or a descent the level budget parked: the self-play rounds
+    // stop with one of them in most slots -- recorded its path from the old root.  Seen from the new root that path begins with the
+    // chain (the same words, path_word), so the chain goes in front of it: its backup then reaches the edges the chain's walk
+    // would have reached.  It fits: every edge of chain and path places a stone, and MAXPATH >= H*W + 2 (async_game).
+    {
+        const int na = d.anc_len[g];
+        const bool parked = d.resume_cur[g] >= 0, posted = d.pend_leaf[g] >= 0;
+        const int plen = parked ? d.resume_depth[g] : d.path_len[g];
+        if (parked || posted) {
+            if (plen + na <= G::MAXPATH) {
+                uint32_t *path = d.path + (size_t)g * G::MAXPATH;
+                const uint32_t *anc = d.anc + (size_t)g * (d.max_plies + 2);
+                for (int k = plen - 1; k >= 0; k--) path[k + na] = path[k];
+                for (int k = 0; k < na; k++) path[k] = anc[k];
+                if (parked) d.resume_depth[g] = plen + na;
+                else d.path_len[g] = plen + na;
+            } else {
+                d.ctr[(size_t)g * 8 + 6] += 1; // (cannot happen on these boards; counted as an overflow, never silent)
+            }
+        }
+    }
     d.root[g] = (int)(d.anc[(size_t)g * (d.max_plies + 2)] >> 6);
     d.root_N[g] = d.top_N[g];
     d.root_W[g] = 0.f;
@@ -793,7 +832,7 @@ __device__ __forceinline__ void reset_slot(const TreeDev &d, int g, int lid, con
     d.sim_serial[g] = 0;
     d.game_lid[g] = lid;
     if (d.leaf_flags) d.leaf_flags[g] = 0;
-    if (d.track_anc) {
+    if (d.track_anc) { // a new game, a new chain (ANC_BROKEN included)
         d.anc_len[g] = 0;
         d.top_N[g] = 0;
     }
@@ -885,7 +924,7 @@ __device__ __forceinline__ void write_example(const TreeDev &d, int lid, int ply
 
 // FindMove's tail + the body of GenerateTrainingSamples' while loop for one slot (all lanes of the group call)
 // (inlined: an out-of-line callee takes TreeDev by reference, the struct then lives in scratch and every field use is a scratch load)
-template <class G>
+template <class G, bool CHAIN = true> // CHAIN: advance_root's
 __device__ __forceinline__ void selfplay_move_body(const TreeDev &d, int g, int lane) {
     using Node = DenseNode<G>;
     constexpr int S = G::S;
@@ -908,7 +947,7 @@ __device__ __forceinline__ void selfplay_move_body(const TreeDev &d, int g, int 
     }
     write_example<G>(d, lid, ply, st, lane, Ni, total, gid); // (s, pi, player) of the state before the move
     typename G::State ns;
-    advance_root<G>(d, g, lane, act, ns);
+    advance_root<G, CHAIN>(d, g, lane, act, ns);
     __threadfence_block();
     ply += 1;
     int w = G::winner(ns, -1); // state.Winner(lastAction=None): full scan (Blackbird.py:253)
@@ -999,7 +1038,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
     bool posted = false;
     for (;;) {
         if (d.sims_left[g] <= 0) { // MCTS.FindMove's tail, GenerateTrainingSamples' loop body
-            selfplay_move_body<G>(d, g, lane);
+            selfplay_move_body<G, !REC>(d, g, lane);
             __threadfence_block();
             if (d.game_lid[g] < 0) break;
         }

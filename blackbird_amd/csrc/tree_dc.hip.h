@@ -374,7 +374,7 @@ __device__ __forceinline__ T *dc_ctl(T *p) {
 // first, and the second half of the same allocation (made twice as long for DragonChess engines) the edge taken from it as the
 // slot's edge index | player << 30 -- the encoding of DCEdges::path_edge.  It is not a field of DCEdges because the persistent
 // kernel copies that struct into its LDS (mega_dc.hip.h), and the chain has no business there.
-#define DC_ANC_BROKEN (-1) // anc_len of a slot whose chain outgrew max_plies + 2 entries: bb_reset_roots refuses it
+#define DC_ANC_BROKEN ANC_BROKEN // (tree.hip.h: one mark and one refusal for every game)
 __device__ __forceinline__ uint32_t *dc_anc_edge(const TreeDev &d, int g) {
     return d.anc + ((size_t)d.n_slots + (size_t)g) * (size_t)(d.max_plies + 2);
 }

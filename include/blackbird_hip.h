@@ -166,9 +166,14 @@ typedef struct {
                               BB_LAUNCH_WAVE is the one value that concerns bb_run_sims instead (opt-in, bb_run_sims_structure) */
     int32_t general_net;   /* 1: run a 16-filter network through the launch-per-layer kernels of wider networks (parity checks) */
     int32_t track_ancestors; /* 1: keep, per slot, the chain of edges from the first root to the current one (at most
-                              max_plies + 2 of them) and back every simulation of bb_run_sims up through it, as the reference's
-                              _backProp does (MCTS.py:238-258) -- what MCTS.ResetRoot (:214-225) needs.  Every game; DragonChess
-                              self-play refuses such an engine (BB_ERR_STATE) */
+                              max_plies + 2 of them) and back every simulation up through it, as the reference's _backProp does
+                              (MCTS.py:238-258) -- what MCTS.ResetRoot (:214-225) needs.  Every game under bb_run_sims.  Self-play
+                              of Connect4 and TicTacToe keeps the chain too, in every launch structure: a slot's chain starts at
+                              its game's first position and grows with every move; with a network and BB_LAUNCH_AUTO such an
+                              engine plays the asynchronous rounds instead of the persistent kernel, whose backups do not walk
+                              the chain (bb_selfplay_mode says 1; the records are the same byte for byte).  DragonChess
+                              self-play refuses such an engine (BB_ERR_STATE).  A chain that outgrows its max_plies + 2 entries
+                              is marked broken, not cut short: bb_reset_roots */
     int32_t search_cache;  /* 1: bb_run_sims / bb_run_sims_masked probe the engine's evaluation cache before the network, answer hits
                               from it and store misses -- where they search through BB_LAUNCH_WAVE with a network (bb_run_sims_structure)
                               and the game has a cache key (Connect4, DragonChess); the engine then owns a table (sized by
@@ -351,7 +356,13 @@ int bb_get_root_states(bb_engine *e, void *states_out);
 /* MCTS.ResetRoot (MCTS.py:214-225): every slot's root goes back to its top-most ancestor (the first position searched) with all
  * statistics intact, including the simulations run from the positions below it (bb_config.track_ancestors; BB_ERR_STATE otherwise).
  * A tree that restarted since (bb_set_roots, a move from an unexpanded root, a full node pool) starts its chain anew: its root
- * stays.  BB_ERR_CAPACITY if a slot moved its root more than max_plies + 2 times since its chain began (nothing is changed). */
+ * stays.  After bb_selfplay_step a slot's top is the first position of the game it is playing (a slot that went on to its next
+ * game: that game's), and its play resumes from there: a simulation that was in flight (the asynchronous rounds stop with one
+ * in most slots) is backed up from the new root down, and the slot's ply counter is not wound back, so the records it writes from
+ * then on are not a game's -- a look at the tree, not a way to replay.  BB_ERR_CAPACITY, in every game, if a slot moved its root more than
+ * max_plies + 2 times since its chain began: its chain is broken -- simulations since then were not backed up above the root, and
+ * no later move mends it -- so nothing is changed for any slot; bb_set_roots, bb_selfplay_begin or a restart of the slot's tree
+ * starts a whole chain again.  (Self-play ends a game at max_plies moves, so only bb_move_roots can break a chain.) */
 int bb_reset_roots(bb_engine *e);
 /* One node of a slot's tree, for a host-side Node view (MCTS.py:7-98: Children, Plays, Value, State): node < 0 = the root, else a pool
  * index taken from an earlier view.  child_node_out / child_plays_out / child_value_out [S]: per child slot the child's pool index (-1:
