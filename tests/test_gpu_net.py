@@ -9,6 +9,7 @@ import pytest
 from blackbird_amd import _lib, weights as W
 
 from tests.net_cases import TOL, boards_for, dragonchess_positions, selfplay_vs_oracle_tree as _selfplay_vs_oracle_tree
+from tests.split_cases import _forward64, _layer_names, _rescaled  # noqa: F401 (the float64 statement and the rescalings live there)
 
 pytestmark = pytest.mark.gpu
 
@@ -201,60 +202,6 @@ def test_split_operand_tower_every_tap_and_plane_contributes(game):
 
 
 # ---- the split-operand arithmetic over its envelope (bb_config.net_form AUTO / SPLIT) -------------------------------------
-def _forward64(w, planes):
-    """The graph of NetworkFactory.py:22-183 in float64 numpy (NHWC, SAME padding, batch-norm epsilon 1e-3): an independent
-    statement of what both the float32 oracle and the GPU forms approximate.  Returns value, logits."""
-    x = planes.astype(np.float64)
-
-    def conv(t, k, b):
-        kh = k.shape[0] // 2
-        tp = np.pad(t, ((0, 0), (kh, kh), (kh, kh), (0, 0)))
-        out = np.zeros(t.shape[:3] + (k.shape[3],))
-        for dy in range(k.shape[0]):
-            for dx in range(k.shape[1]):
-                out += np.einsum("nhwc,cf->nhwf", tp[:, dy:dy + t.shape[1], dx:dx + t.shape[2], :], k[dy, dx].astype(np.float64))
-        return out + b.astype(np.float64)
-
-    def bn(t, p):
-        g, b, m, v = (w[f"{p}/{n}"].astype(np.float64) for n in ("gamma", "beta", "moving_mean", "moving_variance"))
-        return g * (t - m) / np.sqrt(v + 1e-3) + b
-
-    relu = lambda t: np.maximum(t, 0.0)
-    t = relu(bn(conv(x, w["resTower/conv_block/conv/kernel"], w["resTower/conv_block/conv/bias"]), "resTower/conv_block/batch_norm"))
-    i = 0
-    while f"resTower/block_{i}/conv_1/kernel" in w:
-        u = relu(bn(conv(t, w[f"resTower/block_{i}/conv_1/kernel"], w[f"resTower/block_{i}/conv_1/bias"]), f"resTower/block_{i}/batch_norm_1"))
-        u = bn(conv(u, w[f"resTower/block_{i}/conv_2/kernel"], w[f"resTower/block_{i}/conv_2/bias"]), f"resTower/block_{i}/batch_norm_2")
-        t = relu(u + t)
-        i += 1
-    v = relu(bn(conv(t, w["value/convolution/kernel"], w["value/convolution/bias"]), "value/batch_norm"))
-    v = (v @ w["value/dense_1/kernel"].astype(np.float64) + w["value/dense_1/bias"]).sum(axis=(1, 2))
-    v = np.tanh(relu(v) @ w["value/dense_2/kernel"].astype(np.float64) + w["value/dense_2/bias"])[:, 0]
-    p = relu(bn(conv(t, w["policy/convolution/kernel"], w["policy/convolution/bias"]), "policy/batch_norm"))
-    logits = (p @ w["policy/policy/kernel"].astype(np.float64) + w["policy/policy/bias"]).sum(axis=(1, 2))
-    return v, logits
-
-
-def _layer_names(blocks):
-    names = [("resTower/conv_block/conv", "resTower/conv_block/batch_norm")]
-    for i in range(blocks):
-        names += [(f"resTower/block_{i}/conv_{j}", f"resTower/block_{i}/batch_norm_{j}") for j in (1, 2)]
-    return names
-
-
-def _rescaled(w, layer, k, blocks):
-    """Kernel, bias and moving mean of one conv layer times 2^k, its batch-norm gamma divided by 2^k: the network function is
-    unchanged in exact arithmetic, and every scaling is a power of two -- exact in float32 and in every bf16 plane."""
-    conv, bnp = _layer_names(blocks)[layer]
-    out = {n: a.copy() for n, a in w.items()}
-    s = np.float32(2.0) ** k
-    out[conv + "/kernel"] = (w[conv + "/kernel"] * s).astype(np.float32)
-    out[conv + "/bias"] = (w[conv + "/bias"] * s).astype(np.float32)
-    out[bnp + "/moving_mean"] = (w[bnp + "/moving_mean"] * s).astype(np.float32)
-    out[bnp + "/gamma"] = (w[bnp + "/gamma"] / s).astype(np.float32)
-    return out
-
-
 @pytest.mark.parametrize("game", [_lib.GAME_CONNECT4, _lib.GAME_DRAGONCHESS])
 def test_split_operand_envelope(orc, game):
     """The default arithmetic (float32 operands as three exact bf16 planes, six bf16 MFMA products, float32 accumulation) over the

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests.host_cases import host_compiler
+from tests.split_cases import _bf16_nearest, _bits, _widen
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "blackbird_amd", "csrc")
@@ -169,22 +170,9 @@ def images(tmp_path_factory):
     return res
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=F32).view(U32)
-
-
 def _same(a, b):
     """equal float32 arrays, bit for bit"""
     return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _bf16_nearest(x):
-    u = _bits(x).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(U16)
-
-
-def _widen(p):
-    return (np.ascontiguousarray(p, dtype=U16).astype(U32) << 16).view(F32)
 
 
 def _split(x):
