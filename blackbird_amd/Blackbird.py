@@ -401,19 +401,15 @@ def EvaluateDeviceExamples(model, examples=None, batchSize=1024, scorer='trainer
     if examples is None:
         raise ValueError('no device examples for %s version %d: pass `examples`, or set KeepDeviceExamples before '
                          'GenerateTrainingSamples' % (model.Name, model.Version))
+    state = np.random.get_state()      # an engine or a trainer made here draws the seed of its noise from numpy's generator, as any does:
     if scorer == 'engine':
-        state = np.random.get_state()  # an engine made here draws the seed of its noise from numpy's generator, as any does:
         engine = model._engine_for((examples.info.H, examples.info.W, examples.info.C))
-        np.random.set_state(state)     # ... the generator itself is left where it was
-        out = examples.score_with(engine, chunk_rows=max(int(batchSize), 1))
-        bad = examples.bad()
-        if bad:
-            raise _lib.BlackbirdHipError('%d malformed example records were met in the evaluation' % bad)
-        return out
-    state = np.random.get_state()      # a trainer made here draws the seed of its noise from numpy's generator, as any does:
-    trainer = model._trainer_for(examples.info.C)
+    else:
+        trainer = model._trainer_for(examples.info.C)
     np.random.set_state(state)         # ... the generator itself is left where it was
-    if hasattr(trainer, 'evaluate_records'):
+    if scorer == 'engine':
+        out = examples.score_with(engine, chunk_rows=max(int(batchSize), 1))
+    elif hasattr(trainer, 'evaluate_records'):
         out = trainer.evaluate_records(examples)
     else:
         index = examples.index_tensor(np.arange(len(examples)))

@@ -4,7 +4,7 @@
 //   k_score_gather  one thread per row: the record is checked, its packed state copied into a contiguous G::State array
 //   (launch_net)    value[chunk], logits[chunk][A] of those states: no noise, no keys, no evaluation cache
 //   k_score_rows    one wave per row, four rows per workgroup: value, squared error, cross entropy against the record's own label
-//                   and the flags byte (BB_ROW_* of include/blackbird_hip.h, as k_train_eval sets them)
+//                   and the flags byte
 // and k_train_eval_totals (train_eval.hip.h) once over the finished rows.
 //
 // Records: the bb_examples_fetch layout (examples.hip.h) -- ExampleHdr, packed state, u32 visits[S], compact games u16 action[S].
@@ -14,17 +14,13 @@
 // network kernels never see unchecked bytes), ok 0 and one integer atomicAdd on *bad.  k_score_rows reads a record only where
 // ok[k] says that it passed: nothing a record says is used as an address before.  A malformed row is {0, 0, 0}, flags 0.
 //
-// Per row:  value = the engine's, unchanged;  se = (value - z)^2, one subtraction and one multiplication;
-//     pi = (float)((double)visits / (double)total) -- example_share's division --, 0 when total == 0
-//     mx = max_a logit[a];  sum = sum_a expf(logit[a] - mx);  lse = logf(sum)                          (all A logits)
-//     ce = -sum pi * ((logit[a] - mx) - lse)                                                           (labelled actions only)
-// HAS_POLICY: total != 0 and some visit count is not zero; TOP1: first maximum of the logits == first maximum of the label, both
-// in action order; DECIDED: z != 0; SIGN_OK: value and z both > 0 or both < 0; COUNTED: the row is well-formed.
+// Per row: a scored row as train_eval.hip.h states it (score_value_part, score_policy_serial: the figures, their orders and the
+// flags), with value = the engine's, unchanged, target = z and pi = (float)((double)visits / (double)total) -- example_share's
+// division --, 0 when total == 0.
 //
 // Sum orders (float32, no float atomics: the same input gives the same bits).
-//   Dense games (A <= 16): lane 0 of the row's wave, k_train_eval's serial form -- a ascending for mx, for sum and for the fmaf
-//   chain of ce; first maxima by strict > in that order.
-//   DragonChess (A = 4032): the row is read as 1008 16-byte groups; lane l takes groups l, l + 64, ... (16 passes, the last one
+//   Dense games (A <= 16): lane 0 of the row's wave calls score_policy_serial, as k_train_eval does.
+//   DragonChess (A = 4032): the same figures and flags over the whole wave.  The row is read as 1008 16-byte groups; lane l takes groups l, l + 64, ... (16 passes, the last one
 //   lanes 0..47 only), the four logits of a group in action order, so the lane's actions ascend.  The lane's maximum (and its
 //   first position: strict >) and the lane's sum of expf follow that order; the 64 lanes are then combined by one xor butterfly
 //   (offsets 32, 16, 8, 4, 2, 1; float addition commutes, so every lane ends with the same bits; of two equal maxima the smaller
@@ -125,37 +121,14 @@ __global__ void __launch_bounds__(256) k_score_rows(int n_records, const uint8_t
         ExampleHdr h;
         __builtin_memcpy(&h, &h4, 16);
         const uint32_t *vis = (const uint32_t *)(rec + SR::OFF_VIS);
-        const float val = value[k], target = (float)h.z, diff = val - target;
-        out[0] = val;
-        out[1] = diff * diff;
-        flags = BB_ROW_COUNTED;
-        if (target != 0.f) flags |= BB_ROW_DECIDED;
-        if ((val > 0.f && target > 0.f) || (val < 0.f && target < 0.f)) flags |= BB_ROW_SIGN_OK;
+        score_value_part(value[k], (float)h.z, out, flags);
         if constexpr (!SR::COMPACT) {
             static_assert(SR::COMPACT || A <= 16, "the serial form: a handful of actions");
             if (lane == 0) {
                 const float *lg = logits + (size_t)k * A;
-                float pi[A];
-                int best_pi = 0, best_lg = 0;
-                bool any = false;
-                float mx = lg[0], top_pi = 0.f, top_lg = lg[0];
-                for (int a = 0; a < A; a++) { // (first maxima: a later equal entry does not replace an earlier one)
-                    pi[a] = h.total ? (float)((double)vis[a] / (double)h.total) : 0.f;
-                    any = any || (h.total != 0 && vis[a] != 0);
-                    if (a == 0 || pi[a] > top_pi) { top_pi = pi[a]; best_pi = a; }
-                    if (lg[a] > top_lg) { top_lg = lg[a]; best_lg = a; }
-                    mx = fmaxf(mx, lg[a]);
-                }
-                if (any) {
-                    float sum = 0.f;
-                    for (int a = 0; a < A; a++) sum += expf(lg[a] - mx);
-                    const float lse = logf(sum);
-                    float acc = 0.f;
-                    for (int a = 0; a < A; a++) acc = __builtin_fmaf(pi[a], (lg[a] - mx) - lse, acc);
-                    out[2] = -acc;
-                    flags |= BB_ROW_HAS_POLICY;
-                    if (best_pi == best_lg) flags |= BB_ROW_TOP1;
-                }
+                const uint32_t total = h.total;
+                score_policy_serial<A>([=](int a) { return lg[a]; },
+                                       [=](int a) { return total ? (float)((double)vis[a] / (double)total) : 0.f; }, out, flags);
             }
         } else {
             static_assert(!SR::COMPACT || (A % 4 == 0 && G::S <= 192), "16-byte groups; three passes over the children");

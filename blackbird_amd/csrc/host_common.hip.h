@@ -68,6 +68,11 @@ struct Destroyer {
 template <class T, int (*Destroy)(T *)>
 using Building = std::unique_ptr<T, Destroyer<T, Destroy>>;
 
+// what both scorers (bb_trainer_eval*, bb_examples_score) ask of their outputs in the same words: a place for the bb_eval_totals
+static int score_outputs_ok(const void *totals) {
+    return !totals || (uintptr_t)totals % 8 ? fail(BB_ERR_ARG, "totals_out must be an 8-byte aligned device pointer") : BB_OK;
+}
+
 static inline int nblk(size_t n, int per = 256) { return (int)((n + per - 1) / per); }
 // grid and block of every one-wave-per-slot kernel (search_wave*.hip.h, selfplay_wave.hip.h): <<<SW_GRID(d), 0, stream>>>
 #define SW_GRID(d) nblk((d).n_slots, SW_WAVES), 64 * SW_WAVES

@@ -41,7 +41,7 @@ struct bb_engine {
     size_t net_sizes[4] = {0, 0, 0, 0};
     DevOwner own{HIP_OPS}; // every allocation, stream and event below, starts.dev apart; zero fills run on `stream`, its first
     hipStream_t stream = nullptr;
-    hipEvent_t w_event[2] = {nullptr, nullptr}; // bb_load_weights_device: the caller's stream -> the engine's, and back (no timing)
+    hipEvent_t w_event[2] = {nullptr, nullptr}; // engine_stream_after / _release: the caller's stream -> the engine's, and back (no timing)
     int n_games_target = 0;
     StartsTable starts; // bb_selfplay_set_starts: the device copy dev.starts / view[].starts point at (starts.h); not in `own`
     int sched_plies = -1;    // bb_selfplay_set_temp_schedule: plies at the run's own temperature (< 0: no schedule) and the
@@ -88,6 +88,33 @@ static hipError_t sync_all(bb_engine *e) {
         if (r != hipSuccess) return r;
     }
     return hipStreamSynchronize(e->stream);
+}
+
+// The entry points that take a caller's stream do not switch devices: the current device must be the engine's.  `what`: what
+// else of the caller's lives there.
+static int engine_on_current_device(const bb_engine *e, const char *who, const char *what) {
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev != e->cfg.device)
+        return fail(BB_ERR_ARG, "%s: the engine lives on device %d, the current device (the stream's and the %s') is %d", who,
+                    e->cfg.device, what, dev);
+    return BB_OK;
+}
+
+// The engine's stream borrowed for a caller that works on `caller`.  After: nothing of the engine is in flight (its own streams
+// only are waited for, never `caller`), and e->stream stands behind whatever `caller` has queued.  Release: `caller` goes on
+// once e->stream has come this far -- and, with_second, the engine's second stream too.
+static int engine_stream_after(bb_engine *e, hipStream_t caller) {
+    HIPCHK(sync_all(e));
+    HIPCHK(hipEventRecord(e->w_event[0], caller));
+    HIPCHK(hipStreamWaitEvent(e->stream, e->w_event[0], 0));
+    return BB_OK;
+}
+static int engine_stream_release(bb_engine *e, hipStream_t caller, bool with_second = false) {
+    HIPCHK(hipEventRecord(e->w_event[1], e->stream));
+    if (with_second && e->vstream[1]) HIPCHK(hipStreamWaitEvent(e->vstream[1], e->w_event[1], 0));
+    HIPCHK(hipStreamWaitEvent(caller, e->w_event[1], 0));
+    return BB_OK;
 }
 
 template <class G> struct NodeOf { using type = DenseNode<G>; }; // a node of the family's pool

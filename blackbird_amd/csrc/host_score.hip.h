@@ -45,7 +45,7 @@ extern "C" int bb_examples_score(bb_engine *e, int n_records, const void *record
                                  void *stream) {
     if (!e) return fail(BB_ERR_ARG, "null engine");
     if (n < 0 || n_records < 0) return fail(BB_ERR_ARG, "negative count (%d rows of %d records)", n, n_records);
-    if (!totals_out || (uintptr_t)totals_out % 8) return fail(BB_ERR_ARG, "totals_out must be an 8-byte aligned device pointer");
+    if (int rc = score_outputs_ok(totals_out)) return rc;
     if ((uintptr_t)records % 16 || (uintptr_t)workspace % 16 || (uintptr_t)index % sizeof(int64_t) || ((uintptr_t)rows_out | (uintptr_t)bad) % 4)
         return fail(BB_ERR_ARG, "records and workspace must be 16-byte aligned, index 8-byte, rows_out and bad 4-byte");
     if (n > 0 && (!records || !rows_out || !flags_out || !workspace))
@@ -63,16 +63,9 @@ extern "C" int bb_examples_score(bb_engine *e, int n_records, const void *record
     }
     if (e->cfg.evaluator != BB_EVAL_NET) return fail(BB_ERR_WEIGHTS, "bb_examples_score scores with the engine's network; this engine's evaluator is not the network");
     if (!e->has_weights) return fail(BB_ERR_WEIGHTS, "bb_load_weights has not been called");
-    int dev = -1;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev != e->cfg.device)
-        return fail(BB_ERR_ARG, "bb_examples_score: the engine lives on device %d, the current device (the stream's and the records') is %d",
-                    e->cfg.device, dev);
-    hipStream_t caller = (hipStream_t)stream;
-    HIPCHK(sync_all(e)); // a score never runs beside a search: the engine's own streams only, never `stream`
-    // behind whatever `stream` has queued (the records, the index) ...
-    HIPCHK(hipEventRecord(e->w_event[0], caller));
-    HIPCHK(hipStreamWaitEvent(e->stream, e->w_event[0], 0));
+    if (int rc = engine_on_current_device(e, "bb_examples_score", "records")) return rc;
+    // a score never runs beside a search; behind whatever `stream` has queued (the records, the index) ...
+    if (int rc = engine_stream_after(e, (hipStream_t)stream)) return rc;
     if (n > 0) {
         const uint8_t *rec = (const uint8_t *)records;
         GAME_SWITCH(e->cfg.game, if (int rc = examples_score<G>(e, n_records, rec, n, index, rows_out, flags_out, bad, (uint8_t *)workspace, chunk)) return rc;
@@ -81,7 +74,5 @@ extern "C" int bb_examples_score(bb_engine *e, int n_records, const void *record
     k_train_eval_totals<<<1, BB_TRAIN_THREADS, 0, e->stream>>>(n, rows_out, flags_out, (EvalTotals *)totals_out);
     HIPCHK(hipGetLastError());
     // ... and `stream` goes on once the figures are there
-    HIPCHK(hipEventRecord(e->w_event[1], e->stream));
-    HIPCHK(hipStreamWaitEvent(caller, e->w_event[1], 0));
-    return BB_OK;
+    return engine_stream_release(e, (hipStream_t)stream);
 }

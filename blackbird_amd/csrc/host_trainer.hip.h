@@ -272,7 +272,7 @@ static int trainer_eval_prepare(bb_trainer *t, int n, float **rows, uint8_t **fl
     if (!t) return fail(BB_ERR_ARG, "null trainer");
     if (int rc = trainer_not_wide(t, "bb_trainer_eval")) return rc;
     if (n < 0) return fail(BB_ERR_ARG, "negative count (%d rows)", n);
-    if (!totals || (uintptr_t)totals % 8) return fail(BB_ERR_ARG, "totals_out must be an 8-byte aligned device pointer");
+    if (int rc = score_outputs_ok(totals)) return rc;
     if ((uintptr_t)*rows % sizeof(float)) return fail(BB_ERR_ARG, "float32 pointers must be 4-byte aligned");
     if (int rc = trainer_on_device(t)) return rc;
     if ((!*rows || !*flags) && (size_t)n > t->eval_cap) {

@@ -243,15 +243,9 @@ static int load_weights_device(bb_engine *e, const bb_net_weights *w, hipStream_
     const NetHeadOff off = head_offsets(16, w->D, w->A);
     if (off.floats != nd.head_floats || (size_t)off.floats != e->net_sizes[3])
         return fail(BB_ERR_STATE, "%s: the head array holds %d floats, these weights need %d", who, nd.head_floats, off.floats);
-    int dev = -1;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev != e->cfg.device)
-        return fail(BB_ERR_ARG, "%s: the engine lives on device %d, the current device (the stream's and the weights') is %d", who,
-                    e->cfg.device, dev);
-    HIPCHK(sync_all(e)); // weights must not change under a running search: the engine's own streams only, never `stream`
-    // behind whatever `stream` has queued (the steps that made these weights) ...
-    HIPCHK(hipEventRecord(e->w_event[0], stream));
-    HIPCHK(hipStreamWaitEvent(e->stream, e->w_event[0], 0));
+    if (int rc = engine_on_current_device(e, who, "weights")) return rc;
+    // weights must not change under a running search; behind whatever `stream` has queued (the steps that made these weights) ...
+    if (int rc = engine_stream_after(e, stream)) return rc;
     // ... no evaluation outlives the weights it was made with ...
     if (e->eval_cache_bytes) HIPCHK(hipMemsetAsync(e->dev.eval_cache, 0, e->eval_cache_bytes, e->stream));
     auto blocks = [](int threads) { return (unsigned)((threads + NET_PACK_THREADS - 1) / NET_PACK_THREADS); };
@@ -263,10 +257,7 @@ static int load_weights_device(bb_engine *e, const bb_net_weights *w, hipStream_
     HIPCHK(hipGetLastError());
     // ... and everything else waits for the images: the engine's second stream, and `stream` itself, so that the weights may be
     // freed or stepped on as soon as `stream` has come this far
-    HIPCHK(hipEventRecord(e->w_event[1], e->stream));
-    if (e->vstream[1]) HIPCHK(hipStreamWaitEvent(e->vstream[1], e->w_event[1], 0));
-    HIPCHK(hipStreamWaitEvent(stream, e->w_event[1], 0));
-    return BB_OK;
+    return engine_stream_release(e, stream, true);
 }
 
 extern "C" int bb_load_weights_device(bb_engine *e, const bb_net_weights *w_dev, void *stream) {

@@ -24,19 +24,56 @@
 // (-DBB_TRAIN_EVAL_E) was last present at 3be01a0.
 //
 // Arithmetic: float32, every fused multiply-add explicit; the orders are written where the expressions are (tr_conv_fwd,
-// tr_head_*).  The row's figures are taken by one lane, in order:
-//     mx = max_a logit[a] (a ascending);  sum = sum_a expf(logit[a] - mx) (a ascending);  lse = logf(sum)
-//     ce = -(fmaf chain over a ascending of pi[a] * ((logit[a] - mx) - lse)), 0 for a row without a label
+// tr_head_*).  The row's figures are taken by one lane: score_value_part and score_policy_serial below, the one statement of a
+// scored row, which k_score_rows (examples_score.hip.h) takes for the engine's outputs too.
 // (A <= 16: the serial form of k_train_grad's loss; a tree over 16 lanes was not built.)
 #pragma once
 #include "train.hip.h"
-
-// (the flags byte of a row: BB_ROW_* of include/blackbird_hip.h)
 
 struct EvalTotals { // bb_eval_totals
     int64_t rows, policy_rows, top1, decided, sign_ok;
     double se_sum, ce_sum;
 };
+
+// ---- one scored row (the flags byte: BB_ROW_* of include/blackbird_hip.h) ---------------------------------------------
+// A well-formed row's value part: out[0] = val, out[1] = se = (val - target)^2, one subtraction and one multiplication.
+// COUNTED: the row is well-formed; DECIDED: target != 0; SIGN_OK: val and target both > 0 or both < 0.
+__device__ __forceinline__ void score_value_part(float val, float target, float out[3], int &flags) {
+    const float diff = val - target;
+    out[0] = val;
+    out[1] = diff * diff;
+    flags = BB_ROW_COUNTED;
+    if (target != 0.f) flags |= BB_ROW_DECIDED;
+    if ((val > 0.f && target > 0.f) || (val < 0.f && target < 0.f)) flags |= BB_ROW_SIGN_OK;
+}
+
+// The policy part of a row of A <= 16 actions, by one lane, every loop a ascending; logit(a), label(a): the row's entries.
+//     mx = max_a logit[a];  sum = sum_a expf(logit[a] - mx);  lse = logf(sum)                               (all A logits)
+//     out[2] = ce = -(fmaf chain of pi[a] * ((logit[a] - mx) - lse)), left 0 for a row without a label
+// HAS_POLICY: some pi[a] != 0; TOP1: first maximum of the logits == first maximum of the label, both in action order.
+template <int A, class Logit, class Label>
+__device__ __forceinline__ void score_policy_serial(Logit logit, Label label, float out[3], int &flags) {
+    float pi[A];
+    int best_pi = 0, best_lg = 0;
+    bool any = false;
+    float mx = logit(0), top_pi = 0.f, top_lg = logit(0);
+    for (int a = 0; a < A; a++) { // (first maxima: a later equal entry does not replace an earlier one)
+        pi[a] = label(a);
+        any = any || pi[a] != 0.f; // (a record's share visits / total is 0 only for visits == 0: at least 2^-32 otherwise)
+        if (a == 0 || pi[a] > top_pi) { top_pi = pi[a]; best_pi = a; }
+        if (logit(a) > top_lg) { top_lg = logit(a); best_lg = a; }
+        mx = fmaxf(mx, logit(a));
+    }
+    if (!any) return;
+    float sum = 0.f;
+    for (int a = 0; a < A; a++) sum += expf(logit(a) - mx);
+    const float lse = logf(sum);
+    float acc = 0.f;
+    for (int a = 0; a < A; a++) acc = __builtin_fmaf(pi[a], (logit(a) - mx) - lse, acc);
+    out[2] = -acc;
+    flags |= BB_ROW_HAS_POLICY;
+    if (best_pi == best_lg) flags |= BB_ROW_TOP1;
+}
 
 // ---- k_train_eval: one workgroup per row ------------------------------------------------------------------------------
 template <class G, class Src>
@@ -80,42 +117,17 @@ __global__ void __launch_bounds__(BB_TRAIN_THREADS) k_train_eval(TrainLayout lay
     if (tid != 0) return;
     const typename Src::Row row = src.row(b);
     float out[3] = {0.f, 0.f, 0.f};
-    uint8_t flags = 0;
+    int flags = 0;
     if (src.valid(row)) {
-        const float val = tr_head_value(lay, prm, sc + HB), target = src.value_of(row), diff = val - target;
-        out[0] = val;
-        out[1] = diff * diff;
-        flags = BB_ROW_COUNTED;
-        if (target != 0.f) flags |= BB_ROW_DECIDED;
-        if ((val > 0.f && target > 0.f) || (val < 0.f && target < 0.f)) flags |= BB_ROW_SIGN_OK;
-        float pi[A];
-        int best_pi = 0, best_lg = 0;
-        bool any = false;
-        float mx = sc[LG], top_pi = 0.f, top_lg = sc[LG];
-        for (int a = 0; a < A; a++) { // (first maxima: a later equal entry does not replace an earlier one)
-            pi[a] = src.label_of(row, a);
-            any = any || pi[a] != 0.f;
-            if (a == 0 || pi[a] > top_pi) { top_pi = pi[a]; best_pi = a; }
-            if (sc[LG + a] > top_lg) { top_lg = sc[LG + a]; best_lg = a; }
-            mx = fmaxf(mx, sc[LG + a]);
-        }
-        if (any) {
-            float sum = 0.f;
-            for (int a = 0; a < A; a++) sum += expf(sc[LG + a] - mx);
-            const float lse = logf(sum);
-            float acc = 0.f;
-            for (int a = 0; a < A; a++) acc = __builtin_fmaf(pi[a], (sc[LG + a] - mx) - lse, acc);
-            out[2] = -acc;
-            flags |= BB_ROW_HAS_POLICY;
-            if (best_pi == best_lg) flags |= BB_ROW_TOP1;
-        }
+        score_value_part(tr_head_value(lay, prm, sc + HB), src.value_of(row), out, flags);
+        score_policy_serial<A>([=](int a) { return sc[LG + a]; }, [=](int a) { return src.label_of(row, a); }, out, flags);
     } else {
         src.count(row, 0);
     }
     rows_out[(size_t)b * 3] = out[0];
     rows_out[(size_t)b * 3 + 1] = out[1];
     rows_out[(size_t)b * 3 + 2] = out[2];
-    flags_out[b] = flags;
+    flags_out[b] = (uint8_t)flags;
 }
 
 // ---- k_train_eval_totals: one workgroup ------------------------------------------------------------------------------

@@ -240,6 +240,54 @@ def eval_summary(rows, policy_rows, top1, decided, sign_ok, se_sum, ce_sum):
 EVAL_COUNTS = ('rows', 'policy_rows', 'top1', 'decided', 'sign_ok', 'se_sum', 'ce_sum')     # eval_summary's arguments, in order
 
 
+def _device_index(dev):
+    """The number of the GPU a torch.device names (one without an index: torch's current device)."""
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _records_source(examples, game, index, who, what):
+    """What the method `who` of a `what` ('trainer', 'engine') of game `game` on GPU `index` asks of the records it reads: a
+    DeviceExamples of that game on that GPU, or ValueError.  Returns the records' device."""
+    if not isinstance(examples, DeviceExamples):
+        raise ValueError('%s takes a DeviceExamples (merged rows carry sums of their own and are not a records source), got %s'
+                         % (who, type(examples).__name__))
+    if examples.game != game:
+        raise ValueError('the examples are of game %d, the %s of game %d' % (examples.game, what, game))
+    dev = examples.records.device
+    if dev.type != 'cuda' or _device_index(dev) != index:
+        raise ValueError('the examples are on %s, the %s on cuda:%d' % (dev, what, index))
+    return dev
+
+
+def _row_tensors(dev, n, **named):
+    """The per-row tensors a records call takes, by name ('sym': uint8, every other one int64), each None or contiguous, of `n`
+    entries, on `dev`: ValueError otherwise."""
+    for name, t in named.items():
+        dtype = torch.uint8 if name == 'sym' else torch.int64
+        if t is not None and (t.dtype != dtype or t.device != dev or int(t.numel()) != n or not t.is_contiguous()):
+            raise ValueError('%s: a contiguous %s tensor of %d entries on %s is expected' % (name, dtype, n, dev))
+
+
+def _scored(dev, n, launch, keep, rows, outputs_too=False):
+    """The common part of every scorer: the outputs of `n` rows on `dev`, `launch(rows_ptr, flags_ptr, totals_ptr, stream)` on
+    torch's current stream, and the one synchronising read of the totals.  `keep`: the tensors the launch reads (None entries
+    skipped); outputs_too: the launch runs on a stream torch does not know, so the outputs stay alive past it as well."""
+    out_rows = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    out_flags = torch.empty((n,), dtype=torch.uint8, device=dev)
+    totals = torch.empty(np.dtype(_lib.EVAL_TOTALS_DTYPE).itemsize, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        launch(out_rows.data_ptr(), out_flags.data_ptr(), totals.data_ptr(), stream.cuda_stream)
+    for t in tuple(keep) + ((out_rows, out_flags, totals) if outputs_too else ()):   # asynchronous: alive until the stream has used them
+        if t is not None:
+            t.record_stream(stream)
+    tot = totals.cpu().numpy().view(_lib.EVAL_TOTALS_DTYPE)[0]      # (waits for the launches)
+    out = eval_summary(*[tot[k].item() for k in EVAL_COUNTS])
+    if rows:
+        out['per_row'], out['flags'] = out_rows, out_flags
+    return out
+
+
 HIP_TRAINER_LIMITS = 'Connect4 or TicTacToe, 16 filters, 0 to 9 blocks, a dense width of 1 to 64'
 HIP_TRAINER_DC_BLOCKS = 8     # train_max_blocks<DragonChess>() of csrc/train.hip.h: the blocks whose workgroup fits a CU's 160 KB of LDS
 HIP_TRAINER_LIMITS_ALL = ('Connect4 or TicTacToe (0 to 9 blocks) or DragonChess (0 to %d blocks: the LDS of a CU; batch tensors only, no '
@@ -292,7 +340,7 @@ class HipTrainer:
         if seed is None:
             from .MCTS import _seed_from_numpy
             seed = _seed_from_numpy()
-        self._index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self._index = _device_index(self.device)
         self._h = _lib.trainer_create(self.game, W.flatten(weights), self.H, self.Wd, _OPTIMIZERS[optimizer], self.max_batch,
                                       device=self._index, momentum=self.momentum, alpha=self.alpha, epsilon=self.epsilon,
                                       seed=seed)
@@ -311,13 +359,15 @@ class HipTrainer:
         t = t.to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
         return t
 
+    def _batch_tensors(self, boards, evalLabel, policyLabel):
+        """(n, boards [n,H,W,C], evalLabel [n], policyLabel [n,A]): a batch as float32 tensors on the trainer's device."""
+        n = int(policyLabel.shape[0]) if hasattr(policyLabel, 'shape') else len(policyLabel)
+        return n, self._f32(boards, (n, self.H, self.Wd, self.C)), self._f32(evalLabel, (n,)), self._f32(policyLabel, (n, self.A))
+
     def _launch(self, boards, evalLabel, policyLabel, noise, lr, apply):
         """One bb_trainer_step on torch's current stream; returns the device tensor [4] of the loss and its terms."""
         _no_noise(self.loss_kind, noise)
-        n = int(policyLabel.shape[0]) if hasattr(policyLabel, 'shape') else len(policyLabel)
-        boards = self._f32(boards, (n, self.H, self.Wd, self.C))
-        ev = self._f32(evalLabel, (n,))
-        pl = self._f32(policyLabel, (n, self.A))
+        n, boards, ev, pl = self._batch_tensors(boards, evalLabel, policyLabel)
         nz = None if noise is None else self._f32(noise, (self.A,))
         loss = torch.empty(4, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
@@ -366,14 +416,7 @@ class HipTrainer:
         in order), whole batches.  noise: [n_batches, A] or None to draw it.  Malformed rows count in examples.bad()."""
         self._not_wide('epoch_records')
         _no_noise(self.loss_kind, noise)
-        if not isinstance(examples, DeviceExamples):
-            raise ValueError('epoch_records takes a DeviceExamples (merged rows carry sums of their own and are not a records '
-                             'source), got %s' % type(examples).__name__)
-        if examples.game != self.game:
-            raise ValueError('the examples are of game %d, the trainer of game %d' % (examples.game, self.game))
-        dev = examples.records.device
-        if dev.type != 'cuda' or (dev.index if dev.index is not None else torch.cuda.current_device()) != self._index:
-            raise ValueError('the examples are on %s, the trainer on cuda:%d' % (dev, self._index))
+        dev = _records_source(examples, self.game, self._index, 'epoch_records', 'trainer')
         batch = int(batchSize)
         if batch < 1 or batch > self.max_batch:
             raise ValueError('batches of %d examples; the trainer takes 1..%d (max_batch)' % (batch, self.max_batch))
@@ -381,9 +424,7 @@ class HipTrainer:
         if rows % batch:
             raise ValueError('%d rows are no whole number of batches of %d' % (rows, batch))
         n_batches = rows // batch
-        for name, t, dtype in (('order', order, torch.int64), ('sym', sym, torch.uint8)):
-            if t is not None and (t.dtype != dtype or t.device != dev or int(t.numel()) != rows or not t.is_contiguous()):
-                raise ValueError('%s: a contiguous %s tensor of %d entries on %s is expected' % (name, dtype, rows, dev))
+        _row_tensors(dev, rows, order=order, sym=sym)
         nz = None if noise is None else self._f32(noise, (n_batches, self.A))
         loss = torch.empty((n_batches, 4), dtype=torch.float32, device=self.device)
         if n_batches == 0:
@@ -399,24 +440,6 @@ class HipTrainer:
                 t.record_stream(stream)
         return loss
 
-    def _evaluated(self, n, launch, rows, keep):
-        """The common part of the two evaluations: the outputs, `launch(rows_ptr, flags_ptr, totals_ptr, stream)` on torch's
-        current stream, and the one synchronising read of the totals."""
-        out_rows = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        out_flags = torch.empty((n,), dtype=torch.uint8, device=self.device)
-        totals = torch.empty(np.dtype(_lib.EVAL_TOTALS_DTYPE).itemsize, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device)
-            launch(out_rows.data_ptr(), out_flags.data_ptr(), totals.data_ptr(), stream.cuda_stream)
-        for t in keep:                                   # asynchronous: alive until the stream has used them
-            if t is not None:
-                t.record_stream(stream)
-        tot = totals.cpu().numpy().view(_lib.EVAL_TOTALS_DTYPE)[0]      # (waits for the launches)
-        out = eval_summary(*[tot[k].item() for k in EVAL_COUNTS])
-        if rows:
-            out['per_row'], out['flags'] = out_rows, out_flags
-        return out
-
     def evaluate_records(self, examples, index=None, sym=None, rows=False):
         """Score example records with the trainer's current device parameters (bb_trainer_eval: forward only -- no step, no noise,
         no export; parameters, slots, gradients and the noise stream of later steps are untouched).  Row k is record index[k]
@@ -430,41 +453,29 @@ class HipTrainer:
         ValueError).  index, sym: tensors as examples.index_tensor and examples.sym_tensor return them, or anything those take.
         Malformed rows are zeros with flags 0, outside every total, and count in examples.bad()."""
         self._not_wide('evaluate_records')
-        if not isinstance(examples, DeviceExamples):
-            raise ValueError('evaluate_records takes a DeviceExamples (merged rows carry sums of their own and are not a records '
-                             'source), got %s' % type(examples).__name__)
-        if examples.game != self.game:
-            raise ValueError('the examples are of game %d, the trainer of game %d' % (examples.game, self.game))
-        dev = examples.records.device
-        if dev.type != 'cuda' or (dev.index if dev.index is not None else torch.cuda.current_device()) != self._index:
-            raise ValueError('the examples are on %s, the trainer on cuda:%d' % (dev, self._index))
+        dev = _records_source(examples, self.game, self._index, 'evaluate_records', 'trainer')
         if index is not None and not torch.is_tensor(index):
             index = examples.index_tensor(index)
         if sym is not None and not torch.is_tensor(sym):
             sym = examples.sym_tensor(sym)
         n = len(examples) if index is None else int(index.numel())
-        for name, t, dtype in (('index', index, torch.int64), ('sym', sym, torch.uint8)):
-            if t is not None and (t.dtype != dtype or t.device != dev or int(t.numel()) != n or not t.is_contiguous()):
-                raise ValueError('%s: a contiguous %s tensor of %d entries on %s is expected' % (name, dtype, n, dev))
-        return self._evaluated(
-            n, lambda r, f, tot, st: _lib.trainer_eval(self._h, len(examples), examples.records.data_ptr() if len(examples) else None, n,
+        _row_tensors(dev, n, index=index, sym=sym)
+        return _scored(
+            self.device, n, lambda r, f, tot, st: _lib.trainer_eval(self._h, len(examples), examples.records.data_ptr() if len(examples) else None, n,
                                                        None if index is None else index.data_ptr(),
                                                        None if sym is None else sym.data_ptr(), r, f, tot, examples._bad.data_ptr(), st),
-            rows, (examples.records, examples._bad, index, sym))
+            (examples.records, examples._bad, index, sym), rows)
 
     def evaluate_tensors(self, boards, evalLabel, policyLabel, rows=False):
         """`evaluate_records` for rows given as the three tensors of a batch (bb_trainer_eval_tensors): boards [n,H,W,C], evalLabel
         [n], policyLabel [n,A].  The same kernel reads either source: evaluate_records(ex, index, sym) and
         evaluate_tensors(*ex._batch(index, sym)) give the same bits."""
         self._not_wide('evaluate_tensors')
-        n = int(policyLabel.shape[0]) if hasattr(policyLabel, 'shape') else len(policyLabel)
-        boards = self._f32(boards, (n, self.H, self.Wd, self.C))
-        ev = self._f32(evalLabel, (n,))
-        pl = self._f32(policyLabel, (n, self.A))
-        return self._evaluated(
-            n, lambda r, f, tot, st: _lib.trainer_eval_tensors(self._h, n, boards.data_ptr() if n else None, ev.data_ptr() if n else None,
+        n, boards, ev, pl = self._batch_tensors(boards, evalLabel, policyLabel)
+        return _scored(
+            self.device, n, lambda r, f, tot, st: _lib.trainer_eval_tensors(self._h, n, boards.data_ptr() if n else None, ev.data_ptr() if n else None,
                                                                pl.data_ptr() if n else None, r, f, tot, st),
-            rows, (boards, ev, pl))
+            (boards, ev, pl), rows)
 
     def last_noise(self):
         """The noise of the last step (given or drawn), read back from the device."""
@@ -495,7 +506,72 @@ def epoch_order(n, batchSize):
     return np.random.choice(n, n - n % batchSize, replace=False)
 
 
-class DeviceExamples:
+class _ExampleRows:
+    """What DeviceExamples and MergedExamples share: `records` on a device, len(self) rows over them (records, or groups of
+    them), and `batch`, which turns any selection of the rows into the three float32 tensors the loss takes -- one HIP launch
+    on torch's current stream, the class's own (`_to_batch`), nothing staged through the host."""
+
+    def index_tensor(self, index):
+        """`index` (int64 tensor or anything numpy takes) as an int64 tensor on the records' device, range-checked:
+        every entry must name one of the len(self) rows (records; of merged rows, groups)."""
+        if torch.is_tensor(index):
+            idx = index.to(device=self.records.device, dtype=torch.int64).reshape(-1)
+            wrong = bool(((idx < 0) | (idx >= len(self))).any()) if idx.numel() else False
+        else:
+            host = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+            wrong = bool(((host < 0) | (host >= len(self))).any())
+            idx = torch.from_numpy(host).to(self.records.device)
+        if wrong:
+            raise IndexError('example index out of range [0, %d)' % len(self))
+        return idx.contiguous()
+
+    @property
+    def symmetries(self):
+        """How many board symmetries the game has (bb_game_symmetries): the values `sym` may take are 0 .. symmetries - 1."""
+        return _lib.game_symmetries(self.game)
+
+    def sym_tensor(self, sym):
+        """`sym` (uint8 tensor on the records' device, or anything numpy takes) as a uint8 tensor on the records' device.  What
+        arrives from the host is range-checked here against `symmetries` (ValueError); a tensor that is on the device already
+        is left to the kernel, which writes a row of zeros for a symmetry the game does not have and counts it in bad()."""
+        if torch.is_tensor(sym) and sym.device == self.records.device and sym.device.type != 'cpu':
+            if sym.dtype != torch.uint8:
+                raise ValueError('sym: a uint8 tensor is expected on the device, got %s' % sym.dtype)
+            return sym.reshape(-1).contiguous()
+        host = np.asarray(sym.cpu() if torch.is_tensor(sym) else sym).reshape(-1)
+        if host.size and (host.dtype.kind not in 'iub' or int(host.min()) < 0 or int(host.max()) >= self.symmetries):
+            raise ValueError('sym: integers in [0, %d) are expected (the symmetries of game %d)' % (self.symmetries, self.game))
+        return torch.from_numpy(host.astype(np.uint8)).to(self.records.device)
+
+    def batch(self, index=None, sym=None):
+        """(boards [n,H,W,C], value [n], policy [n,A]) of the rows `index` names (None: all, in order), fresh float32
+        tensors on the records' device: what TrainWithExamples stacks per batch, in Network.train's argument order.
+        sym (None: as played): one symmetry of the game per output row, < `symmetries` -- the row is that of the position
+        mirrored or turned so, planes and policy alike (bb_examples_to_batch_sym; an extension, the reference does not
+        augment)."""
+        return self._batch(None if index is None else self.index_tensor(index), None if sym is None else self.sym_tensor(sym))
+
+    def _batch(self, idx, sym=None):
+        """`batch` for an index tensor that index_tensor returned (or a slice of one), and a symmetry tensor that sym_tensor
+        returned (or a slice of one)."""
+        gi, dev = self.info, self.records.device
+        n = len(self) if idx is None else int(idx.numel())
+        if sym is not None and int(sym.numel()) != n:
+            raise ValueError('sym: one entry per output row is expected (%d rows, %d entries)' % (n, int(sym.numel())))
+        boards = torch.empty((n, gi.H, gi.W, gi.C), dtype=torch.float32, device=dev)
+        value = torch.empty((n,), dtype=torch.float32, device=dev)
+        policy = torch.empty((n, gi.A), dtype=torch.float32, device=dev)
+        if n == 0:
+            return boards, value, policy
+        if dev.type != 'cuda':
+            raise _lib.BlackbirdHipError('%s.batch runs on the GPU only (records on %s)' % (type(self).__name__, dev))
+        with torch.cuda.device(dev):
+            self._to_batch(n, None if idx is None else idx.data_ptr(), None if sym is None else sym.data_ptr(), boards.data_ptr(),
+                           policy.data_ptr(), value.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        return boards, value, policy
+
+
+class DeviceExamples(_ExampleRows):
     """Self-play example records that stay on the GPU: a game id and a uint8 tensor [N, example_bytes] in the layout of
     bb_examples_fetch.  `batch` turns any selection of them into the three float32 tensors the loss takes
     (bb_examples_to_batch: one HIP launch on torch's current stream, nothing staged through the host).
@@ -556,66 +632,9 @@ class DeviceExamples:
         held = torch.isin(ids, torch.from_numpy(held_ids).to(ids.device))
         return type(self)(self.game, self.records[~held]), type(self)(self.game, self.records[held])
 
-    def index_tensor(self, index):
-        """`index` (int64 tensor or anything numpy takes) as an int64 tensor on the records' device, range-checked:
-        every entry must name one of the len(self) records."""
-        if torch.is_tensor(index):
-            idx = index.to(device=self.records.device, dtype=torch.int64).reshape(-1)
-            wrong = bool(((idx < 0) | (idx >= len(self))).any()) if idx.numel() else False
-        else:
-            host = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
-            wrong = bool(((host < 0) | (host >= len(self))).any())
-            idx = torch.from_numpy(host).to(self.records.device)
-        if wrong:
-            raise IndexError('example index out of range [0, %d)' % len(self))
-        return idx.contiguous()
-
-    @property
-    def symmetries(self):
-        """How many board symmetries the game has (bb_game_symmetries): the values `sym` may take are 0 .. symmetries - 1."""
-        return _lib.game_symmetries(self.game)
-
-    def sym_tensor(self, sym):
-        """`sym` (uint8 tensor on the records' device, or anything numpy takes) as a uint8 tensor on the records' device.  What
-        arrives from the host is range-checked here against `symmetries` (ValueError); a tensor that is on the device already
-        is left to the kernel, which writes a row of zeros for a symmetry the game does not have and counts it in bad()."""
-        if torch.is_tensor(sym) and sym.device == self.records.device and sym.device.type != 'cpu':
-            if sym.dtype != torch.uint8:
-                raise ValueError('sym: a uint8 tensor is expected on the device, got %s' % sym.dtype)
-            return sym.reshape(-1).contiguous()
-        host = np.asarray(sym.cpu() if torch.is_tensor(sym) else sym).reshape(-1)
-        if host.size and (host.dtype.kind not in 'iub' or int(host.min()) < 0 or int(host.max()) >= self.symmetries):
-            raise ValueError('sym: integers in [0, %d) are expected (the symmetries of game %d)' % (self.symmetries, self.game))
-        return torch.from_numpy(host.astype(np.uint8)).to(self.records.device)
-
-    def batch(self, index=None, sym=None):
-        """(boards [n,H,W,C], value [n], policy [n,A]) of the records `index` names (None: all, in order), fresh float32
-        tensors on the records' device: what TrainWithExamples stacks per batch, in Network.train's argument order.
-        sym (None: as played): one symmetry of the game per output row, < `symmetries` -- the row is that of the position
-        mirrored or turned so, planes and policy alike (bb_examples_to_batch_sym; an extension, the reference does not
-        augment)."""
-        return self._batch(None if index is None else self.index_tensor(index), None if sym is None else self.sym_tensor(sym))
-
-    def _batch(self, idx, sym=None):
-        """`batch` for an index tensor that index_tensor returned (or a slice of one), and a symmetry tensor that sym_tensor
-        returned (or a slice of one)."""
-        gi, dev = self.info, self.records.device
-        n = len(self) if idx is None else int(idx.numel())
-        if sym is not None and int(sym.numel()) != n:
-            raise ValueError('sym: one entry per output row is expected (%d rows, %d entries)' % (n, int(sym.numel())))
-        boards = torch.empty((n, gi.H, gi.W, gi.C), dtype=torch.float32, device=dev)
-        value = torch.empty((n,), dtype=torch.float32, device=dev)
-        policy = torch.empty((n, gi.A), dtype=torch.float32, device=dev)
-        if n == 0:
-            return boards, value, policy
-        if dev.type != 'cuda':
-            raise _lib.BlackbirdHipError('DeviceExamples.batch runs on the GPU only (records on %s)' % dev)
-        with torch.cuda.device(dev):
-            _lib.examples_to_batch_sym(self.game, len(self), self.records.data_ptr(), n,
-                                       None if idx is None else idx.data_ptr(), None if sym is None else sym.data_ptr(),
-                                       boards.data_ptr(), policy.data_ptr(), value.data_ptr(), self._bad.data_ptr(),
-                                       torch.cuda.current_stream(dev).cuda_stream)
-        return boards, value, policy
+    def _to_batch(self, n, idx, sym, boards, policy, value, stream):
+        _lib.examples_to_batch_sym(self.game, len(self), self.records.data_ptr(), n, idx, sym, boards, policy, value,
+                                   self._bad.data_ptr(), stream)
 
     def score_with(self, engine, index=None, rows=False, chunk_rows=4096):
         """Score these records with the network `engine` (an _lib.Engine of this game, on the records' device, with weights
@@ -630,11 +649,7 @@ class DeviceExamples:
         bad()."""
         if not isinstance(engine, _lib.Engine):
             raise ValueError('score_with takes an _lib.Engine, got %s' % type(engine).__name__)
-        if engine.game != self.game:
-            raise ValueError('the examples are of game %d, the engine of game %d' % (self.game, engine.game))
-        dev = self.records.device
-        if dev.type != 'cuda' or (dev.index if dev.index is not None else torch.cuda.current_device()) != int(engine.cfg.device):
-            raise ValueError('the examples are on %s, the engine on cuda:%d' % (dev, int(engine.cfg.device)))
+        dev = _records_source(self, engine.game, int(engine.cfg.device), 'score_with', 'engine')
         if index is not None and not torch.is_tensor(index):
             index = self.index_tensor(index)
         n = len(self) if index is None else int(index.numel())
@@ -645,23 +660,11 @@ class DeviceExamples:
         work = getattr(self, '_score_work', None)
         if work is None or int(work.numel()) < nbytes:
             work = self._score_work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        out_rows = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        out_flags = torch.empty((n,), dtype=torch.uint8, device=dev)
-        totals = torch.empty(np.dtype(_lib.EVAL_TOTALS_DTYPE).itemsize, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            engine.score_examples(len(self), self.records.data_ptr() if len(self) else None, n,
-                                  None if index is None else index.data_ptr(), out_rows.data_ptr() if n else None,
-                                  out_flags.data_ptr() if n else None, totals.data_ptr(), self._bad.data_ptr(),
-                                  work.data_ptr(), nbytes, stream.cuda_stream)
-        for t in (self.records, self._bad, index, work, out_rows, out_flags, totals):   # the engine's stream uses them: alive until `stream` is past its wait
-            if t is not None:
-                t.record_stream(stream)
-        tot = totals.cpu().numpy().view(_lib.EVAL_TOTALS_DTYPE)[0]      # (waits for the launches)
-        out = eval_summary(*[tot[k].item() for k in EVAL_COUNTS])
-        if rows:
-            out['per_row'], out['flags'] = out_rows, out_flags
-        return out
+        return _scored(     # (the engine's stream uses the outputs and the workspace: alive until torch's stream is past its wait)
+            dev, n, lambda r, f, tot, st: engine.score_examples(len(self), self.records.data_ptr() if len(self) else None, n,
+                                                                None if index is None else index.data_ptr(), r if n else None,
+                                                                f if n else None, tot, self._bad.data_ptr(), work.data_ptr(), nbytes, st),
+            (self.records, self._bad, index, work), rows, outputs_too=True)
 
     def bad(self):
         """Rows that bb_examples_to_batch rejected (and wrote as zeros) since this object was made: malformed records.
@@ -718,7 +721,7 @@ def merge_records_host(game, records):
     return group, rep, count, zsum.astype(np.int32), total, visits
 
 
-class MergedExamples:
+class MergedExamples(_ExampleRows):
     """A DeviceExamples with the copies of every position merged into one training row (DeviceExamples.merged): the source
     records plus, per group, its first member `rep`, its size `count` and the integer sums `zsum`, `total`, `visits` -- tensors
     on the records' device, trimmed to the number of groups --, and `group` [records], the group of every record (-1: malformed).
@@ -762,40 +765,14 @@ class MergedExamples:
         """The number of records in every group (int32 tensor on the records' device)."""
         return self.count
 
-    index_tensor = DeviceExamples.index_tensor     # (range-checked against len(self): the number of groups)
-    sym_tensor = DeviceExamples.sym_tensor
-    symmetries = DeviceExamples.symmetries
-
-    def batch(self, index=None, sym=None):
-        """DeviceExamples.batch over merged rows: (boards [n,H,W,C], value [n], policy [n,A]) of the groups `index` names (None:
-        all, in order), each under the symmetry `sym` gives it (None: as played)."""
-        return self._batch(None if index is None else self.index_tensor(index), None if sym is None else self.sym_tensor(sym))
-
-    def _batch(self, idx, sym=None):
-        """`batch` for tensors that index_tensor and sym_tensor returned (or slices of them)."""
-        gi, dev = self.info, self.records.device
-        n = len(self) if idx is None else int(idx.numel())
-        if sym is not None and int(sym.numel()) != n:
-            raise ValueError('sym: one entry per output row is expected (%d rows, %d entries)' % (n, int(sym.numel())))
-        boards = torch.empty((n, gi.H, gi.W, gi.C), dtype=torch.float32, device=dev)
-        value = torch.empty((n,), dtype=torch.float32, device=dev)
-        policy = torch.empty((n, gi.A), dtype=torch.float32, device=dev)
-        if n == 0:
-            return boards, value, policy
-        if dev.type != 'cuda':
-            raise _lib.BlackbirdHipError('MergedExamples.batch runs on the GPU only (records on %s)' % dev)
-        with torch.cuda.device(dev):
-            _lib.examples_merged_to_batch(self.game, int(self.records.shape[0]), self.records.data_ptr(), len(self),
-                                          self.rep.data_ptr(), self.count.data_ptr(), self.zsum.data_ptr(), self.total.data_ptr(),
-                                          self.visits.data_ptr(), n, None if idx is None else idx.data_ptr(),
-                                          None if sym is None else sym.data_ptr(), boards.data_ptr(), policy.data_ptr(),
-                                          value.data_ptr(), self._bad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        return boards, value, policy
+    def _to_batch(self, n, idx, sym, boards, policy, value, stream):
+        _lib.examples_merged_to_batch(self.game, int(self.records.shape[0]), self.records.data_ptr(), len(self), self.rep.data_ptr(),
+                                      self.count.data_ptr(), self.zsum.data_ptr(), self.total.data_ptr(), self.visits.data_ptr(), n, idx,
+                                      sym, boards, policy, value, self._bad.data_ptr(), stream)
 
     def score_with(self, engine, index=None, rows=False, chunk_rows=4096):
         """Merged rows carry sums of their own and are not a records source: ValueError, as HipTrainer.evaluate_records answers."""
-        raise ValueError('score_with takes a DeviceExamples (merged rows carry sums of their own and are not a records source), '
-                         'got %s' % type(self).__name__)
+        _records_source(self, None, None, 'score_with', 'engine')
 
     def bad(self):
         """Malformed records that the merge left out, plus rows that `batch` rejected (and wrote as zeros) since.  Waits for

@@ -702,7 +702,7 @@ int bb_trainer_load_engine(bb_trainer *t, bb_engine *e, void *stream);
  * that chooses the moves.  csrc/examples_score.hip.h: per chunk of rows a gather of the records' packed states, the engine's own
  * network launch (no noise, no keys, no evaluation cache) and one wave per row for the figures; then bb_trainer_eval's totals
  * launch, unchanged.  Per row k (record index[k]; NULL: record k), as bb_trainer_eval defines them:
- *   rows_out[k] = value (the engine's, unchanged), se = (value - z)^2, ce = -sum_a pi[a] (logit[a] - max - log sum exp(logit - max))
+ *   rows_out[k] = value (the engine's, unchanged), se and ce by bb_trainer_eval's expressions above, the max and the sum
  *                 over all A logits, pi[a] = (float)((double)visits / (double)total); DragonChess takes pi from the record's
  *                 compact list (visits[j] at action[j], j < n_children) and forms no 4032-wide label row; ce is 0 without a label
  *   flags_out[k]  BB_ROW_*; BB_ROW_HAS_POLICY: total != 0 and some visit count is not zero; BB_ROW_TOP1: first maximum of the

@@ -11,7 +11,8 @@ kernel's own float32 figures within 1e-12, as tests/test_gpu_trainer_eval.py hol
 Records: a 4-game, 8-simulation self-play run under the hash evaluator per game, behind the hand-built corners of
 score_cases.corners.  Against the trainer's scorer the two flag counts may differ on rows without room only -- the top two
 logits closer than eval_cases.LOGIT_ROOM, |value| below VALUE_ROOM: the trainer's logits cannot be read through any entry point,
-so this is the rule tests/test_gpu_trainer_eval.py compares bits under.  Every test here fails without the entry point."""
+so this is the rule tests/test_gpu_trainer_eval.py compares bits under.  On the corners alone, under weights that leave every
+row that room, the two scorers' flags are equal byte for byte (both call the one score_policy_serial).  Every test here fails without the entry point."""
 import ctypes as C
 
 import numpy as np
@@ -234,6 +235,41 @@ def test_against_the_trainers_scorer():
         eng.close()
     assert ex.bad() == 0
     tr.close()
+
+
+@pytest.mark.parametrize("game", [C4, TTT])
+def test_both_scorers_set_the_same_flags_on_the_corners(game):
+    """The hand-built corners -- 'terminal' (total 0), 'tie' (two top shares), z in {-1, 0, 1}, 'too_many' (malformed) -- scored
+    with the same 16-filter weights by the trainer's scorer and by an engine in the float32 form: the flags bytes are equal row
+    by row, no row left out.  The two networks round differently (1e-5), so a TOP1 or SIGN_OK bit may differ only where two
+    logits, or the value and 0, lie that close; the float64 statement (eval_cases.forward, on the CPU) shows that no corner
+    does under init_weights(seed=2, perturb=True) with 2 blocks: the smallest gap between the top two logits is 0.0578
+    (Connect4; TicTacToe 0.590) and the smallest |value| 0.0110 (TicTacToe; Connect4 0.349), both asserted > 1e-3 here.  The
+    values are negative, so SIGN_OK is set on the z = -1 row and clear on the z = 1 rows."""
+    gi = _lib.game_info(game)
+    rec, at = SC.corners(game)
+    ex = DeviceExamples.from_records(game, rec, DEV)
+    w0 = W.init_weights(gi.C, 16, 2, 16, gi.A, seed=2, perturb=True)
+    good = np.array([r for r in range(len(rec)) if not SC.malformed(game, rec, r)])
+    value, logits = EC.forward(w0, EC.host_rows(game, rec[good])[0])
+    top = np.sort(logits, axis=1)
+    print(game, "smallest top-two logit gap %.4g, smallest |value| %.4g" % ((top[:, -1] - top[:, -2]).min(), np.abs(value).min()))
+    assert (top[:, -1] - top[:, -2]).min() > 1e-3 and np.abs(value).min() > 1e-3
+    want = np.zeros(len(rec), dtype=np.uint8)
+    want[good] = SC.statement(game, logits, value, rec, good)["flags"]
+    tr = HipTrainer(w0, device=DEV, seed=1)
+    eng = _lib.Engine(game, n_slots=1, sims_per_move=2, evaluator=_lib.EVAL_NET, net_form=F32, launch=_lib.LAUNCH_LOCKSTEP)
+    eng.load_weights(W.flatten(w0))
+    assert eng.net_form() == 0
+    theirs = tr.evaluate_records(ex, rows=True)["flags"].cpu().numpy()
+    mine = ex.score_with(eng, rows=True)["flags"].cpu().numpy()
+    eng.close()
+    tr.close()
+    print(game, "trainer", theirs, "engine", mine, "statement", want)
+    assert np.array_equal(mine, theirs), (mine, theirs)
+    assert np.array_equal(mine, want) and mine[at["too_many"]] == 0 and ex.bad() == 2      # (one malformed row, met by each scorer)
+    assert mine[at["terminal"]] & _lib.ROW_COUNTED and not mine[at["terminal"]] & _lib.ROW_HAS_POLICY
+    assert {int(z) for z in rec["z"][good]} == {-1, 0, 1} and (mine[good] & _lib.ROW_SIGN_OK).any()
 
 
 def _cfg(backend, filters=16, hip_games=None):
