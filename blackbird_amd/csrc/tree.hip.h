@@ -34,6 +34,12 @@
 //   sq    = sqrt(1.0 + sum(ChildPlays)) (float64, refreshed by the backup)
 //   cP[i] = ExplorationRate * Priors[i] (float64, fixed at expansion)
 // so that one level of _selectAction costs one row load, one float64 multiply, one divide, one add.
+// What a level of async_game waits for: the plain form requests both lines at the top of the level and waits once, for all of
+// it.  The recorded form (REC) requested the row a level earlier, right behind the parent's argmax (descent_row), so the top of
+// the level waits only for what is left of that round trip -- still one wait for both lines: the leaf / terminal / cached tests,
+// the legality mask and 1 / (1 + N) need line 1, cP * sq needs line 2, but the compiler's wait ahead of the level's first
+// instruction is for every load in flight.  `st` (line 2) is requested behind that wait and used by the exits only; `pad0`
+// (line 1) is read inside the cached-terminal exit.
 template <class G>
 struct alignas(128) DenseNode {
     int32_t flags;       // NODE_EXPANDED | NODE_TERMINAL | Player << 4 | (winner+1) << 8
@@ -1016,6 +1022,53 @@ __global__ void __launch_bounds__(256) k_selfplay_move(TreeDev d) {
 // on_post(g, lane): called by every lane of the game's group right after the leaf's mailbox has been written -- the persistent
 // kernel hands the leaf to its network waves THERE (mega2.hip.h), not when the call returns: a wave's call lasts as long as
 // the slowest of its games' descents.
+// The recorded form's descent reads its rows through the global address space (plain global loads: a flat load also counts as
+// an LDS operation, and every wait for one of the kernel's LDS reads would then wait for the row), one level ahead: descent_row
+// REQUESTS a row -- nothing waits until a value is used.  Line 1 of the row is requested before line 2, in the order a level
+// uses them; as compiled the level still waits once for both.
+struct DescentRow {
+    int flags;
+    uint32_t mask;
+    int all;
+    double sq;
+    int N;
+    float Q;
+    int child;
+    double cP; // line 2
+    float W;
+};
+template <class G>
+__device__ __forceinline__ const __attribute__((address_space(1))) DenseNode<G> *descent_row_ptr(const DenseNode<G> *p) {
+    return (const __attribute__((address_space(1))) DenseNode<G> *)(const void *)p;
+}
+template <class G>
+__device__ __forceinline__ DescentRow descent_row(const DenseNode<G> *p, int lane) {
+    const auto *n = descent_row_ptr<G>(p);
+    DescentRow r;
+    r.flags = n->flags;
+    r.mask = n->legal_mask;
+    r.all = n->all;
+    r.sq = n->sq;
+    r.N = n->N[lane];
+    r.Q = n->Q[lane];
+    r.child = n->child[lane];
+    r.cP = n->cP[lane];
+    r.W = n->W[lane];
+    return r;
+}
+template <class G>
+__device__ __forceinline__ typename G::State descent_state(const DenseNode<G> *p) { // a node's state, word by word (any State)
+    using State = typename G::State;
+    static_assert(sizeof(State) % 8 == 0 && __is_trivially_copyable(State), "a state is whole 64-bit words");
+    const auto *w = (const __attribute__((address_space(1))) uint64_t *)(const void *)&p->st;
+    uint64_t v[sizeof(State) / 8];
+#pragma unroll
+    for (size_t i = 0; i < sizeof(State) / 8; i++) v[i] = w[i];
+    State st;
+    __builtin_memcpy(&st, v, sizeof(State));
+    return st;
+}
+
 struct NoPostHook {
     __device__ __forceinline__ void operator()(int, int) const {}
 };
@@ -1050,30 +1103,39 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
         int flags = 0;
         // Outcome bits of the descent, one integer per lane on purpose: as separate bools they live in scalar lane masks and
         // every exit of the loop below pays a three-instruction merge for each of them on every iteration
-        enum { F_PARKED = 2, F_LEAF = 4, F_TERM = 8, F_EXPAND = 16, F_OVERFLOW = 32 };
-        int fl = 0;
+        enum { F_PARKED = 2, F_LEAF = 4, F_TERM = 8, F_EXPAND = 16, F_OVERFLOW = 32, F_CREATE = 64 };
+        int fl = 0, act = 0;
         IF_STAMPS_LIGHT(int lt_e = (int)clock64();)
+        DescentRow nx = {};
+        if constexpr (REC) nx = descent_row<G>(pool + cur, lane); // the descent's first row (after the backups' stores: fresh)
         for (;;) {
             if (budget <= 0) { fl |= F_PARKED; break; }
             budget--;
             IF_STAMPS_LIGHT(light.levels++; int lt_a = (int)clock64();)
             Node *node = pool + cur;
-            typename G::State st_l = node->st;
-            int flags_l = node->flags;
-            uint32_t mask = node->legal_mask;
-            double sq = node->sq;
-            int Ni = node->N[lane];
-            float Qi = node->Q[lane];
-            double cPi = node->cP[lane];
-            int ci = node->child[lane];
-            double cached = node->pad0;
-            float Wi = 0.f;
+            typename G::State st_l;
+            int flags_l, Ni, ci;
+            uint32_t mask;
+            double sq, cPi, cached = 0.;
+            float Qi, Wi = 0.f;
             int all_l = 0;
-            if (REC) {
-                Wi = node->W[lane];
-                all_l = node->all;
+            if constexpr (REC) { // the row was requested a level ago (descent_row)
+                flags_l = nx.flags, mask = nx.mask, all_l = nx.all, sq = nx.sq, Ni = nx.N, Qi = nx.Q, ci = nx.child;
+                cPi = nx.cP, Wi = nx.W;
+                asm volatile("" ::"v"(flags_l), "v"(mask), "v"(all_l), "v"(sq), "v"(Ni), "v"(Qi), "v"(ci)); // the wait: what is left of the row's round trip
+                st_l = descent_state<G>(node); // second line, for the exits only: nothing on the way down waits for it
+            } else {
+                st_l = node->st;
+                flags_l = node->flags;
+                mask = node->legal_mask;
+                sq = node->sq;
+                Ni = node->N[lane];
+                Qi = node->Q[lane];
+                cPi = node->cP[lane];
+                ci = node->child[lane];
+                cached = node->pad0;
+                asm volatile("" ::"v"(flags_l), "v"(mask), "v"(sq), "v"(Ni), "v"(Qi), "v"(cPi), "v"(ci)); // one wait for the whole row
             }
-            asm volatile("" ::"v"(flags_l), "v"(mask), "v"(sq), "v"(Ni), "v"(Qi), "v"(cPi), "v"(ci)); // one wait for the whole row
             IF_STAMPS_LIGHT(int lt_b = (int)clock64(); light.row_load += lt_b - lt_a;) // the row has arrived (the asm above made the loads' results live)
             st = st_l;
             flags = flags_l;
@@ -1082,6 +1144,7 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
                 if (flags & NODE_TERMINAL) {
                     fl |= F_TERM;
                     if (flags & NODE_CACHED) { // value already known: finish this simulation here
+                        if constexpr (REC) cached = descent_row_ptr<G>(node)->pad0; // (first line: it is in the cache)
                         float v01 = (float)cached;
                         __threadfence_block(); // path stores of this descent
                         backup_path<G, REC>(d, g, lane, pool, depth, v01, gs_prev(st));
@@ -1104,6 +1167,13 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
             // (float32 evaluators only reach this kernel: a child's WinRate is its float32 Q, child_q)
             int child = ci;
             int a = grp_argmax_puct<S>(Qi, cPi, sq, Ni, lane < A && ((mask >> lane) & 1u), child);
+            if constexpr (REC) { // the next level's row, requested the moment its index exists: the exact row, no guess.  No child
+                // yet: the request is clamped to this node (a load inside a conditional is waited for at the end of its branch),
+                // and a descent that parks or ends leaves one requested row unused -- it was a read
+                __builtin_amdgcn_sched_barrier(0);
+                nx = descent_row<G>(pool + (child == CHILD_NONE ? cur : (child & ~CHILD_TERM_BIT)), lane);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             IF_STAMPS_LIGHT(asm volatile("" ::"v"(a), "v"(child)); light.puct += (int)clock64() - lt_b;)
             if (lane == 0) path[depth] = path_word(cur, (flags >> 4) & 3, a);
             if (REC) { // what the backup of this edge will start from
@@ -1114,6 +1184,11 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
                 }
             }
             if (child == CHILD_NONE) {
+                if constexpr (REC) { // the child is created behind the loop, where the requested row's registers are free
+                    fl |= F_CREATE;
+                    act = a;
+                    break;
+                }
                 typename G::State st2;
                 bool terminal;
                 child = create_child<G>(d, g, pool, node, st, a, lane, nn, st2, terminal, &flags);
@@ -1128,6 +1203,21 @@ __device__ bool async_game(const TreeDev &d, int g, int lane, OnPost on_post = O
             }
             depth++;
             cur = child & ~CHILD_TERM_BIT;
+        }
+        if constexpr (REC) {
+            if (fl & F_CREATE) { // the same statements as in the plain form's loop, once for all the wave's games that got here
+                typename G::State st2;
+                bool terminal;
+                const int child = create_child<G>(d, g, pool, pool + cur, st, act, lane, nn, st2, terminal, &flags);
+                if (child == CHILD_NONE) {
+                    fl |= F_OVERFLOW | F_LEAF;
+                } else {
+                    st = st2;
+                    depth++;
+                    cur = child & ~CHILD_TERM_BIT;
+                    fl |= F_LEAF | (terminal ? F_TERM : F_EXPAND);
+                }
+            }
         }
         IF_STAMPS_LIGHT(light.loop += (int)clock64() - lt_e;)
         if (lane == 0) {
